@@ -6,15 +6,18 @@
       + RS ECC) over CHANNELS channels x 1 s of 2.4 Msps cs16 IQ per GPU, resident in HBM.  Channels shard across ranks with no
       data-path collective; the per-channel detection summaries (32 B, written by the frame-sync kernel) are all_gathered from device
       memory once per step.  After the timed loop every channel's last frame is compared with the CPU oracle's frame for
-      the stream that channel saw (`config.verified_channels`).  Extra objects of the default single-GPU run, none of them part of `value`:
+      the stream that channel saw (`config.verified_channels`, --full only).  A plain run sets up, warms up, times exactly K steps and prints
+      the line; everything else is behind --full.  Extra objects of a --full single-GPU run, none of them part of `value`:
       `detect_in_step` (BASELINE configs[4]: the same steps with the dft_detect scanner re-scanning a rotating 1/16 of the channels inside
       every step), `pcie_inclusive` (the same steps fed from pinned host memory), `scan_wide` and `fsk_mixed` (BASELINE configs[2] and
-      configs[3], each with its own ms_per_step / roofline / cpu_baseline — the objects `--config scan_wide|fsk_mixed` print on their own).
+      configs[3], each with its own ms_per_step / roofline / cpu_baseline — the objects `--config scan_wide|fsk_mixed` print on their own),
+      `cpu_baseline`, the per-kernel tables, the HBM stream probe and the device clocks.
+      --dump-outputs DIR: the frames the last timed step produced (and the channels' summary records) as DIR/<name>.npy, float32 / float64.
   --config scan_wide (BASELINE configs[2]): 256 channels out of ONE 10 Msps stream -> dft_detect scanner, per 0.2 s of stream.
   --config fsk_mixed (BASELINE configs[3]): 1024 mixed RS41 / DFM09 / M10 channels through the 2-FSK modem (fsk_demod path).
   --config mixed_2400k (BASELINE configs[4] at configs[3]'s type mix): 512 channels at 2.4 Msps, 50 % RS41 / 30 % DFM09 / 20 % M10, demodulated and block-decoded on the device.
 
-  python bench.py --gpus 1 [--config demod] [--steps K --warmup W]
+  python bench.py --gpus 1 [--config demod] [--steps K --warmup W] [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 """
 from __future__ import annotations
@@ -203,6 +206,7 @@ def bench_demod(args, D: Dist):
     torch = D.torch
     from radiosonde_auto_rx_amd.engine import Engine
     from radiosonde_auto_rx_amd import shard
+    full = args.full
     C = args.channels or int(os.environ.get("SONDE_BENCH_CHANNELS", "512"))
     steps = args.steps or 400
     warmup = 5 if args.warmup is None else args.warmup
@@ -248,20 +252,11 @@ def bench_demod(args, D: Dist):
     for _ in range(warmup):
         step()
     eng.fetch_frames_np(lag=0)
-    # at least 2 s of timed work (2.2 s aimed at: the probe runs a few per cent slow) whatever K is (the driver's GPU-busy sampler needs to see the run): the K steps are repeated R times and
-    # every figure below is over all K x R steps.  R comes from a steady-state probe (the warm-up itself carries first-call costs)
     eng.sync(); torch.cuda.synchronize()
-    t_p = time.perf_counter()
-    for _ in range(10):
-        step()
-    eng.fetch_frames_np(lag=0)
-    eng.sync(); torch.cuda.synchronize()
-    est = max((time.perf_counter() - t_p) / 10, 1e-4)
-    repeats = 1 if os.environ.get("SONDE_BENCH_NO_REPEAT") else max(1, int(np.ceil(2.2 / (est * steps))))
-    total_steps = steps * repeats
-    # what this box's HBM gives a plain read stream over the very buffer the decimator reads (best of five passes), and the clocks around the timed loop
-    stream_gbps = _stream_probe(iq.data_ptr(), int(iq.numel()) * iq.element_size())
-    clocks0 = _device_clocks()
+    total_steps = steps                                                   # exactly K timed steps (--steps): ms_per_step is the time of one of them
+    # --full: what this box's HBM gives a plain read stream over the very buffer the decimator reads (best of five passes), and the clocks around the timed loop
+    stream_gbps = _stream_probe(iq.data_ptr(), int(iq.numel()) * iq.element_size()) if full else None
+    clocks0 = _device_clocks() if full else None
     eng.profile(1)                      # timed region: HIP events around the dominant kernel only (2 events per step)
     D.barrier()
     t0 = time.perf_counter()
@@ -286,18 +281,22 @@ def bench_demod(args, D: Dist):
     eng.sync()
     D.barrier()
     dt_local = time.perf_counter() - t0
-    clocks1 = _device_clocks()
+    clocks1 = _device_clocks() if full else None
     dt, per_rank = D.finish_times(dt_local)
     host_ecc = eng.host_ecc_frames() - host_ecc0
     nframes, nok, nfixed, nsym, host_ecc = D.sum_ints(nframes, nok, nfixed, nsym, host_ecc)
     md_ms, md_n = eng.kernel_ms("mix_decimate")
+    if args.dump_outputs and D.rank == 0:
+        # the frames of the last timed call: the drain's fetch when the fetch runs a step behind, else the last step's own (+ an empty drain)
+        last_call = [fr_tail[-1]] if lag > 0 else fr_tail[-2:]
+        dump_outputs(args.dump_outputs, [a for a in last_call if a is not None], shard.decode_summaries(summary))
 
     # untimed: every channel's last frame against the CPU oracle's last frame of the same stream (frame bytes, length, ECC verdict)
     for arr in fr_tail:
         for f in (arr if arr is not None else ()):
             last[int(f["channel"])] = f
     verified, mismatched = 0, []
-    want = _oracle_last_frames(fqs, caps, fed) if not args.no_verify else None
+    want = _oracle_last_frames(fqs, caps, fed) if full and not args.no_verify else None
     if want is not None:
         for c in range(C):
             f, w = last.get(c), want[ch_bank[c]]
@@ -315,7 +314,7 @@ def bench_demod(args, D: Dist):
     # untimed: the same steps with the Reed-Solomon decoder on the host (the round-3 arrangement: k_framesync leaves first-pass syndromes, the
     # fetch runs rs41_ecc on one host thread) — what the device decoder replaces
     ab = None
-    if D.world == 1 and not args.no_extras:
+    if full and D.world == 1 and not args.no_extras:
         eng.set_device_ecc(False)
         for _ in range(3):
             step()
@@ -336,7 +335,7 @@ def bench_demod(args, D: Dist):
     # input: what k_mix_decimate50 does when no IF-rate kernel of the call before holds CU slots beside it.  `roofline.frac` above is the timed run's figure
     # (two streams: the tail runs beside the decimator and stretches it); this one goes beside it as `frac_kernel_alone`
     alone, kern_serial = None, None
-    if D.world == 1 and not args.no_extras and lag > 0 and args.two_streams:
+    if full and D.world == 1 and not args.no_extras and lag > 0 and args.two_streams:
         # (the Reed-Solomon kernel too: on the timed engine it has a stream of its own beside the next call's decimator; SONDE_ECC_INLINE is read when an engine is made)
         had_inline = os.environ.get("SONDE_ECC_INLINE")
         os.environ["SONDE_ECC_INLINE"] = "1"
@@ -373,16 +372,18 @@ def bench_demod(args, D: Dist):
         e1.close()
 
     # untimed: per-kernel table of a step (events around every kernel cost ~0.1 ms of host time per step, so not in the timed region)
-    # pipelined like the timed loop (a step that waits for its own frames lets the clocks drop between steps and reads 10 % slow)
-    eng.profile(2)
-    nprof = 20
-    for _ in range(nprof):
-        step()
-    eng.fetch_frames_np(lag=0)
-    kern = {}
-    for k in ("mix_decimate", "if_chain", "header_corr", "framesync", "rs_ecc"):
-        ms, n = eng.kernel_ms(k)
-        kern[k] = dict(ms_per_step=round(ms * n / nprof, 4), launches_per_step=n / nprof)
+    # pipelined like the timed loop (a step that waits for its own frames lets the clocks drop between steps and reads 10 % slow); --full only
+    kern = None
+    if full:
+        eng.profile(2)
+        nprof = 20
+        for _ in range(nprof):
+            step()
+        eng.fetch_frames_np(lag=0)
+        kern = {}
+        for k in ("mix_decimate", "if_chain", "header_corr", "framesync", "rs_ecc"):
+            ms, n = eng.kernel_ms(k)
+            kern[k] = dict(ms_per_step=round(ms * n / nprof, 4), launches_per_step=n / nprof)
     eng.profile(0)
     rec = shard.decode_summaries(summary)
     total_samples = D.world * C * SR * total_steps
@@ -402,7 +403,7 @@ def bench_demod(args, D: Dist):
             "config": {"workload": "RS41 2.4 Msps cs16 IQ, rs41mod --ecc2 --IQ fq --lpIQ (BASELINE configs[1]) x %d channels per GPU "
                                    "(per-GPU share of configs[4]), 1 s of signal per channel per step, input resident in HBM" % C,
                        "channels_per_gpu": C, "samples_per_channel_per_step": SR, "realtime_channels": round(value / 2.4, 1),
-                       "repeats": repeats, "timed_steps": total_steps, "timed_seconds": round(dt, 3),
+                       "timed_steps": total_steps, "timed_seconds": round(dt, 3),
                        "frame_fetch_lag": lag, "two_streams": bool(lag > 0 and args.two_streams),
                        "frames_decoded": nframes, "frames_ecc_ok": nok, "frames_ecc_failed": nframes - nok, "frames_repaired": nfixed,
                        "symbols_repaired": nsym, "frames_decoded_by_host_rs": host_ecc,
@@ -435,8 +436,8 @@ def bench_demod(args, D: Dist):
         }
         if want is not None and verified != D.world * C:
             out["config"]["verify_failed"] = True
-    # ---- extras on one GPU (never part of `value`)
-    if D.world == 1 and not args.no_extras:
+    # ---- extras on one GPU (never part of `value`; --full only)
+    if full and D.world == 1 and not args.no_extras:
         out["host_ecc_ab"] = ab
         out["detect_in_step"] = detect_in_step_extra(D, eng, iq, ch_fq, C, STRIDE, lag)
         if not args.no_configs:                                       # the same at higher scan duties (BASELINE configs[4] "full detect" = duty 1)
@@ -447,9 +448,9 @@ def bench_demod(args, D: Dist):
     eng.close()
     del iq
     torch.cuda.empty_cache()
-    if D.world == 1 and not args.no_cpu_baseline:
+    if full and D.world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline_demod(fqs, caps)
-    if D.world == 1 and not args.no_extras and not args.no_configs:
+    if full and D.world == 1 and not args.no_extras and not args.no_configs:
         import bench_configs
         try:
             out["side_paths"] = bench_configs.side_paths(D, caps, fqs)
@@ -463,6 +464,29 @@ def bench_demod(args, D: Dist):
             except Exception as exc:                                      # the headline must survive a failure beside it — and say so
                 out[name] = {"error": repr(exc)}
     return out
+
+
+DUMP_LIMIT = 64 << 20
+
+
+def dump_outputs(path, frame_arrays, summaries):
+    """--dump-outputs: what a caller of the timed path receives from its last step — that call's frame records (sonde_frame_t fields, in
+    (channel, frame position) order) and every channel's summary record — as <path>/<name>.npy, float32 / float64 (exact for the integer fields)"""
+    from radiosonde_auto_rx_amd.engine import Engine
+    fr = np.concatenate(frame_arrays) if frame_arrays else np.zeros(0, Engine.FRAME_DTYPE)
+    fr = fr[np.lexsort((fr["mv_pos"], fr["channel"]))]
+    arrays = {"frames_" + k: fr[k].astype(np.float32 if k == "mv" else np.float64) for k in ("channel", "len", "ecc", "mv_pos", "mv", "nbytes")}
+    arrays["frames_bytes"] = fr["frame"].astype(np.float32)
+    for k in ("channel_id", "type", "inverted", "sample_pos", "frames", "frames_clean"):
+        arrays["summary_" + k] = summaries[k].astype(np.float64)
+    for k in ("score", "freq_offset_hz"):
+        arrays["summary_" + k] = summaries[k].astype(np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit("--dump-outputs: %d bytes exceed the %d byte limit" % (total, DUMP_LIMIT))
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
 
 
 def detect_in_step_extra(D: Dist, eng, iq, ch_fq, C, STRIDE, lag, groups=16, engine_step=None, engine_drain=None):
@@ -592,7 +616,7 @@ def _stream_probe(ptr, nbytes):
 
 
 # ---- the printed line.  The driver keeps the last ~8 KB of stdout: the line must fit with every object in it.  What is printed is the numbers; the prose
-# (notes, method descriptions) stays in the full object, written next to it (gpurun_out/bench_full.json, or $SONDE_BENCH_FULL), and in DESIGN.md §5 / INTEGRATION.md.
+# (notes, method descriptions) stays in the full object, which a --full run also writes to a file ($SONDE_BENCH_FULL names it), and in DESIGN.md §5 / INTEGRATION.md.
 _DROP_KEYS = {"kernels_two_streams", "ecc", "error_mix", "frames_ok_means", "kernel_alone", "clocks_mhz", "rank_ms_per_step", "verify_mismatch_channels", "stdout_bytes", "per_core",
               "samples_per_channel_per_step", "repeats", "scan_duty", "sequential", "summary_records", "algorithmic_gb_per_launch", "launches", "unique_captures_per_family",
               "timed_seconds", "two_streams", "frame_fetch_lag", "fsk_demod_args", "what", "step", "soft_decisions", "detections_last_step", "stages", "stream_rate",
@@ -624,12 +648,13 @@ def compact(obj, top=True, head=True):
     return obj
 
 
-def emit(out):
+def emit(out, write_full=True):
     full = os.environ.get("SONDE_BENCH_FULL") or os.path.join(ROOT, "gpurun_out", "bench_full.json")
     try:
-        os.makedirs(os.path.dirname(full), exist_ok=True)
-        with open(full, "w") as f:
-            json.dump(out, f)
+        if write_full:
+            os.makedirs(os.path.dirname(full), exist_ok=True)
+            with open(full, "w") as f:
+                json.dump(out, f)
     except OSError:
         pass
     if os.environ.get("SONDE_BENCH_VERBOSE"):
@@ -664,7 +689,12 @@ def main():
     ap.add_argument("--lag", type=int, default=1, help="demod: 1 = frame fetch one step behind (default), 0 = every step waits for its own frames")
     ap.add_argument("--two-streams", action="store_true", help="(default since round 4; kept for old command lines)")
     ap.add_argument("--one-stream", action="store_true", help="demod: decimator and IF-rate kernels on ONE in-order stream (the round-3 default; the A/B switch)")
+    ap.add_argument("--full", action="store_true", help="demod: also the oracle check, per-kernel tables, stream probe, clocks, CPU baseline, extras and the other "
+                                                        "configurations (off: set up, warm up, time the K steps, print the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="demod: write the last timed step's frames and summary records to DIR/<name>.npy")
     args = ap.parse_args()
+    if args.dump_outputs and args.config != "demod":
+        ap.error("--dump-outputs: demod configuration only")
     args.two_streams = not args.one_stream
     D = Dist()
     if args.config == "demod":
@@ -673,7 +703,7 @@ def main():
         import bench_configs
         out = bench_configs.run(args, D)
     if D.rank == 0:
-        emit(out)
+        emit(out, write_full=args.full or bool(os.environ.get("SONDE_BENCH_FULL")))
     D.close()
 
 

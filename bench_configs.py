@@ -24,7 +24,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 
 def _timed_steps(D, step, steps, warmup, min_seconds=0.0, drain=None, run_n=None):
     """-> (seconds, per-rank seconds, steps timed).  min_seconds: the step count is raised (from a probe of three untimed steps, the same count on every rank) until
-    the timed region is at least that long — the sub-configurations of the default line are timed over >= 1 s like the headline, not over a few milliseconds.
+    the timed region is at least that long — the sub-configurations of the `--full` line are timed over >= 1 s, not over a few milliseconds.
     drain: called behind the last step of every group of steps, inside the timed region — completes what a pipelined step leaves in flight.
     run_n: instead of `step` / `drain`: run_n(n) does n steps and completes them (a configuration whose steps are driven from several host threads)."""
     drain = drain or (lambda: None)
@@ -782,7 +782,7 @@ def side_paths(D, caps, fqs, C=64, steps=12):
 
 
 def run(args, D, short=False):
-    """short: the reduced runs the default `bench.py` line carries as its `scan_wide` / `fsk_mixed` objects"""
+    """short: the reduced runs the `bench.py --full` line carries as its `scan_wide` / `fsk_mixed` objects"""
     if args.config == "mixed_2400k":
         return bench_mixed_2400k(args, D, short)
     return bench_scan_wide(args, D, short) if args.config == "scan_wide" else bench_fsk_mixed(args, D, short)

@@ -39,3 +39,23 @@ def test_compact_line_fits_and_keeps_every_object():
                         assert r in c[name] and c[name][r].get("frac", c[name][r].get("value")) is not None
         assert not any(str(k).endswith("note") for k, _ in _walk(c))
         assert all(len(v) <= 230 for _, v in _walk(c) if isinstance(v, str))
+
+
+def test_dump_outputs_float_arrays_in_call_order(tmp_path):
+    """--dump-outputs: the frame records of the last call in (channel, frame position) order and the summary records, every array float32 / float64"""
+    import numpy as np
+    import bench
+    from radiosonde_auto_rx_amd import shard
+    from radiosonde_auto_rx_amd.engine import Engine
+    fr = np.zeros(3, Engine.FRAME_DTYPE)
+    fr["channel"], fr["mv_pos"], fr["ecc"] = [2, 0, 2], [9, 5, 4], [0, -1, 3]
+    fr["frame"][:, 0] = [1, 2, 3]
+    summ = np.zeros(4, shard.SUMMARY_DTYPE)
+    summ["sample_pos"] = 1 << 40
+    bench.dump_outputs(str(tmp_path / "out"), [fr[:2], fr[2:]], summ)
+    got = {p.stem: np.load(p) for p in (tmp_path / "out").iterdir()}
+    assert {"frames_channel", "frames_ecc", "frames_bytes", "summary_frames", "summary_sample_pos"} <= set(got)
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert got["frames_channel"].tolist() == [0, 2, 2] and got["frames_mv_pos"].tolist() == [5, 4, 9] and got["frames_ecc"].tolist() == [-1, 3, 0]
+    assert got["frames_bytes"].shape == (3, 518) and got["frames_bytes"][:, 0].tolist() == [2, 3, 1]
+    assert got["summary_sample_pos"].tolist() == [float(1 << 40)] * 4

@@ -15,10 +15,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.mark.parametrize("lag", [1, 0])
 def test_bench_two_ranks_on_one_device(lag):
-    env = dict(os.environ, SONDE_DIST_BACKEND="gloo", SONDE_BENCH_NO_REPEAT="1", HSA_ENABLE_IPC_MODE_LEGACY="0", SONDE_BENCH_VERBOSE="1")      # (the full object, not the compact line)
+    env = dict(os.environ, SONDE_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0", SONDE_BENCH_VERBOSE="1")      # (the full object, not the compact line)
     port = 29600 + (os.getpid() + lag) % 300
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--channels", "40", "--lag", str(lag)]
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--channels", "40", "--lag", str(lag), "--full"]
     r = subprocess.run(cmd, capture_output=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     lines = [l for l in r.stdout.decode().splitlines() if l.startswith("{")]

@@ -11,7 +11,7 @@ OUT=$ROOT/gpurun_out/prof
 rm -rf "$OUT"; mkdir -p "$OUT"
 export TMPDIR=/tmp
 export SONDE_BENCH_VERBOSE=1      # the full objects (bench.py prints the compact line by default)
-timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 2>/dev/null | tail -1 > "$OUT/${TAG}_bench.json"
+timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 --full 2>/dev/null | tail -1 > "$OUT/${TAG}_bench.json"
 cd /tmp
 timeout 300 rocprofv3 --kernel-trace --stats -d "$OUT/t" -o t -- python "$ROOT/bench.py" --steps 200 --no-cpu-baseline --no-extras --no-verify 2>/dev/null | tail -1 > "$OUT/${TAG}_bench_under_rocprof.json"
 timeout 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d "$OUT/f" -o f -- python "$ROOT/bench.py" --steps 3 --warmup 2 --no-cpu-baseline --no-extras --no-verify > /dev/null 2>&1
