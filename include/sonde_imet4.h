@@ -1,0 +1,88 @@
+/*
+ * sonde_imet4.h — iMet-4 / iMet-1-RS (Bell 202 AFSK, 1200 Bd 8N1 on FM) of libsonde_hip.so: the reference's imet/imet4iq.c.
+ *
+ * Two parts:
+ *  - the engine (GPU): per channel the reference's front end (IQ: IQ-dc removal, LUT mixer, --dc rotation, IF low-pass with the
+ *    acquisition / nominal tap sets, FM discriminator, FM low-pass; FM audio: the sample, --dc subtraction), the once-per-second AFC,
+ *    the two-tone sliding DFT and the run-length / majority slicer (imet4iq.c:445-578, 1532-1640).  It hands out complete 1000-bit
+ *    frames; many channels per call.
+ *  - the printer (host only, no GPU): bits -> 8N1 bytes -> GPS / eGPS / PTU / ePTU / XDATA packets -> text, -r, --rawbits, JSON
+ *    (imet4iq.c:873-1315), byte-identical to the reference's stdout.
+ *
+ * Input above the IF rate the reference picks (48 / 32 / 96 / 64 kHz) goes through its decimating front end (decM > 1: IQ-dc removal and
+ * the mixer table at the input rate, the decimator low-pass, k_imet4_decim) first.  Not built (SONDE_E_ARG): --decFM, --noLUT, float32 input,
+ * rates whose filters do not fit the history rings (far above any sonde channel).
+ */
+#ifndef SONDE_IMET4_H
+#define SONDE_IMET4_H
+
+#include <stddef.h>
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define SONDE_IMET4_FRAME_BITS 1000      /* LEN_BITFRAME - 200: the frame is printed at this bit count, imet4iq.c:1586 */
+
+typedef struct {
+    int32_t sample_rate;     /* input rate (Hz)                                                                             */
+    int32_t bits;            /* 8 (unsigned) or 16 (signed) per sample component                                            */
+    int32_t iq;              /* 1: complex IQ (--iq fq), 0: FM audio (mono)                                                 */
+    int32_t lp_iq;           /* --lpIQ / --lpbw: IF low-pass                                                                */
+    int32_t lpbw_hz;         /* IF low-pass bandwidth; <= 0: the reference's default (16 kHz, 80 kHz with imet1)            */
+    int32_t lp_fm;           /* --lpFM: 6 kHz FM low-pass                                                                   */
+    int32_t dc;              /* --dc: AFC                                                                                   */
+    int32_t min;             /* --min: 32 kHz designated IF rate                                                            */
+    int32_t imet1;           /* --imet1: 96 kHz designated IF rate, 80 kHz IF low-pass                                      */
+    int32_t reserved[7];
+} sonde_imet4_cfg_t;
+
+typedef struct {
+    int32_t  channel;
+    int32_t  nbits;                            /* SONDE_IMET4_FRAME_BITS                                                    */
+    uint64_t sample;                           /* IF-rate sample index of the frame's last bit decision                     */
+    uint8_t  bits[SONDE_IMET4_FRAME_BITS];     /* 0 / 1; the first ten are the SOH character of the header                  */
+} sonde_imet4_frame_t;
+
+typedef struct sonde_imet4 sonde_imet4_t;
+
+/* fq[c] = --iq fq of channel c (ignored for FM audio); max_chunk = most input samples per channel in one process call (rounded down to a
+ * multiple of the decimation).
+ * Writes the IF rate and decimation the reference reports ("IF:", "dec:") to *if_rate / *dec_m when not NULL. */
+int  sonde_imet4_create(const sonde_imet4_cfg_t *cfg, int32_t n_channels, const double *fq, int32_t max_chunk,
+                        sonde_imet4_t **out, int32_t *if_rate, int32_t *dec_m);
+void sonde_imet4_destroy(sonde_imet4_t *e);
+/* n input samples per channel (a multiple of the decimation, SONDE_E_RANGE otherwise), channel-major: channel c's samples (IQ interleaved
+ * for iq = 1) start at c * n * (iq ? 2 : 1).  SONDE_E_OVERFLOW: the frame queue of this call overflowed (frames lost; reported once). */
+int  sonde_imet4_process_host(sonde_imet4_t *e, const void *samples, int32_t n);
+int  sonde_imet4_process_device(sonde_imet4_t *e, const void *dev_samples, int32_t n);
+/* completed frames in channel / time order; returns their number (<= max) or a SONDE_E_* code.  Frames not fetched stay queued.
+ * There is no finish / flush: a frame still in progress at the end of the input is never printed by the reference (imet4iq.c:1638), so
+ * nothing is handed out for it. */
+int  sonde_imet4_fetch_frames(sonde_imet4_t *e, sonde_imet4_frame_t *out, int32_t max);
+
+/* ------------------------------------------------------------------ printer (host code) */
+typedef struct sonde_imet4_printer sonde_imet4_printer_t;
+
+typedef struct {
+    int32_t raw;             /* -r                                                                                          */
+    int32_t rawbits;         /* --rawbits                                                                                   */
+    int32_t json;            /* --json                                                                                      */
+    int32_t jsn_freq_khz;    /* "freq" of the JSON when > 0                                                                 */
+    char    version[32];     /* "version" of the JSON; "" = omit                                                            */
+    int32_t reserved[4];
+} sonde_imet4_opts_t;
+
+int  sonde_imet4_printer_create(const sonde_imet4_opts_t *opts, sonde_imet4_printer_t **out);
+void sonde_imet4_printer_destroy(sonde_imet4_printer_t *p);
+/* one frame of nbits bits (print_frame(dsp, nbits / 10)): writes what the reference prints NUL-terminated into out; returns its length
+ * or a negative SONDE_E_* code */
+int  sonde_imet4_print_frame(sonde_imet4_printer_t *p, const uint8_t *bits, int32_t nbits, char *out, size_t outlen);
+/* CRC-16 of the packets (CCITT polynomial, initial value 0x1D0F) */
+int  sonde_imet4_crc16(const uint8_t *bytes, int32_t len);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

@@ -7,6 +7,7 @@
 //   design_decimator IF rate / decM / tap count                            demod_mod.c:1222-1259
 //   design_mixer     16-Hz-snapped mixer frequency + table period           demod_mod.c:1262-1296
 //   design_match     Gaussian-pulse header template, 2-norm                demod_mod.c:1190-1195,1398-1421
+//   design_imet4     imet4iq's IF rate / decM, IF tap sets, FM low-pass    imet4iq.c:600-646,692-741
 #include "sonde_host.h"
 #include <cmath>
 
@@ -186,6 +187,50 @@ void slice_range(uint32_t q0, uint32_t q1, double mid, float l, uint32_t &qa, ui
         if (fb < (double)qb) qb = (fb > 0.0) ? (uint32_t)fb : 0u;
     }
     if (qb < qa) qb = qa;
+}
+
+// imet4iq's variant of the front-end design: its own IF rate rule (48 kHz, 32 kHz with --min, doubled with --imet1; decM from the
+// same search as demod_mod; FM audio stays at its rate) and decimator taps, the IF low-pass as an acquisition set at 1.5x the bandwidth plus the nominal set (both of the nominal
+// set's odd tap count), and the 6 kHz FM low-pass with its own tap rule (halved above 100 kHz).
+Imet4Design design_imet4(int sr_base, bool iq, bool if_min, bool imet1, float lpiq_bw) {
+    Imet4Design d;
+    int if_sr = if_min ? 32000 : 48000;
+    if (imet1) if_sr *= 2;
+    d.decM = 1;
+    if (!iq) if_sr = sr_base;                 // FM audio: every filter at the input rate
+    if (if_sr > sr_base) if_sr = sr_base;
+    if (if_sr < sr_base) {
+        while (sr_base % if_sr) if_sr += 1;
+        d.decM = sr_base / if_sr;
+    }
+    if (d.decM > 1) {                         // the decimator's own design, imet4iq.c:618-635
+        float f_lp = (float)((if_sr + 20e3) / (4.0 * sr_base));
+        float t_bw = (float)(if_sr - 20e3);
+        if (imet1) { f_lp = (float)((if_sr + 80e3) / (4.0 * sr_base)); t_bw = (float)(if_sr - 80e3); }
+        if (if_min) {
+            t_bw = (float)(if_sr - 12e3);
+            if (imet1) { f_lp = (float)((if_sr + 60e3) / (4.0 * sr_base)); t_bw = (float)((if_sr - 60e3) / 2); }
+        }
+        if (t_bw < 0) t_bw = 10e3f;
+        t_bw /= sr_base;
+        int taps = (int)(4.0 / t_bw);
+        if (taps % 2 == 0) taps++;
+        d.lp_dec = design_lowpass(f_lp, taps);
+    }
+    d.if_sr = if_sr;
+    const int sr = if_sr;
+    const float f_lp = (float)(lpiq_bw / (float)sr / 2.0);
+    int taps = (int)(4 * sr / 4e3);
+    if (taps % 2 == 0) taps++;
+    d.lp_iq0 = design_lowpass((float)(1.5 * f_lp), taps);
+    d.lp_iq1 = design_lowpass(f_lp, (int)d.lp_iq0.size());
+    const float f_fm = 6e3f / (float)sr;
+    int tfm = (int)(4 * sr / 2e3);
+    if (tfm % 2 == 0) tfm++;
+    if (sr > 100e3) tfm = tfm / 2;
+    if (tfm % 2 == 0) tfm++;
+    d.lp_fm = design_lowpass(f_fm, tfm);
+    return d;
 }
 
 }  // namespace sonde

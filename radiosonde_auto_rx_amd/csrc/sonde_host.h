@@ -14,6 +14,8 @@ std::vector<float> design_lowpass(float f, int taps);
 Decimator design_decimator(int sr_base, bool if_min);
 Decimator design_decimator_scan(int sr_base, bool if_min, float set_lpIQ);
 Decimator design_decimator_if(int sr_base, int if_target, bool narrow);
+struct Imet4Design { int if_sr = 0, decM = 1; std::vector<float> lp_iq0, lp_iq1, lp_fm, lp_dec; };
+Imet4Design design_imet4(int sr_base, bool iq, bool if_min, bool imet1, float lpiq_bw);
 struct Mixer { double f0 = 0; int lut_len = 1; };
 Mixer design_mixer(double xlt_fq, int sr_base);
 std::vector<float> design_match(const std::string &hdr, float sps, float bt);

@@ -1,0 +1,134 @@
+"""ctypes mirror of include/sonde_imet4.h: the iMet-4 / iMet-1-RS engine (GPU, many channels per call) and its printer (host code).
+
+    eng = Imet4Engine(fqs, sr, bits=16, iq=True, lp_iq=True, dc=True)      # the auto_rx IMET form: --iq 0.0 --lpIQ --dc - 48000 16
+    eng.process_host(x)           # x: (n_channels, n * 2) int16 IQ (or (n_channels, n) for FM audio), n <= max_chunk, a multiple of dec_m
+    for f in eng.fetch_frames():  # {"channel", "sample", "bits"}
+        text = printer.frame(f["bits"])
+
+Imet4Printer(json=True).frame(bits) returns the characters the reference's imet4iq prints for that frame."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from .engine import SondeError, lib
+
+FRAME_BITS = 1000
+
+
+class Imet4Cfg(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("sample_rate", "bits", "iq", "lp_iq", "lpbw_hz", "lp_fm", "dc", "min", "imet1")] + \
+               [("reserved", C.c_int32 * 7)]
+
+
+class Imet4Frame(C.Structure):
+    _fields_ = [("channel", C.c_int32), ("nbits", C.c_int32), ("sample", C.c_uint64), ("bits", C.c_uint8 * FRAME_BITS)]
+
+
+class Imet4Opts(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("raw", "rawbits", "json", "jsn_freq_khz")] + [("version", C.c_char * 32), ("reserved", C.c_int32 * 4)]
+
+
+def _sigs(L):
+    if getattr(L, "_imet4_sigs", False):
+        return L
+    P = C.c_void_p
+    L.sonde_imet4_create.argtypes = [C.POINTER(Imet4Cfg), C.c_int32, C.POINTER(C.c_double), C.c_int32, C.POINTER(P),
+                                     C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    L.sonde_imet4_destroy.argtypes = [P]
+    L.sonde_imet4_destroy.restype = None
+    L.sonde_imet4_process_host.argtypes = [P, P, C.c_int32]
+    L.sonde_imet4_process_device.argtypes = [P, P, C.c_int32]
+    L.sonde_imet4_fetch_frames.argtypes = [P, C.POINTER(Imet4Frame), C.c_int32]
+    L.sonde_imet4_printer_create.argtypes = [C.POINTER(Imet4Opts), C.POINTER(P)]
+    L.sonde_imet4_printer_destroy.argtypes = [P]
+    L.sonde_imet4_printer_destroy.restype = None
+    L.sonde_imet4_print_frame.argtypes = [P, C.POINTER(C.c_uint8), C.c_int32, C.c_char_p, C.c_size_t]
+    L.sonde_imet4_crc16.argtypes = [C.POINTER(C.c_uint8), C.c_int32]
+    L._imet4_sigs = True
+    return L
+
+
+def crc16(data: bytes) -> int:
+    b = (C.c_uint8 * max(1, len(data))).from_buffer_copy(bytes(data) or b"\0")
+    return _sigs(lib()).sonde_imet4_crc16(b, len(data))
+
+
+class Imet4Printer:
+    """bits -> the reference's text / -r / --rawbits / JSON lines (host code, no GPU)."""
+
+    def __init__(self, *, raw: bool = False, rawbits: bool = False, json: bool = False, jsn_freq_khz: int = 0, version: str = ""):
+        self._L = _sigs(lib())
+        o = Imet4Opts(raw=int(raw), rawbits=int(rawbits), json=int(json), jsn_freq_khz=int(jsn_freq_khz), version=version.encode())
+        self._p = C.c_void_p()
+        rc = self._L.sonde_imet4_printer_create(C.byref(o), C.byref(self._p))
+        if rc:
+            raise SondeError(rc, "sonde_imet4_printer_create")
+        self._out = C.create_string_buffer(1 << 16)
+
+    def frame(self, bits) -> str:
+        b = np.ascontiguousarray(bits, dtype=np.uint8)
+        n = self._L.sonde_imet4_print_frame(self._p, b.ctypes.data_as(C.POINTER(C.c_uint8)), len(b), self._out, len(self._out))
+        if n < 0:
+            raise SondeError(n, "sonde_imet4_print_frame")
+        return self._out.raw[:n].decode("latin-1")
+
+    def close(self):
+        if self._p:
+            self._L.sonde_imet4_printer_destroy(self._p)
+            self._p = C.c_void_p()
+
+    __del__ = close
+
+
+class Imet4Engine:
+    """k_imet4_afsk behind sonde_imet4_create: one channel per entry of fqs (ignored for FM audio), all at sample rate sr."""
+
+    def __init__(self, fqs, sr: int, *, bits: int = 16, iq: bool = True, lp_iq: bool = True, lpbw_hz: int = 0, lp_fm: bool = False,
+                 dc: bool = True, min: bool = False, imet1: bool = False, max_chunk: int | None = None):
+        self._L = _sigs(lib())
+        self.n_ch = len(fqs)
+        self.iq, self.bits = bool(iq), bits
+        self.max_chunk = int(max_chunk or sr // 4)
+        cfg = Imet4Cfg(sample_rate=sr, bits=bits, iq=int(iq), lp_iq=int(lp_iq), lpbw_hz=int(lpbw_hz), lp_fm=int(lp_fm), dc=int(dc),
+                       min=int(min), imet1=int(imet1))
+        fq = (C.c_double * self.n_ch)(*[float(f) for f in fqs])
+        self._e = C.c_void_p()
+        ifr, dec = C.c_int32(), C.c_int32()
+        rc = self._L.sonde_imet4_create(C.byref(cfg), self.n_ch, fq, self.max_chunk, C.byref(self._e), C.byref(ifr), C.byref(dec))
+        self.if_rate, self.dec_m = ifr.value, dec.value
+        if rc:
+            raise SondeError(rc, "sonde_imet4_create")
+        self._buf = (Imet4Frame * 64)()
+
+    def process_host(self, x: np.ndarray):
+        dt = np.int16 if self.bits == 16 else np.uint8
+        x = np.ascontiguousarray(x, dtype=dt).reshape(self.n_ch, -1)
+        n = x.shape[1] // (2 if self.iq else 1)
+        rc = self._L.sonde_imet4_process_host(self._e, x.ctypes.data, n)
+        if rc:
+            raise SondeError(rc, "sonde_imet4_process_host")
+
+    def process_device(self, ptr: int, n: int):
+        rc = self._L.sonde_imet4_process_device(self._e, C.c_void_p(ptr), n)
+        if rc:
+            raise SondeError(rc, "sonde_imet4_process_device")
+
+    def fetch_frames(self) -> list[dict]:
+        out = []
+        while True:
+            k = self._L.sonde_imet4_fetch_frames(self._e, self._buf, len(self._buf))
+            if k < 0:
+                raise SondeError(k, "sonde_imet4_fetch_frames")
+            for f in self._buf[:k]:
+                out.append({"channel": f.channel, "sample": int(f.sample), "bits": np.frombuffer(bytes(f.bits), np.uint8)[:f.nbits].copy()})
+            if k < len(self._buf):
+                return out
+
+    def close(self):
+        if self._e:
+            self._L.sonde_imet4_destroy(self._e)
+            self._e = C.c_void_p()
+
+    __del__ = close

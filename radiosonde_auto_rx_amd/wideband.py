@@ -1,4 +1,4 @@
-"""One wideband IQ stream -> every RS41, DFM, M10, M20 (and LMS6, iMet-54, Meisei, MRZ, MTS01) in it, in one process on one GPU.
+"""One wideband IQ stream -> every RS41, DFM, M10, M20 (and LMS6, iMet-54, Meisei, MRZ, MTS01, iMet-4 / iMet-1-RS) in it, in one process on one GPU.
 
 The reference handles a wideband source by starting one detector process per candidate peak (auto_rx/autorx/scan.py:413-656:
 rtl_power peaks -> `dft_detect` per peak) and then one decoder pipeline per sonde (decode.py).  Here the same two steps run
@@ -20,7 +20,11 @@ import numpy as np
 from .engine import Engine, snap_fq
 from .scan import Scanner
 from .family import FAMILY, LMS_BASE, FamilyDecoder
+from .imet4 import Imet4Engine, Imet4Printer
 from .telemetry import DfmTelemetry, M10Telemetry, M20Telemetry, Rs41Telemetry
+
+
+IMET_AFSK = ("IMET4", "IMET1RS")          # dft_detect's IMETafsk outcomes (sonde_scan.cpp): decoded by imet4.py
 
 
 class WidebandReceiver:
@@ -51,7 +55,10 @@ class WidebandReceiver:
                 return
         fq = snap_fq(fq, self.sr)
         khz = int(round((self.cfreq + fq * self.sr) / 1000.0)) if self.cfreq else 0
-        if typ in FAMILY:                                      # generic sonde description + the type's bit-rate tier (family.py)
+        if typ in IMET_AFSK:                                   # imet4iq --iq fq --lpIQ --dc (--imet1: 96 kHz IF), as auto_rx starts it
+            eng = Imet4Engine([fq], self.sr, bits=16, iq=True, lp_iq=True, dc=True, imet1=(typ == "IMET1RS"), max_chunk=self.chunk)
+            tel = Imet4Printer(json=True, jsn_freq_khz=khz, version=self.version)
+        elif typ in FAMILY:                                    # generic sonde description + the type's bit-rate tier (family.py)
             eng = self._family_engine(typ, fq)
             tel = FamilyDecoder(typ, freq_khz=khz, version=self.version)
         elif typ == "DFM":
@@ -99,6 +106,8 @@ class WidebandReceiver:
                     self._start(self.raster[d["channel"]] + d["df"], "DFM")
                 elif d["type"] in ("M10", "M20"):                           # differential code: polarity does not matter
                     self._start(self.raster[d["channel"]] + d["df"], d["type"])
+                elif d["type"] in IMET_AFSK:                                # the scanner's AFSK check decided the variant
+                    self._start(self.raster[d["channel"]] + d["df"], d["type"])
                 elif d["type"] in FAMILY and (d["score"] > 0 or FAMILY[d["type"]]["auto"]):
                     self._start(self.raster[d["channel"]] + d["df"], d["type"])
             self.t += (len(x) // 2) / self.sr
@@ -123,6 +132,14 @@ class WidebandReceiver:
     @staticmethod
     def _drain(s, finish):
         e = s["engine"]
+        if s["type"] in IMET_AFSK:                           # a frame in progress at the end prints nothing (imet4iq.c:1638)
+            out = []
+            for f in e.fetch_frames():
+                s["frames"] += 1
+                js = [json.loads(line) for line in s["telemetry"].frame(f["bits"]).split("\n") if line.startswith("{")]
+                s["good"] = s.get("good", 0) + (1 if js else 0)
+                out += js
+            return out
         if s["type"] in FAMILY:
             out = []
             for h in e.fetch_hits(finish=finish):

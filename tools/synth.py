@@ -692,6 +692,90 @@ def imet_capture(sr: int = 48_000, seconds: float = 3.0, *, f_offset_hz: float =
     return out
 
 
+def imet4_crc16(data) -> int:
+    """CRC-16/CCITT with initial value 0x1D0F, MSB first (the iMet-1-RS packet check, imet4iq.c:911-928)."""
+    rem = 0x1D0F
+    for b in bytes(data):
+        rem ^= b << 8
+        for _ in range(8):
+            rem = ((rem << 1) ^ 0x1021) if rem & 0x8000 else (rem << 1)
+            rem &= 0xFFFF
+    return rem
+
+
+def _imet4_seal(pkt: bytearray, corrupt: bool = False) -> bytes:
+    crc = imet4_crc16(pkt) ^ (0x0100 if corrupt else 0)
+    return bytes(pkt) + bytes([crc >> 8, crc & 0xFF])            # CRC stored big-endian
+
+
+def imet4_packets(k: int, *, imet1: bool = False, egps: bool = False, xdata=(), corrupt: bool = False,
+                  lat=39.765432, lon=-105.012345, alt_m=1234) -> bytes:
+    """The packets of iMet frame k (iMet-1-RS data protocol, imet4iq.c:946-1141): GPS (0x02) or eGPS (0x05, CRC at its own offset 28),
+    then ePTU (0x04; PTU 0x01 with imet1), then XDATA (0x03) packets: xdata = list of payload byte strings (N = len)."""
+    import struct
+    sec = 3600 * 12 + 60 * 34 + k
+    hh, mm, ss = (sec // 3600) % 24, (sec // 60) % 60, sec % 60
+    g = bytearray([0x01, 0x05 if egps else 0x02]) + struct.pack("<ffHB", lat + 1e-4 * k, lon - 2e-4 * k, alt_m + 5 * k + 5000, 9)
+    if egps:
+        g += struct.pack("<fff", 3.5, -4.25, 5.0 + 0.1 * k)
+    g += bytes([hh, mm, ss])
+    pnum = 100 + k
+    P = 85432 - 13 * k                                    # 854.32 hPa
+    T = (-1234 - 7 * k) & 0xFFFF                          # -12.34 C
+    U = 4567 + k
+    p = bytearray([0x01, 0x01 if imet1 else 0x04]) + struct.pack("<H", pnum) + bytes([P & 0xFF, (P >> 8) & 0xFF, P >> 16]) \
+        + struct.pack("<HHB", T, U, 59)
+    if not imet1:
+        p += struct.pack("<hhh", 2150, -3050, -1875)
+    out = _imet4_seal(g, corrupt) + _imet4_seal(p)
+    for x in xdata:
+        out += _imet4_seal(bytearray([0x01, 0x03, len(x)]) + bytes(x))
+    return out
+
+
+def imet4_bits(payload: bytes) -> np.ndarray:
+    """8N1, LSB first: start bit 0, eight data bits, stop bit 1 per byte."""
+    b = np.frombuffer(bytes(payload), np.uint8)
+    data = (b[:, None] >> np.arange(8)[None, :]) & 1
+    return np.concatenate([np.zeros((len(b), 1), np.int64), data, np.ones((len(b), 1), np.int64)], axis=1).ravel()
+
+
+def imet4_capture(sr: int = 48_000, seconds: float = 6.0, fq: float = 0.0, *, f_offset_hz: float = 0.0, imet1: bool = False,
+                  dev_hz: float = 4000.0, amp: float = 0.5, noise_sigma: float = 0.01, seed: int = 1, t_first: float = 0.35,
+                  egps=(), xdata=None, corrupt=(), audio: bool = False, audio_dc: float = 0.0) -> np.ndarray:
+    """iMet-4 (one frame/s) or iMet-1-RS (imet1: two frames/s, plain PTU) capture: real packets with CRC-16 (frames listed in `corrupt`
+    get a wrong GPS CRC, frames in `egps` carry an eGPS packet), 8N1 at 1200 Bd between idle marks, continuous-phase Bell 202 audio
+    (mark 1200 Hz, space 2200 Hz) frequency-modulating a carrier at fq * sr + f_offset_hz with peak deviation dev_hz.
+    Interleaved complex int16; with audio=True the FM-audio form instead: mono int16 of the Bell 202 tone (+ audio_dc) and noise.
+    xdata(k) -> list of XDATA payloads of frame k."""
+    rng = np.random.default_rng(seed)
+    n = int(round(sr * seconds))
+    nb = int(seconds * 1200) + 1
+    bits = np.ones(nb, np.int64)                                  # idle: mark
+    per = 600 if imet1 else 1200
+    k = 0
+    while True:
+        b0 = int(round(t_first * 1200)) + k * per
+        pk = imet4_packets(k, imet1=imet1, egps=k in egps, xdata=(xdata(k) if xdata else ()), corrupt=k in corrupt)
+        fb = imet4_bits(pk)
+        if b0 + len(fb) + 20 > nb:
+            break
+        bits[b0:b0 + len(fb)] = fb
+        k += 1
+    idx = np.minimum((np.arange(n) * 1200) // sr, nb - 1)
+    tone = np.where(bits[idx] == 1, 1200.0, 2200.0)
+    a = np.sin(2 * np.pi * np.cumsum(tone) / sr)
+    if audio:
+        s = 0.35 * a + audio_dc + noise_sigma * rng.standard_normal(n)
+        return np.clip(np.round(s * 32767), -32768, 32767).astype(np.int16)
+    phase = 2 * np.pi * np.cumsum(dev_hz * a + f_offset_hz + fq * sr) / sr
+    x = amp * np.exp(1j * phase) + noise_sigma * (rng.standard_normal(n) + 1j * rng.standard_normal(n))
+    out = np.empty(2 * n, dtype=np.int16)
+    out[0::2] = np.clip(np.round(x.real * 32767 * 0.9), -32768, 32767).astype(np.int16)
+    out[1::2] = np.clip(np.round(x.imag * 32767 * 0.9), -32768, 32767).astype(np.int16)
+    return out
+
+
 def mfsk_capture(bits: np.ndarray, sr: int, baud: int, M: int = 2, *, f_low: float = 1500.0, shift: float = 400.0, amp: float = 0.4,
                  noise_sigma: float = 0.02, seed: int = 1) -> np.ndarray:
     """Continuous-phase M-FSK (M = 2 or 4) as interleaved complex int16: symbol m = tone f_low + m * shift, MSB first for 4-FSK
