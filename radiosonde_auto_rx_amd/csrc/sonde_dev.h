@@ -144,10 +144,7 @@ struct WinFftArgs {
     int n_ch, stride, W, K, L, ring_len;
     const uint32_t *work, *work_count; int round_parity;
     unsigned long long *prof; // SONDE_WF_PROF: cycles per phase of workgroup 0 (nullptr = off)
-    int small_wg;             // the half-array form of the transform (39 KB of LDS, 256 threads): fits the slot of one decimator workgroup
-    float2 *park;             // small_wg: [SONDE_WFH_MAXGRID][8192] per-workgroup parking array in global memory (L2-resident): the half that waits
 };
-#define SONDE_WFH_MAXGRID 768
 
 struct CorrArgs {
     const float *bufs; float *corr; const float *match;
@@ -182,7 +179,6 @@ struct SyncArgs {
     float sps, thres, l_win;
     int rs41;                 // RS41 byte framing + syndromes on the device; else packed hard bits + soft bits
     int ecc_level;            // rs41: 1 / 2 = rs41_ecc() of whole frames on the device (--ecc / --ecc2); 0 = first-pass syndromes only
-    int small_wg;             // 256-thread workgroups (fit the slot one decimator workgroup frees) instead of 1024
     uint32_t *ecc_list; unsigned *ecc_count;       // work list of k_rs41_ecc_frames (record slots), nullptr = none (damaged frames are decoded by the host)
     int eof;                  // end of stream: emit the frame in progress with the bits that exist
     int eof_ch;               // with eof: only this channel (-1 = all)

@@ -101,8 +101,6 @@ struct sonde_engine {
     std::vector<char> m10_bits;                    // M10: gpx.frame_bits per channel (persists between frames like the reference's)   // [n_ch][518] gpx.frame of the reference persists across frames
     bool overflow = false;
     bool in_call = false, ecc_listed = false;   // inside sonde_engine_process_device; a frame sync of this call was given a work list
-    float2 *d_park = nullptr;          // parking arrays of k_sync_window_fft_h
-    bool small_tail = false;           // header search and frame sync in workgroups that fit the slot of one decimator workgroup (two-stream engines)
     bool dev_ecc = true;               // rs41_ecc() of whole frames in k_framesync (SONDE_HOST_ECC=1: on the host from the device syndromes, the A/B switch)
     long long host_ecc_frames = 0;     // frames whose RS decoder ran on the host (fetch_rs41)
     bool m10_chk3 = false;                         // m10mod --chk3 (sonde_engine_set_m10_chk3)
@@ -461,15 +459,12 @@ static int create_impl(const sonde_cfg_t *cfg, const double *fq, const sonde_gen
     }
     // ---- 2.4 Msps -> 48 kHz class (D = 50, Q = 7, float table phase, rows aligned with the mixer table): the hand-scheduled
     // decimator, which subtracts the IQ-DC mean per output as avg * E — E tabulated here, once (k_md_etable)
-    {
-        static const bool no_fast = getenv("SONDE_MD_NOFAST") != nullptr;       // A/B aid: the compiler-scheduled kernels
-        if (D == 50 && e->Q == 7 && !audio && cfg->bits != 32 && cfg->sonde_type != SONDE_FRONTEND && !cfg->opt_nolut && e->lut_len % D == 0 && !no_fast
-            && cfg->input == SONDE_IN_IQ && !is_group) {
-            e->etab_len = e->lut_len / D;
-            if (dalloc(&e->d_etab, (size_t)C * e->etab_len, false) || dalloc(&e->d_dcavg_prev, C)) { sonde_engine_destroy(e); return SONDE_E_NOMEM; }
-            sonde_launch_md_etable(e->d_chanf0, e->d_wtab, D, e->Q, e->etab_len, C, e->d_etab, nullptr);
-            HIPCHK(hipDeviceSynchronize());
-        }
+    if (D == 50 && e->Q == 7 && !audio && cfg->bits != 32 && cfg->sonde_type != SONDE_FRONTEND && !cfg->opt_nolut && e->lut_len % D == 0
+        && cfg->input == SONDE_IN_IQ && !is_group) {
+        e->etab_len = e->lut_len / D;
+        if (dalloc(&e->d_etab, (size_t)C * e->etab_len, false) || dalloc(&e->d_dcavg_prev, C)) { sonde_engine_destroy(e); return SONDE_E_NOMEM; }
+        sonde_launch_md_etable(e->d_chanf0, e->d_wtab, D, e->Q, e->etab_len, C, e->d_etab, nullptr);
+        HIPCHK(hipDeviceSynchronize());
     }
     int bad = 0;
     bad |= dalloc(&e->d_dcavg, C); bad |= dalloc(&e->d_dcsums, 2 * (size_t)C);
@@ -489,15 +484,8 @@ static int create_impl(const sonde_cfg_t *cfg, const double *fq, const sonde_gen
     if (bad) { sonde_engine_destroy(e); return SONDE_E_NOMEM; }
     HIPCHK(hipMemcpy(e->d_match, e->match.data(), L * sizeof(float), hipMemcpyHostToDevice));
     e->dev_ecc = getenv("SONDE_HOST_ECC") == nullptr;
-    {   // SONDE_SMALL_TAIL=1: header search and frame sync in workgroups of the size of one decimator workgroup (k_sync_window_fft_h, k_framesync<.., 256>).
-        // With them the whole IF-rate tail does run beside the next call's decimator — and the decimator slows down by as much as the tail takes
-        // (profiles/r4k_*: 1.35 ms per step either way), so the plain forms stay the default; kept as the measurement's other arm, parity-tested
-        const char *st = getenv("SONDE_SMALL_TAIL");
-        e->small_tail = st && atoi(st) != 0;
-    }
     {   // Fm = rdft(time-reversed match) with the reference's transform (init_buffers, demod_mod.c:1446-1449); N = 8192 only
-        static const bool no_fft = getenv("SONDE_NO_FFTSYNC") != nullptr;        // A/B aid: time-domain correlation ring
-        if (!cfg->opt_dc && M == 8192 && K + L <= M && !no_fft) {
+        if (!cfg->opt_dc && M == 8192 && K + L <= M) {
             std::vector<float> m(2 * (size_t)M, 0.f);
             for (int i = 0; i < L; i++) m[2 * (size_t)(L - 1 - i)] = e->match[i];
             ref_dft_8192(m);
@@ -617,8 +605,7 @@ static int create_impl(const sonde_cfg_t *cfg, const double *fq, const sonde_gen
         // the IF-rate tail of call k runs beside the decimator of call k+1: few, latency-bound workgroups against thousands of bandwidth-bound
         // ones — B gets the higher dispatch priority so that its workgroups take the next free CU slot instead of queueing behind the decimator's
         int lo = 0, hi = 0;
-        const char *pr = getenv("SONDE_B_PRIO");                    // A/B aid: 0 = default priority, 1 (default) = highest
-        if ((!pr || atoi(pr) != 0) && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && hi != lo)
+        if (hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && hi != lo)
             HIPCHK(hipStreamCreateWithPriority(&e->stream_b, hipStreamNonBlocking, hi));
         else HIPCHK(hipStreamCreateWithFlags(&e->stream_b, hipStreamNonBlocking));
     }
@@ -682,7 +669,7 @@ void sonde_engine_destroy(sonde_engine_t *e) {
     if (e->stream_e) hipStreamDestroy(e->stream_e);
     if (e->ev_s) hipEventDestroy(e->ev_s);
     hipFree(e->d_dfm_out); hipFree(e->d_m10_out); hipFree(e->d_blk_done); hipFree(e->d_m10_bits);
-    hipFree(e->d_ecc_list); hipFree(e->d_ecc_cnt); hipFree(e->d_park);
+    hipFree(e->d_ecc_list); hipFree(e->d_ecc_cnt);
     for (int i = 0; i < 4; i++) { if (e->ev_a[i]) hipEventDestroy(e->ev_a[i]); if (e->ev_b[i]) hipEventDestroy(e->ev_b[i]); if (e->ev_if[i]) hipEventDestroy(e->ev_if[i]); }
     if (e->ev_copy) hipEventDestroy(e->ev_copy);
     if (e->h_pending) hipHostFree(e->h_pending);
@@ -728,8 +715,7 @@ static void tail_begin(sonde_engine *t, hipStream_t fs) {
     // two streams: this call's decimator overwrites the part of the y ring that call-2 occupied (ring_len >= 2 * max_if + history), so it must
     // not start before the IF chain of call-2 has read it.  Only the IF chain reads y: the header search and the frame sync behind it work on
     // rings stream B writes itself, so however late they run (they wait for CU slots the decimator frees) the decimators stay back to back.
-    static const bool wait_tail = getenv("SONDE_A_WAITS_TAIL") != nullptr;       // A/B aid: the round-3 dependency on the whole tail of call-2
-    if (t->stream_b != fs && t->call >= 2) hipStreamWaitEvent(fs, wait_tail ? t->ev_b[(t->call - 2) & 3] : t->ev_if[(t->call - 2) & 3], 0);
+    if (t->stream_b != fs && t->call >= 2) hipStreamWaitEvent(fs, t->ev_if[(t->call - 2) & 3], 0);
 }
 static int tail_enqueue(sonde_engine *e, int32_t n_samples, uint32_t m_first, hipStream_t fs, hipEvent_t front_done);
 static int tail_enqueue_merged(sonde_engine *e, int32_t n_samples, uint32_t m_first);
@@ -953,8 +939,7 @@ static int tail_enqueue(sonde_engine *e, int32_t n_samples, uint32_t m_first, hi
         } else if (!fe) {
             // two passes (corr_tile_unused in sonde_kernels.hip): correlate what two search windows can reach, sync up to there, then the
             // rest with the state that is known by then — nothing at all for a channel whose new frame covers the rest of the call
-            static const bool one_pass = getenv("SONDE_CORR_ONEPASS") != nullptr;         // A/B aid
-            const uint32_t lim = (!one_pass && n_if > 3 * e->info.K) ? (uint32_t)(2 * e->info.K + 64) : 0u;
+            const uint32_t lim = (n_if > 3 * e->info.K) ? (uint32_t)(2 * e->info.K + 64) : 0u;
             if (lim) {
                 c.limit = lim; e->corr_limit = lim;
                 prof_begin(e, "header_corr", e->stream_b); sonde_launch_header_corr(&c, e->stream_b); prof_end(e, e->stream_b);
@@ -1043,8 +1028,7 @@ static void fill_round(sonde_engine *e, int W, WinPlanArgs &p, WinFftArgs &f) {
     p.work = e->d_work; p.work_count = e->d_work_count; p.round_parity = e->sync_rounds & 1;
     f = WinFftArgs{}; f.bufs = e->d_bufs; f.items = e->d_win; f.Fm = e->d_Fm; f.tws = e->d_tws; f.n_ch = C; f.stride = e->win_W; f.W = W;
     f.K = e->info.K; f.L = e->info.L; f.ring_len = e->ring_len;
-    f.work = e->d_work; f.work_count = e->d_work_count; f.round_parity = e->sync_rounds & 1; f.small_wg = e->small_tail; f.park = e->d_park;
-    if (f.small_wg && !e->d_park) { if (hipMalloc((void **)&e->d_park, (size_t)SONDE_WFH_MAXGRID * 8192 * sizeof(float2)) != hipSuccess) f.small_wg = 0; f.park = e->d_park; }
+    f.work = e->d_work; f.work_count = e->d_work_count; f.round_parity = e->sync_rounds & 1;
     static const bool want_prof = getenv("SONDE_WF_PROF") != nullptr;          // profiling aid: cycles per phase of workgroup 0, printed when the engine is destroyed
     if (want_prof && !e->d_wfprof) { if (hipMalloc((void **)&e->d_wfprof, 32 * sizeof(unsigned long long)) == hipSuccess) hipMemset(e->d_wfprof, 0, 32 * sizeof(unsigned long long)); }
     f.prof = e->d_wfprof;
@@ -1071,7 +1055,6 @@ static SyncArgs fill_sync(sonde_engine *e, int eof) {
     s.bufs = e->d_bufs; s.corr = e->d_corr; s.state = e->d_state; s.frames = e->d_frames; s.frame_count = e->d_fcount; s.soft = e->d_soft; s.soft1 = e->d_soft1;
     s.hdr = e->d_consts; s.hdr_bytes = e->d_consts + 64; s.mask = e->d_consts + 72; s.gf_exp = e->d_consts + 136; s.gf_log = e->d_consts + 648;
     s.bitwin = e->d_bitwin; s.bitend = e->d_bitend;
-    s.small_wg = e->small_tail && !e->cfg.opt_dc;
     s.n_ch = C; s.ring_len = e->ring_len; s.max_frames = e->max_frames; s.avail = e->m_out;
     s.K = e->info.K; s.L = e->info.L; s.delay = e->info.delay; s.hdrlen = e->hdrlen; s.symhd = e->symhd; s.symlen = e->symlen;
     s.hdmax = e->hdmax; s.bitofs = e->bitofs; s.nbits = e->nbits; s.frame_samples = e->frame_samples;
@@ -1604,11 +1587,10 @@ int sonde_engine_create_mixed(const sonde_cfg_t *cfg, const double *fq, const so
         if (t != SONDE_RS41 && t != SONDE_DFM09 && t != SONDE_M10 && t != SONDE_M20) return SONDE_E_ARG;
     }
     // One stream B for all groups when their IF-rate stages share launches (k_*_multi: one IF chain, one plan / window transform / frame sync per round over all rows) —
-    // the default for up to SONDE_MAX_GROUPS groups; SONDE_MIXED_SPLIT=1: every group enqueues its own kernels on its own stream B (the A/B arm)
-    static const bool split = getenv("SONDE_MIXED_SPLIT") != nullptr;
+    // up to SONDE_MAX_GROUPS groups; beyond that every group enqueues its own kernels on its own stream B
     int n_used = 0;
     for (int g = 0; g < n_groups; g++) n_used += ch_of[(size_t)g].empty() ? 0 : 1;
-    const bool merged = !split && n_used <= SONDE_MAX_GROUPS;
+    const bool merged = n_used <= SONDE_MAX_GROUPS;
     hipStream_t shared_b = nullptr;
     if (merged) {
         int lo = 0, hi = 0;
@@ -1655,7 +1637,7 @@ int sonde_engine_create_mixed(const sonde_cfg_t *cfg, const double *fq, const so
     const int rc = create_impl(&cf, f_rows.data(), nullptr, &lf, &e);
     if (rc) { drop(); if (shared_b) hipStreamDestroy(shared_b); return rc; }
     e->cfg.sonde_type = SONDE_MIXED; e->merged = merged;
-    for (sonde_engine *g : parts) if (merged && (!g->d_win || g->small_tail)) e->merged = false;      // (every group must be on the window-transform search, plain forms)
+    for (sonde_engine *g : parts) if (merged && !g->d_win) e->merged = false;      // (every group must be on the window-transform search)
     e->groups = parts; e->ch_of_grp.resize(parts.size());
     e->grp_of_ch.assign((size_t)C, 0); e->row_of_ch.assign((size_t)C, 0);
     int row = 0;

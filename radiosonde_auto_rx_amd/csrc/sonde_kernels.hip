@@ -242,7 +242,7 @@ __device__ __forceinline__ float2v md_dc_boundary(const MixDecArgs &a, int ch, d
 
 // ------------------------------------------------------------------------------------------------
 // k_mix_decimate50: the 2.4 Msps -> 48 kHz decimator (D = 50, Q = 7, float table phase) with everything around the sample
-// loop arranged for the memory system.  Measured on the plain kernel (tools/ab_variants.sh, empty sample loop): with ONE tile
+// loop arranged for the memory system.  Measured on the plain kernel (empty sample loop, profiles/r3_md_variants.txt): with ONE tile
 // (12.8 KB) per wave in flight, 12 waves per CU, the launch takes 0.9 ms without any arithmetic — 154 KB per CU in flight
 // against a loaded HBM latency of ~7 us caps the stream at 5.3 TB/s (a pure read of the same bytes in the same pattern:
 // 6.3 TB/s, 6.8 with non-temporal loads; tools/probes/read_bw.hip).  So here
@@ -252,7 +252,7 @@ __device__ __forceinline__ float2v md_dc_boundary(const MixDecArgs &a, int ch, d
 //     forms the diagonal sum delivers both this tile's terms and the next tile's carry) instead of a copy of all P rows;
 //   * the IQ-DC mean is subtracted per output (avg * E, see md_fast_tile); the 2^-15 of the int16 scale sits in the tap table.
 // That only fits 3 waves per SIMD (168 VGPRs) with every register placed by hand, so a wave's whole run of full tiles is ONE
-// generated statement (MD50_LOOP_*, tools/gen_md_fast.py); C++ does the set-up, a tile that sticks out of the chunk, the P tail
+// generated statement (MD50_LOOP_1, tools/gen_md_fast.py); C++ does the set-up, a tile that sticks out of the chunk, the P tail
 // and the IQ-DC sums.  Requires nblocks even (every 16-byte piece of a tile is then either inside or outside the chunk) and
 // >= 64, and rows aligned with the mixer table (lut_len % 50 == 0, lut_phase % 50 == 0: no row wraps around the table end).
 // ------------------------------------------------------------------------------------------------
@@ -271,7 +271,6 @@ __device__ __forceinline__ float2v md_dc_boundary(const MixDecArgs &a, int ch, d
           [etab] "s"(etab), [nfull] "s"(nfull), [outmask] "s"(outmask) \
         : MD50_CLOBBERS)
 
-template <int VAR>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3)))
 void k_mix_decimate50(const MixDecArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint32_t smem_u[];
@@ -325,20 +324,7 @@ void k_mix_decimate50(const MixDecArgs a) {
         const uint32_t *tb = iq + (size_t)jt0 * D;
         const uint32_t jm = a.m0 + (uint32_t)jt0;
         const uint64_t outmask = (seg == 0) ? ~0ull : ~0ull << H;           // the H halo rows of a later segment produce no output
-        if constexpr (VAR == 1) { MD50_ASM(MD50_LOOP_1); }
-        // timing experiments (tools/ab_variants.sh; streams from `gen_md_fast.py --experiments ...`): results may be garbage
-#ifdef MD50_LOOP_2
-        if constexpr (VAR == 2) { MD50_ASM(MD50_LOOP_2); }
-#endif
-#ifdef MD50_LOOP_3
-        if constexpr (VAR == 3) { MD50_ASM(MD50_LOOP_3); }
-#endif
-#ifdef MD50_LOOP_4
-        if constexpr (VAR == 4) { MD50_ASM(MD50_LOOP_4); }
-#endif
-#ifdef MD50_LOOP_5
-        if constexpr (VAR == 5) { MD50_ASM(MD50_LOOP_5); }
-#endif
+        MD50_ASM(MD50_LOOP_1);
         const int j = jt0 + (nfull - 1) * MD_ROWS + lane;      // rows of the last tile walked above
         if (j >= a.nblocks - H && j < a.nblocks) {             // P rows of the last Q-1 blocks go to the next call
 #pragma unroll
@@ -1705,22 +1691,21 @@ __device__ __forceinline__ double window_sum(const float *bufs, uint32_t base, u
     return sum;
 }
 
-#define FS_THREADS 1024           // default workgroup of k_framesync; FS_THREADS_SMALL = the form that fits the slot of one decimator workgroup
-#define FS_THREADS_SMALL 256
+#define FS_THREADS 1024           // workgroup of k_framesync
 
 // One correlation window of getCorrDFT (demod_mod.c:148-225) evaluated from the precomputed correlation ring: arg-max of
 // c^2 over the K+1 end positions p = pos-K .. pos (first maximum wins), edge rejection, L-sample norm.
 // DC (--dc, :174-188): the reference zeroes bin 0 of the zero-padded N-point transform, i.e. subtracts mu = sum(window)/N
 // from every sample including the padding; the circular correlation then drops by mu * sum(match) at every lag and
 // the norm runs over (x - mu).  Returns the peak index 0..K, or -4 (edge / empty window); mv, mpos only when >= 0.
-template <bool DC, int NT>
+template <bool DC>
 __device__ __forceinline__ int fs_window(const float *x, const float *corr, uint32_t mask, uint32_t pos, int K, int L, int N,
                                          float match_sum, int tid, int lane, int wave, float *s_rf, int *s_ri,
                                          float &mv, uint32_t &mpos) {
     float mu = 0.f;
     if (DC) {
         float s = 0.f;
-        for (int t = tid; t < K + L; t += NT) {
+        for (int t = tid; t < K + L; t += FS_THREADS) {
             const int64_t p = (int64_t)pos - (K + L - 1) + t;
             if (p >= 0) s += x[(uint32_t)p & mask];
         }
@@ -1728,7 +1713,7 @@ __device__ __forceinline__ int fs_window(const float *x, const float *corr, uint
         if (lane == 0) s_rf[wave] = s;
         __syncthreads();
         s = 0.f;
-        for (int w = 0; w < (NT / WAVE); w++) s += s_rf[w];
+        for (int w = 0; w < (FS_THREADS / WAVE); w++) s += s_rf[w];
         __syncthreads();
         mu = s / (float)N;
     }
@@ -1738,7 +1723,7 @@ __device__ __forceinline__ int fs_window(const float *x, const float *corr, uint
         float cv[8];
 #pragma unroll
         for (int u = 0; u < 8; u++) {
-            const int t = tid + u * NT;
+            const int t = tid + u * FS_THREADS;
             const int64_t p = (int64_t)pos - K + t;
             cv[u] = (t <= K && p >= 0) ? corr[(uint32_t)p & mask] : 0.f;
             if (DC) cv[u] = (t <= K) ? cv[u] - off : 0.f;
@@ -1746,9 +1731,9 @@ __device__ __forceinline__ int fs_window(const float *x, const float *corr, uint
 #pragma unroll
         for (int u = 0; u < 8; u++) {
             const float c2 = cv[u] * cv[u];
-            if (c2 > best) { best = c2; bidx = tid + u * NT; }
+            if (c2 > best) { best = c2; bidx = tid + u * FS_THREADS; }
         }
-        for (int t = tid + 8 * NT; t <= K; t += NT) {      // K > 8191 only
+        for (int t = tid + 8 * FS_THREADS; t <= K; t += FS_THREADS) {      // K > 8191 only
             const int64_t p = (int64_t)pos - K + t;
             float c = (p >= 0) ? corr[(uint32_t)p & mask] : 0.f;
             if (DC) c -= off;
@@ -1762,7 +1747,7 @@ __device__ __forceinline__ int fs_window(const float *x, const float *corr, uint
     if (lane == 0) { s_rf[wave] = best; s_ri[wave] = bidx; }
     __syncthreads();
     best = 0.f; bidx = -1;
-    for (int w = 0; w < (NT / WAVE); w++) {
+    for (int w = 0; w < (FS_THREADS / WAVE); w++) {
         const float ob = s_rf[w]; const int oi = s_ri[w];
         if (ob > best || (ob == best && oi >= 0 && (bidx < 0 || oi < bidx))) { best = ob; bidx = oi; }
     }
@@ -1771,7 +1756,7 @@ __device__ __forceinline__ int fs_window(const float *x, const float *corr, uint
     if (bidx == 0 || bidx == K) return -4;                         // edge value -> -4 (mv stays 0)
     mpos = pos - (uint32_t)K + (uint32_t)bidx;
     float e = 0.f;
-    for (int t = tid; t < L; t += NT) {
+    for (int t = tid; t < L; t += FS_THREADS) {
         const int64_t p = (int64_t)mpos - t;
         float v = (p >= 0) ? x[(uint32_t)p & mask] : 0.f;
         if (DC) v -= mu;
@@ -1781,7 +1766,7 @@ __device__ __forceinline__ int fs_window(const float *x, const float *corr, uint
     if (lane == 0) s_rf[wave] = e;
     __syncthreads();
     e = 0.f;
-    for (int w = 0; w < (NT / WAVE); w++) e += s_rf[w];
+    for (int w = 0; w < (FS_THREADS / WAVE); w++) e += s_rf[w];
     __syncthreads();
     float c = corr[mpos & mask];
     if (DC) c -= off;
@@ -1793,18 +1778,18 @@ __device__ __forceinline__ int fs_window(const float *x, const float *corr, uint
 // decisions depend only on workgroup-uniform values); the data-parallel parts — window arg-max (K+1 candidates),
 // L-sample energy, header bit check, the nbits soft bits, RS syndromes — are spread over the 1024 threads so that
 // each phase costs about one memory round trip instead of a chain of them.
-template <bool DC, int NT>
+template <bool DC>
 __device__ __forceinline__ void framesync_body(const SyncArgs &a, const int ch) {
     __shared__ uint8_t s_frame[520];
     __shared__ uint8_t s_exp[512];
     __shared__ uint8_t s_log[256];
-    __shared__ float s_rf[(NT / WAVE)];
-    __shared__ int s_ri[(NT / WAVE)];
+    __shared__ float s_rf[(FS_THREADS / WAVE)];
+    __shared__ int s_ri[(FS_THREADS / WAVE)];
     __shared__ int s_cnt[2];
     __shared__ unsigned s_slot;
-    __shared__ uint8_t s_syn[(NT / WAVE)][48];
+    __shared__ uint8_t s_syn[(FS_THREADS / WAVE)][48];
     __shared__ uint8_t s_S[48];                // first-pass syndromes of the frame in hand
-    __shared__ double s_rd[(NT / WAVE)];
+    __shared__ double s_rd[(FS_THREADS / WAVE)];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (ch >= a.n_ch) return;
     const uint32_t mask = (uint32_t)a.ring_len - 1;
@@ -1821,8 +1806,8 @@ __device__ __forceinline__ void framesync_body(const SyncArgs &a, const int ch) 
     // profiling aid (SONDE_WF_PROF): thread 0 of channel 0 adds the shader-clock cycles since the previous mark to phase k
 #define FS_MARK(k) do { if (a.prof && ch == 0 && tid == 0) { const unsigned long long t_ = __builtin_readcyclecounter(); a.prof[k] += t_ - t_prev; t_prev = t_; } } while (0)
     unsigned long long t_prev = a.prof ? __builtin_readcyclecounter() : 0ull;
-    for (int i = tid; i < 512; i += NT) s_exp[i] = a.gf_exp[i];
-    for (int i = tid; i < 256; i += NT) s_log[i] = a.gf_log[i];
+    for (int i = tid; i < 512; i += FS_THREADS) s_exp[i] = a.gf_exp[i];
+    for (int i = tid; i < 256; i += FS_THREADS) s_log[i] = a.gf_log[i];
     __syncthreads();
     FS_MARK(0);
     // pass 1 of two: the correlation ring is valid below this end position only (corr_tile_unused with the same state and limit)
@@ -1849,7 +1834,7 @@ __device__ __forceinline__ void framesync_body(const SyncArgs &a, const int ch) 
             float mv; uint32_t mpos;
             if (wi) { if (wi->rc < 0) { if (wi->rc == -5) st.mv_pos = wi->mpos; continue; } mv = wi->mv; mpos = wi->mpos; }
             else {
-                const int rc = fs_window<DC, NT>(bufs, corr, mask, pos, K, L, a.N, a.match_sum, tid, lane, wave, s_rf, s_ri, mv, mpos);
+                const int rc = fs_window<DC>(bufs, corr, mask, pos, K, L, a.N, a.match_sum, tid, lane, wave, s_rf, s_ri, mv, mpos);
                 if (rc == -5) { st.mv_pos = mpos; if (DC) af.dc = 0.0; }       // an all-zero window: position taken, nothing found (getCorrDFT with mp = -1)
                 if (rc < 0) continue;
             }
@@ -1862,19 +1847,19 @@ __device__ __forceinline__ void framesync_body(const SyncArgs &a, const int ch) 
                 uint32_t dpos = mpos, mv2_pos = 0;
                 if (a.opt_iq >= 2 && fabsf(mv) < a.thres) {
                     float mv2; uint32_t mpos2;
-                    if (fs_window<true, NT>(fm, a.corr2 + (size_t)ch * a.ring_len, mask, pos, K, L, a.N, a.match_sum, tid, lane, wave, s_rf, s_ri, mv2, mpos2) < 0) continue;
+                    if (fs_window<true>(fm, a.corr2 + (size_t)ch * a.ring_len, mask, pos, K, L, a.N, a.match_sum, tid, lane, wave, s_rf, s_ri, mv2, mpos2) < 0) continue;
                     mv2_pos = (uint32_t)((float)mpos2 - hofs);
                     dpos = mpos2;
                     if (mv2 > a.thres || mv2 < -a.thres) { st.mv = mv2; st.mv_pos = mv2_pos; }
                 }
                 const int mp_ofs = (a.opt_iq >= 2 && mv2_pos == 0) ? (int)hofs : 0;
                 double dsum = 0.0;
-                for (int t = tid; t < L; t += NT) dsum += (double)fm[((uint32_t)mp_ofs + dpos - (uint32_t)t) & mask];
+                for (int t = tid; t < L; t += FS_THREADS) dsum += (double)fm[((uint32_t)mp_ofs + dpos - (uint32_t)t) & mask];
                 for (int o = 32; o > 0; o >>= 1) dsum += __shfl_xor(dsum, o);
                 if (lane == 0) s_rd[wave] = dsum;
                 __syncthreads();
                 dsum = 0.0;
-                for (int w = 0; w < (NT / WAVE); w++) dsum += s_rd[w];
+                for (int w = 0; w < (FS_THREADS / WAVE); w++) dsum += s_rd[w];
                 __syncthreads();
                 af.dc = dsum / (double)(float)L;
                 mv = st.mv; mpos = st.mv_pos;
@@ -1910,7 +1895,7 @@ __device__ __forceinline__ void framesync_body(const SyncArgs &a, const int ch) 
             const int nsym = a.hdrlen / a.symhd;
             const uint32_t mvp = mpos + 1 - (uint32_t)L;
             const double hdc = (DC && a.opt_iq < 2) ? af.dc : 0.0;     // read_bufbit: bufs - dc for the FM-sliced forms (demod_mod.c:879)
-            for (int p = tid; p < nsym; p += NT) {
+            for (int p = tid; p < nsym; p += FS_THREADS) {
                 double edge = (double)((float)(p * a.symhd) * a.sps);
                 uint32_t cnt = (uint32_t)ceil(edge);
                 double sum = 0.0;
@@ -1937,7 +1922,7 @@ __device__ __forceinline__ void framesync_body(const SyncArgs &a, const int ch) 
             if (lane == 0) s_ri[wave] = errs;
             __syncthreads();
             errs = 0;
-            for (int w = 0; w < (NT / WAVE); w++) errs += s_ri[w];
+            for (int w = 0; w < (FS_THREADS / WAVE); w++) errs += s_ri[w];
             __syncthreads();
             FS_MARK(2);
             if (errs > a.hdmax) continue;
@@ -1956,12 +1941,12 @@ __device__ __forceinline__ void framesync_body(const SyncArgs &a, const int ch) 
             const int32_t q_lim = enough ? (int32_t)a.frame_samples : (int32_t)(avail - (st.mv_pos + (uint32_t)a.delay + 1));
             const uint32_t base = st.mv_pos + 1 + (uint32_t)a.bitofs;
             if (tid == 0) { s_slot = atomicAdd(a.frame_count, 1u) % (unsigned)a.max_frames; s_cnt[0] = 0; s_cnt[1] = 0; }
-            for (int i = tid; i < 520; i += NT) s_frame[i] = (a.rs41 && i < 8) ? a.hdr_bytes[i] : 0;
+            for (int i = tid; i < 520; i += FS_THREADS) s_frame[i] = (a.rs41 && i < 8) ? a.hdr_bytes[i] : 0;
             __syncthreads();
             const unsigned slot = s_slot;                              // monotonic counter, ring of records
             FrameRec *rec = a.frames + slot;
             FS_MARK(3);
-            for (int p0 = 0; p0 < a.nbits; p0 += NT) {
+            for (int p0 = 0; p0 < a.nbits; p0 += FS_THREADS) {
                 const int bp = p0 + tid;
                 double sum = 0.0;
                 bool valid = bp < a.nbits;
@@ -2026,7 +2011,7 @@ __device__ __forceinline__ void framesync_body(const SyncArgs &a, const int ch) 
                     const int cw = lane / 24, jx = lane % 24;
                     const uint8_t x = s_exp[jx];
                     uint8_t hsum = 0;
-                    constexpr int CH = 256 / (NT / WAVE);                  // coefficients per wave
+                    constexpr int CH = 256 / (FS_THREADS / WAVE);                  // coefficients per wave
                     for (int i = CH - 1; i >= 0; i--) {
                         const int n = CH * wave + i;
                         uint8_t v = 0;
@@ -2041,17 +2026,17 @@ __device__ __forceinline__ void framesync_body(const SyncArgs &a, const int ch) 
                     s_syn[wave][lane] = hsum ? s_exp[(s_log[hsum] + sh) % 255] : 0;
                 }
                 __syncthreads();
-                if (tid < 48) { uint8_t syn = 0; for (int w = 0; w < (NT / WAVE); w++) syn ^= s_syn[w][tid]; s_S[tid] = syn; }
+                if (tid < 48) { uint8_t syn = 0; for (int w = 0; w < (FS_THREADS / WAVE); w++) syn ^= s_syn[w][tid]; s_S[tid] = syn; }
                 __syncthreads();
                 if (a.ecc_level > 0 && 8 + nbytes_ok >= 518) {
                     bool clean = true;
                     for (int k = 0; k < 48; k++) clean &= (s_S[k] == 0);
-                    if (clean) { ecc_done = 1; for (int i = flen + tid; i < 518; i += NT) s_frame[i] = 0; }
+                    if (clean) { ecc_done = 1; for (int i = flen + tid; i < 518; i += FS_THREADS) s_frame[i] = 0; }
                     else if (a.ecc_list) { ecc_done = 2; if (tid == 0) a.ecc_list[atomicAdd(a.ecc_count, 1u) % (unsigned)a.max_frames] = slot; }
                 }
             }
             __syncthreads();
-            for (int i = tid; i < 518; i += NT) rec->frame[i] = s_frame[i];
+            for (int i = tid; i < 518; i += FS_THREADS) rec->frame[i] = s_frame[i];
             if (a.rs41 && tid < 48) rec->synd[tid] = s_S[tid];
             if (tid == 0) {
                 rec->channel = ch; rec->mv = st.mv; rec->mv_pos = st.mv_pos; rec->len = a.rs41 ? flen : a.nbits; rec->nbytes = a.rs41 ? 8 + nbytes_ok : nbits_ok;
@@ -2084,14 +2069,14 @@ __device__ __forceinline__ void framesync_body(const SyncArgs &a, const int ch) 
     }
 }
 
-template <bool DC, int NT>
-__global__ __launch_bounds__(NT, (NT == 1024 ? 4 : 3))      // small form: at most 168 registers, a wave per SIMD
-void k_framesync(const SyncArgs a) { framesync_body<DC, NT>(a, (int)blockIdx.x); }
+template <bool DC>
+__global__ __launch_bounds__(FS_THREADS, 4)
+void k_framesync(const SyncArgs a) { framesync_body<DC>(a, (int)blockIdx.x); }
 // mixed engines: one workgroup per row of the engine, the row's group brings its preset (header, bit clock, frame length, thresholds, record queue)
 __global__ __launch_bounds__(1024, 4)
 void k_framesync_multi(const MultiArgs<SyncArgs> m) {
     const int g = multi_group(m, (int)blockIdx.x);
-    framesync_body<false, 1024>(m.g[g], (int)blockIdx.x - m.row0[g]);
+    framesync_body<false>(m.g[g], (int)blockIdx.x - m.row0[g]);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2311,208 +2296,6 @@ void k_sync_window_fft_multi(const MultiArgs<WinFftArgs> m) {
     const int g = multi_group(m, (int)blockIdx.x);
     sync_window_fft_body(m.g[g], blockIdx.x - (uint32_t)m.row0[g], (uint32_t)(m.row0[g + 1] - m.row0[g]));
 }
-// ---- the same window transform in HALF the LDS (round 4): a decimation-in-time network on bit-reversed input never mixes the two halves of its
-// array before the last stage (stage s pairs i with i + 2^s inside blocks of 2^(s+1) <= 4096 for s <= 11).  So the half [0, 4096) — the EVEN window
-// samples — goes through stages 0..11 in a 4096-point array, its results wait in registers (8 per thread), the half [4096, 8192) — the odd samples —
-// follows in the same array, and the last stage combines registers with LDS.  35 KB + 4 KB of twiddles instead of 74 KB; with 256 threads (sixteen butterflies of the last
-// stage each, <= 168 registers) the workgroup fits the slot ONE decimator workgroup frees (51 KB, a wave per SIMD), which is what lets the header
-// search run beside the next call's decimator instead of waiting for it to drain.  Every butterfly is the same cmul / add / sub on
-// the same operands with the same twiddle as in dft_ref: scores and positions identical to the bit.
-#define WFH_THREADS 256               // four waves, one per SIMD at <= 168 registers: exactly the slot of one decimator workgroup
-#define SCH_N (SC_N / 2)
-#define SCH_XN (SCH_N + SCH_N / 16 + SCH_N / 256)
-template <int R>
-__device__ __forceinline__ void dit_pass_h(float2 *x, const float2 *tws, const int t0, const int tid) {
-    constexpr int E = 1 << R;
-    const int p_lo = t0;
-#pragma unroll 1
-    for (int g = tid; g < (SCH_N >> R); g += WFH_THREADS) {
-        const int low = g & ((1 << p_lo) - 1), high = g >> p_lo;
-        const int base = (high << (p_lo + R)) | low;
-        float2 v[E];
-#pragma unroll
-        for (int e = 0; e < E; e++) v[e] = x[XI(base + (e << p_lo))];
-#pragma unroll
-        for (int s2 = 0; s2 < R; s2++) {
-            const int t = t0 + s2, bit = 1 << s2;
-#pragma unroll
-            for (int e = 0; e < E; e++) {
-                if (e & bit) continue;
-                const int idx = base + (e << p_lo);
-                const float2 w = tws[((1 << t) - 1) + (idx & ((1 << t) - 1))];
-                const float2 p = v[e], r = cmul(v[e | bit], w);
-                v[e] = make_float2(p.x + r.x, p.y + r.y);
-                v[e | bit] = make_float2(p.x - r.x, p.y - r.y);
-            }
-        }
-#pragma unroll
-        for (int e = 0; e < E; e++) x[XI(base + (e << p_lo))] = v[e];
-    }
-    __syncthreads();
-}
-__device__ __forceinline__ void dft_half(float2 *x, const float2 *tws, const float2 *tws_g, const int tid) {      // stages 0..11 of one half
-    dit_pass_h<3>(x, tws, 0, tid);
-    dit_pass_h<3>(x, tws, 3, tid);
-    dit_pass_h<3>(x, tws, 6, tid);
-    dit_pass_h<3>(x, tws_g, 9, tid);
-}
-__device__ __forceinline__ int brev12(int k) { return (int)(__brev((unsigned)k) >> 20); }
-
-// the parking array is written by one thread and read by another of the same workgroup (and re-used window after window): device-scope accesses,
-// so that a read never hits a line an earlier window left in the CU's L1
-__device__ __forceinline__ float2 park_ld(const float2 *p) {
-    const unsigned long long v = __hip_atomic_load(reinterpret_cast<const unsigned long long *>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return make_float2(__uint_as_float((unsigned)(v & 0xffffffffull)), __uint_as_float((unsigned)(v >> 32)));
-}
-__device__ __forceinline__ void park_st(float2 *p, const float2 v) {
-    __hip_atomic_store(reinterpret_cast<unsigned long long *>(p), ((unsigned long long)__float_as_uint(v.y) << 32) | __float_as_uint(v.x), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void sync_eval_window_h(const WinFftArgs &a, const int ch, WinItem *it, float2 *x, float2 *tws, float *s_rf, int *s_ri, float2 *park) {
-    constexpr int NU = SCH_N / WFH_THREADS;      // 16: butterflies of the last stage per thread, g = tid + WFH_THREADS u
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (it->state != 1) return;
-    const int K = a.K, L = a.L, N = SC_N, wl = K + L;
-    const uint32_t pos = it->pos, mask = (uint32_t)a.ring_len - 1;
-    const float *bufs = a.bufs + (size_t)ch * a.ring_len;
-    const int64_t start = (int64_t)pos - (wl - 1);
-    // xn[i] = bufs[pos - (K+L-1) + i], i < K+L, zero padded (:168-169).  Slot brev12(k) of the even half holds xn[2k], of the odd half xn[2k+1].
-    for (int par = 0; par < 2; par++) {
-        float v[NU];
-#pragma unroll
-        for (int u = 0; u < NU; u++) {
-            const int i = 2 * (tid + WFH_THREADS * u) + par;
-            const int64_t p = start + i;
-            v[u] = (i < wl && p >= 0) ? bufs[(uint32_t)p & mask] : 0.f;
-        }
-        if (par == 1) {                                                  // the even half's results wait in the parking array while the odd half uses the LDS
-#pragma unroll 4
-            for (int u = 0; u < NU; u++) park_st(park + tid + WFH_THREADS * u, x[XI(tid + WFH_THREADS * u)]);
-            __syncthreads();
-        }
-#pragma unroll
-        for (int u = 0; u < NU; u++) x[XI(brev12(tid + WFH_THREADS * u))] = make_float2(v[u], 0.f);
-        __syncthreads();
-        dft_half(x, tws, a.tws, tid);
-    }
-    // last stage of X = rdft(xn), then Z = X * Fm (:190) and conj(Z) as the natural-order input of Nidft's transform (:78-80), parked in natural order:
-    // park[n] = conj(Z[n]); element n goes to slot brev13(n) of that transform: even n to its even half (slot brev12(n / 2)), odd n to its odd half
-#pragma unroll 2
-    for (int u = 0; u < NU; u++) {
-        const int g = tid + WFH_THREADS * u;
-        const float2 w = a.tws[((1 << 12) - 1) + g];
-        const float2 p = park_ld(park + g), r = cmul(x[XI(g)], w);
-        const float2 x0 = make_float2(p.x + r.x, p.y + r.y), x1 = make_float2(p.x - r.x, p.y - r.y);
-        const float2 q0 = cmul(x0, a.Fm[g]), q1 = cmul(x1, a.Fm[g + SCH_N]);
-        park_st(park + g, make_float2(q0.x, -q0.y)); park_st(park + g + SCH_N, make_float2(q1.x, -q1.y));       // (g is read and written by this thread only)
-    }
-    __syncthreads();
-    for (int par = 0; par < 2; par++) {
-        if (par == 1) {
-            // the even half's results: into the (now free) even-n places of the parking array
-            float2 t[4];
-#pragma unroll 1
-            for (int u0 = 0; u0 < NU; u0 += 4) {
-#pragma unroll
-                for (int q = 0; q < 4; q++) t[q] = x[XI(tid + WFH_THREADS * (u0 + q))];
-#pragma unroll
-                for (int q = 0; q < 4; q++) park_st(park + 2 * (tid + WFH_THREADS * (u0 + q)), t[q]);
-            }
-            __syncthreads();
-        }
-        float2 v2[4];
-#pragma unroll 1
-        for (int u0 = 0; u0 < NU; u0 += 4) {
-#pragma unroll
-            for (int q = 0; q < 4; q++) v2[q] = park_ld(park + 2 * (tid + WFH_THREADS * (u0 + q)) + par);
-#pragma unroll
-            for (int q = 0; q < 4; q++) x[XI(brev12(tid + WFH_THREADS * (u0 + q)))] = v2[q];
-        }
-        __syncthreads();
-        dft_half(x, tws, a.tws, tid);
-    }
-    // last stage in registers: only re(cx) is looked at — the arg-max of re(cx)^2 over i in [L-1, K+L), first maximum wins (:200-207)
-    float best = 0.f, bestc = 0.f; int bidx = -1;
-#pragma unroll 4
-    for (int u = 0; u < NU; u++) {
-        const int g = tid + u * WFH_THREADS;
-        const float2 w = a.tws[((1 << 12) - 1) + g];
-        const float2 p = park_ld(park + 2 * g), r = cmul(x[XI(g)], w);
-        const float c0 = p.x + r.x, c1 = p.x - r.x;
-        const int i0 = g, i1 = g + (1 << 12);
-        if (i0 >= L - 1 && i0 < wl) { const float c2 = c0 * c0; if (c2 > best || (c2 == best && bidx >= 0 && i0 < bidx)) { best = c2; bidx = i0; bestc = c0; } }
-        if (i1 >= L - 1 && i1 < wl) { const float c2 = c1 * c1; if (c2 > best || (c2 == best && bidx >= 0 && i1 < bidx)) { best = c2; bidx = i1; bestc = c1; } }
-    }
-    {
-        float rb = best; int ri = bidx;
-        for (int off = 32; off > 0; off >>= 1) {
-            const float ob = __shfl_xor(rb, off); const int oi = __shfl_xor(ri, off);
-            if (ob > rb || (ob == rb && oi >= 0 && (ri < 0 || oi < ri))) { rb = ob; ri = oi; }
-        }
-        if (lane == 0) { s_rf[wave] = rb; s_ri[wave] = ri; }
-    }
-    __syncthreads();
-    int mp = -1;
-    {
-        float b = 0.f;
-        for (int w = 0; w < WFH_THREADS / WAVE; w++) {
-            const float ob = s_rf[w]; const int oi = s_ri[w];
-            if (ob > b || (ob == b && oi >= 0 && (mp < 0 || oi < mp))) { b = ob; mp = oi; }
-        }
-    }
-    __syncthreads();
-    if (mp < 0) {
-        // not one correlation value above zero — a stream that begins with digital silence.  The reference's loop leaves mp = -1 (:200-207), which is no edge value:
-        // getCorrDFT runs on and sets mv = 0 / (a norm read in front of the array) and mv_pos = pos - (K + L - 1) - 1, which wraps in the first window of a stream —
-        // and `mv_pos > mvpos0` (find_header, :1603) then fails for the header the NEXT window finds.  Handed on as rc = -5 (k_framesync takes the position)
-        if (tid == 0) { it->rc = -5; it->mv = 0.f; it->mpos = pos - (uint32_t)(wl - 1) - 1u; __threadfence(); it->state = 2; }
-        return;
-    }
-    if (mp == L - 1 || mp == wl - 1) {                                    // edge value: -4 (:208)
-        if (tid == 0) { it->rc = -4; it->mv = 0.f; it->mpos = 0; __threadfence(); it->state = 2; }
-        return;
-    }
-    // xnorm = sqrt(sum_{i<L} xn[mp-i]^2) (:215-217), added up in k_sync_window_fft's order so that the header score is the same float: a thread keeps the
-    // partial sums of the WF_THREADS / WFH_THREADS threads of that kernel it stands for (same lane, waves wave + 4 j) apart
-    constexpr int NV = WF_THREADS / WFH_THREADS;
-    static_assert(WF_THREADS % WFH_THREADS == 0, "the energy sum follows k_sync_window_fft's partition");
-    float e[NV];
-#pragma unroll
-    for (int j = 0; j < NV; j++) {
-        e[j] = 0.f;
-        for (int k = tid + j * WFH_THREADS; k < L; k += WF_THREADS) {
-            const int i = mp - k; const int64_t p2 = start + i;
-            const float v = (i < wl && p2 >= 0) ? bufs[(uint32_t)p2 & mask] : 0.f;
-            e[j] += v * v;
-        }
-        for (int off = 32; off > 0; off >>= 1) e[j] += __shfl_xor(e[j], off);
-        if (lane == 0) s_rf[wave + j * (WFH_THREADS / WAVE)] = e[j];
-    }
-    if (bidx == mp) s_rf[WF_THREADS / WAVE] = bestc;
-    __syncthreads();
-    if (tid == 0) {
-        float es = 0.f;
-        for (int w = 0; w < WF_THREADS / WAVE; w++) es += s_rf[w];
-        const float xnorm = sqrtf(es);
-        it->rc = mp; it->mv = s_rf[WF_THREADS / WAVE] / (xnorm * (float)N); it->mpos = pos - (uint32_t)(wl - 1) + (uint32_t)mp;
-        __threadfence(); it->state = 2;
-    }
-}
-__global__ __launch_bounds__(WFH_THREADS) __attribute__((amdgpu_waves_per_eu(3, 3)))
-void k_sync_window_fft_h(const WinFftArgs a) {
-    extern __shared__ __attribute__((aligned(16))) float2 smem2[];
-    float2 *x = smem2;                           // [SCH_XN] padded (XI): one half of the transform's array at a time
-    float2 *tws = smem2 + SCH_XN;                // [SC_TW_LDS + 1] twiddles of stages 0..8
-    __shared__ float s_rf[WF_THREADS / WAVE + 1];
-    __shared__ int s_ri[WFH_THREADS / WAVE];
-    const uint32_t count = a.work_count[a.round_parity];
-    if (blockIdx.x >= count) return;
-    for (int k = threadIdx.x; k < SC_TW_LDS; k += WFH_THREADS) tws[k] = a.tws[k];
-    for (uint32_t w = blockIdx.x; w < count; w += gridDim.x) {
-        const uint32_t item = a.work[w];
-        __syncthreads();
-        sync_eval_window_h(a, (int)(item / (uint32_t)a.stride), a.items + item, x, tws, s_rf, s_ri, a.park + (size_t)blockIdx.x * SC_N);
-    }
-}
 #pragma clang fp contract(fast)
 
 // ------------------------------------------------------------------------------------------------
@@ -2542,34 +2325,16 @@ extern "C" int sonde_launch_mix_decimate(const MixDecArgs *a, hipStream_t s) {
     const size_t lds = (size_t)4 * (MD_ROWS * a->D + 4) * sizeof(uint32_t);
 #define MD_LAUNCH(QT) do { if (a->phase_f64) hipLaunchKernelGGL((k_mix_decimate<QT, true, 0, 0>), grid, blk, lds, s, b); \
                          else hipLaunchKernelGGL((k_mix_decimate<QT, false, 0, 0>), grid, blk, lds, s, b); } while (0)
-    static const bool no_dt = getenv("SONDE_NO_DT") != nullptr;      // debugging aid: force the runtime-D variant
-    if (a->Q == 7 && a->D == 50 && !no_dt) {            // 2.4 Msps -> 48 kHz: decimation known at compile time
+    if (a->Q == 7 && a->D == 50) {                      // 2.4 Msps -> 48 kHz: decimation known at compile time
         // fast / fold mode is a property of the ENGINE (a->etab set): the P tail between calls then holds sums without the IQ-DC
         // term, so every launch of such an engine goes through one of the two kernels that subtract avg * E per output
-        static const bool no_k50 = getenv("SONDE_MD_NO50") != nullptr;        // A/B aid: the kernel with one tile in flight
         if (a->etab && !a->phase_f64 && a->nd_base == 0.0 && a->lut_phase % 50 == 0) {
-            if (a->nblocks >= 64 && a->nblocks % 2 == 0 && !no_k50) {
-                static const int var = getenv("SONDE_MD_VARIANT") ? atoi(getenv("SONDE_MD_VARIANT")) : 1;
-#ifdef MD50_LOOP_2
-                if (var == 2) { hipLaunchKernelGGL((k_mix_decimate50<2>), grid, blk, lds, s, b); return 0; }
-#endif
-#ifdef MD50_LOOP_3
-                if (var == 3) { hipLaunchKernelGGL((k_mix_decimate50<3>), grid, blk, lds, s, b); return 0; }
-#endif
-#ifdef MD50_LOOP_4
-                if (var == 4) { hipLaunchKernelGGL((k_mix_decimate50<4>), grid, blk, lds, s, b); return 0; }
-#endif
-#ifdef MD50_LOOP_5
-                if (var == 5) { hipLaunchKernelGGL((k_mix_decimate50<5>), grid, blk, lds, s, b); return 0; }
-#endif
-                (void)var;
-                hipLaunchKernelGGL((k_mix_decimate50<1>), grid, blk, lds, s, b);
-            }
+            if (a->nblocks >= 64 && a->nblocks % 2 == 0) hipLaunchKernelGGL(k_mix_decimate50, grid, blk, lds, s, b);
             else hipLaunchKernelGGL((k_mix_decimate<7, false, 50, 1>), grid, blk, lds, s, b);
         }
         else if (a->etab) return -1;                          // a fold-mode engine must never fall back to sums with the IQ-DC term
         else if (a->phase_f64 && a->dc_seg && a->nd_base == 0.0 && !a->epoch_phase && a->lut_len % 50 == 0 && a->lut_phase % 50 == 0 && a->dc_seg_blocks > 0
-                 && a->nblocks >= 64 && a->nblocks % 2 == 0 && !no_k50 && a->wtab_scaled)
+                 && a->nblocks >= 64 && a->nblocks % 2 == 0 && a->wtab_scaled)
             hipLaunchKernelGGL(k_mix_decimate50s, grid, blk, lds, s, b);      // the scanner's front end on the generated tile loop
         else if (a->phase_f64) hipLaunchKernelGGL((k_mix_decimate<7, true, 50, 0>), grid, blk, lds, s, b);
         else hipLaunchKernelGGL((k_mix_decimate<7, false, 50, 0>), grid, blk, lds, s, b);
@@ -2690,6 +2455,11 @@ template <class A> static MultiArgs<A> multi_pack(const A *a, const int *rows, i
     for (int g = 0; g < n_groups; g++) { m.g[g] = a[g]; m.row0[g + 1] = m.row0[g] + rows[g]; }
     return m;
 }
+// a launch's arguments must fit the 4 KB kernel argument segment (SONDE_MAX_GROUPS copies of a group's struct)
+static_assert(sizeof(MultiArgs<IfArgs>) <= 4096, "MultiArgs<IfArgs> exceeds the kernel argument segment");
+static_assert(sizeof(MultiArgs<WinPlanArgs>) <= 4096, "MultiArgs<WinPlanArgs> exceeds the kernel argument segment");
+static_assert(sizeof(MultiArgs<WinFftArgs>) <= 4096, "MultiArgs<WinFftArgs> exceeds the kernel argument segment");
+static_assert(sizeof(MultiArgs<SyncArgs>) <= 4096, "MultiArgs<SyncArgs> exceeds the kernel argument segment");
 extern "C" int sonde_launch_if_chain_multi(const IfArgs *a, int n_groups, hipStream_t s) {
     if (n_groups < 1 || n_groups > SONDE_MAX_GROUPS) return -1;
     size_t lds = 0; int rows[SONDE_MAX_GROUPS], n = a[0].n;
@@ -2741,11 +2511,6 @@ extern "C" void sonde_launch_sync_plan(const WinPlanArgs *a, hipStream_t s) {
 extern "C" void sonde_launch_sync_window_fft(const WinFftArgs *a, hipStream_t s) {
     const size_t lds = (size_t)(SC_XN + SC_TW_LDS + 1) * sizeof(float2);
     int grid = a->W * a->n_ch;
-    if (a->small_wg) {                                          // the half-array form: fits the slot of one decimator workgroup (three per CU)
-        if (grid > SONDE_WFH_MAXGRID) grid = SONDE_WFH_MAXGRID;
-        hipLaunchKernelGGL(k_sync_window_fft_h, dim3(grid), dim3(WFH_THREADS), (size_t)(SCH_XN + SC_TW_LDS + 1) * sizeof(float2), s, *a);
-        return;
-    }
     if (grid > 512) grid = 512;                                 // two waves of workgroups on 256 CUs at most; the kernel strides over the list
     hipLaunchKernelGGL(k_sync_window_fft, dim3(grid), dim3(WF_THREADS), lds, s, *a);
 }
@@ -2833,7 +2598,6 @@ extern "C" int sonde_launch_framesync_multi(const SyncArgs *a, int n_groups, hip
     return 0;
 }
 extern "C" void sonde_launch_framesync(const SyncArgs *a, hipStream_t s) {
-    if (a->opt_dc) hipLaunchKernelGGL((k_framesync<true, FS_THREADS>), dim3(a->n_ch), dim3(FS_THREADS), 0, s, *a);
-    else if (a->small_wg) hipLaunchKernelGGL((k_framesync<false, FS_THREADS_SMALL>), dim3(a->n_ch), dim3(FS_THREADS_SMALL), 0, s, *a);
-    else hipLaunchKernelGGL((k_framesync<false, FS_THREADS>), dim3(a->n_ch), dim3(FS_THREADS), 0, s, *a);
+    if (a->opt_dc) hipLaunchKernelGGL(k_framesync<true>, dim3(a->n_ch), dim3(FS_THREADS), 0, s, *a);
+    else hipLaunchKernelGGL(k_framesync<false>, dim3(a->n_ch), dim3(FS_THREADS), 0, s, *a);
 }

@@ -815,7 +815,6 @@ int sonde_scan_process_device(sonde_scan_t *s, const void *d_in, int64_t ch_stri
         // int16 base-rate input with a decimation the lane-per-block kernel takes in one piece: ONE decimator launch for the whole call, the IQ-DC
         // windows it spans (1/32 s each: 32 per second of signal) handled by a table of means (MixDecArgs.dc_seg) that two small kernels fill first —
         // a launch per window made the front end launch-bound (64 launches of ~9 us per second of signal)
-        static const bool no_segtab = getenv("SONDE_SCAN_NO_SEGTAB") != nullptr;      // A/B aid
         if (s->front_raw) {
             // one pass over the input: raw mix + block sums, then window sums -> means -> y -= mean * E at the IF rate
             if (mode != SONDE_SCAN_BBIQ || f32in || n_samples % D || s->dc_cnt % (uint32_t)D) return SONDE_E_ARG;      // (cannot happen: whole blocks per call)
@@ -853,7 +852,7 @@ int sonde_scan_process_device(sonde_scan_t *s, const void *d_in, int64_t ch_stri
             s->dc_cnt = (uint32_t)(((uint64_t)s->dc_cnt + (uint64_t)n_samples) % s->dc_max);
             done = n_samples;
         }
-        if (done < n_samples && mode == SONDE_SCAN_BBIQ && !f32in && D <= 64 && n_samples % D == 0 && s->dc_cnt % (uint32_t)D == 0 && !no_segtab) {
+        if (done < n_samples && mode == SONDE_SCAN_BBIQ && !f32in && D <= 64 && n_samples % D == 0 && s->dc_cnt % (uint32_t)D == 0) {
             const int nseg_cap = s->cfg.max_chunk / (int)s->dc_max + 2;
             if (!s->d_segsums) {
                 HIPCHK(hipMalloc((void **)&s->d_segsums, (size_t)C * nseg_cap * 2 * sizeof(long long)));
@@ -878,7 +877,7 @@ int sonde_scan_process_device(sonde_scan_t *s, const void *d_in, int64_t ch_stri
         }
         // float32 IF-rate input (the channelizer's output: 256 channels at 50 kHz): the same table of window means, one k_mix_f32 launch for the call
         // instead of a mixer launch and a mean update per 1/32 s window (63 launches of 4-9 us per second of signal: 0.4 of scan_wide's 2.5 ms)
-        if (mode != SONDE_SCAN_BBIQ && f32in && !no_segtab && n_samples > 0) {
+        if (mode != SONDE_SCAN_BBIQ && f32in && n_samples > 0) {
             const int nseg_cap = s->cfg.max_chunk / (int)s->dc_max + 2;
             if (!s->d_dcsums_f) { HIPCHK(hipMalloc((void **)&s->d_dcsums_f, 2 * (size_t)C * sizeof(double))); HIPCHK(hipMemset(s->d_dcsums_f, 0, 2 * (size_t)C * sizeof(double))); }
             if (!s->d_segsums) {

@@ -10,7 +10,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_md_fast_gen_in_sync():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "gen_md_fast.py"), "--print"], capture_output=True, text=True, check=True).stdout
     cur = open(os.path.join(ROOT, "radiosonde_auto_rx_amd", "csrc", "md_fast_gen.h")).read()
-    assert out == cur, "run `python3 tools/gen_md_fast.py` (without --experiments) and rebuild"
+    assert out == cur, "run `python3 tools/gen_md_fast.py` and rebuild"
 
 
 def test_md_loop_structure():

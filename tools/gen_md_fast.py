@@ -65,7 +65,6 @@ class Regs:
 RAW = False   # the scanner's front end in ONE pass over the input (round 4): double mixer phase like SCAN, NO mean anywhere in the loop — the outputs are the
               # raw sum W x ex, and every row's sum of raw samples (the IQ-DC sum of its D samples, exact integers) goes to a side array; the means of the
               # 1/32 s windows and y -= mean * E follow at the IF rate (k_dc_rows_to_segments, k_scan_dc_fold), where the input is 1/50 of the bytes
-EXP = ""      # experiment variants (tools/ab_variants.sh): timing only, results are garbage
 SCAN = False  # the scanner's front end (scan/dft_detect.c): mixer phase kept in DOUBLE (t = f0 * n, :1090-1093: fract in f64, then one rounding to f32)
               # and the IQ-DC mean of the row's 1/32 s window taken off every sample ((x - avg) ex, :579-588; the means come from a table, a
               # launch spans many windows) instead of folded out per output — same instruction count: the subtraction takes the slot of the
@@ -117,25 +116,13 @@ def block(R, r, init=False):
         I["z"] = f"v_pk_fma_f32 {R.Z}, {R.X[o]}, {R.CS[o]}, {R.TT} op_sel_hi:[0,1,1]"
         for q in range(Q): I[f"a{q}"] = tap_fma(R, q, r - 1, init and r == 1)
     order = "cvt64 tt add64 fract z xr cos a0 xi sin a1 a2 dcs a3 a4 a5 a6"
-    if "nodc" in EXP: order = order.replace(" dcs", "")
-    if "nocmul" in EXP: order = order.replace(" tt ", " ").replace(" z ", " ")
-    L = [I[k] for k in order.split() if k in I]
-    if "nosincos" in EXP:
-        L = [l.replace("v_cos_f32", "v_mov_b32").replace("v_sin_f32", "v_mov_b32") for l in L]
-    if "nof64" in EXP:
-        L = [l for l in L if not l.startswith("v_add_f64")]
-        L = [f"v_mov_b32 {R.TP}, {R.XR[0]}" if l.startswith("v_cvt_f32_f64") else l for l in L]
-    if "nofir" in EXP:
-        L = [l for l in L if not any(l.startswith(f"v_pk_fma_f32 {R.acc[q]},") or l.startswith(f"v_pk_mul_f32 {R.acc[q]},") for q in range(1, Q))]
-    return L
+    return [I[k] for k in order.split() if k in I]
 
 
 def walk(R, init=False, hook=()):
     """the 50 samples of one tile; ends with every LDS / SMEM access complete.  init: the accumulators and the DC sum start
     from the first sample instead of from their old values.  hook: instructions placed behind the first wait (by then every
     LDS operation issued before the walk has completed as well)"""
-    if "empty" in EXP:
-        return ["s_waitcnt lgkmcnt(0)"] + list(hook)
     L = [f"ds_read_b64 {R.RAW[0]}, {R.row}", f"s_load_dwordx8 s[{TAPSET[0]}:{TAPSET[0] + 7}], {R.wt}, 0x0"]
     for r in range(D + 1):
         if r % 2 == 0:
@@ -143,8 +130,6 @@ def walk(R, init=False, hook=()):
             L += loads_after_wait(R, r // 2)
             if r == 0: L += list(hook)
         L += block(R, r, init)
-    if "noloads" in EXP:
-        L = [l for l in L if not (l.startswith("ds_read") or l.startswith("s_load") or l.startswith("s_waitcnt"))]
     return L
 
 
@@ -197,7 +182,6 @@ def diag_issue(rb):
         k = H - q
         L += [f"ds_bpermute_b32 v{rb + 2 * q}, %[lane4], v{ACC0 + 2 * q} offset:{256 - 4 * k}",
               f"ds_bpermute_b32 v{rb + 2 * q + 1}, %[lane4], v{ACC0 + 2 * q + 1} offset:{256 - 4 * k}"]
-    if "nodiag" in EXP: L = []
     Y, T1 = rb + 12, rb + 14
     L += [f"v_pk_add_f32 {pair(Y)}, {ACC[H]}, {pair(CARRY)}", f"v_mov_b64 {pair(CARRY)}, 0",
           f"v_lshrrev_b32 v{T1}, 2, %[lane4]", f"v_add_u32 v{T1}, s{S_JM}, v{T1}", f"v_and_b32 v{T1}, %[rmask], v{T1}",
@@ -219,9 +203,6 @@ def diag_finish(rb):
               f"v_pk_fma_f32 {pair(Y)}, {pair(EREG)}, %[navg], {pair(Y)} op_sel:[1,1,0] op_sel_hi:[0,1,1] neg_lo:[1,0,0]"]
     L += [f"global_store_dwordx2 v{T1}, {pair(Y)}, %[yout]",
           "s_mov_b64 exec, -1", f"s_mov_b64 s[{S_OUT}:{S_OUT + 1}], -1"]
-    if "nostore" in EXP: L = [l for l in L if not l.startswith("global_store")]
-    if "sc1store" in EXP: L = [l + " sc1" if l.startswith("global_store") else l for l in L]
-    if "sc01store" in EXP: L = [l + " sc0 sc1" if l.startswith("global_store") else l for l in L]
     return L
 
 
@@ -255,12 +236,11 @@ def gen_loop():
                      f"v_cvt_u32_f32 v{T1}, v{T1}", f"v_min_u32 v{T1}, %[segmax], v{T1}", f"v_lshlrev_b32 v{T1}, 3, v{T1}",
                      f"global_load_dwordx2 {pair(EREG)}, v{T1}, %[dcseg]"]
         elif RAW: pass                                        # neither a mean nor E: the fold happens at the IF rate
-        elif "noE" not in EXP: hook += [f"v_lshlrev_b32 v{T1}, 3, %[e]", f"global_load_dwordx2 {pair(EREG)}, v{T1}, %[etab]"]
+        else: hook += [f"v_lshlrev_b32 v{T1}, 3, %[e]", f"global_load_dwordx2 {pair(EREG)}, v{T1}, %[etab]"]
         fe = [f"s_add_i32 s{S_TMP}, s{S_T}, 2", f"s_cmp_lt_i32 s{S_TMP}, %[nfull]", f"s_cbranch_scc0 {lab + 2}f"] + fetch(STAGE[h]) + [f"{lab + 2}:"]
-        if "latefetch" not in EXP: hook += fe
+        hook += fe
         L += [f"{lab}:", f"v_mul_u32_u24 v{T1}, 50, %[e]", f"v_cvt_f64_u32 {pair(TREG)}, v{T1}", f"v_mul_f64 {pair(TREG)}, {pair(TREG)}, %[f0]"]
         L += walk(R, init=True, hook=hook)
-        if "latefetch" in EXP: L += fe
         # the lane's block in the next tile: e = (e + 64) mod P; IQ-DC sums of the rows that count
         L += [f"v_add_u32 %[e], 64, %[e]", f"v_subrev_u32 v{T1}, %[P], %[e]", f"v_min_u32 %[e], v{T1}, %[e]"]
         if SCAN: L += [f"v_add_u32 %[jrow], 64, %[jrow]"]
@@ -293,8 +273,7 @@ def as_macro(name, lines):
 
 
 def main():
-    """md_fast_gen.h: MD_FAST_BODY_1 / MD50_LOOP_1 = production; with --experiments <spec>... also _2.. (timing only)"""
-    global EXP
+    """md_fast_gen.h: MD_FAST_BODY_1 / MD50_LOOP_1 = production, _S = the scanner's front end, _R = its one-pass form"""
     text = "// generated by tools/gen_md_fast.py — do not edit (tests/test_generated_sources.py checks it is in sync)\n"
     text += as_macro("MD_FAST_BODY_1", body_operands()) + as_macro("MD50_LOOP_1", gen_loop())
     global SCAN
@@ -307,10 +286,6 @@ def main():
     text += "// the scanner's front end in one pass: double mixer phase, no mean in the loop, the rows' raw sums to a side array (RAW in tools/gen_md_fast.py)\n"
     text += as_macro("MD_FAST_BODY_R", body_operands()) + as_macro("MD50_LOOP_R", gen_loop())
     RAW = False
-    if len(sys.argv) > 1 and sys.argv[1] == "--experiments":
-        for k, e in enumerate(sys.argv[2:], 2):
-            EXP = e
-            text += f"// experiment {k}: {e}\n" + as_macro(f"MD50_LOOP_{k}", gen_loop())
     if len(sys.argv) > 1 and sys.argv[1] == "--print":
         sys.stdout.write(text); return
     base = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "radiosonde_auto_rx_amd", "csrc")
