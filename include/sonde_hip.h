@@ -251,6 +251,18 @@ long long sonde_engine_host_ecc_frames(sonde_engine_t *e);
  * (Hamming(8,4) of the sliced frames / differential decoding + checkM10): on the device behind the frame sync, or on the host inside the fetch; there the
  * switch takes effect between records only — everything queued must have been fetched (SONDE_E_ARG otherwise). */
 int  sonde_engine_set_device_ecc(sonde_engine_t *e, int32_t on);
+/* Header search of the engines that evaluate windows with the reference's transform (every type without --dc): by default a process call
+ * runs it and the frame sync as ONE launch (k_search_sync), which transforms only the windows the reference evaluates.  on = 1: the calls
+ * that follow run it in rounds instead (k_sync_plan -> k_sync_window_fft -> k_framesync, what mixed engines do); frames, records and sync
+ * state are the same.  For tests and measurements. */
+int  sonde_engine_set_search_rounds(sonde_engine_t *e, int32_t on);
+/* Window counting of a single-type engine (measurements): on = 1 counts from now on the windows the header search transforms — the rounds
+ * read their counts back after every round, which synchronises.  out (nullable, [3]): windows so far in first rounds, in later rounds, in
+ * k_search_sync launches. */
+int  sonde_engine_count_windows(sonde_engine_t *e, int32_t on, int64_t *out);
+/* Per-channel sync state of a single-type engine after the calls issued so far (waits for them): 8 words per channel {sample_in, k, mv_pos,
+ * mode, mv (float bits), inv, 0, 0}.  Returns the number of channels written. */
+int  sonde_engine_read_sync_state(sonde_engine_t *e, uint32_t *out, int32_t max_channels);
 /* Pipelined variant: return only the frames of process calls issued at least `lag` calls ago and wait only for those.
  * With lag = 1 the IF-rate kernels of call k (stream B) overlap the decimator of call k+1 (stream A); lag = 0 is
  * sonde_engine_fetch_frames().  Frames are never lost: what is not returned stays queued. */

@@ -196,6 +196,14 @@ struct SyncArgs {
     unsigned long long *prof; // SONDE_WF_PROF: cycles per phase of channel 0 (nullptr = off)
 };
 
+// k_search_sync (single-type engines on the transform path): one workgroup per channel runs k_framesync's state machine and evaluates each
+// window it reaches with k_sync_window_fft's code in its own LDS, so only the windows the reference evaluates are transformed.  sync.win is unused.
+struct SearchSyncArgs {
+    SyncArgs sync;
+    WinFftArgs win;           // bufs, Fm, tws, K, L, ring_len, prof; the item table and work list are unused
+    unsigned long long *wcount;   // nullable: windows evaluated (sonde_engine_count_windows)
+};
+
 #define SONDE_MAX_GROUPS 6      // groups of a mixed engine whose IF-rate stages share a launch (the argument structs of all groups travel in the kernel argument segment: 4 KB)
 extern "C" {
 int  sonde_launch_if_chain_multi(const IfArgs *a, int n_groups, hipStream_t s);
@@ -226,5 +234,6 @@ void sonde_launch_header_corr(const CorrArgs *a, hipStream_t s);
 void sonde_launch_sync_plan(const WinPlanArgs *a, hipStream_t s);
 void sonde_launch_sync_window_fft(const WinFftArgs *a, hipStream_t s);
 void sonde_launch_framesync(const SyncArgs *a, hipStream_t s);
+void sonde_launch_search_sync(const SearchSyncArgs *a, hipStream_t s);
 }
 #endif

@@ -68,6 +68,10 @@ struct sonde_engine {
     // header search with the reference's transform (k_sync_plan / k_sync_window_fft): per channel win_W planned windows
     WinItem *d_win = nullptr; float2 *d_Fm = nullptr, *d_tws = nullptr; int win_W = 0;
     uint32_t *d_work = nullptr, *d_work_count = nullptr; int sync_rounds = 0;      // compact window list of the round, counters [2]
+    // a single-type engine runs a call's header search and frame sync as ONE k_search_sync launch; search_rounds (sonde_engine_set_search_rounds,
+    // tests) keeps it on the rounds above.  Window counts (sonde_engine_count_windows): d_wcount = k_search_sync's, wcount_rounds = round 0 / later rounds
+    bool search_rounds = false;
+    bool count_windows = false; unsigned long long *d_wcount = nullptr; long long wcount_rounds[2] = { 0, 0 };
     sonde_summary_t *d_summary = nullptr; uint32_t summary_base = 0;      // caller-owned device buffer (sonde_engine_set_summary)
     sonde_summary_t *d_summary_snap = nullptr;                            // caller-owned, 2 x n_channels records (sonde_engine_set_summary_snapshots)
     int corr_types = 0, corr_isps = 0; float *d_shapes = nullptr, *d_symsign = nullptr; int *d_symtype = nullptr;
@@ -210,6 +214,7 @@ static void launch_blockcodes(sonde_engine *e) {
 }
 static void launch_framesync(sonde_engine *e, int eof) { launch_framesync_impl(e, eof); launch_blockcodes(e); if (eof) e->eof_pending = true; }
 static void sync_round(sonde_engine *e, int W);
+static void launch_search_sync(sonde_engine *e);
 
 static bool blockcodes_on_device(const sonde_engine *e) {
     return e->dev_ecc && e->d_soft && e->d_blk_done && ((e->cfg.sonde_type == SONDE_DFM09 && e->d_dfm_out) || (e->cfg.sonde_type == SONDE_M10 && e->d_m10_out));
@@ -679,7 +684,7 @@ void sonde_engine_destroy(sonde_engine_t *e) {
                      e->d_bufs, e->d_corr, e->d_wiq, e->d_wfm, e->d_match, e->d_state, e->d_frames, e->d_fcount, e->d_soft, e->d_soft1,
                      e->d_epoch, e->d_work, e->d_work_count, e->d_consts, e->d_stage, e->d_shapes, e->d_symtype, e->d_symsign, e->d_bitwin, e->d_bitend, e->d_raw, e->d_wtab, e->d_conv, e->d_conv32,
                      e->d_dcsums_f, e->d_zring, e->d_taps_f, e->d_wiq0, e->d_yrot, e->d_fmraw, e->d_corr2, e->d_afc, e->d_start, e->d_pending,
-                     e->d_etab, e->d_dcavg_prev, e->d_win, e->d_Fm, e->d_tws, e->d_epoch_phase, e->d_pcs_cnt, e->d_pcs_max, e->d_pcs_since, e->d_in_row, e->d_sum_map };
+                     e->d_etab, e->d_dcavg_prev, e->d_win, e->d_Fm, e->d_tws, e->d_epoch_phase, e->d_pcs_cnt, e->d_pcs_max, e->d_pcs_since, e->d_in_row, e->d_sum_map, e->d_wcount };
     for (void *p : ptrs) if (p) hipFree(p);
     delete e;
 }
@@ -928,14 +933,26 @@ static int tail_enqueue(sonde_engine *e, int32_t n_samples, uint32_t m_first, hi
     } else {
         if (e->cfg.input != SONDE_IN_AUDIO) { prof_begin(e, "if_chain", e->stream_b); sonde_launch_if_chain(&b, e->stream_b); prof_end(e, e->stream_b); }
         if (e->stream_b != fs) hipEventRecord(e->ev_if[slot], e->stream_b);
-        if (!fe && e->d_win) {
-            // header search with the reference's own transform: rounds of plan -> evaluate -> sync; the sync stops where the planned
-            // windows end and the next round plans from the state it left.  First round: the two windows a received sonde needs.
+        if (!fe && e->d_win && !e->search_rounds) {
+            // header search with the reference's own transform and frame sync in one launch: each channel's workgroup evaluates the
+            // windows its search reaches, one after the other, and slices the frames it finds
+            launch_search_sync(e);
+        } else if (!fe && e->d_win) {
+            // the same in rounds (mixed engines' arrangement; sonde_engine_set_search_rounds): plan -> evaluate -> sync; the sync stops where the
+            // planned windows end and the next round plans from the state it left.  First round: the two windows a received sonde needs.
             // A round ends when the planned windows are used up or a hit's frame has been sliced (the search then resumes at a place the
             // plan could not know), so it covers at least min(W windows, one window + one frame) samples: two rounds for a call of up to
             // about a second, more for longer ones.
             const int rounds = sync_rounds_of(e, n_if);
-            for (int round = 0; round < rounds; round++) sync_round(e, round == 0 ? 2 : e->win_W);
+            for (int round = 0; round < rounds; round++) {
+                sync_round(e, round == 0 ? 2 : e->win_W);
+                if (e->count_windows) {                // windows the round evaluated (the counter of its parity holds them until the next round's plan)
+                    uint32_t n = 0;
+                    hipMemcpyAsync(&n, e->d_work_count + ((e->sync_rounds - 1) & 1), sizeof n, hipMemcpyDeviceToHost, e->stream_b);
+                    hipStreamSynchronize(e->stream_b);
+                    e->wcount_rounds[round == 0 ? 0 : 1] += n;
+                }
+            }
         } else if (!fe) {
             // two passes (corr_tile_unused in sonde_kernels.hip): correlate what two search windows can reach, sync up to there, then the
             // rest with the state that is known by then — nothing at all for a channel whose new frame covers the rest of the call
@@ -1019,6 +1036,14 @@ static int tail_finish(sonde_engine *e) {
 
 extern "C" {
 
+// arguments of the window transform (k_sync_window_fft, k_search_sync) without a round's list
+static void fill_winfft(sonde_engine *e, WinFftArgs &f) {
+    f = WinFftArgs{}; f.bufs = e->d_bufs; f.items = e->d_win; f.Fm = e->d_Fm; f.tws = e->d_tws; f.n_ch = e->cfg.n_channels; f.stride = e->win_W;
+    f.K = e->info.K; f.L = e->info.L; f.ring_len = e->ring_len;
+    static const bool want_prof = getenv("SONDE_WF_PROF") != nullptr;          // profiling aid: cycles per phase of workgroup 0, printed when the engine is destroyed
+    if (want_prof && !e->d_wfprof) { if (hipMalloc((void **)&e->d_wfprof, 32 * sizeof(unsigned long long)) == hipSuccess) hipMemset(e->d_wfprof, 0, 32 * sizeof(unsigned long long)); }
+    f.prof = e->d_wfprof;
+}
 // arguments of one header-search round (k_sync_plan + k_sync_window_fft); advances the round counter
 static void fill_round(sonde_engine *e, int W, WinPlanArgs &p, WinFftArgs &f) {
     // the item table has win_W slots per channel; this round plans and evaluates the first W of them (the others are cleared)
@@ -1026,12 +1051,8 @@ static void fill_round(sonde_engine *e, int W, WinPlanArgs &p, WinFftArgs &f) {
     p = WinPlanArgs{}; p.state = e->d_state; p.items = e->d_win; p.n_ch = C; p.stride = e->win_W; p.W = W; p.K = e->info.K; p.L = e->info.L;
     p.delay = e->info.delay; p.frame_samples = e->frame_samples; p.avail = e->m_out; p.epoch = e->d_epoch;
     p.work = e->d_work; p.work_count = e->d_work_count; p.round_parity = e->sync_rounds & 1;
-    f = WinFftArgs{}; f.bufs = e->d_bufs; f.items = e->d_win; f.Fm = e->d_Fm; f.tws = e->d_tws; f.n_ch = C; f.stride = e->win_W; f.W = W;
-    f.K = e->info.K; f.L = e->info.L; f.ring_len = e->ring_len;
+    fill_winfft(e, f); f.W = W;
     f.work = e->d_work; f.work_count = e->d_work_count; f.round_parity = e->sync_rounds & 1;
-    static const bool want_prof = getenv("SONDE_WF_PROF") != nullptr;          // profiling aid: cycles per phase of workgroup 0, printed when the engine is destroyed
-    if (want_prof && !e->d_wfprof) { if (hipMalloc((void **)&e->d_wfprof, 32 * sizeof(unsigned long long)) == hipSuccess) hipMemset(e->d_wfprof, 0, 32 * sizeof(unsigned long long)); }
-    f.prof = e->d_wfprof;
     e->sync_rounds++;
 }
 static void sync_round(sonde_engine *e, int W) {
@@ -1071,6 +1092,15 @@ static SyncArgs fill_sync(sonde_engine *e, int eof) {
 static void launch_framesync_impl(sonde_engine *e, int eof) {
     const SyncArgs s = fill_sync(e, eof);
     prof_begin(e, "framesync", e->stream_b); sonde_launch_framesync(&s, e->stream_b); prof_end(e, e->stream_b);
+}
+// a process call's header search and frame sync in one launch (k_search_sync); timed as "framesync" ("header_corr" stays empty)
+static void launch_search_sync(sonde_engine *e) {
+    SearchSyncArgs a{};
+    a.sync = fill_sync(e, 0); a.sync.win = nullptr; a.sync.win_W = 0;
+    fill_winfft(e, a.win);
+    a.wcount = e->count_windows ? e->d_wcount : nullptr;
+    prof_begin(e, "framesync", e->stream_b); sonde_launch_search_sync(&a, e->stream_b); prof_end(e, e->stream_b);
+    launch_blockcodes(e);
 }
 
 int sonde_engine_process_host(sonde_engine_t *e, const void *h_iq, int64_t ch_stride, int32_t n_samples) {
@@ -1156,6 +1186,32 @@ long long sonde_engine_host_ecc_frames(sonde_engine_t *e) {
     if (!e) return SONDE_E_ARG;
     long long n = e->host_ecc_frames;
     for (sonde_engine *g : e->groups) n += g->host_ecc_frames;
+    return n;
+}
+int sonde_engine_set_search_rounds(sonde_engine_t *e, int32_t on) {
+    if (!e) return SONDE_E_ARG;
+    for (sonde_engine *g : e->groups) { const int rc = sonde_engine_set_search_rounds(g, on); if (rc) return rc; }
+    e->search_rounds = on != 0;
+    return 0;
+}
+int sonde_engine_count_windows(sonde_engine_t *e, int32_t on, int64_t *out) {
+    if (!e || !e->groups.empty()) return SONDE_E_ARG;
+    if (on && !e->d_wcount && e->d_win && dalloc(&e->d_wcount, 1)) return SONDE_E_NOMEM;
+    if (hipStreamSynchronize(e->stream_b) != hipSuccess) return SONDE_E_NOGPU;
+    e->count_windows = on != 0;
+    if (out) {
+        unsigned long long n = 0;
+        if (e->d_wcount && hipMemcpy(&n, e->d_wcount, sizeof n, hipMemcpyDeviceToHost) != hipSuccess) return SONDE_E_NOGPU;
+        out[0] = e->wcount_rounds[0]; out[1] = e->wcount_rounds[1]; out[2] = (int64_t)n;
+    }
+    return 0;
+}
+int sonde_engine_read_sync_state(sonde_engine_t *e, uint32_t *out, int32_t max_channels) {
+    if (!e || !out || !e->groups.empty() || !e->d_state) return SONDE_E_ARG;
+    const int n = std::min<int>(max_channels, e->cfg.n_channels);
+    if (n <= 0) return 0;
+    if (hipStreamSynchronize(e->stream_b) != hipSuccess) return SONDE_E_NOGPU;
+    if (hipMemcpy(out, e->d_state, (size_t)n * sizeof(SyncState), hipMemcpyDeviceToHost) != hipSuccess) return SONDE_E_NOGPU;
     return n;
 }
 int sonde_engine_set_device_ecc(sonde_engine_t *e, int32_t on) {

@@ -25,7 +25,9 @@ __device__ __forceinline__ int brev13(int k) { return (int)(__brev((unsigned)k) 
 // accumulated in float (dft_raw, dft_detect.c:306-319), tabulated by the host at tws[2^t - 1 + j].  The recurrence
 // drifts by up to ~2e-4 in the last stages, and the reference's scores carry that drift; using its table reproduces
 // them instead of the exact DFT.
-template <int R>
+// V only tells copies apart: a kernel that needs the transform beside other work (k_search_sync) instantiates its own, so that the
+// code generated for the kernels that share V = 0 does not depend on it.
+template <int R, int V = 0>
 __device__ __forceinline__ void dit_pass(float2 *x, const float2 *tws, const int t0, const int tid) {
     constexpr int E = 1 << R;
     const int p_lo = t0;
@@ -60,15 +62,17 @@ __device__ __forceinline__ void dit_pass(float2 *x, const float2 *tws, const int
 // 1024 threads fit on a CU
 #define SC_TW_LDS 511
 // stages 0..11; the caller runs the last stage (12) itself when it wants the outputs in registers
+template <int V = 0>
 __device__ __forceinline__ void dft_ref_head(float2 *x, const float2 *tws, const float2 *tws_g, const int tid) {
-    dit_pass<3>(x, tws, 0, tid);
-    dit_pass<3>(x, tws, 3, tid);
-    dit_pass<3>(x, tws, 6, tid);
-    dit_pass<3>(x, tws_g, 9, tid);
+    dit_pass<3, V>(x, tws, 0, tid);
+    dit_pass<3, V>(x, tws, 3, tid);
+    dit_pass<3, V>(x, tws, 6, tid);
+    dit_pass<3, V>(x, tws_g, 9, tid);
 }
+template <int V = 0>
 __device__ __forceinline__ void dft_ref(float2 *x, const float2 *tws, const float2 *tws_g, const int tid) {
-    dft_ref_head(x, tws, tws_g, tid);
-    dit_pass<1>(x, tws_g, 12, tid);
+    dft_ref_head<V>(x, tws, tws_g, tid);
+    dit_pass<1, V>(x, tws_g, 12, tid);
 }
 
 #endif

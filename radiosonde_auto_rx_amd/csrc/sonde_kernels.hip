@@ -13,6 +13,8 @@
 //                    windows and the FM-stream fallback are evaluated from the correlation ring)
 //   k_framesync      per-channel find_header / headcmp / read_softbit2p state machine + RS41 byte framing
 //                    + RS(255,231) syndromes (demod_mod.c:1533-1617,870-938,1087-1175; rs41mod.c:2900-2962)
+//   k_search_sync    both in one launch for the single-type engines: k_framesync's state machine evaluates each window it reaches
+//                    with k_sync_window_fft's code in its own LDS (the rounds above remain for mixed engines)
 //   k_dc_update      running IQ-DC mean hand-over at segment boundaries (demod_mod.c:495-504)
 //
 // One wave = 64 lanes everywhere.  No CUDA compatibility paths.
@@ -1698,14 +1700,14 @@ __device__ __forceinline__ double window_sum(const float *bufs, uint32_t base, u
 // DC (--dc, :174-188): the reference zeroes bin 0 of the zero-padded N-point transform, i.e. subtracts mu = sum(window)/N
 // from every sample including the padding; the circular correlation then drops by mu * sum(match) at every lag and
 // the norm runs over (x - mu).  Returns the peak index 0..K, or -4 (edge / empty window); mv, mpos only when >= 0.
-template <bool DC>
+template <bool DC, int NT = FS_THREADS>
 __device__ __forceinline__ int fs_window(const float *x, const float *corr, uint32_t mask, uint32_t pos, int K, int L, int N,
                                          float match_sum, int tid, int lane, int wave, float *s_rf, int *s_ri,
                                          float &mv, uint32_t &mpos) {
     float mu = 0.f;
     if (DC) {
         float s = 0.f;
-        for (int t = tid; t < K + L; t += FS_THREADS) {
+        for (int t = tid; t < K + L; t += NT) {
             const int64_t p = (int64_t)pos - (K + L - 1) + t;
             if (p >= 0) s += x[(uint32_t)p & mask];
         }
@@ -1713,7 +1715,7 @@ __device__ __forceinline__ int fs_window(const float *x, const float *corr, uint
         if (lane == 0) s_rf[wave] = s;
         __syncthreads();
         s = 0.f;
-        for (int w = 0; w < (FS_THREADS / WAVE); w++) s += s_rf[w];
+        for (int w = 0; w < (NT / WAVE); w++) s += s_rf[w];
         __syncthreads();
         mu = s / (float)N;
     }
@@ -1723,7 +1725,7 @@ __device__ __forceinline__ int fs_window(const float *x, const float *corr, uint
         float cv[8];
 #pragma unroll
         for (int u = 0; u < 8; u++) {
-            const int t = tid + u * FS_THREADS;
+            const int t = tid + u * NT;
             const int64_t p = (int64_t)pos - K + t;
             cv[u] = (t <= K && p >= 0) ? corr[(uint32_t)p & mask] : 0.f;
             if (DC) cv[u] = (t <= K) ? cv[u] - off : 0.f;
@@ -1731,9 +1733,9 @@ __device__ __forceinline__ int fs_window(const float *x, const float *corr, uint
 #pragma unroll
         for (int u = 0; u < 8; u++) {
             const float c2 = cv[u] * cv[u];
-            if (c2 > best) { best = c2; bidx = tid + u * FS_THREADS; }
+            if (c2 > best) { best = c2; bidx = tid + u * NT; }
         }
-        for (int t = tid + 8 * FS_THREADS; t <= K; t += FS_THREADS) {      // K > 8191 only
+        for (int t = tid + 8 * NT; t <= K; t += NT) {      // K >= 8 NT only
             const int64_t p = (int64_t)pos - K + t;
             float c = (p >= 0) ? corr[(uint32_t)p & mask] : 0.f;
             if (DC) c -= off;
@@ -1747,7 +1749,7 @@ __device__ __forceinline__ int fs_window(const float *x, const float *corr, uint
     if (lane == 0) { s_rf[wave] = best; s_ri[wave] = bidx; }
     __syncthreads();
     best = 0.f; bidx = -1;
-    for (int w = 0; w < (FS_THREADS / WAVE); w++) {
+    for (int w = 0; w < (NT / WAVE); w++) {
         const float ob = s_rf[w]; const int oi = s_ri[w];
         if (ob > best || (ob == best && oi >= 0 && (bidx < 0 || oi < bidx))) { best = ob; bidx = oi; }
     }
@@ -1756,7 +1758,7 @@ __device__ __forceinline__ int fs_window(const float *x, const float *corr, uint
     if (bidx == 0 || bidx == K) return -4;                         // edge value -> -4 (mv stays 0)
     mpos = pos - (uint32_t)K + (uint32_t)bidx;
     float e = 0.f;
-    for (int t = tid; t < L; t += FS_THREADS) {
+    for (int t = tid; t < L; t += NT) {
         const int64_t p = (int64_t)mpos - t;
         float v = (p >= 0) ? x[(uint32_t)p & mask] : 0.f;
         if (DC) v -= mu;
@@ -1766,7 +1768,7 @@ __device__ __forceinline__ int fs_window(const float *x, const float *corr, uint
     if (lane == 0) s_rf[wave] = e;
     __syncthreads();
     e = 0.f;
-    for (int w = 0; w < (FS_THREADS / WAVE); w++) e += s_rf[w];
+    for (int w = 0; w < (NT / WAVE); w++) e += s_rf[w];
     __syncthreads();
     float c = corr[mpos & mask];
     if (DC) c -= off;
@@ -1774,22 +1776,28 @@ __device__ __forceinline__ int fs_window(const float *x, const float *corr, uint
     return bidx;
 }
 
-// One workgroup of 16 waves per channel.  The state machine is evaluated redundantly by every thread (all
+// One workgroup of 16 waves per channel (k_search_sync: 8).  The state machine is evaluated redundantly by every thread (all
 // decisions depend only on workgroup-uniform values); the data-parallel parts — window arg-max (K+1 candidates),
-// L-sample energy, header bit check, the nbits soft bits, RS syndromes — are spread over the 1024 threads so that
+// L-sample energy, header bit check, the nbits soft bits, RS syndromes — are spread over the NT threads so that
 // each phase costs about one memory round trip instead of a chain of them.
-template <bool DC>
-__device__ __forceinline__ void framesync_body(const SyncArgs &a, const int ch) {
+// NT threads per workgroup; Eval: how a window on the transform path is evaluated — NoWinEval looks it up in the table k_sync_window_fft
+// filled (a.win), k_search_sync passes one that transforms it in the workgroup's own LDS (SearchWinEval).
+struct NoWinEval {
+    static constexpr bool fused = false;
+    __device__ int operator()(int, uint32_t, float &, uint32_t &) const { return -4; }
+};
+template <bool DC, int NT = FS_THREADS, class Eval = NoWinEval>
+__device__ __forceinline__ void framesync_body(const SyncArgs &a, const int ch, const Eval &eval = Eval{}) {
     __shared__ uint8_t s_frame[520];
     __shared__ uint8_t s_exp[512];
     __shared__ uint8_t s_log[256];
-    __shared__ float s_rf[(FS_THREADS / WAVE)];
-    __shared__ int s_ri[(FS_THREADS / WAVE)];
+    __shared__ float s_rf[(NT / WAVE)];
+    __shared__ int s_ri[(NT / WAVE)];
     __shared__ int s_cnt[2];
     __shared__ unsigned s_slot;
-    __shared__ uint8_t s_syn[(FS_THREADS / WAVE)][48];
+    __shared__ uint8_t s_syn[(NT / WAVE)][48];
     __shared__ uint8_t s_S[48];                // first-pass syndromes of the frame in hand
-    __shared__ double s_rd[(FS_THREADS / WAVE)];
+    __shared__ double s_rd[(NT / WAVE)];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (ch >= a.n_ch) return;
     const uint32_t mask = (uint32_t)a.ring_len - 1;
@@ -1806,8 +1814,8 @@ __device__ __forceinline__ void framesync_body(const SyncArgs &a, const int ch) 
     // profiling aid (SONDE_WF_PROF): thread 0 of channel 0 adds the shader-clock cycles since the previous mark to phase k
 #define FS_MARK(k) do { if (a.prof && ch == 0 && tid == 0) { const unsigned long long t_ = __builtin_readcyclecounter(); a.prof[k] += t_ - t_prev; t_prev = t_; } } while (0)
     unsigned long long t_prev = a.prof ? __builtin_readcyclecounter() : 0ull;
-    for (int i = tid; i < 512; i += FS_THREADS) s_exp[i] = a.gf_exp[i];
-    for (int i = tid; i < 256; i += FS_THREADS) s_log[i] = a.gf_log[i];
+    for (int i = tid; i < 512; i += NT) s_exp[i] = a.gf_exp[i];
+    for (int i = tid; i < 256; i += NT) s_log[i] = a.gf_log[i];
     __syncthreads();
     FS_MARK(0);
     // pass 1 of two: the correlation ring is valid below this end position only (corr_tile_unused with the same state and limit)
@@ -1825,7 +1833,7 @@ __device__ __forceinline__ void framesync_body(const SyncArgs &a, const int ch) 
             if (horizon_on && (int32_t)(s_in_w - 1 - (uint32_t)a.delay - horizon) >= 0) break;      // this window is pass 2's
             const uint32_t pos = s_in_w - 1 - (uint32_t)a.delay;      // sample_out
             const WinItem *wi = nullptr;
-            if (!DC && a.win && pos >= (uint32_t)L) {                  // precomputed with the reference's transform (k_sync_window_fft)
+            if (!DC && !Eval::fused && a.win && pos >= (uint32_t)L) {  // precomputed with the reference's transform (k_sync_window_fft)
                 for (int w = 0; w < a.win_W; w++) { const WinItem *c = a.win + (size_t)ch * a.win_W + w; if (c->state == 2 && c->pos == pos) { wi = c; break; } }
                 if (!wi) break;                                        // planned windows used up: the next round continues here
             }
@@ -1833,8 +1841,11 @@ __device__ __forceinline__ void framesync_body(const SyncArgs &a, const int ch) 
             if (pos - ep < (uint32_t)L) continue;                      // getCorrDFT returns -2 (position counted from the channel's stream start)
             float mv; uint32_t mpos;
             if (wi) { if (wi->rc < 0) { if (wi->rc == -5) st.mv_pos = wi->mpos; continue; } mv = wi->mv; mpos = wi->mpos; }
-            else {
-                const int rc = fs_window<DC>(bufs, corr, mask, pos, K, L, a.N, a.match_sum, tid, lane, wave, s_rf, s_ri, mv, mpos);
+            else if (Eval::fused && pos >= (uint32_t)L) {              // the reference's transform, here and now (k_search_sync)
+                const int rc = eval(ch, pos, mv, mpos);
+                if (rc < 0) { if (rc == -5) st.mv_pos = mpos; continue; }
+            } else {
+                const int rc = fs_window<DC, NT>(bufs, corr, mask, pos, K, L, a.N, a.match_sum, tid, lane, wave, s_rf, s_ri, mv, mpos);
                 if (rc == -5) { st.mv_pos = mpos; if (DC) af.dc = 0.0; }       // an all-zero window: position taken, nothing found (getCorrDFT with mp = -1)
                 if (rc < 0) continue;
             }
@@ -1847,19 +1858,19 @@ __device__ __forceinline__ void framesync_body(const SyncArgs &a, const int ch) 
                 uint32_t dpos = mpos, mv2_pos = 0;
                 if (a.opt_iq >= 2 && fabsf(mv) < a.thres) {
                     float mv2; uint32_t mpos2;
-                    if (fs_window<true>(fm, a.corr2 + (size_t)ch * a.ring_len, mask, pos, K, L, a.N, a.match_sum, tid, lane, wave, s_rf, s_ri, mv2, mpos2) < 0) continue;
+                    if (fs_window<true, NT>(fm, a.corr2 + (size_t)ch * a.ring_len, mask, pos, K, L, a.N, a.match_sum, tid, lane, wave, s_rf, s_ri, mv2, mpos2) < 0) continue;
                     mv2_pos = (uint32_t)((float)mpos2 - hofs);
                     dpos = mpos2;
                     if (mv2 > a.thres || mv2 < -a.thres) { st.mv = mv2; st.mv_pos = mv2_pos; }
                 }
                 const int mp_ofs = (a.opt_iq >= 2 && mv2_pos == 0) ? (int)hofs : 0;
                 double dsum = 0.0;
-                for (int t = tid; t < L; t += FS_THREADS) dsum += (double)fm[((uint32_t)mp_ofs + dpos - (uint32_t)t) & mask];
+                for (int t = tid; t < L; t += NT) dsum += (double)fm[((uint32_t)mp_ofs + dpos - (uint32_t)t) & mask];
                 for (int o = 32; o > 0; o >>= 1) dsum += __shfl_xor(dsum, o);
                 if (lane == 0) s_rd[wave] = dsum;
                 __syncthreads();
                 dsum = 0.0;
-                for (int w = 0; w < (FS_THREADS / WAVE); w++) dsum += s_rd[w];
+                for (int w = 0; w < (NT / WAVE); w++) dsum += s_rd[w];
                 __syncthreads();
                 af.dc = dsum / (double)(float)L;
                 mv = st.mv; mpos = st.mv_pos;
@@ -1895,7 +1906,7 @@ __device__ __forceinline__ void framesync_body(const SyncArgs &a, const int ch) 
             const int nsym = a.hdrlen / a.symhd;
             const uint32_t mvp = mpos + 1 - (uint32_t)L;
             const double hdc = (DC && a.opt_iq < 2) ? af.dc : 0.0;     // read_bufbit: bufs - dc for the FM-sliced forms (demod_mod.c:879)
-            for (int p = tid; p < nsym; p += FS_THREADS) {
+            for (int p = tid; p < nsym; p += NT) {
                 double edge = (double)((float)(p * a.symhd) * a.sps);
                 uint32_t cnt = (uint32_t)ceil(edge);
                 double sum = 0.0;
@@ -1922,7 +1933,7 @@ __device__ __forceinline__ void framesync_body(const SyncArgs &a, const int ch) 
             if (lane == 0) s_ri[wave] = errs;
             __syncthreads();
             errs = 0;
-            for (int w = 0; w < (FS_THREADS / WAVE); w++) errs += s_ri[w];
+            for (int w = 0; w < (NT / WAVE); w++) errs += s_ri[w];
             __syncthreads();
             FS_MARK(2);
             if (errs > a.hdmax) continue;
@@ -1941,12 +1952,12 @@ __device__ __forceinline__ void framesync_body(const SyncArgs &a, const int ch) 
             const int32_t q_lim = enough ? (int32_t)a.frame_samples : (int32_t)(avail - (st.mv_pos + (uint32_t)a.delay + 1));
             const uint32_t base = st.mv_pos + 1 + (uint32_t)a.bitofs;
             if (tid == 0) { s_slot = atomicAdd(a.frame_count, 1u) % (unsigned)a.max_frames; s_cnt[0] = 0; s_cnt[1] = 0; }
-            for (int i = tid; i < 520; i += FS_THREADS) s_frame[i] = (a.rs41 && i < 8) ? a.hdr_bytes[i] : 0;
+            for (int i = tid; i < 520; i += NT) s_frame[i] = (a.rs41 && i < 8) ? a.hdr_bytes[i] : 0;
             __syncthreads();
             const unsigned slot = s_slot;                              // monotonic counter, ring of records
             FrameRec *rec = a.frames + slot;
             FS_MARK(3);
-            for (int p0 = 0; p0 < a.nbits; p0 += FS_THREADS) {
+            for (int p0 = 0; p0 < a.nbits; p0 += NT) {
                 const int bp = p0 + tid;
                 double sum = 0.0;
                 bool valid = bp < a.nbits;
@@ -2011,7 +2022,7 @@ __device__ __forceinline__ void framesync_body(const SyncArgs &a, const int ch) 
                     const int cw = lane / 24, jx = lane % 24;
                     const uint8_t x = s_exp[jx];
                     uint8_t hsum = 0;
-                    constexpr int CH = 256 / (FS_THREADS / WAVE);                  // coefficients per wave
+                    constexpr int CH = 256 / (NT / WAVE);                  // coefficients per wave
                     for (int i = CH - 1; i >= 0; i--) {
                         const int n = CH * wave + i;
                         uint8_t v = 0;
@@ -2026,17 +2037,17 @@ __device__ __forceinline__ void framesync_body(const SyncArgs &a, const int ch) 
                     s_syn[wave][lane] = hsum ? s_exp[(s_log[hsum] + sh) % 255] : 0;
                 }
                 __syncthreads();
-                if (tid < 48) { uint8_t syn = 0; for (int w = 0; w < (FS_THREADS / WAVE); w++) syn ^= s_syn[w][tid]; s_S[tid] = syn; }
+                if (tid < 48) { uint8_t syn = 0; for (int w = 0; w < (NT / WAVE); w++) syn ^= s_syn[w][tid]; s_S[tid] = syn; }
                 __syncthreads();
                 if (a.ecc_level > 0 && 8 + nbytes_ok >= 518) {
                     bool clean = true;
                     for (int k = 0; k < 48; k++) clean &= (s_S[k] == 0);
-                    if (clean) { ecc_done = 1; for (int i = flen + tid; i < 518; i += FS_THREADS) s_frame[i] = 0; }
+                    if (clean) { ecc_done = 1; for (int i = flen + tid; i < 518; i += NT) s_frame[i] = 0; }
                     else if (a.ecc_list) { ecc_done = 2; if (tid == 0) a.ecc_list[atomicAdd(a.ecc_count, 1u) % (unsigned)a.max_frames] = slot; }
                 }
             }
             __syncthreads();
-            for (int i = tid; i < 518; i += FS_THREADS) rec->frame[i] = s_frame[i];
+            for (int i = tid; i < 518; i += NT) rec->frame[i] = s_frame[i];
             if (a.rs41 && tid < 48) rec->synd[tid] = s_S[tid];
             if (tid == 0) {
                 rec->channel = ch; rec->mv = st.mv; rec->mv_pos = st.mv_pos; rec->len = a.rs41 ? flen : a.nbits; rec->nbytes = a.rs41 ? 8 + nbytes_ok : nbits_ok;
@@ -2142,12 +2153,22 @@ __global__ void k_sync_plan_multi(const MultiArgs<WinPlanArgs> m) {
 #endif
 // profiling aid (SONDE_WF_PROF): thread 0 of workgroup 0 adds the shader-clock cycles since the previous mark to phase k
 #define WF_MARK(k) do { if (a.prof && blockIdx.x == 0 && tid == 0) { const unsigned long long t_ = __builtin_readcyclecounter(); a.prof[k] += t_ - t_prev; t_prev = t_; } } while (0)
-__device__ __forceinline__ void sync_eval_window(const WinFftArgs &a, const int ch, WinItem *it, float2 *x, float2 *tws, float *s_rf, int *s_ri) {
+// Io: where the window comes from and its result goes — io.planned() (else nothing is done), io.pos(), and io.put(rc, mv, mpos) from thread 0:
+// rc = peak index, -4 (edge value) or -5 (nothing above zero).  WinItemIo: an item of the table k_sync_plan filled.
+struct WinItemIo {
+    static constexpr int copy = 0;            // the transform's instantiation (dit_pass)
+    WinItem *it;
+    __device__ bool planned() const { return it->state == 1; }
+    __device__ uint32_t pos() const { return it->pos; }
+    __device__ void put(int rc, float mv, uint32_t mpos) const { it->rc = rc; it->mv = mv; it->mpos = mpos; __threadfence(); it->state = 2; }
+};
+template <class Io>
+__device__ __forceinline__ void sync_eval_window(const WinFftArgs &a, const int ch, const Io &io, float2 *x, float2 *tws, float *s_rf, int *s_ri) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (it->state != 1) return;
+    if (!io.planned()) return;
     unsigned long long t_prev = a.prof ? __builtin_readcyclecounter() : 0ull;
     const int K = a.K, L = a.L, N = SC_N, wl = K + L;
-    const uint32_t pos = it->pos, mask = (uint32_t)a.ring_len - 1;
+    const uint32_t pos = io.pos(), mask = (uint32_t)a.ring_len - 1;
     const float *bufs = a.bufs + (size_t)ch * a.ring_len;
     const int64_t start = (int64_t)pos - (wl - 1);
     // xn[i] = bufs[pos - (K+L-1) + i], i < K+L, zero padded (:168-169); bit-reversed for the DIT network, natural order for the norm
@@ -2169,7 +2190,7 @@ __device__ __forceinline__ void sync_eval_window(const WinFftArgs &a, const int 
     }
     __syncthreads();
     WF_MARK(0);
-    dft_ref(x, tws, a.tws, tid);                                         // X = rdft(xn)
+    dft_ref<Io::copy>(x, tws, a.tws, tid);                                         // X = rdft(xn)
     WF_MARK(1);
     // Z = X * Fm (:190); Nidft() transforms conj(Z) (:78-80): conjugate and swap into bit-reversed order for the same network.
     // Pairs (i, r = brev(i)), r >= i; Fm[r] comes from the bit-reversed copy of the table behind it (a.Fm + N) — coalesced like Fm[i]
@@ -2197,7 +2218,7 @@ __device__ __forceinline__ void sync_eval_window(const WinFftArgs &a, const int 
     }
     __syncthreads();
     WF_MARK(2);
-    dft_ref_head(x, tws, a.tws, tid);                                    // cx = Nidft(Z), real part used
+    dft_ref_head<Io::copy>(x, tws, a.tws, tid);                                    // cx = Nidft(Z), real part used
     // last stage (dit_pass<1> at t = 12) in registers: only re(cx) is looked at, so nothing is stored — the arg-max of re(cx)^2 over
     // i in [L-1, K+L), first maximum wins (:200-207), is taken from the butterfly outputs as they come
     float best = 0.f, bestc = 0.f; int bidx = -1;
@@ -2235,11 +2256,11 @@ __device__ __forceinline__ void sync_eval_window(const WinFftArgs &a, const int 
         // not one correlation value above zero — a stream that begins with digital silence.  The reference's loop leaves mp = -1 (:200-207), which is no edge value:
         // getCorrDFT runs on and sets mv = 0 / (a norm read in front of the array) and mv_pos = pos - (K + L - 1) - 1, which wraps in the first window of a stream —
         // and `mv_pos > mvpos0` (find_header, :1603) then fails for the header the NEXT window finds.  Handed on as rc = -5 (k_framesync takes the position)
-        if (tid == 0) { it->rc = -5; it->mv = 0.f; it->mpos = pos - (uint32_t)(wl - 1) - 1u; __threadfence(); it->state = 2; }
+        if (tid == 0) io.put(-5, 0.f, pos - (uint32_t)(wl - 1) - 1u);
         return;
     }
     if (mp == L - 1 || mp == wl - 1) {                                    // edge value: -4 (:208)
-        if (tid == 0) { it->rc = -4; it->mv = 0.f; it->mpos = 0; __threadfence(); it->state = 2; }
+        if (tid == 0) io.put(-4, 0.f, 0u);
         return;
     }
     // xnorm = sqrt(sum_{i<L} xn[mp-i]^2) (:215-217); mx /= xnorm * N
@@ -2257,8 +2278,7 @@ __device__ __forceinline__ void sync_eval_window(const WinFftArgs &a, const int 
         float es = 0.f;
         for (int w = 0; w < WF_THREADS / WAVE; w++) es += s_rf[w];
         const float xnorm = sqrtf(es);
-        it->rc = mp; it->mv = s_rf[WF_THREADS / WAVE] / (xnorm * (float)N); it->mpos = pos - (uint32_t)(wl - 1) + (uint32_t)mp;
-        __threadfence(); it->state = 2;
+        io.put(mp, s_rf[WF_THREADS / WAVE] / (xnorm * (float)N), pos - (uint32_t)(wl - 1) + (uint32_t)mp);
     }
     WF_MARK(5);
     if (a.prof && blockIdx.x == 0 && tid == 0) a.prof[15] += 1;
@@ -2285,7 +2305,7 @@ __device__ __forceinline__ void sync_window_fft_body(const WinFftArgs &a, const 
     for (uint32_t w = b; w < count; w += nb) {
         const uint32_t item = a.work[w];
         __syncthreads();                         // the previous window's last reads of x / s_rf are over
-        sync_eval_window(a, (int)(item / (uint32_t)a.stride), a.items + item, x, tws, s_rf, s_ri);
+        sync_eval_window(a, (int)(item / (uint32_t)a.stride), WinItemIo{a.items + item}, x, tws, s_rf, s_ri);
     }
 }
 __global__ __launch_bounds__(WF_THREADS) WF_WAVES_ATTR
@@ -2297,6 +2317,47 @@ void k_sync_window_fft_multi(const MultiArgs<WinFftArgs> m) {
     sync_window_fft_body(m.g[g], blockIdx.x - (uint32_t)m.row0[g], (uint32_t)(m.row0[g + 1] - m.row0[g]));
 }
 #pragma clang fp contract(fast)
+
+// ------------------------------------------------------------------------------------------------
+// k_search_sync: header search and frame sync of a single-type engine on the transform path, one launch per call
+// ------------------------------------------------------------------------------------------------
+// One workgroup per channel runs framesync_body; every window its search reaches is evaluated on the spot by sync_eval_window in the
+// workgroup's own LDS — the code and thread count of k_sync_window_fft, so the same bits.  Only the windows the reference evaluates are
+// transformed (a round of k_sync_plan -> k_sync_window_fft -> k_framesync also transforms the planned windows behind a hit), and a call is
+// one launch instead of three per round.  76 KB of LDS and 512 threads: two workgroups per CU, 512 channels are one wave of workgroups.
+// (framesync_body is defined under contraction `fast`, sync_eval_window under `off`: each keeps its own mode here.)
+struct LdsWinIo {              // window `at`, the result to the workgroup's LDS
+    static constexpr int copy = 1;
+    uint32_t at; int *rc_; float *mv_; uint32_t *mpos_;
+    __device__ bool planned() const { return true; }
+    __device__ uint32_t pos() const { return at; }
+    __device__ void put(int rc, float mv, uint32_t mpos) const { *rc_ = rc; *mv_ = mv; *mpos_ = mpos; }
+};
+struct SearchWinEval {
+    static constexpr bool fused = true;
+    const WinFftArgs &a; float2 *x, *tws; float *s_rf; int *s_ri;
+    int *s_rc; float *s_mv; uint32_t *s_mpos;       // the result, from thread 0 to the workgroup
+    unsigned long long *wcount;
+    __device__ int operator()(int ch, uint32_t pos, float &mv, uint32_t &mpos) const {
+        sync_eval_window(a, ch, LdsWinIo{pos, s_rc, s_mv, s_mpos}, x, tws, s_rf, s_ri);
+        if (wcount && threadIdx.x == 0) atomicAdd(wcount, 1ull);
+        __syncthreads();                 // (the next window writes x only after the barriers of this one's last reads)
+        mv = *s_mv; mpos = *s_mpos;
+        return *s_rc;
+    }
+};
+__global__ __launch_bounds__(WF_THREADS) WF_WAVES_ATTR
+void k_search_sync(const SearchSyncArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float2 smem_ss[];
+    float2 *x = smem_ss;                         // [SC_XN] padded (XI)
+    float2 *tws = smem_ss + SC_XN;               // [SC_TW_LDS + 1] twiddles of stages 0..8
+    __shared__ float s_rf[WF_THREADS / WAVE + 1];
+    __shared__ int s_ri[WF_THREADS / WAVE];
+    __shared__ int s_rc; __shared__ float s_mv; __shared__ uint32_t s_mpos;
+    for (int k = threadIdx.x; k < SC_TW_LDS; k += WF_THREADS) tws[k] = a.win.tws[k];      // (framesync_body's first barrier publishes them)
+    const SearchWinEval ev{a.win, x, tws, s_rf, s_ri, &s_rc, &s_mv, &s_mpos, a.wcount};
+    framesync_body<false, WF_THREADS>(a.sync, (int)blockIdx.x, ev);
+}
 
 // ------------------------------------------------------------------------------------------------
 // launch wrappers (called from sonde_engine.cpp)
@@ -2600,4 +2661,8 @@ extern "C" int sonde_launch_framesync_multi(const SyncArgs *a, int n_groups, hip
 extern "C" void sonde_launch_framesync(const SyncArgs *a, hipStream_t s) {
     if (a->opt_dc) hipLaunchKernelGGL(k_framesync<true>, dim3(a->n_ch), dim3(FS_THREADS), 0, s, *a);
     else hipLaunchKernelGGL(k_framesync<false>, dim3(a->n_ch), dim3(FS_THREADS), 0, s, *a);
+}
+extern "C" void sonde_launch_search_sync(const SearchSyncArgs *a, hipStream_t s) {
+    const size_t lds = (size_t)(SC_XN + SC_TW_LDS + 1) * sizeof(float2);
+    hipLaunchKernelGGL(k_search_sync, dim3(a->sync.n_ch), dim3(WF_THREADS), lds, s, *a);
 }

@@ -128,6 +128,9 @@ def lib() -> C.CDLL:
         L.sonde_engine_host_ecc_frames.argtypes = [C.c_void_p]
         L.sonde_engine_host_ecc_frames.restype = C.c_longlong
         L.sonde_engine_set_device_ecc.argtypes = [C.c_void_p, C.c_int32]
+        L.sonde_engine_set_search_rounds.argtypes = [C.c_void_p, C.c_int32]
+        L.sonde_engine_count_windows.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+        L.sonde_engine_read_sync_state.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
         L.sonde_rs41_ecc_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
@@ -260,6 +263,22 @@ class Engine:
 
     def set_device_ecc(self, on: bool):
         _chk(lib().sonde_engine_set_device_ecc(self._h, 1 if on else 0))
+
+    def set_search_rounds(self, on: bool):
+        """on: header search in rounds (k_sync_plan -> k_sync_window_fft -> k_framesync) instead of one k_search_sync launch per call (tests)"""
+        _chk(lib().sonde_engine_set_search_rounds(self._h, 1 if on else 0))
+
+    def count_windows(self, on: bool = True):
+        """-> windows transformed so far {"round0", "rounds", "search_sync"}; on: keep counting (include/sonde_hip.h)"""
+        out = np.zeros(3, dtype=np.int64)
+        _chk(lib().sonde_engine_count_windows(self._h, 1 if on else 0, out.ctypes.data))
+        return {"round0": int(out[0]), "rounds": int(out[1]), "search_sync": int(out[2])}
+
+    def sync_state(self) -> np.ndarray:
+        """per-channel sync state after the calls so far: [n_channels, 8] uint32 {sample_in, k, mv_pos, mode, mv bits, inv, 0, 0}"""
+        out = np.zeros((self.n_channels, 8), dtype=np.uint32)
+        _chk(lib().sonde_engine_read_sync_state(self._h, out.ctypes.data, self.n_channels))
+        return out
 
     def fetch_frames(self, max_frames: int | None = None, with_soft: bool = False, finish: bool = False):
         """Frames completed so far; finish=True = end of input (also emits the frame in progress, like the reference at EOF)."""
