@@ -8,6 +8,7 @@
 //   design_mixer     16-Hz-snapped mixer frequency + table period           demod_mod.c:1262-1296
 //   design_match     Gaussian-pulse header template, 2-norm                demod_mod.c:1190-1195,1398-1421
 //   design_imet4     imet4iq's IF rate / decM, IF tap sets, FM low-pass    imet4iq.c:600-646,692-741
+//   design_mk2a      mk2a1680mod's L-band rates, tap sets, K/L/M, template   mk2a1680mod.c:1141-1442,2285-2343
 #include "sonde_host.h"
 #include <cmath>
 
@@ -230,6 +231,142 @@ Imet4Design design_imet4(int sr_base, bool iq, bool if_min, bool imet1, float lp
     if (sr > 100e3) tfm = tfm / 2;
     if (tfm % 2 == 0) tfm++;
     d.lp_fm = design_lowpass(f_fm, tfm);
+    return d;
+}
+
+// mk2a1680mod: main's option handling (:2285-2343) and init_buffers_Lband (:1141-1442).  The L-band copy of the demod DSP has its own rules:
+// designated IF 4 x 48 kHz (4 x 32 kHz with --min) raised to a divisor of the input rate, decimator pass band (IF + 60 kHz) / 4 and
+// transition IF - 180 kHz, IF low-pass of 4 sr / 8 kHz taps halved above 100 and again above 200 kHz in an acquisition (1.5 x) and a nominal
+// set, FM low-pass 6.8 kHz (--iq) / 8 kHz (--IQ) doubled and shortened under --decFM, the IQFM low-pass of --IQ --decFM, N forced to 8192,
+// K <= 790 bits (the header distance), and the header template with t in double.
+Mk2aDesign design_mk2a(int sr_base, int opt_iq, bool lp_iq, float lpiq_bw, bool lp_fm, int opt_decFM, bool dc, bool if_min, float baud, int shift) {
+    Mk2aDesign d;
+    int lp = (lp_iq ? 1 : 0) | (lp_fm ? 2 : 0);
+    if (opt_decFM) {
+        lp |= opt_iq == 5 ? 4 : 2;
+        if (sr_base > 4 * 44000) d.fmdec = 1;
+    }
+    float sps = (float)sr_base / 9616.0f;
+    d.decFM = 1;
+    if (d.fmdec) {
+        d.decFM = opt_decFM;
+        while (sr_base % d.decFM > 0 && d.decFM > 1) d.decFM /= 2;
+        sps /= (float)d.decFM;
+    }
+    if (opt_iq == 5 && dc) lp |= 2;
+    d.lp = lp;
+    const int lpIQ_bw = (int)lpiq_bw;
+    const int lpFM_bw = opt_iq == 6 ? (int)6.8e3 : (int)8e3;
+    if (baud > 0) sps = (float)sr_base / baud;                        // (:2321-2325: the FM decimation is not taken into account again)
+    // decimator (:1157-1194)
+    int if_sr = if_min ? 32000 * 4 : 48000 * 4;
+    d.decM = 1;
+    if (if_sr > sr_base) if_sr = sr_base;
+    if (if_sr < sr_base) {
+        while (sr_base % if_sr) if_sr += 1;
+        d.decM = sr_base / if_sr;
+    }
+    if (d.decM > 1) {
+        const float f_lp = (float)((if_sr + 60e3) / (4.0 * sr_base));
+        float t_bw = (float)(if_sr - 180e3);
+        if (if_min) t_bw = (float)(if_sr - 80e3);
+        if (t_bw < 0) t_bw = 160e3f;
+        t_bw /= sr_base;
+        int taps = (int)(4.0 / t_bw);
+        if (taps % 2 == 0) taps++;
+        d.lp_dec = design_lowpass(f_lp, taps);
+    }
+    d.if_sr = if_sr;
+    const int sr = if_sr;
+    sps /= (float)d.decM;
+    d.sps = sps;
+    if (lp & 1) {                                                     // IF low-pass (:1241-1267)
+        float f_lp = (float)(160e3 / (float)sr / 2.0);
+        if (lpIQ_bw) f_lp = (float)(lpIQ_bw / (float)sr / 2.0);
+        int taps = (int)(4 * sr / 8e3);
+        if (sr > 100e3) taps = taps / 2;
+        if (sr > 200e3) taps = taps / 2;
+        if (taps % 2 == 0) taps++;
+        d.lp_iq0 = design_lowpass((float)(1.5 * f_lp), taps);
+        d.lp_iq1 = design_lowpass(f_lp, (int)d.lp_iq0.size());
+    }
+    if (lp & 2) {                                                     // FM low-pass (:1270-1292)
+        float f_lp = (float)(10e3 / (float)sr);
+        if (lpFM_bw > 0) f_lp = lpFM_bw / (float)sr;
+        int taps = (int)(4 * sr / 4e3);
+        if (d.decFM > 1) { f_lp *= 2; taps = taps / 2; }
+        if (sr > 100e3) taps = taps / 2;
+        if (sr > 200e3) taps = taps / 2;
+        if (opt_iq == 5) taps = taps / 2;
+        if (taps % 2 == 0) taps++;
+        d.lp_fm = design_lowpass(f_lp, taps);
+    }
+    if (lp & 4) {                                                     // IQFM low-pass (:1295-1318)
+        float f_lp = (float)(10e3 / (float)sr);
+        int taps = (int)(4 * sr / 4e3);
+        f_lp = (float)(f_lp * (2.0 * 2));
+        taps = taps / 2;
+        if (sr > 100e3) taps = taps / 2;
+        if (sr > 200e3) taps = taps / 2;
+        taps = taps / 2;
+        taps = taps / 2;
+        if (taps % 2 == 0) taps++;
+        d.lp_iqfm = design_lowpass(f_lp, taps);
+    }
+    // header window (:1330-1353)
+    const int hdrlen = 50;
+    const int L = (int)(hdrlen * sps + 0.5);
+    int M = 3 * L;
+    d.delay = L / 16;
+    int p2 = 1;
+    while (p2 < M) p2 <<= 1;
+    while (p2 < 0x2000) p2 <<= 1;
+    M = p2;
+    int K = M - L - d.delay;
+    while (K > 790 * sps) K--;
+    d.L = L; d.M = M; d.N = p2; d.K = K;
+    // header template (:1366-1389): CA CA CA 24 52 in 8N1, BT = 1.0, t in double
+    static const char hdr[] = "0010100111" "0010100111" "0010100111" "0001001001" "0010010101";
+    const double sigma = std::sqrt(std::log(2)) / (kTwoPi * 1.0f);
+    d.match.resize(L);
+    for (int i = 0; i < L; i++) {
+        const int pos = (int)(i / sps);
+        const double t = (i - pos * sps) / sps - 0.5;
+        const float b1 = (float)(((hdr[pos] & 1) - 0.5) * 2.0);
+        float b = (float)(b1 * gauss_pulse(t, sigma));
+        if (pos > 0) {
+            const float b0 = (float)(((hdr[pos - 1] & 1) - 0.5) * 2.0);
+            b = (float)(b + b0 * gauss_pulse(t + 1, sigma));
+        }
+        if (pos < hdrlen - 1) {
+            const float b2 = (float)(((hdr[pos + 1] & 1) - 0.5) * 2.0);
+            b = (float)(b + b2 * gauss_pulse(t - 1, sigma));
+        }
+        d.match[i] = b;
+    }
+    double n2 = 0.0;
+    for (int i = 0; i < L; i++) { const double x = d.match[i]; n2 += x * x; }
+    const float nm = (float)std::sqrt(n2);
+    for (int i = 0; i < L; i++) d.match[i] /= nm;
+    // --IQ tone correlator (:881-902, :1433-1439)
+    d.f1 = -(d.h * sr) / (2.0 * sps);
+    d.tone_sps = sps * d.decFM;
+    {
+        int n = (int)d.tone_sps;
+        const float sk = d.tone_sps / 2.4f;
+        while (n > 0) {
+            n--;
+            if (n > sk && n < d.tone_sps - sk) d.tone_n.push_back(n);
+        }
+    }
+    // header dc offset of the --IQ form while locked (:465)
+    d.mp_ofs = (int)(((int)d.lp_fm.size() - (int)d.lp_iqfm.size() - (sps - 1)) / (2 * d.decFM));
+    // main (:2339-2343)
+    d.bitofs = (d.fmdec ? 0 : 1) + shift;
+    float bl = (float)(0.7 * sps / 2.0);
+    if (bl < 2.0) bl = -1;
+    if (d.fmdec) bl = -1;
+    d.bl = bl;
     return d;
 }
 

@@ -16,6 +16,16 @@ Decimator design_decimator_scan(int sr_base, bool if_min, float set_lpIQ);
 Decimator design_decimator_if(int sr_base, int if_target, bool narrow);
 struct Imet4Design { int if_sr = 0, decM = 1; std::vector<float> lp_iq0, lp_iq1, lp_fm, lp_dec; };
 Imet4Design design_imet4(int sr_base, bool iq, bool if_min, bool imet1, float lpiq_bw);
+// mk2a1680mod's L-band design (init_buffers_Lband and the option handling of its main)
+struct Mk2aDesign {
+    int if_sr = 0, decM = 1, decFM = 1, fmdec = 0, lp = 0;        // lp: 1 IF low-pass, 2 FM low-pass, 4 IQFM low-pass
+    float sps = 0, bl = -1, tone_sps = 0, h = 10.4f;
+    int L = 0, M = 0, K = 0, N = 0, delay = 0, bitofs = 0, mp_ofs = 0;
+    std::vector<float> lp_dec, lp_iq0, lp_iq1, lp_fm, lp_iqfm, match;
+    std::vector<int> tone_n;                                       // sample lags of the --IQ tone correlator, in the reference's order
+    double f1 = 0;                                                 // its lower tone (Hz); the upper one is -f1
+};
+Mk2aDesign design_mk2a(int sr_base, int opt_iq, bool lp_iq, float lpiq_bw, bool lp_fm, int opt_decFM, bool dc, bool if_min, float baud, int shift);
 struct Mixer { double f0 = 0; int lut_len = 1; };
 Mixer design_mixer(double xlt_fq, int sr_base);
 std::vector<float> design_match(const std::string &hdr, float sps, float bt);

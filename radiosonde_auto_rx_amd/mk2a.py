@@ -1,0 +1,174 @@
+"""ctypes mirror of include/sonde_mk2a.h: the LMS6-1680 / MkIIa engine (GPU, many channels per call) and its printer (host code).
+
+    eng = Mk2aEngine(fqs, 240000, lp_iq=True, lpbw_hz=160000, dec_fm=4, dc=True)     # auto_rx: --iq fq --lpIQ --lpbw 160 --decFM --dc
+    eng.process_host(x)           # x: (n_channels, n * 2) int16 IQ, n <= max_chunk, a multiple of dec_m
+    eng.finish()                  # at the end of the input: the frame in progress is handed out as it is
+    for f in eng.fetch_frames():  # {"channel", "bits", "mv", "df", "inv", "mv_pos", "sample"}
+        text = printer.frame(f["bits"], f["mv"], f["df"])
+
+Mk2aPrinter(json=True).frame(...) returns the characters the reference's mk2a1680mod prints for that frame."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from .engine import SondeError, lib
+
+MAX_BITS = 1760
+
+
+class Mk2aCfg(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("sample_rate", "bits", "opt_iq", "lp_iq", "lpbw_hz", "lp_fm", "dec_fm", "dc", "min", "invert", "shift")] + \
+               [("thres", C.c_float), ("baud", C.c_float), ("reserved", C.c_int32 * 7)]
+
+
+class Mk2aInfo(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("if_rate", "dec_m", "dec_fm", "L", "M", "K", "N", "taps_dec", "taps_iq", "taps_fm", "taps_iqfm")] + \
+               [("sps", C.c_float), ("reserved", C.c_int32 * 8)]
+
+
+class Mk2aFrame(C.Structure):
+    _fields_ = [("channel", C.c_int32), ("nbits", C.c_int32), ("inv", C.c_int32), ("mv", C.c_float), ("df", C.c_double), ("mv_pos", C.c_uint32),
+                ("reserved", C.c_uint32), ("sample", C.c_uint64), ("bits", C.c_uint8 * MAX_BITS)]
+
+
+class Mk2aOpts(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("raw", "crc", "vbs", "json", "jsn_freq_khz", "show_df", "if_rate", "sample_rate")] + \
+               [("version", C.c_char * 32), ("reserved", C.c_int32 * 4)]
+
+
+def _sigs(L):
+    if getattr(L, "_mk2a_sigs", False):
+        return L
+    P = C.c_void_p
+    L.sonde_mk2a_create.argtypes = [C.POINTER(Mk2aCfg), C.c_int32, C.POINTER(C.c_double), C.c_int32, C.POINTER(P)]
+    L.sonde_mk2a_destroy.argtypes = [P]
+    L.sonde_mk2a_destroy.restype = None
+    L.sonde_mk2a_info.argtypes = [P, C.POINTER(Mk2aInfo)]
+    L.sonde_mk2a_design.argtypes = [C.POINTER(Mk2aCfg), C.POINTER(Mk2aInfo)]
+    L.sonde_mk2a_process_host.argtypes = [P, P, C.c_int32]
+    L.sonde_mk2a_process_device.argtypes = [P, P, C.c_int32]
+    L.sonde_mk2a_finish.argtypes = [P]
+    L.sonde_mk2a_fetch_frames.argtypes = [P, C.POINTER(Mk2aFrame), C.c_int32]
+    L.sonde_mk2a_printer_create.argtypes = [C.POINTER(Mk2aOpts), C.POINTER(P)]
+    L.sonde_mk2a_printer_destroy.argtypes = [P]
+    L.sonde_mk2a_printer_destroy.restype = None
+    L.sonde_mk2a_print_frame.argtypes = [P, C.POINTER(C.c_uint8), C.c_int32, C.c_float, C.c_double, C.c_char_p, C.c_size_t]
+    L.sonde_mk2a_crc16.argtypes = [C.POINTER(C.c_uint8), C.c_int32]
+    L._mk2a_sigs = True
+    return L
+
+
+def crc16(data: bytes) -> int:
+    b = (C.c_uint8 * max(1, len(data))).from_buffer_copy(bytes(data) or b"\0")
+    return _sigs(lib()).sonde_mk2a_crc16(b, len(data))
+
+
+def _cfg(sr, bits, opt_iq, lp_iq, lpbw_hz, lp_fm, dec_fm, dc, min, invert, shift, thres, baud):
+    return Mk2aCfg(sample_rate=sr, bits=bits, opt_iq=opt_iq, lp_iq=int(lp_iq), lpbw_hz=int(lpbw_hz), lp_fm=int(lp_fm), dec_fm=int(dec_fm), dc=int(dc),
+                   min=int(min), invert=int(invert), shift=int(shift), thres=float(thres), baud=float(baud))
+
+
+def design(sr: int, *, bits: int = 16, opt_iq: int = 6, lp_iq: bool = True, lpbw_hz: int = 0, lp_fm: bool = False, dec_fm: int = 0, dc: bool = False,
+           min: bool = False, invert: bool = False, shift: int = 0, thres: float = 0.0, baud: float = 0.0) -> dict:
+    """the rates, tap counts and window sizes init_buffers_Lband derives for that configuration (host code, no GPU)"""
+    L = _sigs(lib())
+    cfg, inf = _cfg(sr, bits, opt_iq, lp_iq, lpbw_hz, lp_fm, dec_fm, dc, min, invert, shift, thres, baud), Mk2aInfo()
+    rc = L.sonde_mk2a_design(C.byref(cfg), C.byref(inf))
+    if rc:
+        raise SondeError(rc, "sonde_mk2a_design")
+    return {n: getattr(inf, n) for n, _ in Mk2aInfo._fields_ if n != "reserved"}
+
+
+class Mk2aPrinter:
+    """frame bits -> the reference's text / -r / -v.. / JSON lines (host code, no GPU)."""
+
+    def __init__(self, *, raw: bool = False, crc: bool = False, vbs: int = 0, json: bool = False, jsn_freq_khz: int = 0, show_df: bool = False,
+                 if_rate: int = 240000, sample_rate: int = 240000, version: str = ""):
+        self._L = _sigs(lib())
+        o = Mk2aOpts(raw=int(raw), crc=int(crc), vbs=int(vbs), json=int(json), jsn_freq_khz=int(jsn_freq_khz), show_df=int(show_df),
+                     if_rate=int(if_rate), sample_rate=int(sample_rate), version=version.encode())
+        self._p = C.c_void_p()
+        rc = self._L.sonde_mk2a_printer_create(C.byref(o), C.byref(self._p))
+        if rc:
+            raise SondeError(rc, "sonde_mk2a_printer_create")
+        self._out = C.create_string_buffer(1 << 16)
+
+    def frame(self, bits, mv: float = 0.0, df: float = 0.0) -> str:
+        b = np.ascontiguousarray(bits, dtype=np.uint8)
+        n = self._L.sonde_mk2a_print_frame(self._p, b.ctypes.data_as(C.POINTER(C.c_uint8)), len(b), mv, df, self._out, len(self._out))
+        if n < 0:
+            raise SondeError(n, "sonde_mk2a_print_frame")
+        return self._out.raw[:n].decode("latin-1")
+
+    def close(self):
+        if self._p:
+            self._L.sonde_mk2a_printer_destroy(self._p)
+            self._p = C.c_void_p()
+
+    __del__ = close
+
+
+class Mk2aEngine:
+    """k_mk2a_mix + k_mk2a behind sonde_mk2a_create: one channel per entry of fqs, all at sample rate sr."""
+
+    def __init__(self, fqs, sr: int, *, bits: int = 16, opt_iq: int = 6, lp_iq: bool = True, lpbw_hz: int = 160000, lp_fm: bool = False, dec_fm: int = 4,
+                 dc: bool = True, min: bool = False, invert: bool = False, shift: int = 0, thres: float = 0.0, baud: float = 0.0,
+                 max_chunk: int | None = None):
+        self._L = _sigs(lib())
+        self.n_ch = len(fqs)
+        self.bits = bits
+        self.max_chunk = int(max_chunk or sr // 4)
+        cfg = _cfg(sr, bits, opt_iq, lp_iq, lpbw_hz, lp_fm, dec_fm, dc, min, invert, shift, thres, baud)
+        fq = (C.c_double * self.n_ch)(*[float(f) for f in fqs])
+        self._e = C.c_void_p()
+        rc = self._L.sonde_mk2a_create(C.byref(cfg), self.n_ch, fq, self.max_chunk, C.byref(self._e))
+        if rc:
+            raise SondeError(rc, "sonde_mk2a_create")
+        inf = Mk2aInfo()
+        self._L.sonde_mk2a_info(self._e, C.byref(inf))
+        self.info = {n: getattr(inf, n) for n, _ in Mk2aInfo._fields_ if n != "reserved"}
+        self.if_rate, self.dec_m = inf.if_rate, inf.dec_m
+        self._buf = (Mk2aFrame * 32)()
+
+    @staticmethod
+    def dec_m_of(sr: int) -> int:
+        """the decimation the front end applies to an input rate (calls take whole multiples of it)"""
+        return design(sr)["dec_m"]
+
+    def process_host(self, x: np.ndarray):
+        dt = np.int16 if self.bits == 16 else np.uint8
+        x = np.ascontiguousarray(x, dtype=dt).reshape(self.n_ch, -1)
+        rc = self._L.sonde_mk2a_process_host(self._e, x.ctypes.data, x.shape[1] // 2)
+        if rc:
+            raise SondeError(rc, "sonde_mk2a_process_host")
+
+    def process_device(self, ptr: int, n: int):
+        rc = self._L.sonde_mk2a_process_device(self._e, C.c_void_p(ptr), n)
+        if rc:
+            raise SondeError(rc, "sonde_mk2a_process_device")
+
+    def finish(self):
+        rc = self._L.sonde_mk2a_finish(self._e)
+        if rc:
+            raise SondeError(rc, "sonde_mk2a_finish")
+
+    def fetch_frames(self) -> list[dict]:
+        out = []
+        while True:
+            k = self._L.sonde_mk2a_fetch_frames(self._e, self._buf, len(self._buf))
+            if k < 0:
+                raise SondeError(k, "sonde_mk2a_fetch_frames")
+            for f in self._buf[:k]:
+                out.append({"channel": f.channel, "sample": int(f.sample), "mv": float(f.mv), "df": float(f.df), "inv": f.inv, "mv_pos": f.mv_pos,
+                            "bits": np.frombuffer(bytes(f.bits), np.uint8)[:f.nbits].copy()})
+            if k < len(self._buf):
+                return out
+
+    def close(self):
+        if self._e:
+            self._L.sonde_mk2a_destroy(self._e)
+            self._e = C.c_void_p()
+
+    __del__ = close

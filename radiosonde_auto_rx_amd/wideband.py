@@ -21,10 +21,12 @@ from .engine import Engine, snap_fq
 from .scan import Scanner
 from .family import FAMILY, LMS_BASE, FamilyDecoder
 from .imet4 import Imet4Engine, Imet4Printer
+from .mk2a import Mk2aEngine, Mk2aPrinter
 from .telemetry import DfmTelemetry, M10Telemetry, M20Telemetry, Rs41Telemetry
 
 
 IMET_AFSK = ("IMET4", "IMET1RS")          # dft_detect's IMETafsk outcomes (sonde_scan.cpp): decoded by imet4.py
+MK2LMS = "MK2LMS"                         # LMS6-1680 / MkIIa (scan type 18): decoded by mk2a.py
 
 
 class WidebandReceiver:
@@ -58,6 +60,11 @@ class WidebandReceiver:
         if typ in IMET_AFSK:                                   # imet4iq --iq fq --lpIQ --dc (--imet1: 96 kHz IF), as auto_rx starts it
             eng = Imet4Engine([fq], self.sr, bits=16, iq=True, lp_iq=True, dc=True, imet1=(typ == "IMET1RS"), max_chunk=self.chunk)
             tel = Imet4Printer(json=True, jsn_freq_khz=khz, version=self.version)
+        elif typ == MK2LMS:                                    # mk2a1680mod --iq fq --lpIQ --lpbw 160 --decFM --dc, as auto_rx starts it
+            eng = Mk2aEngine([fq], self.sr, bits=16, opt_iq=6, lp_iq=True, lpbw_hz=160000, dec_fm=4, dc=True,
+                             max_chunk=self.chunk + Mk2aEngine.dec_m_of(self.sr))     # its own IF rule (4 x 48 kHz): pieces are cut for it in push()
+            tel = Mk2aPrinter(json=True, jsn_freq_khz=int((self.cfreq + fq * self.sr + 500) / 1e3) if self.cfreq > 0 else 0, show_df=True,
+                              if_rate=eng.if_rate, sample_rate=self.sr, version=self.version)
         elif typ in FAMILY:                                    # generic sonde description + the type's bit-rate tier (family.py)
             eng = self._family_engine(typ, fq)
             tel = FamilyDecoder(typ, freq_khz=khz, version=self.version)
@@ -72,6 +79,12 @@ class WidebandReceiver:
             tel = Rs41Telemetry(freq_khz=khz, version=self.version)
         self.sondes.append(dict(fq=fq, type=typ, engine=eng, telemetry=tel, frames=0, khz=khz, t_last=self.t))
         self.log.append(dict(event="detected", type=typ, fq=fq, freq_khz=khz))
+
+    def add_channel(self, typ: str, fq: float):
+        """start a decoder of sonde type `typ` (a scanner type name: "RS41", "DFM", "M10", "IMET4", "MK2LMS", ...) at fq (fraction of the
+        sample rate) without waiting for the scanner — what a detection does, for signals the caller knows about or the scanner's 48 kHz IF
+        cannot see (an MkIIa deviates by +/- 50 kHz)."""
+        self._start(fq, typ)
 
     def _family_engine(self, typ: str, fq: float):
         f = FAMILY[typ]
@@ -108,11 +121,20 @@ class WidebandReceiver:
                     self._start(self.raster[d["channel"]] + d["df"], d["type"])
                 elif d["type"] in IMET_AFSK:                                # the scanner's AFSK check decided the variant
                     self._start(self.raster[d["channel"]] + d["df"], d["type"])
+                elif d["type"] == MK2LMS:
+                    self.add_channel(MK2LMS, self.raster[d["channel"]] + d["df"])
                 elif d["type"] in FAMILY and (d["score"] > 0 or FAMILY[d["type"]]["auto"]):
                     self._start(self.raster[d["channel"]] + d["df"], d["type"])
             self.t += (len(x) // 2) / self.sr
             for s in list(self.sondes):
-                s["engine"].process_host(x)
+                if s["type"] == MK2LMS:                        # whole multiples of its decimation; the rest waits for the next piece
+                    xs = np.concatenate([s["rest"], x]) if len(s.get("rest", ())) else np.asarray(x)
+                    m = (len(xs) // 2) // s["engine"].dec_m * s["engine"].dec_m
+                    if m:
+                        s["engine"].process_host(xs[:2 * m])
+                    s["rest"] = np.array(xs[2 * m:], np.int16)
+                else:
+                    s["engine"].process_host(x)
                 before, hits = s.get("good", 0), s["frames"]
                 out += self._drain(s, False)
                 if s["frames"] != hits and s["type"] in ("LMS6", "LMSX"):     # any block tells what the sonde is, accepted or not
@@ -126,6 +148,8 @@ class WidebandReceiver:
                     self.log.append(dict(event="released", type=s["type"], fq=s["fq"], freq_khz=s["khz"], frames=s["frames"]))
         if finish:
             for s in self.sondes:
+                if s["type"] == MK2LMS:
+                    s["engine"].finish()                       # the frame in progress at the end is printed as it is (mk2a1680mod.c:2409-2424)
                 out += self._drain(s, True)
         return out
 
@@ -137,6 +161,14 @@ class WidebandReceiver:
             for f in e.fetch_frames():
                 s["frames"] += 1
                 js = [json.loads(line) for line in s["telemetry"].frame(f["bits"]).split("\n") if line.startswith("{")]
+                s["good"] = s.get("good", 0) + (1 if js else 0)
+                out += js
+            return out
+        if s["type"] == MK2LMS:
+            out = []
+            for f in e.fetch_frames():
+                s["frames"] += 1
+                js = [json.loads(line) for line in s["telemetry"].frame(f["bits"], f["mv"], f["df"]).split("\n") if line.startswith("{")]
                 s["good"] = s.get("good", 0) + (1 if js else 0)
                 out += js
             return out

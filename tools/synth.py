@@ -1320,3 +1320,104 @@ def mrz_capture(sr: int = 48_000, seconds: float = 5.0, fq: float = 0.0, *, amp:
     out[0::2] = np.clip(np.round(z.real * 32767), -32768, 32767)
     out[1::2] = np.clip(np.round(z.imag * 32767), -32768, 32767)
     return out
+
+
+# --------------------------------------------------------------------------------------------------------------
+# LMS6-1680 / MkIIa (reference mk2a/mk2a1680mod.c): 9616 Bd 8N1 bytes on +/- 50 kHz FSK, 0xCA fill, subframes `24 52 54` (GPS) and `24 52 4D` (config)
+def mk2a_crc16(data) -> int:
+    """CRC-16, polynomial 0x1021, initial value 0 (crc16_0, mk2a1680mod.c:1773-1792)"""
+    rem = 0
+    for b in bytes(data):
+        rem ^= b << 8
+        for _ in range(8):
+            rem = ((rem << 1) ^ 0x1021) & 0xFFFF if rem & 0x8000 else (rem << 1) & 0xFFFF
+    return rem
+
+
+def mk2a_subframes(k: int, *, sn: int = 0x00BC614E, rng=None, corrupt: bool = False, crc_ca: bool = False, lat=41.2345, lon=-72.6789, alt_m=1234.5):
+    """-> (the 174 bytes of the k-th `24 52 54` subframe, the 69 bytes of the `24 52 4D` subframe), CRC included; payload bytes never 0xCA.
+    crc_ca: a payload byte is chosen so that the CRC of the 54 subframe ends in 0xCA (it then looks like fill to the decoder)."""
+    rng = rng or np.random.default_rng(k)
+
+    def fill(n):
+        b = rng.integers(0, 255, n).astype(np.uint8)
+        b[b >= 0xCA] += 1                                   # 0..254 without 0xCA -> 0..255 without 0xCA
+        return bytearray(b.tobytes())
+
+    def be(v, n):
+        return int(v & ((1 << (8 * n)) - 1)).to_bytes(n, "big")
+
+    f = fill(172)
+    f[0:3] = b"\x24\x52\x54"
+    f[4:6] = be(sn, 2)
+    f[6:8] = be(100 + k, 2)
+    f[10:14] = be(3 * 86400_000 + 12 * 3600_000 + 34 * 60_000 + 1000 * k + 250, 4)
+    f[18:22] = be(int(round(lat * 0xB60B60)), 4)
+    f[22:26] = be(int(round(lon * 0xB60B60)), 4)
+    f[26:30] = be(int(round((alt_m + 5.0 * k) * 1000)), 4)
+    f[30:33] = be(int(round((3.2 + 0.1 * k) * 1000)), 3)
+    f[33:36] = be(int(round((-7.5 + 0.2 * k) * 1000)), 3)
+    f[36:39] = be(int(round(5.1 * 1000)), 3)
+    for i in range(172):
+        if f[i] == 0xCA:
+            f[i] = 0xCB
+    c = mk2a_crc16(f)
+    v = 0
+    while crc_ca and (c & 0xFF) != 0xCA:
+        v += 1
+        f[100], f[101] = (v & 0x7F), (v >> 7) & 0x7F
+        c = mk2a_crc16(f)
+    f += bytes([c >> 8, c & 0xFF])
+    if corrupt:
+        f[60] ^= 0x10
+    m = fill(67)
+    m[0:3] = b"\x24\x52\x4D"
+    m[4:6] = be(sn, 2)
+    m[50:52] = be(sn, 2)
+    m[52:54] = be(sn >> 16, 2)
+    for i in range(67):
+        if m[i] == 0xCA:
+            m[i] = 0xCB
+    c = mk2a_crc16(m)
+    m += bytes([c >> 8, c & 0xFF])
+    return bytes(f), bytes(m)
+
+
+def mk2a_bits(data: bytes) -> np.ndarray:
+    """8N1, LSB first"""
+    b = np.unpackbits(np.frombuffer(bytes(data), np.uint8)[:, None], axis=1, bitorder="little")
+    out = np.ones((len(data), 10), np.uint8)
+    out[:, 0] = 0
+    out[:, 1:9] = b
+    return out.reshape(-1)
+
+
+def mk2a_capture(sr: int = 240_000, seconds: float = 6.0, fq: float = 0.0, *, f_offset_hz: float = 0.0, amp: float = 0.5,
+                 noise_sigma: float = 0.01, corrupt=(), crc_ca=(), invert: bool = False, seed: int = 1, dev_hz: float = 50_000.0,
+                 baud: float = 9616.0, lead_bytes: int = 60) -> np.ndarray:
+    """Interleaved int16 IQ of a continuous MkIIa stream: 0xCA fill, then `24 52 54` subframes (174 bytes, CA-padded to 1790 bits) and
+    `24 52 4D` subframes (69 bytes, padded to 790 bits) alternating back to back; frame number and GPS time step per pair.
+    corrupt: indices of pairs whose 54 subframe gets a wrong byte; crc_ca: indices of pairs whose 54 subframe has a CRC ending in 0xCA;
+    invert: deviation sign flipped."""
+    rng = np.random.default_rng(seed)
+    n = int(round(sr * seconds))
+    nbits = int(seconds * baud) + 20
+    stream = bytearray(b"\xCA" * lead_bytes)
+    k = 0
+    while 10 * len(stream) < nbits:
+        f, m = mk2a_subframes(k, rng=np.random.default_rng(seed * 131 + k), corrupt=k in set(corrupt), crc_ca=k in set(crc_ca))
+        stream += f + b"\xCA" * (179 - len(f)) + m + b"\xCA" * (79 - len(m))
+        k += 1
+    bits = mk2a_bits(bytes(stream))[:nbits]
+    if invert:
+        bits = 1 - bits
+    x = amp * gfsk_baseband(bits, sr, baud, dev_hz, bt=1.0)[:n]
+    if len(x) < n:
+        x = np.concatenate([x, np.zeros(n - len(x))])
+    if fq != 0.0 or f_offset_hz != 0.0:
+        x = x * np.exp(2j * np.pi * (fq + f_offset_hz / sr) * np.arange(n))
+    x = x + noise_sigma * (rng.standard_normal(n) + 1j * rng.standard_normal(n))
+    out = np.empty(2 * n, dtype=np.int16)
+    out[0::2] = np.clip(np.round(x.real * 32767 * 0.9), -32768, 32767).astype(np.int16)
+    out[1::2] = np.clip(np.round(x.imag * 32767 * 0.9), -32768, 32767).astype(np.int16)
+    return out
