@@ -1721,3 +1721,15 @@ int sonde_engine_group_info(const sonde_engine_t *e, int32_t channel, int32_t *s
 }
 
 }  // extern "C"
+
+// sonde_host.h: the device ring behind the FM tap of a single-type engine once everything enqueued has run (row c at base + c * ring_len,
+// sample m at index m & (ring_len - 1)) — for stages inside the library that go on from the tap on the device (sonde_wxr.cpp)
+int sonde::engine_fm_tap_device(sonde_engine *e, const float **base, int *ring_len) {
+    if (!e || !base || !ring_len || !e->groups.empty() || !e->d_fm) return SONDE_E_ARG;
+    HIPCHK(hipStreamSynchronize(e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream_b));
+    if (e->stream_e) HIPCHK(hipStreamSynchronize(e->stream_e));
+    prof_collect(e);
+    *base = e->d_fm; *ring_len = e->ring_len;
+    return 0;
+}

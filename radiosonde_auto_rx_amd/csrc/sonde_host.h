@@ -6,6 +6,8 @@
 #include <string>
 #include <vector>
 
+struct sonde_engine;
+
 namespace sonde {
 
 struct Decimator { int if_sr = 0, decM = 1; std::vector<float> taps; };
@@ -26,6 +28,7 @@ struct Mk2aDesign {
     double f1 = 0;                                                 // its lower tone (Hz); the upper one is -f1
 };
 Mk2aDesign design_mk2a(int sr_base, int opt_iq, bool lp_iq, float lpiq_bw, bool lp_fm, int opt_decFM, bool dc, bool if_min, float baud, int shift);
+int engine_fm_tap_device(sonde_engine *e, const float **base, int *ring_len);
 struct Mixer { double f0 = 0; int lut_len = 1; };
 Mixer design_mixer(double xlt_fq, int sr_base);
 std::vector<float> design_match(const std::string &hdr, float sps, float bt);

@@ -1,4 +1,4 @@
-"""One wideband IQ stream -> every RS41, DFM, M10, M20 (and LMS6, iMet-54, Meisei, MRZ, MTS01, iMet-4 / iMet-1-RS) in it, in one process on one GPU.
+"""One wideband IQ stream -> every RS41, DFM, M10, M20 (and LMS6, iMet-54, Meisei, MRZ, MTS01, iMet-4 / iMet-1-RS, MkIIa, WxR-301D) in it, in one process on one GPU.
 
 The reference handles a wideband source by starting one detector process per candidate peak (auto_rx/autorx/scan.py:413-656:
 rtl_power peaks -> `dft_detect` per peak) and then one decoder pipeline per sonde (decode.py).  Here the same two steps run
@@ -22,11 +22,14 @@ from .scan import Scanner
 from .family import FAMILY, LMS_BASE, FamilyDecoder
 from .imet4 import Imet4Engine, Imet4Printer
 from .mk2a import Mk2aEngine, Mk2aPrinter
+from .wxr import WxrEngine, WxrPrinter
 from .telemetry import DfmTelemetry, M10Telemetry, M20Telemetry, Rs41Telemetry
 
 
 IMET_AFSK = ("IMET4", "IMET1RS")          # dft_detect's IMETafsk outcomes (sonde_scan.cpp): decoded by imet4.py
 MK2LMS = "MK2LMS"                         # LMS6-1680 / MkIIa (scan type 18): decoded by mk2a.py
+WXR = ("WXR301", "WXRPN9")                # Weathex WxR-301D, 4800 Bd / PN9 at 5000 Bd (scan types 16, 17): decoded by wxr.py
+OWN_DEC = (MK2LMS,) + WXR                 # engines with a decimation of their own: pieces are cut for them in push()
 
 
 class WidebandReceiver:
@@ -53,7 +56,7 @@ class WidebandReceiver:
 
     def _start(self, fq: float, typ: str):
         for s in self.sondes:
-            if abs(s["fq"] - fq) * self.sr < self.merge_hz * (3 if typ in ("M10", "M20") else 1):    # 9.6 kBd: seen from neighbouring raster points too
+            if abs(s["fq"] - fq) * self.sr < self.merge_hz * (8 if typ in WXR else 3 if typ in ("M10", "M20") else 1):    # 9.6 kBd, and more so 64 kHz of width: seen from neighbouring raster points too
                 return
         fq = snap_fq(fq, self.sr)
         khz = int(round((self.cfreq + fq * self.sr) / 1000.0)) if self.cfreq else 0
@@ -65,6 +68,11 @@ class WidebandReceiver:
                              max_chunk=self.chunk + Mk2aEngine.dec_m_of(self.sr))     # its own IF rule (4 x 48 kHz): pieces are cut for it in push()
             tel = Mk2aPrinter(json=True, jsn_freq_khz=int((self.cfreq + fq * self.sr + 500) / 1e3) if self.cfreq > 0 else 0, show_df=True,
                               if_rate=eng.if_rate, sample_rate=self.sr, version=self.version)
+        elif typ in WXR:                                       # iq_dec --FM --IFbw 64 --lpFM --iq fq | weathex301d -b --json [--pn9], as auto_rx starts it
+            eng = WxrEngine([fq], self.sr, bits=16, pn9=(typ == "WXRPN9"), opt_b=True, if_bw_khz=64,
+                            max_chunk=self.chunk + WxrEngine.dec_m_of(self.sr))
+            tel = WxrPrinter(json=True, pn9=(typ == "WXRPN9"), jsn_freq_khz=int((self.cfreq + fq * self.sr + 500) / 1e3) if self.cfreq > 0 else 0,
+                             version=self.version)
         elif typ in FAMILY:                                    # generic sonde description + the type's bit-rate tier (family.py)
             eng = self._family_engine(typ, fq)
             tel = FamilyDecoder(typ, freq_khz=khz, version=self.version)
@@ -83,7 +91,7 @@ class WidebandReceiver:
     def add_channel(self, typ: str, fq: float):
         """start a decoder of sonde type `typ` (a scanner type name: "RS41", "DFM", "M10", "IMET4", "MK2LMS", ...) at fq (fraction of the
         sample rate) without waiting for the scanner — what a detection does, for signals the caller knows about or the scanner's 48 kHz IF
-        cannot see (an MkIIa deviates by +/- 50 kHz)."""
+        cannot see (an MkIIa deviates by +/- 50 kHz, a WxR-301D is 64 kHz wide)."""
         self._start(fq, typ)
 
     def _family_engine(self, typ: str, fq: float):
@@ -123,11 +131,13 @@ class WidebandReceiver:
                     self._start(self.raster[d["channel"]] + d["df"], d["type"])
                 elif d["type"] == MK2LMS:
                     self.add_channel(MK2LMS, self.raster[d["channel"]] + d["df"])
+                elif d["type"] in WXR:                                      # WXR301: the offset estimate is dropped, as auto_rx's scan.py does (not accurate without whitening)
+                    self.add_channel(d["type"], self.raster[d["channel"]] + (d["df"] if d["type"] == "WXRPN9" else 0.0))
                 elif d["type"] in FAMILY and (d["score"] > 0 or FAMILY[d["type"]]["auto"]):
                     self._start(self.raster[d["channel"]] + d["df"], d["type"])
             self.t += (len(x) // 2) / self.sr
             for s in list(self.sondes):
-                if s["type"] == MK2LMS:                        # whole multiples of its decimation; the rest waits for the next piece
+                if s["type"] in OWN_DEC:                       # whole multiples of its decimation; the rest waits for the next piece
                     xs = np.concatenate([s["rest"], x]) if len(s.get("rest", ())) else np.asarray(x)
                     m = (len(xs) // 2) // s["engine"].dec_m * s["engine"].dec_m
                     if m:
@@ -148,8 +158,8 @@ class WidebandReceiver:
                     self.log.append(dict(event="released", type=s["type"], fq=s["fq"], freq_khz=s["khz"], frames=s["frames"]))
         if finish:
             for s in self.sondes:
-                if s["type"] == MK2LMS:
-                    s["engine"].finish()                       # the frame in progress at the end is printed as it is (mk2a1680mod.c:2409-2424)
+                if s["type"] in OWN_DEC:
+                    s["engine"].finish()                       # the frame in progress at the end is printed as it is (mk2a1680mod.c:2409-2424, weathex301d.c:692-704)
                 out += self._drain(s, True)
         return out
 
@@ -169,6 +179,14 @@ class WidebandReceiver:
             for f in e.fetch_frames():
                 s["frames"] += 1
                 js = [json.loads(line) for line in s["telemetry"].frame(f["bits"], f["mv"], f["df"]).split("\n") if line.startswith("{")]
+                s["good"] = s.get("good", 0) + (1 if js else 0)
+                out += js
+            return out
+        if s["type"] in WXR:                                 # -b: a frame cut short by the end of the input is printed with what it has
+            out = []
+            for f in e.fetch_frames():
+                s["frames"] += 1
+                js = [json.loads(line) for line in s["telemetry"].frame(f["bits"]).split("\n") if line.startswith("{")]
                 s["good"] = s.get("good", 0) + (1 if js else 0)
                 out += js
             return out

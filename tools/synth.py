@@ -1421,3 +1421,89 @@ def mk2a_capture(sr: int = 240_000, seconds: float = 6.0, fq: float = 0.0, *, f_
     out[0::2] = np.clip(np.round(x.real * 32767 * 0.9), -32768, 32767).astype(np.int16)
     out[1::2] = np.clip(np.round(x.imag * 32767 * 0.9), -32768, 32767).astype(np.int16)
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------- Weathex WxR-301D
+WXR_PN9 = bytes.fromhex("FF87B859B7A1CC24575E4B9C0EE9EA502ABEB41BB6B05DF1E69AE345FD2C53180CCAC9FB4937E5A8513B2F61AA72188402"
+                        "2323AB638951B3E78B72904CE8FBC1")        # the format's whitening sequence from frame byte 6 on (TI SWRA322)
+
+
+def wxr_xor8sum(data) -> int:
+    x = s = 0
+    for b in bytes(data):
+        x ^= b
+        s = (s + b) & 0xFF
+    return (x << 8) | s
+
+
+def wxr_frame(sn: int = 20230117, cnt: int = 0, frid: int = 2, pn9: bool = False, *, hms=(12, 34, 56), lat=52.20912, lon=14.12034, alt_m=1234.5,
+              corrupt: bool = False, rng=None) -> bytes:
+    """The 69 on-air bytes of one WxR-301D frame: AA AA AA + sync (2D D4, PN9 variant C1 94), then from byte `ofs` (6, PN9 variant 8) serial(4)
+    counter(2) id(1) payload(46) and the check (xor8, sum8) over those 53 bytes; id 2 carries hhmmss / alt / lat / lon as the decoder reads them.
+    With pn9 everything from byte 6 on is whitened."""
+    rng = rng or np.random.default_rng(sn % 65521 + 7 * cnt + frid)
+    ofs = 8 if pn9 else 6
+    f = bytearray(69)
+    f[0:5] = bytes.fromhex("AAAAAAC194" if pn9 else "AAAAAA2DD4")
+    f[5] = 0x3A
+    f[ofs:ofs + 4] = int(sn).to_bytes(4, "little")
+    f[ofs + 4:ofs + 6] = int(cnt & 0xFFFF).to_bytes(2, "little")
+    f[ofs + 6] = frid
+    f[ofs + 7:ofs + 53] = rng.integers(0, 256, 46, dtype=np.uint8).tobytes()
+    if frid == 2:
+        h, m, s = hms
+        f[ofs + 7:ofs + 10] = int((h * 10000 + m * 100 + s) & 0x3FFFF).to_bytes(3, "little")
+        word = (int(round(alt_m * 10)) & 0x7FFFF) << 4 | (int(round(lat * 1e5)) & 0x1FFFFFF) << 23      # bytes ofs+13 .. ofs+18
+        f[ofs + 13:ofs + 19] = word.to_bytes(6, "little")
+        f[ofs + 19:ofs + 23] = (int(round(lon * 1e5)) & 0x3FFFFFF).to_bytes(4, "little")
+    chk = wxr_xor8sum(f[ofs:ofs + 53])
+    f[ofs + 53], f[ofs + 54] = chk >> 8, chk & 0xFF
+    if corrupt:
+        f[ofs + 30] ^= 0x41
+    if pn9:
+        for j in range(6, 69):
+            f[j] ^= WXR_PN9[(j - 6) % 64]
+    return bytes(f)
+
+
+def wxr_frames(n_frames: int = 16, pn9: bool = False, sn: int = 20230117, cnt0: int = 100, corrupt=()) -> list:
+    """ids 1, 2 alternating, the counter stepping every second frame, the time with it"""
+    out = []
+    for k in range(n_frames):
+        c = cnt0 + k // 2
+        out.append(wxr_frame(sn, c, 1 + k % 2, pn9, hms=(12, 34, c % 60), lat=52.20912 + 1e-4 * (k // 2), lon=14.12034 - 2e-4 * (k // 2),
+                             alt_m=1234.5 + 5.0 * (k // 2), corrupt=k in set(corrupt)))
+    return out
+
+
+def wxr_capture(sr: int = 96_000, *, n_frames: int = 16, pn9: bool = False, dev_hz: float = 25_000.0, f_offset_hz: float = 0.0, noise: float | None = 30.0,
+                flips: int = 0, fq: float = 0.0, seed: int = 1, invert: bool = False, corrupt=(), gap_bytes: int = 12, lead_s: float = 0.25,
+                amp: float = 8000.0) -> np.ndarray:
+    """Interleaved int16 IQ of n_frames WxR-301D frames: 2-FSK (bit 1 = positive deviation), 4800 Bd or with pn9 5000 Bd, NRZ smoothed with a
+    Hann window of 9 samples at 96 kHz, gap_bytes of AA between frames, lead_s of noise alone before and after.  noise: carrier power over the
+    complex noise power in a 96 kHz band, in dB (None: no noise); flips: that many frame bits at random places are inverted."""
+    rng = np.random.default_rng(seed)
+    baud = 5000.0 if pn9 else 4800.0
+    stream = b"".join(b"\xAA" * gap_bytes + f for f in wxr_frames(n_frames, pn9, corrupt=corrupt)) + b"\xAA" * gap_bytes
+    bits = np.unpackbits(np.frombuffer(stream, np.uint8)).astype(np.int8)
+    if flips:
+        bits[rng.choice(len(bits), flips, replace=False)] ^= 1
+    if invert:
+        bits = 1 - bits
+    n_sig = int(len(bits) * sr / baud)
+    nrz = 2.0 * bits[np.minimum((np.arange(n_sig) * (baud / sr)).astype(np.int64), len(bits) - 1)] - 1.0
+    w = np.hanning(max(3, int(round(9 * sr / 96000))) + 2)[1:-1]
+    nrz = np.convolve(nrz, w / w.sum(), mode="same")
+    ph = 2 * np.pi * np.cumsum(nrz * (dev_hz / sr))
+    lead = int(lead_s * sr)
+    x = np.concatenate([np.zeros(lead, np.complex128), amp * np.exp(1j * ph), np.zeros(lead, np.complex128)])
+    n = len(x)
+    if fq != 0.0 or f_offset_hz != 0.0:
+        x = x * np.exp(2j * np.pi * (fq + f_offset_hz / sr) * np.arange(n))
+    if noise is not None:
+        sigma = amp * np.sqrt(10.0 ** (-noise / 10.0) * (sr / 96000.0) / 2.0)
+        x = x + sigma * (rng.standard_normal(n) + 1j * rng.standard_normal(n))
+    out = np.empty(2 * n, dtype=np.int16)
+    out[0::2] = np.clip(np.round(x.real), -32768, 32767).astype(np.int16)
+    out[1::2] = np.clip(np.round(x.imag), -32768, 32767).astype(np.int16)
+    return out
