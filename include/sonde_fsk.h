@@ -12,6 +12,7 @@
 #define SONDE_FSK_H
 
 #include "sonde_hip.h"
+#include "sonde_drop.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -107,7 +108,9 @@ int  sonde_fsk_kernel_ms(sonde_fsk_t *f, double *avg_ms, int64_t *launches);
  * device memory; only completed frames (518 bytes each) come to the host.  invert_stream = --softinv, opt_inv = -i, opt_auto = --auto.
  * sonde_type: SONDE_RS41; SONDE_DFM09 = `dfm09mod --softin [-i] [--ecc|--ecc2]` (dfm09mod.c:1604-1720: 32 raw header symbols, two soft symbols per bit, eight frames
  * per header hit, de-interleave + Hamming(8,4) incl. the soft 2-bit pass :231-345 on a lane per codeword); SONDE_M10 = `m10mod --softin` (m10mod.c:1405-1510: header
- * threshold 0.8 in either polarity, differential decoding, the rest of the second skipped, checkM10 :594-628).  No CPU fallback. */
+ * threshold 0.8 in either polarity, differential decoding, the rest of the second skipped, checkM10 :594-628); SONDE_RD94RD41 = `rd94rd41drop --softin / --softinv [-i]`
+ * (rd94rd41drop.c:1357-1386: the sign of every soft bit, the 40-bit header ring, 2400 raw bits a frame, then Manchester pairs -> bytes -> five chksum16 and seven
+ * CRC-16 checks on the device; ecc_level and opt_auto are ignored).  No CPU fallback. */
 typedef struct sonde_softin_dev sonde_softin_dev_t;
 int  sonde_softin_dev_create(int32_t n_channels, int32_t sonde_type, int32_t ecc_level, int32_t invert_stream, int32_t opt_inv, int32_t opt_auto,
                              sonde_softin_dev_t **out);
@@ -133,7 +136,9 @@ int  sonde_softin_dev_fetch(sonde_softin_dev_t *s, sonde_frame_t *out, int32_t m
 /* SONDE_DFM09 / SONDE_M10 consumers: their frames (ecc[3] = hamming()'s value per block; cs_ok / cs_calc = the frame checksum) */
 int  sonde_softin_dev_fetch_dfm(sonde_softin_dev_t *s, sonde_dfm_frame_t *out, int32_t max);
 int  sonde_softin_dev_fetch_m10(sonde_softin_dev_t *s, sonde_m10_frame_t *out, int32_t max);
-/* tallies since creation: frames completed, frames accepted (RS41: rs41_ecc() >= 0; DFM: no block uncorrectable; M10: checksum good), frames repaired, symbols / codewords repaired, frames lost to a full buffer */
+/* SONDE_RD94RD41 consumers: the frame record of include/sonde_drop.h (sample = soft bits read when the header matched) */
+int  sonde_softin_dev_fetch_drop(sonde_softin_dev_t *s, sonde_drop_frame_t *out, int32_t max);
+/* tallies since creation: frames completed, frames accepted (RS41: rs41_ecc() >= 0; DFM: no block uncorrectable; M10: checksum good; RD94RD41: every block of the type print_frame chooses good), frames repaired, symbols / codewords repaired, frames lost to a full buffer */
 int  sonde_softin_dev_counts(sonde_softin_dev_t *s, int64_t *frames, int64_t *ecc_ok, int64_t *repaired, int64_t *symbols, int64_t *dropped);
 
 #ifdef __cplusplus

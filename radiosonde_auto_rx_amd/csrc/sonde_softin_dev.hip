@@ -16,6 +16,8 @@
 #include "sonde_fsk_dev.h"
 #include "sonde_host.h"
 #include "sonde_pinned.h"
+#include "sonde_drop_dev.h"
+#include "../../include/sonde_drop.h"
 #include <cstdio>
 #include <cstring>
 #include <vector>
@@ -502,6 +504,77 @@ void k_softin_m10(const SoftinM10Args A) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// RD94 / RD41 dropsondes: rd94rd41drop --softin / --softinv [-i] (rd94rd41drop.c:1357-1386) — no correlation: the sign of every soft bit (s >= 0 after the two
+// inversions, which cancel each other) goes into the 40-bit ring, a frame is the 2360 raw bits behind a ring that equals FC 1D as Manchester-coded 8N1, and the
+// bits of a frame enter the ring too.  64 soft bits a pass: signs by ballot, every lane tests the ring as it stands behind its bit (values and "holds a bit"
+// masks, as in k_drop_slice); inside a frame the lanes write up to 64 raw bits a pass.  A finished frame is completed on the device (drop_complete_frame).
+// ------------------------------------------------------------------------------------------------
+struct SoftinDropChan {
+    int found, pos;                                // header open; raw bits of the frame so far (40 = the header alone)
+    unsigned long long hist, valid, bits_in, t_hdr;
+    unsigned char frame[DROP_RAWBITS];
+};
+struct SoftinDropArgs { SoftinArgs base; SoftinDropChan *chan; DropFrame *out; int inv; };
+
+// the ring after bits 0 .. k of the pass (bm: bit i = soft bit i of the pass), newest bit lowest
+__device__ __forceinline__ void drop_ring_after(unsigned long long hist, unsigned long long valid, unsigned long long bm, int k, unsigned long long &h, unsigned long long &v) {
+    constexpr unsigned long long M40 = (1ULL << DROP_HEADLEN) - 1;
+    const unsigned long long fresh = __brevll(bm) >> (63 - k), ones = (2ULL << k) - 1;       // bits 0 .. k, bit 0 highest
+    h = ((k + 1 >= DROP_HEADLEN ? 0 : hist << (k + 1)) | fresh) & M40;
+    v = ((k + 1 >= DROP_HEADLEN ? 0 : valid << (k + 1)) | ones) & M40;
+}
+
+__global__ __launch_bounds__(64)
+void k_softin_drop(const SoftinDropArgs A) {
+    const SoftinArgs &a = A.base;
+    constexpr unsigned long long M40 = (1ULL << DROP_HEADLEN) - 1;
+    __shared__ unsigned char s_fb[DROP_RAWBITS];
+    __shared__ unsigned char s_by[128];
+    const int ch = a.ch_list ? a.ch_list[blockIdx.x] : (int)blockIdx.x, lane = threadIdx.x;
+    if (ch >= a.n_ch) return;
+    SoftinDropChan *st = A.chan + ch;
+    int nb = a.nbits;
+    if (a.fsk_chan) { const int fr = a.fsk_chan[ch].frames; nb = fr > 0 ? fr * a.bits_per_frame : 0; }
+    else if (a.nbits_ch) nb = a.nbits_ch[ch];
+    nb = __builtin_amdgcn_readfirstlane(nb);
+    const float *x = a.sd + (size_t)ch * a.ch_stride;
+    int found = __builtin_amdgcn_readfirstlane(st->found), pos = __builtin_amdgcn_readfirstlane(st->pos);
+    unsigned long long hist = st->hist, valid = st->valid, t_hdr = st->t_hdr;
+    const unsigned long long bits0 = st->bits_in;
+    for (int i = lane; i < DROP_RAWBITS; i += 64) s_fb[i] = st->frame[i];
+    __syncthreads();
+    int cur = 0;
+    while (cur < nb) {
+        if (!found) {
+            const int q = cur + lane, nv = min(64, nb - cur);
+            const float s = q < nb ? x[q] : 0.f;
+            const unsigned long long bm = __ballot(q < nb && (A.inv ? s <= 0.0f : s >= 0.0f));
+            unsigned long long h, v;
+            drop_ring_after(hist, valid, bm, lane, h, v);
+            const unsigned long long hm = __ballot(lane < nv && h == DROP_HDR40 && v == M40);
+            const int used = hm ? __builtin_ctzll(hm) + 1 : nv;
+            drop_ring_after(hist, valid, bm, used - 1, h, v);
+            hist = h; valid = v;
+            if (hm) { found = 1; pos = DROP_HEADLEN; t_hdr = bits0 + (unsigned long long)(cur + used); }
+            cur += used;
+        } else {
+            const int take = min(nb - cur, DROP_RAWBITS - pos);
+            for (int j = lane; j < take; j += 64) { const float s = x[cur + j]; s_fb[pos + j] = (unsigned char)(A.inv ? s <= 0.0f : s >= 0.0f); }
+            pos += take; cur += take;
+            if (pos == DROP_RAWBITS) {
+                drop_complete_frame(s_fb, DROP_RAWBITS, s_by, A.out, (int *)a.count, a.cap, ch, t_hdr, 1, lane);
+                const unsigned long long tail = __ballot(lane < DROP_HEADLEN && s_fb[DROP_RAWBITS - DROP_HEADLEN + lane]);
+                hist = __brevll(tail) >> 24; valid = M40;
+                found = 0; pos = DROP_HEADLEN;
+            }
+        }
+    }
+    __syncthreads();
+    for (int i = lane; i < DROP_RAWBITS; i += 64) st->frame[i] = s_fb[i];
+    if (lane == 0) { st->found = found; st->pos = pos; st->hist = hist; st->valid = valid; st->t_hdr = t_hdr; st->bits_in = bits0 + (unsigned long long)nb; }
+}
+
+// ------------------------------------------------------------------------------------------------
 // The same block codes for the BASE-RATE engine's hits (sonde_engine.cpp): what sonde_engine_fetch_dfm / _m10 used to do per frame on one host thread
 // now runs over the records a process call has queued, behind its frame-sync kernel on the same stream.  Only decoded frames come to the host (DFM: 8 x 104 bytes
 // a hit instead of 2224 soft bits).
@@ -639,6 +712,7 @@ struct sonde_softin_dev {
     int C = 0, ecc_level = 0, cap = 0, type = SONDE_RS41;
     SoftinDfmChan *d_dfm_chan = nullptr; sonde_dfm_frame_t *d_dfm_out = nullptr; std::vector<sonde_dfm_frame_t> qdfm; Pinned<sonde_dfm_frame_t> h_dfm;
     SoftinM10Chan *d_m10_chan = nullptr; sonde_m10_frame_t *d_m10_out = nullptr; std::vector<sonde_m10_frame_t> qm10; Pinned<sonde_m10_frame_t> h_m10;
+    SoftinDropChan *d_drop_chan = nullptr; DropFrame *d_drop_out = nullptr; std::vector<sonde_drop_frame_t> qdrop; Pinned<DropFrame> h_drop; int drop_inv = 0;
     SoftinArgs args{};
     hipStream_t stream = nullptr; bool own_stream = false;
     SoftinChan *d_chan = nullptr; unsigned char *d_frames = nullptr, *d_hdr = nullptr, *d_gf = nullptr, *d_synd = nullptr;
@@ -655,13 +729,14 @@ struct sonde_softin_dev {
 extern "C" {
 
 int sonde_softin_dev_create(int32_t n_channels, int32_t sonde_type, int32_t ecc_level, int32_t invert_stream, int32_t opt_inv, int32_t opt_auto, sonde_softin_dev_t **out) {
-    if (!out || n_channels < 1 || (sonde_type != SONDE_RS41 && sonde_type != SONDE_DFM09 && sonde_type != SONDE_M10) || ecc_level < 0 || ecc_level > 2) return SONDE_E_ARG;
+    if (!out || n_channels < 1 || (sonde_type != SONDE_RS41 && sonde_type != SONDE_DFM09 && sonde_type != SONDE_M10 && sonde_type != SONDE_RD94RD41) || ecc_level < 0 || ecc_level > 2) return SONDE_E_ARG;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { fprintf(stderr, "libsonde_hip: no usable HIP device (the batched soft-bit framer has no CPU fallback)\n"); return SONDE_E_NOGPU; }
     sonde_softin_dev *s = new sonde_softin_dev();
     s->C = n_channels; s->ecc_level = ecc_level; s->type = sonde_type;
-    // frames a call of about a second can complete per channel: RS41 two, DFM09 six (280 bits at 1250 b/s), M10 two (one per second; the rest of the second is skipped)
-    s->cap = (sonde_type == SONDE_DFM09 ? 8 : 2) * n_channels + 16;
+    // frames a call of about a second can complete per channel: RS41 two, DFM09 six (280 bits at 1250 b/s), M10 two (one per second; the rest of the second is skipped),
+    // dropsondes three (two a second)
+    s->cap = (sonde_type == SONDE_DFM09 ? 8 : sonde_type == SONDE_RD94RD41 ? 4 : 2) * n_channels + 16;
     const size_t C = (size_t)n_channels, cap = (size_t)s->cap;
     std::vector<SoftinChan> init(C);
     memset(init.data(), 0, C * sizeof(SoftinChan));
@@ -694,12 +769,21 @@ int sonde_softin_dev_create(int32_t n_channels, int32_t sonde_type, int32_t ecc_
           && hipMemcpy(s->d_m10_chan, mi.data(), C * sizeof(SoftinM10Chan), hipMemcpyHostToDevice) == hipSuccess;
         ok = ok && s->h_m10.alloc(cap);
     }
+    if (ok && sonde_type == SONDE_RD94RD41) {
+        std::vector<SoftinDropChan> di(C);
+        memset(di.data(), 0, C * sizeof(SoftinDropChan));
+        for (auto &c : di) { c.pos = DROP_HEADLEN; for (int i = 0; i < DROP_HEADLEN; i++) c.frame[i] = (unsigned char)((DROP_HDR40 >> (DROP_HEADLEN - 1 - i)) & 1); }
+        s->drop_inv = (invert_stream ? 1 : 0) ^ (opt_inv ? 1 : 0);
+        ok = hipMalloc((void **)&s->d_drop_chan, C * sizeof(SoftinDropChan)) == hipSuccess && hipMalloc((void **)&s->d_drop_out, cap * sizeof(DropFrame)) == hipSuccess
+          && hipMemcpy(s->d_drop_chan, di.data(), C * sizeof(SoftinDropChan), hipMemcpyHostToDevice) == hipSuccess;
+        ok = ok && s->h_drop.alloc(cap);
+    }
     if (!ok) { sonde_softin_dev_destroy(s); return SONDE_E_NOMEM; }
     SoftinArgs &a = s->args;
     a.n_ch = n_channels; a.inv_in = invert_stream ? 1 : 0; a.opt_auto = opt_auto ? 1 : 0; a.ths = sonde_type == SONDE_M10 ? 0.8f : 0.7f;
     a.chan = s->d_chan; a.frames = s->d_frames; a.flen = s->d_flen; a.meta = s->d_meta; a.count = s->d_count; a.cap = s->cap; a.hdr = s->d_hdr;
     if (!s->h_ecc.alloc(cap) || !s->h_meta.alloc(cap) || !s->h_frames.alloc(cap * 518)) { sonde_softin_dev_destroy(s); return SONDE_E_NOMEM; }
-    s->head = std::min(s->cap, (sonde_type == SONDE_DFM09 ? 5 : 1) * n_channels + 16);
+    s->head = std::min(s->cap, (sonde_type == SONDE_DFM09 ? 5 : sonde_type == SONDE_RD94RD41 ? 2 : 1) * n_channels + 16);
     (void)hipGetLastError();
     *out = s;
     return 0;
@@ -713,7 +797,7 @@ void sonde_softin_dev_destroy(sonde_softin_dev_t *s) {
     if (s->h_nbits) hipHostFree(s->h_nbits);
     if (s->d_nbits) hipFree(s->d_nbits);
     (void)hipGetLastError();
-    void *p[] = { s->d_chan, s->d_frames, s->d_hdr, s->d_gf, s->d_synd, s->d_flen, s->d_ecc, s->d_codes, s->d_meta, s->d_count, s->d_dfm_chan, s->d_dfm_out, s->d_m10_chan, s->d_m10_out };
+    void *p[] = { s->d_chan, s->d_frames, s->d_hdr, s->d_gf, s->d_synd, s->d_flen, s->d_ecc, s->d_codes, s->d_meta, s->d_count, s->d_dfm_chan, s->d_dfm_out, s->d_m10_chan, s->d_m10_out, s->d_drop_chan, s->d_drop_out };
     for (void *q : p) if (q) hipFree(q);
     delete s;
 }
@@ -735,6 +819,7 @@ static int softin_pass(sonde_softin_dev *s, hipStream_t st, const int off, const
         if (lds > attr) { if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_softin_m10), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess) attr = lds; else m.stage_cap = 0; }
         hipLaunchKernelGGL(k_softin_m10, dim3(nblocks), dim3(64), m.stage_cap ? lds : 0, st, m);
     }
+    else if (s->type == SONDE_RD94RD41) { SoftinDropArgs d{a, s->d_drop_chan, s->d_drop_out + off, s->drop_inv}; hipLaunchKernelGGL(k_softin_drop, dim3(nblocks), dim3(64), 0, st, d); }
     else {
         hipLaunchKernelGGL(k_softin_rs41, dim3(nblocks), dim3(64), 0, st, a);
         if (s->ecc_level > 0)
@@ -750,6 +835,7 @@ static int softin_copy(sonde_softin_dev *s, hipStream_t st, const int from, cons
     const size_t n = (size_t)(to - from);
     if (s->type == SONDE_DFM09) HIPCHK(hipMemcpyAsync(s->h_dfm.data() + from, s->d_dfm_out + from, n * sizeof(sonde_dfm_frame_t), hipMemcpyDeviceToHost, st));
     else if (s->type == SONDE_M10) HIPCHK(hipMemcpyAsync(s->h_m10.data() + from, s->d_m10_out + from, n * sizeof(sonde_m10_frame_t), hipMemcpyDeviceToHost, st));
+    else if (s->type == SONDE_RD94RD41) HIPCHK(hipMemcpyAsync(s->h_drop.data() + from, s->d_drop_out + from, n * sizeof(DropFrame), hipMemcpyDeviceToHost, st));
     else {
         HIPCHK(hipMemcpyAsync(s->h_meta.data() + from, s->d_meta + from, n * sizeof(SoftinMeta), hipMemcpyDeviceToHost, st));
         HIPCHK(hipMemcpyAsync(s->h_ecc.data() + from, s->d_ecc + from, n * 4, hipMemcpyDeviceToHost, st));
@@ -786,6 +872,16 @@ static int softin_finish(sonde_softin_dev *s) {
         }
     } else if (s->type == SONDE_M10) {
         for (long long i = 0; i < n; i++) { s->qm10.push_back(s->h_m10[i]); s->frames_total++; if (s->h_m10[i].cs_ok) s->ecc_ok_total++; }
+    } else if (s->type == SONDE_RD94RD41) {
+        for (long long i = 0; i < n; i++) {
+            const DropFrame &g = s->h_drop[i];
+            sonde_drop_frame_t f; memset(&f, 0, sizeof f);
+            f.channel = g.channel; f.nraw = g.nraw; f.complete = g.complete; f.err94 = g.err94; f.err41 = g.err41; f.sample = g.sample;
+            memcpy(f.bytes, g.bytes, sizeof f.bytes);
+            s->qdrop.push_back(f); s->frames_total++;
+            // print_frame's type choice and frm_ok (rd94rd41drop.c:1028-1038, :1213): more than two failing RD41 blocks = RD94
+            if (__builtin_popcount((unsigned)g.err41) > 2 ? g.err94 == 0 : g.err41 == 0) s->ecc_ok_total++;
+        }
     } else {
         for (long long i = 0; i < n; i++) {
             sonde_frame_t f; memset(&f, 0, sizeof f);
@@ -907,6 +1003,15 @@ int sonde_softin_dev_fetch_m10(sonde_softin_dev_t *s, sonde_m10_frame_t *out, in
     const int n = (int)std::min<size_t>(s->qm10.size(), (size_t)(max < 0 ? 0 : max));
     for (int i = 0; i < n; i++) out[i] = s->qm10[i];
     s->qm10.erase(s->qm10.begin(), s->qm10.begin() + n);
+    return n;
+}
+
+int sonde_softin_dev_fetch_drop(sonde_softin_dev_t *s, sonde_drop_frame_t *out, int32_t max) {
+    if (s && s->pending) { const int rc_ = softin_finish(s); if (rc_) return rc_; }
+    if (!s || (!out && max > 0)) return SONDE_E_ARG;
+    const int n = (int)std::min<size_t>(s->qdrop.size(), (size_t)(max < 0 ? 0 : max));
+    for (int i = 0; i < n; i++) out[i] = s->qdrop[i];
+    s->qdrop.erase(s->qdrop.begin(), s->qdrop.begin() + n);
     return n;
 }
 

@@ -61,6 +61,7 @@ def _lib():
         L.sonde_softin_dev_counts.argtypes = [C.c_void_p] + [C.POINTER(C.c_int64)] * 5
         L.sonde_softin_dev_fetch_dfm.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
         L.sonde_softin_dev_fetch_m10.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+        L.sonde_softin_dev_fetch_drop.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
         _proto = True
     return L
 
@@ -168,11 +169,12 @@ class SoftinDev:
     without the soft-decision stream crossing to the host.  No CPU fallback."""
 
     def __init__(self, n_channels: int, *, ecc: int = 2, softinv: bool = False, inv: bool = True, auto: bool = False, kind: str = "rs41"):
-        """kind: "rs41" (rs41mod --softin), "dfm" (dfm09mod --softin: ecc 0 / 1 = --ecc / 2 = --ecc2) or "m10" (m10mod --softin)"""
-        from .engine import SONDE_RS41, SONDE_DFM09, SONDE_M10
+        """kind: "rs41" (rs41mod --softin), "dfm" (dfm09mod --softin: ecc 0 / 1 = --ecc / 2 = --ecc2), "m10" (m10mod --softin) or "drop" (rd94rd41drop --softin /
+        --softinv [-i]: auto_rx runs it as softinv=True, inv=False; ecc and auto are ignored)"""
+        from .engine import SONDE_RS41, SONDE_DFM09, SONDE_M10, SONDE_RD94RD41
         h = C.c_void_p()
         self.kind, self.ecc = kind, ecc
-        _chk(_lib().sonde_softin_dev_create(n_channels, {"rs41": SONDE_RS41, "dfm": SONDE_DFM09, "m10": SONDE_M10}[kind], ecc, int(softinv), int(inv), int(auto), C.byref(h)))
+        _chk(_lib().sonde_softin_dev_create(n_channels, {"rs41": SONDE_RS41, "dfm": SONDE_DFM09, "m10": SONDE_M10, "drop": SONDE_RD94RD41}[kind], ecc, int(softinv), int(inv), int(auto), C.byref(h)))
         self._h, self.n_channels = h, n_channels
 
     def close(self):
@@ -240,6 +242,13 @@ class SoftinDev:
             ll = lib().sonde_m10_rawline(C.byref(f), verbose, line, 420)
             out.append(dict(channel=f.channel, nbits=f.nbits, len=f.len, cs_ok=f.cs_ok, cs_calc=f.cs_calc, mv=f.mv, mv_pos=f.mv_pos, frame=bytes(f.frame), line=line.raw[:ll].decode()))
         return out
+
+    def fetch_drop(self, max_frames: int = 4096):
+        """dropsonde consumers: the frame records of drop.py (channel, sample = soft bits read at the header, bytes, err94, err41, nraw, complete)"""
+        from .drop import DropFrame, _frame_dict
+        buf = (DropFrame * max_frames)()
+        n = _chk(_lib().sonde_softin_dev_fetch_drop(self._h, buf, max_frames))
+        return [_frame_dict(buf[i]) for i in range(n)]
 
     def counts(self):
         v = [C.c_int64(0) for _ in range(5)]

@@ -1,4 +1,4 @@
-"""One wideband IQ stream -> every RS41, DFM, M10, M20 (and LMS6, iMet-54, Meisei, MRZ, MTS01, iMet-4 / iMet-1-RS, MkIIa, WxR-301D) in it, in one process on one GPU.
+"""One wideband IQ stream -> every RS41, DFM, M10, M20 (and LMS6, iMet-54, Meisei, MRZ, MTS01, iMet-4 / iMet-1-RS, MkIIa, WxR-301D, RD94 / RD41 dropsondes) in it, in one process on one GPU.
 
 The reference handles a wideband source by starting one detector process per candidate peak (auto_rx/autorx/scan.py:413-656:
 rtl_power peaks -> `dft_detect` per peak) and then one decoder pipeline per sonde (decode.py).  Here the same two steps run
@@ -23,13 +23,15 @@ from .family import FAMILY, LMS_BASE, FamilyDecoder
 from .imet4 import Imet4Engine, Imet4Printer
 from .mk2a import Mk2aEngine, Mk2aPrinter
 from .wxr import WxrEngine, WxrPrinter
+from .drop import DropEngine, DropPrinter
 from .telemetry import DfmTelemetry, M10Telemetry, M20Telemetry, Rs41Telemetry
 
 
 IMET_AFSK = ("IMET4", "IMET1RS")          # dft_detect's IMETafsk outcomes (sonde_scan.cpp): decoded by imet4.py
 MK2LMS = "MK2LMS"                         # LMS6-1680 / MkIIa (scan type 18): decoded by mk2a.py
 WXR = ("WXR301", "WXRPN9")                # Weathex WxR-301D, 4800 Bd / PN9 at 5000 Bd (scan types 16, 17): decoded by wxr.py
-OWN_DEC = (MK2LMS,) + WXR                 # engines with a decimation of their own: pieces are cut for them in push()
+DROP = ("RD94RD41", "RD94", "RD41")       # Vaisala dropsondes (scan type 10): decoded by drop.py; the frames say which of the two it is
+OWN_DEC = (MK2LMS,) + WXR + DROP          # engines with a decimation of their own: pieces are cut for them in push()
 
 
 class WidebandReceiver:
@@ -54,7 +56,7 @@ class WidebandReceiver:
         self.sondes: list[dict] = []           # {fq, engine, telemetry, type, frames}
         self.log: list[dict] = []
 
-    def _start(self, fq: float, typ: str):
+    def _start(self, fq: float, typ: str, invert: bool = False):
         for s in self.sondes:
             if abs(s["fq"] - fq) * self.sr < self.merge_hz * (8 if typ in WXR else 3 if typ in ("M10", "M20") else 1):    # 9.6 kBd, and more so 64 kHz of width: seen from neighbouring raster points too
                 return
@@ -73,6 +75,10 @@ class WidebandReceiver:
                             max_chunk=self.chunk + WxrEngine.dec_m_of(self.sr))
             tel = WxrPrinter(json=True, pn9=(typ == "WXRPN9"), jsn_freq_khz=int((self.cfreq + fq * self.sr + 500) / 1e3) if self.cfreq > 0 else 0,
                              version=self.version)
+        elif typ in DROP:                                      # iq_dec --FM --lpFM --wav --bo 16 --iq fq | rd94rd41drop -b --json [-i]
+            eng = DropEngine([fq], self.sr, bits=16, invert=invert, opt_b=True, max_chunk=self.chunk + DropEngine.dec_m_of(self.sr))
+            tel = DropPrinter(json=True, type={"RD94": 94, "RD41": 41}.get(typ, 0),
+                              jsn_freq_khz=int((self.cfreq + fq * self.sr + 500) / 1e3) if self.cfreq > 0 else 0, version=self.version)
         elif typ in FAMILY:                                    # generic sonde description + the type's bit-rate tier (family.py)
             eng = self._family_engine(typ, fq)
             tel = FamilyDecoder(typ, freq_khz=khz, version=self.version)
@@ -88,11 +94,12 @@ class WidebandReceiver:
         self.sondes.append(dict(fq=fq, type=typ, engine=eng, telemetry=tel, frames=0, khz=khz, t_last=self.t))
         self.log.append(dict(event="detected", type=typ, fq=fq, freq_khz=khz))
 
-    def add_channel(self, typ: str, fq: float):
-        """start a decoder of sonde type `typ` (a scanner type name: "RS41", "DFM", "M10", "IMET4", "MK2LMS", ...) at fq (fraction of the
-        sample rate) without waiting for the scanner — what a detection does, for signals the caller knows about or the scanner's 48 kHz IF
-        cannot see (an MkIIa deviates by +/- 50 kHz, a WxR-301D is 64 kHz wide)."""
-        self._start(fq, typ)
+    def add_channel(self, typ: str, fq: float, invert: bool = False):
+        """start a decoder of sonde type `typ` (a scanner type name: "RS41", "DFM", "M10", "IMET4", "MK2LMS", "RD94RD41", ...) at fq (fraction
+        of the sample rate) without waiting for the scanner — what a detection does, for signals the caller knows about or the scanner's
+        48 kHz IF cannot see (an MkIIa deviates by +/- 50 kHz, a WxR-301D is 64 kHz wide).  invert: the decoder's -i (dropsondes only; a
+        detection sets it from the sign of its score)."""
+        self._start(fq, typ, invert)
 
     def _family_engine(self, typ: str, fq: float):
         f = FAMILY[typ]
@@ -133,6 +140,8 @@ class WidebandReceiver:
                     self.add_channel(MK2LMS, self.raster[d["channel"]] + d["df"])
                 elif d["type"] in WXR:                                      # WXR301: the offset estimate is dropped, as auto_rx's scan.py does (not accurate without whitening)
                     self.add_channel(d["type"], self.raster[d["channel"]] + (d["df"] if d["type"] == "WXRPN9" else 0.0))
+                elif d["type"] == DROP[0]:                                  # either polarity: a negative score starts the decoder with -i
+                    self._start(self.raster[d["channel"]] + d["df"], DROP[0], invert=d["score"] < 0)
                 elif d["type"] in FAMILY and (d["score"] > 0 or FAMILY[d["type"]]["auto"]):
                     self._start(self.raster[d["channel"]] + d["df"], d["type"])
             self.t += (len(x) // 2) / self.sr
@@ -159,7 +168,7 @@ class WidebandReceiver:
         if finish:
             for s in self.sondes:
                 if s["type"] in OWN_DEC:
-                    s["engine"].finish()                       # the frame in progress at the end is printed as it is (mk2a1680mod.c:2409-2424, weathex301d.c:692-704)
+                    s["engine"].finish()                       # the frame in progress at the end is printed as it is (mk2a1680mod.c:2409-2424, weathex301d.c:692-704, rd94rd41drop.c:1430-1445)
                 out += self._drain(s, True)
         return out
 
@@ -188,6 +197,16 @@ class WidebandReceiver:
                 s["frames"] += 1
                 js = [json.loads(line) for line in s["telemetry"].frame(f["bits"]).split("\n") if line.startswith("{")]
                 s["good"] = s.get("good", 0) + (1 if js else 0)
+                out += js
+            return out
+        if s["type"] in DROP:                                # JSON only for a frame with every block good; the type is what the frames say,
+            out = []                                         # as auto_rx takes it from the "type" field (decode.py:1713-1717)
+            for f in e.fetch_frames():
+                s["frames"] += 1
+                js = [json.loads(line) for line in s["telemetry"].frame(f["bytes"]).split("\n") if line.startswith("{")]
+                s["good"] = s.get("good", 0) + (1 if js else 0)
+                if js:
+                    s["type"] = js[-1]["type"]
                 out += js
             return out
         if s["type"] in FAMILY:

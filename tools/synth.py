@@ -1507,3 +1507,145 @@ def wxr_capture(sr: int = 96_000, *, n_frames: int = 16, pn9: bool = False, dev_
     out[0::2] = np.clip(np.round(x.real), -32768, 32767).astype(np.int16)
     out[1::2] = np.clip(np.round(x.imag), -32768, 32767).astype(np.int16)
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------- Vaisala RD94 / RD41 dropsondes
+DROP_BLK94 = ((2, 3), (7, 17), (26, 47), (75, 18), (95, 21))                                  # chksum16 blocks: start, length; check word behind
+DROP_BLK41 = ((2, 3), (7, 16), (25, 17), (44, 12), (58, 13), (73, 27), (102, 14))             # CRC-16 blocks
+
+
+def drop_chksum16(data) -> int:
+    s1 = s2 = 0
+    for b in bytes(data):
+        s1 = (s1 + b) & 0xFF
+        s2 = (s2 + s1) & 0xFF
+    return s2 | (s1 << 8)
+
+
+def drop_crc16(data) -> int:
+    """CRC-16, polynomial 0x1021, start 0, no reflection"""
+    rem = 0
+    for b in bytes(data):
+        rem ^= b << 8
+        for _ in range(8):
+            rem = ((rem << 1) ^ 0x1021 if rem & 0x8000 else rem << 1) & 0xFFFF
+    return rem
+
+
+def _f32_rd94(x: float) -> bytes:
+    """a float as the RD94 sends it: exponent, then the sign, then the mantissa, high byte first"""
+    u = int(np.float32(x).view(np.uint32))
+    return (((u >> 23) & 0xFF) << 24 | (u >> 31) << 23 | (u & 0x7FFFFF)).to_bytes(4, "big")
+
+
+def _ecef_cm(lat: float, lon: float, alt: float):
+    a, b = 6378137.0, 6356752.31424518
+    e2 = (a * a - b * b) / (a * a)
+    la, lo = np.radians(lat), np.radians(lon)
+    N = a / np.sqrt(1 - e2 * np.sin(la) ** 2)
+    return [int(round(100 * v)) for v in ((N + alt) * np.cos(la) * np.cos(lo), (N + alt) * np.cos(la) * np.sin(lo), (N * (1 - e2) + alt) * np.sin(la))]
+
+
+def drop_frame(kind: int = 41, k: int = 0, *, sn: int = 162345678, lat=47.60621, lon=-122.33207, alt_m=9876.5, corrupt=(), rng=None) -> bytes:
+    """The 120 bytes of one dropsonde frame, kind 41 (RD41: seven CRC-16 blocks) or 94 (RD94: five chksum16 blocks), every check correct:
+    FC 1D, the blocks as the decoder reads them, 1A CF.  k = frame number (two frames a second); corrupt = numbers of the blocks of that
+    kind that get one byte changed after the check words are set."""
+    rng = rng or np.random.default_rng(1000 * kind + k)
+    f = bytearray(rng.integers(0, 256, 120, dtype=np.uint8).tobytes())
+    f[0:2], f[118:120] = b"\xFC\x1D", b"\x1A\xCF"
+    alt = alt_m - 5.5 * k
+    la, lo = lat + 2e-5 * k, lon - 3e-5 * k
+    P, T, U1, U2, Ti = 301.25 + 0.75 * k, -41.5 + 0.1 * k, 23.5 + 0.5 * k, 24.25 + 0.5 * k, 21.75
+    h, m, s, cs = 14, 25 + (k // 120) % 30, (k // 2) % 60, 50 * (k % 2)
+    if kind == 41:
+        f[3:5] = int(k & 0xFFFF).to_bytes(2, "big")
+        f[7:23] = np.array([P, T, U1, U2], "<f4").tobytes()
+        f[25:31] = np.array([int(round(100 * (12.3 + 0.1 * k))), int(round(100 * (123.4 + k))), int(round(100 * (11.0 + 0.05 * k)))], ">i2").tobytes()
+        f[31:34] = (int(round(100 * alt)) & 0xFFFFFF).to_bytes(3, "big")
+        f[34:39] = bytes([h, m, s, cs, 9])
+        f[44:52] = np.array([int(round(la * 1e7)), int(round(lo * 1e7))], ">i4").tobytes()
+        f[58:64] = np.array([int(round(100 * (12.4 + 0.1 * k))), int(round(100 * (123.9 + k))), int(round(100 * (11.1 + 0.05 * k)))], ">i2").tobytes()
+        f[64:67] = (int(round(100 * (alt - 2.75))) & 0xFFFFFF).to_bytes(3, "big")
+        f[67] = 10
+        f[73:100] = b"\x0A" * 27
+        f[102:106] = int(sn).to_bytes(4, "big")
+        f[108:110] = int(8950 - k).to_bytes(2, "big")
+        f[110:114] = np.array([Ti], "<f4").tobytes()
+        f[114:116] = b"A5"
+        for p, n in DROP_BLK41:
+            f[p + n:p + n + 2] = drop_crc16(f[p:p + n]).to_bytes(2, "big")
+        blocks = DROP_BLK41
+    elif kind == 94:
+        f[3:5] = int(k & 0xFFFF).to_bytes(2, "little")
+        f[7:23] = b"".join(_f32_rd94(v) for v in (P, T, U1, U2))
+        tow = ((3 * 24 + h) * 3600 + m * 60 + s) * 1000 + 10 * cs
+        f[26:30] = int(tow).to_bytes(4, "little")
+        f[34:36] = int(2280).to_bytes(2, "little")
+        f[38:50] = np.array(_ecef_cm(la, lo, alt), "<i4").tobytes()
+        f[50:54] = int(250 + k).to_bytes(4, "little")
+        f[54:66] = np.array([-512 + 3 * k, 640 - 2 * k, 1130 + k], "<i4").tobytes()
+        f[66:70] = int(35).to_bytes(4, "little")
+        f[72] = 9
+        f[76:88] = np.array([-508 + 3 * k, 636 - 2 * k, 1127 + k], "<i4").tobytes()
+        f[88:92] = int(36).to_bytes(4, "little")
+        f[92] = 10
+        f[95:99] = int(sn).to_bytes(4, "big")
+        f[99:101] = b"A5"
+        f[104:106] = int(8950 - k).to_bytes(2, "little")
+        f[106:110] = _f32_rd94(Ti)
+        for p, n in DROP_BLK94:
+            f[p + n:p + n + 2] = drop_chksum16(f[p:p + n]).to_bytes(2, "big")
+        blocks = DROP_BLK94
+    else:
+        raise ValueError("kind is 41 or 94")
+    for b in corrupt:
+        f[blocks[b][0] + 1] ^= 0x5A
+    return bytes(f)
+
+
+def drop_frames(n_frames: int = 8, kind: int = 41, k0: int = 100, corrupt=None, **kw) -> list:
+    """consecutive frames; corrupt = {frame index: block list}"""
+    corrupt = {int(i): tuple(b) for i, b in dict(corrupt or {}).items()}
+    return [drop_frame(kind, k0 + i, corrupt=corrupt.get(i, ()), **kw) for i in range(n_frames)]
+
+
+def drop_rawbits(frames) -> np.ndarray:
+    """8N1 (start 0, data LSB first, stop 1), every bit Manchester-coded: 1 -> 01, 0 -> 10; frames without gaps"""
+    by = np.frombuffer(b"".join(frames), np.uint8)
+    bits = np.ones((len(by), 10), np.int8)
+    bits[:, 0] = 0
+    bits[:, 1:9] = (by[:, None] >> np.arange(8)) & 1
+    bits = bits.reshape(-1)
+    return np.stack([1 - bits, bits], axis=1).reshape(-1).astype(np.int8)
+
+
+def drop_capture(sr: int = 48_000, *, n_frames: int = 8, kind: int = 41, dev_hz: float = 4_800.0, f_offset_hz: float = 0.0, noise: float | None = 25.0,
+                 flips: int = 0, invert: bool = False, fq: float = 0.0, seed: int = 1, lead_s: float = 0.25, amp: float = 8000.0, corrupt=None) -> np.ndarray:
+    """Interleaved int16 IQ of n_frames dropsonde frames sent without gaps behind the two sync bytes 1A CF of a frame before them: 2-FSK at
+    4800 raw bits/s (raw bit 1 = positive deviation), NRZ smoothed with a Hann window of 5 samples at 48 kHz, lead_s of noise alone before
+    and after.  noise: carrier power over the complex noise power in a 48 kHz band, in dB (None: no noise); flips: that many raw bits at
+    random places are inverted."""
+    rng = np.random.default_rng(seed)
+    baud = 4800.0
+    bits = drop_rawbits([b"\x1A\xCF"] + drop_frames(n_frames, kind, corrupt=corrupt))
+    if flips:
+        bits[rng.choice(len(bits), flips, replace=False)] ^= 1
+    if invert:
+        bits = 1 - bits
+    n_sig = int(len(bits) * sr / baud)
+    nrz = 2.0 * bits[np.minimum((np.arange(n_sig) * (baud / sr)).astype(np.int64), len(bits) - 1)] - 1.0
+    w = np.hanning(max(3, int(round(5 * sr / 48000))) + 2)[1:-1]
+    nrz = np.convolve(nrz, w / w.sum(), mode="same")
+    ph = 2 * np.pi * np.cumsum(nrz * (dev_hz / sr))
+    lead = int(lead_s * sr)
+    x = np.concatenate([np.zeros(lead, np.complex128), amp * np.exp(1j * ph), np.zeros(lead, np.complex128)])
+    n = len(x)
+    if fq != 0.0 or f_offset_hz != 0.0:
+        x = x * np.exp(2j * np.pi * (fq + f_offset_hz / sr) * np.arange(n))
+    if noise is not None:
+        sigma = amp * np.sqrt(10.0 ** (-noise / 10.0) * (sr / 48000.0) / 2.0)
+        x = x + sigma * (rng.standard_normal(n) + 1j * rng.standard_normal(n))
+    out = np.empty(2 * n, dtype=np.int16)
+    out[0::2] = np.clip(np.round(x.real), -32768, 32767).astype(np.int16)
+    out[1::2] = np.clip(np.round(x.imag), -32768, 32767).astype(np.int16)
+    return out
