@@ -262,6 +262,10 @@ int  sonde_engine_set_search_rounds(sonde_engine_t *e, int32_t on);
  * read their counts back after every round, which synchronises.  out (nullable, [3]): windows so far in first rounds, in later rounds, in
  * k_search_sync launches. */
 int  sonde_engine_count_windows(sonde_engine_t *e, int32_t on, int64_t *out);
+/* Workgroups per compute unit that the device can keep resident of the two IF-rate kernels of a single-type engine's process call, with the
+ * dynamic LDS the engine launches them with (hipOccupancyMaxActiveBlocksPerMultiprocessor): out[0] the IF chain (k_if_chain), out[1] the one-launch
+ * header search and frame sync (k_search_sync); 0 where the engine does not run that kernel.  For tests and measurements. */
+int  sonde_engine_tail_residency(sonde_engine_t *e, int32_t *out);
 /* Per-channel sync state of a single-type engine after the calls issued so far (waits for them): 8 words per channel {sample_in, k, mv_pos,
  * mode, mv (float bits), inv, 0, 0}.  Returns the number of channels written. */
 int  sonde_engine_read_sync_state(sonde_engine_t *e, uint32_t *out, int32_t max_channels);

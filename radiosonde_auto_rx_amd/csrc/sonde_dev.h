@@ -235,5 +235,8 @@ void sonde_launch_sync_plan(const WinPlanArgs *a, hipStream_t s);
 void sonde_launch_sync_window_fft(const WinFftArgs *a, hipStream_t s);
 void sonde_launch_framesync(const SyncArgs *a, hipStream_t s);
 void sonde_launch_search_sync(const SearchSyncArgs *a, hipStream_t s);
+// workgroups of k_if_chain (with the dynamic LDS a launch with these arguments asks for) / of k_search_sync that one CU holds at a time; -1: the runtime refused
+int  sonde_if_chain_residency(const IfArgs *a);
+int  sonde_search_sync_residency(void);
 }
 #endif

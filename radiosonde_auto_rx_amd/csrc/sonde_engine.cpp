@@ -891,6 +891,7 @@ static IfArgs fill_if(sonde_engine *e, int n_if, uint32_t m_first) {
     b.tone_on = (e->cfg.input != SONDE_IN_IFIQ0); b.nwin = (int)e->sps;           // --iq0 slices the FM stream (opt_iq = 1)
     b.fm_on = (e->cfg.keep_soft || fe || !e->w_fm.empty() || !b.tone_on) ? 1 : 0;   // fm_buffer feeds only --dc/--lpFM and the parity taps
     b.w_iq = e->d_wiq; b.w_fm = e->d_wfm; b.rho = e->rho; b.sps = e->sps; b.epoch = e->d_epoch;
+    if (e->cfg.opt_dc && e->cfg.input != SONDE_IN_AUDIO) b.fm_on = 1;               // --dc with IQ input: header dc and AFC read the FM stream
     return b;
 }
 // The IF-rate part of a process call: IF chain, header search rounds, frame sync (+ block codes), decoder, counter publish — everything behind the decimator.
@@ -914,7 +915,7 @@ static int tail_enqueue(sonde_engine *e, int32_t n_samples, uint32_t m_first, hi
         // reports the sample, and everything IF-rate is redone from there with the new state until no channel reports one.
         hipStream_t sb = e->stream_b;
         sonde_launch_fill_u32(e->d_start, m_first, C, sb);
-        b.y = e->d_yrot; b.tap_ifiq = e->d_ifiq; b.afc = e->d_afc; b.start = e->d_start; b.fmraw = e->d_fmraw; b.w_iq0 = e->d_wiq0; b.fm_on = 1;
+        b.y = e->d_yrot; b.tap_ifiq = e->d_ifiq; b.afc = e->d_afc; b.start = e->d_start; b.fmraw = e->d_fmraw; b.w_iq0 = e->d_wiq0;
         c.start = e->d_start;
         AfcRotArgs r{}; r.y = e->d_y; r.yrot = e->d_yrot; r.afc = e->d_afc; r.start = e->d_start; r.n_ch = C; r.ring_len = e->ring_len;
         r.sr = e->info.if_sr; r.m_end = e->m_out;
@@ -1205,6 +1206,13 @@ int sonde_engine_count_windows(sonde_engine_t *e, int32_t on, int64_t *out) {
         out[0] = e->wcount_rounds[0]; out[1] = e->wcount_rounds[1]; out[2] = (int64_t)n;
     }
     return 0;
+}
+int sonde_engine_tail_residency(sonde_engine_t *e, int32_t *out) {
+    if (!e || !out || !e->groups.empty()) return SONDE_E_ARG;
+    const IfArgs b = fill_if(e, 0, 0);
+    out[0] = e->cfg.input != SONDE_IN_AUDIO ? sonde_if_chain_residency(&b) : 0;
+    out[1] = (e->cfg.sonde_type != SONDE_FRONTEND && e->d_win && !e->cfg.opt_dc) ? sonde_search_sync_residency() : 0;
+    return (out[0] < 0 || out[1] < 0) ? SONDE_E_NOGPU : 0;
 }
 int sonde_engine_read_sync_state(sonde_engine_t *e, uint32_t *out, int32_t max_channels) {
     if (!e || !out || !e->groups.empty() || !e->d_state) return SONDE_E_ARG;

@@ -24,6 +24,7 @@
 #include "md_fast_gen.h"
 #include "sonde_rs_dev.h"
 #include <cstdlib>
+#include <algorithm>
 
 typedef short  short2v __attribute__((ext_vector_type(2)));
 
@@ -1259,6 +1260,20 @@ __global__ void k_fill_u32(uint32_t *p, uint32_t v, int n) {
 #define IF_LD 5
 #endif
 
+// (X1, X2) over storage that is dead by the time the tone sums read it (layout B of if_chain_body).  A thread parks the X values of IF_NB outputs in registers while
+// other threads still read what lies there, so the X values that are READ — k >= if_chain_xlo: the tone windows never reach the first T2-1 samples of the history — must
+// come from at most ONE pass of a thread through the low-pass loop: two passes k0 and k0 + IF_NB * IF_THREADS of a thread cannot both lie in [xlo, nz) then.
+__host__ __device__ __forceinline__ int  if_chain_xlo(int T2) { return (T2 - 1) & ~(IF_NB - 1); }
+__host__ __device__ __forceinline__ bool if_chain_overlay(int tone_on, int T2, int hz) { return tone_on && hz + IF_TILE - if_chain_xlo(T2) <= IF_NB * IF_THREADS; }
+// dynamic LDS of a workgroup (the layouts at the top of if_chain_body, for a full tile)
+static size_t if_chain_lds(const IfArgs &a) {
+    const int T1 = a.lpiq_on ? a.lpiq_taps : 1, T2 = a.lpfm_on ? a.lpfm_taps : 1, hz = (T2 - 1) + std::max(1, a.nwin - 1);
+    const int nz = hz + IF_TILE, ny = nz + T1 - 1, nsf = a.fm_on ? T2 - 1 + IF_TILE : 0;
+    const size_t sy = (size_t)((ny + 2 * IF_NB + 1) & ~1) * 8, sz = (size_t)(a.fm_on ? nz + 1 : 0) * 8, tail = (size_t)(T1 + T2) * 4 + 32;
+    if (if_chain_overlay(a.tone_on, T2, hz)) return std::max(sy + sz, (size_t)((nsf + 3) & ~3) * 4 + (size_t)(nz - if_chain_xlo(T2)) * 16) + tail;
+    return sy + sz + (size_t)(a.tone_on ? nz : 0) * 16 + (size_t)nsf * 4 + tail;
+}
+
 // (the body serves two kernels: k_if_chain — one sonde type, arguments in the kernel argument segment — and k_if_chain_multi, the channel groups of a mixed engine in one launch)
 __device__ __forceinline__ void if_chain_body(const IfArgs &a, const int ch, const int bx) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -1281,11 +1296,16 @@ __device__ __forceinline__ void if_chain_body(const IfArgs &a, const int ch, con
     float2 *sy = reinterpret_cast<float2 *>(smem);            // [nyp]
     const int nzs = a.fm_on ? nz + (nz & 1) : 0;               // z' is kept for the discriminator only
     float2 *sz = sy + nyp;                                     // [nz]   z'[t0 - hz + k]
-    float4 *sx4 = reinterpret_cast<float4 *>(sz + nzs);        // [nz]   (X1, X2): X1 = z' * e^{+i 2 pi m rho}, X2 = z' * e^{-i 2 pi m rho}
-    float  *sf = reinterpret_cast<float *>(sx4 + (a.tone_on ? nz : 0));   // [T2-1+nout] raw s_fm (the tone products exist with the tone correlator only)
+    // Layout A: y | z' | (X1, X2) | raw s_fm | taps.  Layout B (if_chain_overlay): y and z' are dead once the low-pass and the discriminator are through, so the raw
+    // s_fm goes where y began (written after the barrier behind the low-pass) and (X1, X2) behind it, over the rest of y and z' — a thread keeps the X values of
+    // IF_NB outputs in registers until the discriminator's last read of z' is over and stores them then.  Entry k of (X1, X2) lies at sx4[k - xlo].
+    const bool ovl = if_chain_overlay(a.tone_on, T2, hz);
+    const int xlo = ovl ? if_chain_xlo(T2) : 0;
     const int nsf = a.fm_on ? T2 - 1 + nout : 0;
-    float  *wf = sf + nsf;                                     // [T2]
-    float  *wq = sf + ((nsf + T2 + 3) & ~3);                   // [T1] IF low-pass taps, 16-byte aligned (sf is): read 4 at a time
+    float  *sf = ovl ? smem : reinterpret_cast<float *>(sz + nzs) + (a.tone_on ? 4 * nz : 0);   // [T2-1+nout] raw s_fm
+    float4 *sx4 = ovl ? reinterpret_cast<float4 *>(smem + ((nsf + 3) & ~3)) : reinterpret_cast<float4 *>(sz + nzs);   // [nz - xlo]   (X1, X2): X1 = z' * e^{+i 2 pi m rho}, X2 = z' * e^{-i 2 pi m rho} (with the tone correlator only)
+    float  *wf = ovl ? smem + max(2 * nyp + 2 * nzs, ((nsf + 3) & ~3) + 4 * (nz - xlo)) : sf + nsf;     // [T2]
+    float  *wq = ovl ? wf + ((T2 + 3) & ~3) : sf + ((nsf + T2 + 3) & ~3);   // [T1] IF low-pass taps, 16-byte aligned: read 4 at a time
 
     const float2 *yr = a.y + (size_t)ch * a.ring_len;
     // the tile's y samples: IF_LD loads per thread in flight before the first is parked (a workgroup has nothing else to do until they are there)
@@ -1314,6 +1334,7 @@ __device__ __forceinline__ void if_chain_body(const IfArgs &a, const int ch, con
     // wave-uniform: four at a time as one broadcast LDS read; (re, im) pairs accumulate with packed FMAs — per component the same fused multiply-adds in the
     // same tap order as before.  The tone phasors e^{+-i 2 pi m rho} are applied once per sample here (X1, X2), not once per window term.
     typedef float v2f __attribute__((ext_vector_type(2)));
+    float4 xr[IF_NB]; int xk0 = -1;                            // layout B: this thread's (X1, X2) of outputs xk0 .. xk0 + IF_NB - 1, parked until their place is free
     for (int k0 = IF_NB * threadIdx.x; k0 < nz; k0 += IF_NB * IF_THREADS) {
         v2f acc[IF_NB];
 #pragma unroll
@@ -1396,13 +1417,15 @@ __device__ __forceinline__ void if_chain_body(const IfArgs &a, const int ch, con
                 // (which product of a*b + c*d is rounded before the fused multiply-add is the compiler's choice under contraction, and it chose differently in the
                 // two kernels that share this body — one ulp apart; spelled out: the cosine products are rounded, the sine products fused)
                 const float rc = re * cs, ic = im * cs;
-                sx4[k] = make_float4(__builtin_fmaf(-sn, im, rc), __builtin_fmaf(sn, re, ic), __builtin_fmaf(sn, im, rc), __builtin_fmaf(-sn, re, ic));
+                const float4 x4 = make_float4(__builtin_fmaf(-sn, im, rc), __builtin_fmaf(sn, re, ic), __builtin_fmaf(sn, im, rc), __builtin_fmaf(-sn, re, ic));
+                if (!ovl) sx4[k] = x4;
+                else if (k0 >= xlo) { xr[j] = x4; xk0 = k0; }
             }
             if (a.tap_ifiq && m >= (int64_t)t0 && (int32_t)((uint32_t)m - start) >= 0)
                 a.tap_ifiq[(size_t)ch * a.ring_len + ((uint32_t)m & mask)] = make_float2(re, im);
         }
     }
-    __syncthreads();
+    __syncthreads();                                           // (layout B: the last read of y is over)
 
     // FM discriminator on [-(T2-1), nout): s_fm = 0.8 * arg(z[m] * conj(z[m-1])) / pi   (demod_mod.c:771-773)
     if (a.fm_on)
@@ -1422,6 +1445,13 @@ __device__ __forceinline__ void if_chain_body(const IfArgs &a, const int ch, con
             else if (m >= (int64_t)t0) fr[(uint32_t)m & mask] = v;
         }
         sf[k] = v;
+    }
+    if (ovl) {
+        if (a.fm_on) __syncthreads();                          // the last read of z' is over
+        if (xk0 >= 0) {
+#pragma unroll
+            for (int j = 0; j < IF_NB; j++) { const int k = xk0 + j; if (k < nz) sx4[k - xlo] = xr[j]; }
+        }
     }
     __syncthreads();
 
@@ -1444,12 +1474,12 @@ __device__ __forceinline__ void if_chain_body(const IfArgs &a, const int ch, con
             const uint32_t m = t0 + (uint32_t)k;
             if (a.tone_on) {
 #ifdef IF_EXP_NOWIN
-                if (1) { f = sx4[hz + k]; } else
+                if (1) { f = sx4[hz + k - xlo]; } else
 #endif
                 if (r == 0) {
-                    for (int j = nwin - 1; j >= 0; j--) { const float4 x = sx4[hz + k - j]; f.x += x.x; f.y += x.y; f.z += x.z; f.w += x.w; }
+                    for (int j = nwin - 1; j >= 0; j--) { const float4 x = sx4[hz + k - xlo - j]; f.x += x.x; f.y += x.y; f.z += x.z; f.w += x.w; }
                 } else {
-                    const float4 xn = sx4[hz + k], xo = sx4[hz + k - nwin];
+                    const float4 xn = sx4[hz + k - xlo], xo = sx4[hz + k - xlo - nwin];
                     f.x += xn.x - xo.x; f.y += xn.y - xo.y; f.z += xn.z - xo.z; f.w += xn.w - xo.w;
                 }
             }
@@ -1480,7 +1510,12 @@ __device__ __forceinline__ void if_chain_body(const IfArgs &a, const int ch, con
     }
 }
 
-__global__ __launch_bounds__(IF_THREADS)
+// Eight workgroups (a wave per SIMD each) per CU: 16-20 KB of LDS in layout B, and registers for eight waves per SIMD (left to itself the compiler takes 68 vector
+// registers and keeps the argument struct's fields live in 100 scalar ones: seven waves)
+#ifndef IF_WAVES_ATTR
+#define IF_WAVES_ATTR __attribute__((amdgpu_waves_per_eu(8, 8), amdgpu_num_sgpr(96)))
+#endif
+__global__ __launch_bounds__(IF_THREADS) IF_WAVES_ATTR
 void k_if_chain(const IfArgs a) { if_chain_body(a, blockIdx.y, blockIdx.x); }
 // Mixed engines: the groups (one sonde type each: own taps, tone spacing, window) side by side in ONE launch; blockIdx.y = row of the engine, rows grouped by type
 template <class A> struct MultiArgs { A g[SONDE_MAX_GROUPS]; int row0[SONDE_MAX_GROUPS + 1]; int n_groups; };
@@ -1489,7 +1524,7 @@ template <class A> __device__ __forceinline__ int multi_group(const MultiArgs<A>
     while (g + 1 < m.n_groups && row >= m.row0[g + 1]) g++;
     return __builtin_amdgcn_readfirstlane(g);
 }
-__global__ __launch_bounds__(IF_THREADS)
+__global__ __launch_bounds__(IF_THREADS) IF_WAVES_ATTR
 void k_if_chain_multi(const MultiArgs<IfArgs> m) {
     const int g = multi_group(m, (int)blockIdx.y);
     if_chain_body(m.g[g], (int)blockIdx.y - m.row0[g], blockIdx.x);
@@ -1641,6 +1676,10 @@ void k_header_corr_fact(const CorrArgs a) {
 // ------------------------------------------------------------------------------------------------
 // k_framesync: one wave per channel
 // ------------------------------------------------------------------------------------------------
+// The thread index as a value the compiler cannot trace back: what a phase derives from it (LDS addresses of every element a thread touches, table
+// offsets) is then computed where it is used.  Otherwise all of it is hoisted out of the loop around it (over windows, over the passes of the sync state machine) and stays live, in registers the
+// transform needs, across every other phase: that was the kernel's scratch.  No instruction is emitted.
+#define WF_FRESH(t) asm volatile("" : "+v"(t))
 __device__ __forceinline__ float wave_sum(float v) {
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
     return v;
@@ -1798,7 +1837,7 @@ __device__ __forceinline__ void framesync_body(const SyncArgs &a, const int ch, 
     __shared__ uint8_t s_syn[(NT / WAVE)][48];
     __shared__ uint8_t s_S[48];                // first-pass syndromes of the frame in hand
     __shared__ double s_rd[(NT / WAVE)];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int tid = threadIdx.x;
     if (ch >= a.n_ch) return;
     const uint32_t mask = (uint32_t)a.ring_len - 1;
     const float *bufs = a.bufs + (size_t)ch * a.ring_len;
@@ -1825,6 +1864,8 @@ __device__ __forceinline__ void framesync_body(const SyncArgs &a, const int ch, 
     // every pass consumes a window (K-4 samples) or a frame, or ends at `avail`: the bound only guards against a corrupted state
     for (int guard = 0; guard < (1 << 20); guard++) {
         if (st.mode == 2) break;                       // stream finished
+        WF_FRESH(tid);
+        const int lane = tid & 63, wave = tid >> 6;
         if (st.mode == 0) {
             // ---- find_header: next correlation once K-4 new samples were consumed (demod_mod.c:1540-1548)
             const uint32_t need = (uint32_t)(K - 4) - st.k;
@@ -2164,7 +2205,9 @@ struct WinItemIo {
 };
 template <class Io>
 __device__ __forceinline__ void sync_eval_window(const WinFftArgs &a, const int ch, const Io &io, float2 *x, float2 *tws, float *s_rf, int *s_ri) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int tid = threadIdx.x;
+    WF_FRESH(tid);
+    const int lane = tid & 63, wave = tid >> 6;
     if (!io.planned()) return;
     unsigned long long t_prev = a.prof ? __builtin_readcyclecounter() : 0ull;
     const int K = a.K, L = a.L, N = SC_N, wl = K + L;
@@ -2190,8 +2233,10 @@ __device__ __forceinline__ void sync_eval_window(const WinFftArgs &a, const int 
     }
     __syncthreads();
     WF_MARK(0);
+    WF_FRESH(tid);
     dft_ref<Io::copy>(x, tws, a.tws, tid);                                         // X = rdft(xn)
     WF_MARK(1);
+    WF_FRESH(tid);
     // Z = X * Fm (:190); Nidft() transforms conj(Z) (:78-80): conjugate and swap into bit-reversed order for the same network.
     // Pairs (i, r = brev(i)), r >= i; Fm[r] comes from the bit-reversed copy of the table behind it (a.Fm + N) — coalesced like Fm[i]
     {
@@ -2218,6 +2263,7 @@ __device__ __forceinline__ void sync_eval_window(const WinFftArgs &a, const int 
     }
     __syncthreads();
     WF_MARK(2);
+    WF_FRESH(tid);
     dft_ref_head<Io::copy>(x, tws, a.tws, tid);                                    // cx = Nidft(Z), real part used
     // last stage (dit_pass<1> at t = 12) in registers: only re(cx) is looked at, so nothing is stored — the arg-max of re(cx)^2 over
     // i in [L-1, K+L), first maximum wins (:200-207), is taken from the butterfly outputs as they come
@@ -2503,11 +2549,7 @@ extern "C" void sonde_launch_audio_chain(const AudioChainArgs *a, hipStream_t s)
     hipLaunchKernelGGL(k_audio_chain, dim3(gx, a->n_ch), dim3(256), 0, s, *a);
 }
 extern "C" void sonde_launch_if_chain(const IfArgs *a, hipStream_t s) {
-    const int T1 = a->lpiq_on ? a->lpiq_taps : 1, T2 = a->lpfm_on ? a->lpfm_taps : 1;
-    const int hz = (T2 - 1) + (a->nwin - 1 > 1 ? a->nwin - 1 : 1);
-    const int nz = hz + IF_TILE, ny = nz + T1 - 1;
-    const size_t lds = (size_t)((ny + 2 * IF_NB + 1) & ~1) * 8 + (size_t)(a->fm_on ? nz + 1 : 0) * 8 + (size_t)(a->tone_on ? nz : 0) * 16 + (size_t)(a->fm_on ? T2 - 1 + IF_TILE : 0) * 4 + (size_t)(T1 + T2) * 4 + 32;
-    hipLaunchKernelGGL(k_if_chain, dim3((a->n + IF_TILE - 1) / IF_TILE, a->n_ch), dim3(IF_THREADS), lds, s, *a);
+    hipLaunchKernelGGL(k_if_chain, dim3((a->n + IF_TILE - 1) / IF_TILE, a->n_ch), dim3(IF_THREADS), if_chain_lds(*a), s, *a);
 }
 // the groups of a mixed engine in one launch each (rows = channels in the engine's order, group after group)
 template <class A> static MultiArgs<A> multi_pack(const A *a, const int *rows, int n_groups) {
@@ -2525,10 +2567,7 @@ extern "C" int sonde_launch_if_chain_multi(const IfArgs *a, int n_groups, hipStr
     if (n_groups < 1 || n_groups > SONDE_MAX_GROUPS) return -1;
     size_t lds = 0; int rows[SONDE_MAX_GROUPS], n = a[0].n;
     for (int g = 0; g < n_groups; g++) {
-        const int T1 = a[g].lpiq_on ? a[g].lpiq_taps : 1, T2 = a[g].lpfm_on ? a[g].lpfm_taps : 1;
-        const int hz = (T2 - 1) + (a[g].nwin - 1 > 1 ? a[g].nwin - 1 : 1);
-        const int nz = hz + IF_TILE, ny = nz + T1 - 1;
-        const size_t l = (size_t)((ny + 2 * IF_NB + 1) & ~1) * 8 + (size_t)(a[g].fm_on ? nz + 1 : 0) * 8 + (size_t)(a[g].tone_on ? nz : 0) * 16 + (size_t)(a[g].fm_on ? T2 - 1 + IF_TILE : 0) * 4 + (size_t)(T1 + T2) * 4 + 32;
+        const size_t l = if_chain_lds(a[g]);
         if (l > lds) lds = l;
         rows[g] = a[g].n_ch;
         if (a[g].n != n) return -1;                              // (one call = the same samples for every channel)
@@ -2662,7 +2701,15 @@ extern "C" void sonde_launch_framesync(const SyncArgs *a, hipStream_t s) {
     if (a->opt_dc) hipLaunchKernelGGL(k_framesync<true>, dim3(a->n_ch), dim3(FS_THREADS), 0, s, *a);
     else hipLaunchKernelGGL(k_framesync<false>, dim3(a->n_ch), dim3(FS_THREADS), 0, s, *a);
 }
+static constexpr size_t SEARCH_SYNC_LDS = (size_t)(SC_XN + SC_TW_LDS + 1) * sizeof(float2);
 extern "C" void sonde_launch_search_sync(const SearchSyncArgs *a, hipStream_t s) {
-    const size_t lds = (size_t)(SC_XN + SC_TW_LDS + 1) * sizeof(float2);
-    hipLaunchKernelGGL(k_search_sync, dim3(a->sync.n_ch), dim3(WF_THREADS), lds, s, *a);
+    hipLaunchKernelGGL(k_search_sync, dim3(a->sync.n_ch), dim3(WF_THREADS), SEARCH_SYNC_LDS, s, *a);
+}
+extern "C" int sonde_if_chain_residency(const IfArgs *a) {
+    int n = 0;
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_if_chain, IF_THREADS, if_chain_lds(*a)) == hipSuccess ? n : -1;
+}
+extern "C" int sonde_search_sync_residency(void) {
+    int n = 0;
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_search_sync, WF_THREADS, SEARCH_SYNC_LDS) == hipSuccess ? n : -1;
 }

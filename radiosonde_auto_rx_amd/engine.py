@@ -275,6 +275,14 @@ class Engine:
         _chk(lib().sonde_engine_count_windows(self._h, 1 if on else 0, out.ctypes.data))
         return {"round0": int(out[0]), "rounds": int(out[1]), "search_sync": int(out[2])}
 
+    def tail_residency(self):
+        """-> workgroups per compute unit {"if_chain", "search_sync"} of the IF-rate kernels as this engine launches them (include/sonde_hip.h)"""
+        out = np.zeros(2, dtype=np.int32)
+        f = lib().sonde_engine_tail_residency          # (looked up here: a library of an earlier revision given with SONDE_HIP_LIB for an A/B run lacks it)
+        f.argtypes = [C.c_void_p, C.c_void_p]
+        _chk(f(self._h, out.ctypes.data))
+        return {"if_chain": int(out[0]), "search_sync": int(out[1])}
+
     def sync_state(self) -> np.ndarray:
         """per-channel sync state after the calls so far: [n_channels, 8] uint32 {sample_in, k, mv_pos, mode, mv bits, inv, 0, 0}"""
         out = np.zeros((self.n_channels, 8), dtype=np.uint32)
