@@ -123,17 +123,20 @@ def reflib(name: str = "libref_demod.so") -> C.CDLL:
     return _reflibs[name]
 
 
-def _refcfg(sr, bps, iq_mode, fq, lp_iq, lp_fm, afc, baud, bt, h, lpiq_bw, lpfm_bw, hdr, symlen, symhd, iqdc=False):
-    return RefCfg(sr, bps, iq_mode, (1 if lp_iq else 0) | (2 if lp_fm else 0), int(afc), int(iqdc), 0, 0, -fq, baud,
+def _refcfg(sr, bps, iq_mode, fq, lp_iq, lp_fm, afc, baud, bt, h, lpiq_bw, lpfm_bw, hdr, symlen, symhd, iqdc=False,
+            opt_min=False, nolut=False):
+    return RefCfg(sr, bps, iq_mode, (1 if lp_iq else 0) | (2 if lp_fm else 0), int(afc), int(iqdc), int(opt_min), int(nolut), -fq, baud,
                   symlen, symhd, bt, h, lpiq_bw, lpfm_bw, hdr)
 
 
 def ref_streams(iq, sr, *, bps=16, iq_mode=5, fq=0.0, lp_iq=True, lp_fm=False, afc=False, baud=4800.0,
                 bt=0.5, h=0.6, lpiq_bw=7400, lpfm_bw=6000, hdr=RS41_HDR, symlen=1, symhd=1,
-                max_if=None, want_iq=True, libname="libref_demod.so"):
+                max_if=None, want_iq=True, libname="libref_demod.so", opt_min=False, nolut=False):
+    """opt_min / nolut: the reference's --min (IF 32 kHz class) and --noLUT (mixer from a running double phase, no table)"""
     if max_if is None:
         max_if = len(iq) // 2 + 16
-    cfg = _refcfg(sr, bps, iq_mode, fq, lp_iq, lp_fm, afc, baud, bt, h, lpiq_bw, lpfm_bw, hdr, symlen, symhd)
+    cfg = _refcfg(sr, bps, iq_mode, fq, lp_iq, lp_fm, afc, baud, bt, h, lpiq_bw, lpfm_bw, hdr, symlen, symhd,
+                  opt_min=opt_min, nolut=nolut)
     L = reflib(libname)
     L.ref_streams.restype = C.c_int
 

@@ -834,7 +834,7 @@ int sonde_engine_process_device(sonde_engine_t *e, const void *d_iq, int64_t ch_
         if (e->dc_since < (1 << 20)) e->dc_since += take / D;
         if (e->pcs) { a.epoch_phase = e->d_epoch_phase; a.dc_since_ch = e->d_pcs_since; a.dc_avg_prev = e->d_etab ? e->d_dcavg_prev : nullptr; }
         prof_begin(e, "mix_decimate", e->stream); const int lrc = sonde_launch_mix_decimate(&a, e->stream); prof_end(e, e->stream);
-        if (lrc < 0) { e->in_call = false; e->ecc_listed = false; for (sonde_engine *g : e->groups) { g->in_call = false; g->ecc_listed = false; } return SONDE_E_ARG; }
+        if (lrc < 0) { e->in_call = false; e->ecc_listed = false; for (sonde_engine *g : e->groups) { g->in_call = false; g->ecc_listed = false; } return lrc == -2 ? SONDE_E_NOGPU : SONDE_E_ARG; }
         e->ptail_cur ^= 1;
         e->samples_in += (uint64_t)take; e->m_out += (uint32_t)(take / D); e->dc_cnt += (uint32_t)take; done += take;
         if (e->pcs) {                                    // per-channel segment edges: the device keeps the counters, the host mirrors them

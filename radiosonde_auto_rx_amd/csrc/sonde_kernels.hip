@@ -291,9 +291,13 @@ void k_mix_decimate50(const MixDecArgs a) {
     if (ch >= a.n_ch) return;
     const int seg = wg * 4 + wave;
     const int rows_per_seg = MD_ROWS * a.G - H;
-    const int jb = seg * rows_per_seg;
+    // Segment 0 has no halo rows in front, so its G tiles reach H rows further than rows_per_seg: it owns them (all of its rows produce output and
+    // count for the IQ-DC sum, the tile loop has no mask for a wave's last tile), and the later segments start H rows later than seg * rows_per_seg.
+    // (Before, segment 0 stopped at rows_per_seg on paper only: the last H rows of its tile were written and ADDED TO THE IQ-DC SUM a second time by
+    // segment 1 — six blocks too many in every launch's mean, 1.3e-3 of error on a channel at the stream's centre, where the mean is in the passband.)
+    const int jb = (seg == 0) ? 0 : seg * rows_per_seg + H;
     if (jb >= a.nblocks) return;
-    const int je = min(a.nblocks, jb + rows_per_seg);
+    const int je = min(a.nblocks, (seg + 1) * rows_per_seg + H);
     const int jt0 = (seg == 0) ? jb : jb - H;
     const int ntiles = (je - jt0 + MD_ROWS - 1) / MD_ROWS;
     const int nfull = min(ntiles, (a.nblocks - jt0) / MD_ROWS);        // leading tiles that lie completely inside the chunk
@@ -309,15 +313,16 @@ void k_mix_decimate50(const MixDecArgs a) {
     const float2 *etab = a.etab + (size_t)ch * P;
 
     // carry: what the P rows before this tile add to its first H outputs (lane l < H: sum over q of P[l-(H-q)][q], rows < 0)
+    // (the correction for a change of the IQ-DC mean first, then the rows in the order of q: the sequence every output is summed in, see MD50_LOOP_1)
     float2v carry = {0.f, 0.f};
     if (seg == 0 && lane < H) {
+        carry = md_dc_boundary(a, ch, f0, lane);
 #pragma unroll
         for (int q = 0; q < H; q++) {
             const int i = lane + q;                            // row l - (H-q) of the chunk = row l + q of the P tail (blocks -H .. -1)
             if (i < H) { const float2 v = a.ptail_in[((size_t)ch * 8 + i) * 8 + q]; carry += (float2v){v.x, v.y}; }
         }
     }
-    if (seg == 0 && lane < H) carry += md_dc_boundary(a, ch, f0, lane);
     int sx = 0, sy = 0;
     // the lane's block as an index into the period of the mixer table (table index = D * eidx): phase seed and E index
     uint32_t eidx = (uint32_t)(((uint64_t)(md_lut_phase(a, ch) / D) + (uint64_t)(jt0 + lane)) % P);
@@ -351,13 +356,14 @@ void k_mix_decimate50(const MixDecArgs a) {
         const float m = outrow ? 1.f : 0.f;
         md_fast_tile(row_lds, wt_s, f0, f0 * (double)(eidx * (uint32_t)D), (float2v){m, m}, acc, dcs);
         sx += (int)dcs.x; sy += (int)dcs.y;
-        float2v y = acc[H] + carry;
+        float2v y = carry;                                    // the earlier rows' terms first, in the order of q, the row's own last: as MD50_LOOP_1
 #pragma unroll
         for (int q = 0; q < H; q++) {
             const int k = H - q, src = (lane - k) & 63;
             const float2v r = { __shfl(acc[q].x, src), __shfl(acc[q].y, src) };
             if (lane >= k) y += r;
         }
+        y += acc[H];
         y = md_dc_correct(y, avg, etab[eidx]);
         if (outrow) yout[(a.m0 + (uint32_t)j) & rmask] = make_float2(y.x, y.y);
         if (j >= a.nblocks - H && j < a.nblocks) {
@@ -776,7 +782,10 @@ void k_mix_decimate(const MixDecArgs a) {
         sx += (int)dcs.x; sy += (int)dcs.y;
 
         // y[j] = sum_q P[j-(H-q)][q]: shift column q down by H-q lanes, the first lanes take the previous tile's rows
+        // FAST: the order of additions of k_mix_decimate50 — the correction for a change of the IQ-DC mean within reach (md_dc_boundary), the Q-1 terms of
+        // the earlier rows in the order of q, the row's own P[j][H] last — so that either kernel gives an output the same bits wherever the calls cut
         float yr = acc[H].x, yi = acc[H].y;
+        if constexpr (FAST > 0) { const float2v bnd = j < H ? md_dc_boundary(a, ch, f0, j) : (float2v){0.f, 0.f}; yr = bnd.x; yi = bnd.y; }
 #pragma unroll
         for (int q = 0; q < H; q++) {
             // lane l takes row l-k: this tile's for l >= k, the previous tile's row l-k+64 otherwise — one rotation of
@@ -787,9 +796,9 @@ void k_mix_decimate(const MixDecArgs a) {
             yi += __shfl(old ? pv[q].y : acc[q].y, src);
         }
         if constexpr (FAST > 0) {                             // the IQ-DC mean, per output: y -= avg * E (md_fast_tile)
+            yr += acc[H].x; yi += acc[H].y;
             if (outrow) {
-                float2v yc = md_dc_correct((float2v){yr, yi}, avg, a.etab[(size_t)ch * a.etab_len + (rown / (uint32_t)D)]);
-                if (j < H) yc += md_dc_boundary(a, ch, f0, j);
+                const float2v yc = md_dc_correct((float2v){yr, yi}, avg, a.etab[(size_t)ch * a.etab_len + (rown / (uint32_t)D)]);
                 yr = yc.x; yi = yc.y;
             }
         }
@@ -1267,7 +1276,7 @@ __host__ __device__ __forceinline__ int  if_chain_xlo(int T2) { return (T2 - 1) 
 __host__ __device__ __forceinline__ bool if_chain_overlay(int tone_on, int T2, int hz) { return tone_on && hz + IF_TILE - if_chain_xlo(T2) <= IF_NB * IF_THREADS; }
 // dynamic LDS of a workgroup (the layouts at the top of if_chain_body, for a full tile)
 static size_t if_chain_lds(const IfArgs &a) {
-    const int T1 = a.lpiq_on ? a.lpiq_taps : 1, T2 = a.lpfm_on ? a.lpfm_taps : 1, hz = (T2 - 1) + std::max(1, a.nwin - 1);
+    const int T1 = a.lpiq_on ? a.lpiq_taps : 1, T2 = a.lpfm_on ? a.lpfm_taps : 1, hz = (T2 - 1) + std::max(1, a.nwin - 1) + (a.tone_on ? IF_RUN - 1 : 0);
     const int nz = hz + IF_TILE, ny = nz + T1 - 1, nsf = a.fm_on ? T2 - 1 + IF_TILE : 0;
     const size_t sy = (size_t)((ny + 2 * IF_NB + 1) & ~1) * 8, sz = (size_t)(a.fm_on ? nz + 1 : 0) * 8, tail = (size_t)(T1 + T2) * 4 + 32;
     if (if_chain_overlay(a.tone_on, T2, hz)) return std::max(sy + sz, (size_t)((nsf + 3) & ~3) * 4 + (size_t)(nz - if_chain_xlo(T2)) * 16) + tail;
@@ -1289,7 +1298,9 @@ __device__ __forceinline__ void if_chain_body(const IfArgs &a, const int ch, con
     const int nwin = a.nwin;                          // tone window = (int)sps
     const int64_t ep = a.epoch ? (int64_t)a.epoch[ch] : 0;   // this channel's stream start: phase origin of the tone mixer (history before it is zeroed by the host)
     // sample ranges (relative to t0): s_fm needed on [-(T2-1), nout); z' on [-(T2-1)-max(1,nwin-1)..]
-    const int hz = (T2 - 1) + max(1, nwin - 1);       // history of z' needed
+    // history of z' needed: the FM low-pass, the tone window, and — the tone sums run in groups of IF_RUN outputs that start at ABSOLUTE multiples of IF_RUN, so
+    // that a sum is the same sequence of additions wherever a call or a tile begins — the part of a tile's first group that lies in front of the tile
+    const int hz = (T2 - 1) + max(1, nwin - 1) + (a.tone_on ? IF_RUN - 1 : 0);
     const int nz = hz + nout;                         // z' count
     const int ny = nz + (T1 - 1);                     // y count
     const int nyp = (ny + 2 * IF_NB + 1) & ~1;                 // padded: the IF_NB-output groups read a little past ny
@@ -1460,12 +1471,15 @@ __device__ __forceinline__ void if_chain_body(const IfArgs &a, const int ch, con
     // two-tone correlator: windowed sums over the last nwin samples (the reference keeps them as recursive sliding sums over the whole stream,
     // demod_mod.c:796-803 — same value up to its float drift).  Each thread takes IF_RUN consecutive outputs: a full window sum for the first,
     // then + newest - oldest for the next IF_RUN - 1 (the run is short, so no drift builds up: <= 2 (IF_RUN - 1) roundings on top of the sum's own).
+    // The runs start at absolute multiples of IF_RUN (k0 may be up to IF_RUN - 1 in front of the tile: those sums are formed, not stored), so every output is
+    // the same window sum and the same + newest - oldest steps however the stream is cut into calls and tiles.
     const float inv_sps = 1.0f / a.sps;
-    for (int k0 = IF_RUN * threadIdx.x; k0 < nout; k0 += IF_RUN * IF_THREADS) {
+    const int koff = a.tone_on ? (int)(t0 & (uint32_t)(IF_RUN - 1)) : 0;
+    for (int k0 = IF_RUN * threadIdx.x - koff; k0 < nout; k0 += IF_RUN * IF_THREADS) {
         float4 f = make_float4(0.f, 0.f, 0.f, 0.f);
         float so[IF_RUN], sfm[IF_RUN];
         // a full run at a 16-byte boundary of the ring leaves as one store per stream (the ring length is a power of two >= IF_RUN: no wrap inside it)
-        const bool vec = !afc && k0 + IF_RUN <= nout && ((t0 + (uint32_t)k0) & (IF_RUN - 1)) == 0;
+        const bool vec = !afc && k0 >= 0 && k0 + IF_RUN <= nout && ((t0 + (uint32_t)k0) & (IF_RUN - 1)) == 0;
 #pragma unroll
         for (int r = 0; r < IF_RUN; r++) {
             const int k = k0 + r;
@@ -1483,7 +1497,7 @@ __device__ __forceinline__ void if_chain_body(const IfArgs &a, const int ch, con
                     f.x += xn.x - xo.x; f.y += xn.y - xo.y; f.z += xn.z - xo.z; f.w += xn.w - xo.w;
                 }
             }
-            if (afc && (int32_t)(m - start) < 0) continue;
+            if (k < 0 || (afc && (int32_t)(m - start) < 0)) continue;
             float s_fm = 0.f;
             if (a.fm_on) {
                 s_fm = sf[T2 - 1 + k];
@@ -2430,8 +2444,13 @@ extern "C" int sonde_launch_mix_decimate(const MixDecArgs *a, hipStream_t s) {
         return 0;
     }
     const size_t lds = (size_t)4 * (MD_ROWS * a->D + 4) * sizeof(uint32_t);
-#define MD_LAUNCH(QT) do { if (a->phase_f64) hipLaunchKernelGGL((k_mix_decimate<QT, true, 0, 0>), grid, blk, lds, s, b); \
-                         else hipLaunchKernelGGL((k_mix_decimate<QT, false, 0, 0>), grid, blk, lds, s, b); } while (0)
+    // D = 64 (3.072 / 3.2 Msps, 2.048 Msps --min): four tiles of 64 x 64 samples and their pads are 65 600 bytes, 64 bytes above what a launch may ask
+    // for without saying so first (the CU has 160 KB).  The runtime has granted it unannounced so far; announced, a refusal is an error here and not a
+    // ring that keeps what it held
+#define MD_GO(K) do { if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void *>(K), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) \
+                          { (void)hipGetLastError(); return -2; } \
+                      hipLaunchKernelGGL(K, grid, blk, lds, s, b); } while (0)
+#define MD_LAUNCH(QT) do { if (a->phase_f64) MD_GO((k_mix_decimate<QT, true, 0, 0>)); else MD_GO((k_mix_decimate<QT, false, 0, 0>)); } while (0)
     if (a->Q == 7 && a->D == 50) {                      // 2.4 Msps -> 48 kHz: decimation known at compile time
         // fast / fold mode is a property of the ENGINE (a->etab set): the P tail between calls then holds sums without the IQ-DC
         // term, so every launch of such an engine goes through one of the two kernels that subtract avg * E per output
@@ -2458,6 +2477,7 @@ extern "C" int sonde_launch_mix_decimate(const MixDecArgs *a, hipStream_t s) {
         default: MD_LAUNCH(8); break;
     }
 #undef MD_LAUNCH
+#undef MD_GO
     return 0;
 }
 extern "C" void sonde_launch_dc_segments(const int16_t *iq, long long ch_stride, int n_ch, int n_samples, unsigned dc_cnt0, unsigned dc_max,

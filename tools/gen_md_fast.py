@@ -183,7 +183,9 @@ def diag_issue(rb):
         L += [f"ds_bpermute_b32 v{rb + 2 * q}, %[lane4], v{ACC0 + 2 * q} offset:{256 - 4 * k}",
               f"ds_bpermute_b32 v{rb + 2 * q + 1}, %[lane4], v{ACC0 + 2 * q + 1} offset:{256 - 4 * k}"]
     Y, T1 = rb + 12, rb + 14
-    L += [f"v_pk_add_f32 {pair(Y)}, {ACC[H]}, {pair(CARRY)}", f"v_mov_b64 {pair(CARRY)}, 0",
+    # the decoder's loop sums the Q-1 terms of the earlier rows FIRST (starting from the carry, in the order of q) and adds the row's own P[j][H] last
+    # (diag_finish): every output is then the same sequence of additions wherever its row lies in a tile — calls that cut the stream elsewhere give the same bits
+    L += [f"v_pk_add_f32 {pair(Y)}, {ACC[H]}, {pair(CARRY)}" if (SCAN or RAW) else f"v_mov_b64 {pair(Y)}, {pair(CARRY)}", f"v_mov_b64 {pair(CARRY)}, 0",
           f"v_lshrrev_b32 v{T1}, 2, %[lane4]", f"v_add_u32 v{T1}, s{S_JM}, v{T1}", f"v_and_b32 v{T1}, %[rmask], v{T1}",
           f"v_lshlrev_b32 v{T1}, 3, v{T1}", f"s_add_i32 s{S_JM}, s{S_JM}, 64"]
     return L
@@ -199,6 +201,7 @@ def diag_finish(rb):
         L += [f"s_mov_b64 exec, {(1 << (H - q)) - 1}", f"v_pk_add_f32 {pair(CARRY)}, {pair(CARRY)}, {pair(rb + 2 * q)}"]
     L += [f"s_mov_b64 exec, s[{S_OUT}:{S_OUT + 1}]"]
     if not (SCAN or RAW):
+        L += [f"v_pk_add_f32 {pair(Y)}, {pair(Y)}, {ACC[H]}"]      # (the accumulators still hold this tile: the next walk writes them behind its first wait)
         L += [f"v_pk_fma_f32 {pair(Y)}, {pair(EREG)}, %[navg], {pair(Y)} op_sel_hi:[1,0,1]",
               f"v_pk_fma_f32 {pair(Y)}, {pair(EREG)}, %[navg], {pair(Y)} op_sel:[1,1,0] op_sel_hi:[0,1,1] neg_lo:[1,0,0]"]
     L += [f"global_store_dwordx2 v{T1}, {pair(Y)}, %[yout]",
