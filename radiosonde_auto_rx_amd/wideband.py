@@ -9,6 +9,9 @@ telemetry tier.  Everything sample-rate runs on the GPU; this module is the orch
     python -m radiosonde_auto_rx_amd.wideband --cfreq 403000000 --raster 10000 - 2400000 16 < capture.cs16
 
 prints one JSON object per decoded frame (the reference's `rs41mod --json` object, "freq" = channel frequency in kHz).
+
+With `--survey SECONDS` the receiver works the way auto_rx does instead of scanning a raster all the time: a spectrum survey of the stream
+(power.py, the rtl_power step), auto_rx's peak pick on it, and a scanner channel per peak for the samples that follow.
 """
 from __future__ import annotations
 
@@ -36,15 +39,30 @@ OWN_DEC = (MK2LMS,) + WXR + DROP          # engines with a decimation of their o
 
 class WidebandReceiver:
     def __init__(self, sample_rate: int, *, cfreq_hz: int = 0, raster_hz: int = 10_000, span: float = 0.45, chunk: int | None = None,
-                 merge_hz: float = 6_000.0, version: str = "sonde_hip", idle_s: float = 30.0):
+                 merge_hz: float = 6_000.0, version: str = "sonde_hip", idle_s: float = 30.0, survey_s: float | None = None,
+                 survey_nfft: int = 4096, dwell_s: float = 2.0, max_peaks: int = 10, snr_threshold: float = 10.0, min_distance: float = 1000.0,
+                 quantization: float = 10000.0):
         """idle_s: a decoder that has produced no frame for that long (a false detection, a sonde that has landed) is closed and its engine
-        freed; the scanner starts a new one if the signal comes back."""
+        freed; the scanner starts a new one if the signal comes back.
+        survey_s: None = a scanner channel on every raster point, all the time.  A number = auto_rx's cycle instead of the raster: the spectrum
+        of survey_s seconds of stream (Hann, survey_nfft points, 25 % of the band edge cropped), auto_rx's peak pick on it (snr_threshold dB over
+        the median, min_distance, quantization, at most max_peaks — its defaults), then a Scanner(fq=peaks, dc=True) over the next dwell_s
+        seconds (what `dft_detect` per peak is to auto_rx), then the next survey.  Peaks that already have a decoder are not scanned again."""
         self.sr, self.cfreq, self.merge_hz, self.version, self.idle_s = sample_rate, cfreq_hz, merge_hz, version, idle_s
         self.t = 0.0                           # stream time in seconds
-        kmax = int(span * sample_rate / raster_hz)
-        self.raster = [snap_fq(k * raster_hz / sample_rate, sample_rate) for k in range(-kmax, kmax + 1)]
         self.chunk = chunk or sample_rate // 4
-        self.scanner = Scanner(sample_rate, fq=self.raster, dc=True, cont=True, max_chunk=self.chunk)
+        self.survey_s, self.survey = survey_s, None
+        if survey_s is None:
+            kmax = int(span * sample_rate / raster_hz)
+            self.raster = [snap_fq(k * raster_hz / sample_rate, sample_rate) for k in range(-kmax, kmax + 1)]
+            self.scanner = Scanner(sample_rate, fq=self.raster, dc=True, cont=True, max_chunk=self.chunk)
+        else:
+            from .power import HANN, PowerSurvey
+            self.raster = [0.0]
+            self.scanner = Scanner(sample_rate, fq=self.raster, dc=True, max_chunk=self.chunk)      # (only asked for its decimation factor)
+            self.survey = PowerSurvey(sample_rate, survey_nfft, center_hz=float(cfreq_hz), window=HANN, crop=0.25, max_chunk=self.chunk)
+            self.pick = dict(snr_threshold=snr_threshold, min_distance=min_distance, quantization=quantization, max_peaks=max_peaks)
+            self.dwell_s, self._survey_t, self._scan_t0 = dwell_s, 0.0, 0.0
         # the demodulators decimate to the reference's IF rate (48 kHz, raised until it divides the sample rate, demod_mod.c:1229-1236);
         # pushes are cut at multiples of both decimation factors, the rest of a push waits for the next one
         if_sr = min(48000, sample_rate)
@@ -55,6 +73,27 @@ class WidebandReceiver:
         self.chunk -= self.chunk % D
         self.sondes: list[dict] = []           # {fq, engine, telemetry, type, frames}
         self.log: list[dict] = []
+        if self.survey is not None:            # no scanner until the first survey has named its peaks
+            self.scanner.close()
+            self.scanner = None
+
+    def _survey_round(self, now: float):
+        """auto_rx's scan step (scan.py:974-1137) on the spectrum gathered since the last round: pick the peaks, leave out those a decoder already
+        works on, start a scanner channel on each of the others; the round's spectrum and peaks go to the log as auto_rx's scan_result has them."""
+        from .power import pick_peaks
+        freq, power, step = self.survey.fetch(reset=True)
+        q = self.pick["quantization"]
+        peaks, floor = pick_peaks(freq, power, step, min_freq=freq[0] / 1e6, max_freq=freq[-1] / 1e6, return_floor=True, **self.pick)
+        lvl = [float(power[np.abs(freq - p) <= q / 2.0].max()) if (np.abs(freq - p) <= q / 2.0).any() else float(floor) for p in peaks]
+        self.log.append(dict(event="survey", t=now, freq=[round(f, 6) for f in (freq / 1e6).tolist()], power=[round(v, 2) for v in power.tolist()],
+                             threshold=floor, peak_freq=[p / 1e6 for p in peaks.tolist()], peak_lvl=lvl))
+        active = [self.cfreq + s["fq"] * self.sr for s in self.sondes]
+        todo = [p for p in peaks.tolist() if not any(abs(p - a) < q / 2.0 for a in active)]
+        self._survey_t = 0.0
+        if todo:
+            self.raster = [snap_fq((p - self.cfreq) / self.sr, self.sr) for p in todo]
+            self.scanner = Scanner(self.sr, fq=self.raster, dc=True, max_chunk=self.chunk)
+            self._scan_t0 = now
 
     def _start(self, fq: float, typ: str, invert: bool = False):
         for s in self.sondes:
@@ -116,6 +155,25 @@ class WidebandReceiver:
             self.log.append(dict(event="retuned", type=want, was=s["type"], fq=s["fq"], freq_khz=s["khz"]))
             s["type"], s["telemetry"].moved = want, True
 
+    def _on_detection(self, d):
+        """one scanner detection -> a decoder of its type at the channel's frequency plus the offset the scanner measured"""
+        if d["type"] == "RS41" and d["score"] > 0:
+            self._start(self.raster[d["channel"]] + d["df"], "RS41")
+        elif d["type"] == "DFM9":                                   # either polarity: the decoder runs with --auto
+            self._start(self.raster[d["channel"]] + d["df"], "DFM")
+        elif d["type"] in ("M10", "M20"):                           # differential code: polarity does not matter
+            self._start(self.raster[d["channel"]] + d["df"], d["type"])
+        elif d["type"] in IMET_AFSK:                                # the scanner's AFSK check decided the variant
+            self._start(self.raster[d["channel"]] + d["df"], d["type"])
+        elif d["type"] == MK2LMS:
+            self.add_channel(MK2LMS, self.raster[d["channel"]] + d["df"])
+        elif d["type"] in WXR:                                      # WXR301: the offset estimate is dropped, as auto_rx's scan.py does (not accurate without whitening)
+            self.add_channel(d["type"], self.raster[d["channel"]] + (d["df"] if d["type"] == "WXRPN9" else 0.0))
+        elif d["type"] == DROP[0]:                                  # either polarity: a negative score starts the decoder with -i
+            self._start(self.raster[d["channel"]] + d["df"], DROP[0], invert=d["score"] < 0)
+        elif d["type"] in FAMILY and (d["score"] > 0 or FAMILY[d["type"]]["auto"]):
+            self._start(self.raster[d["channel"]] + d["df"], d["type"])
+
     def push(self, iq: np.ndarray, finish: bool = False):
         """iq: interleaved int16 I/Q, a whole number of chunks is not required; returns the JSON objects of this call."""
         out = []
@@ -126,24 +184,19 @@ class WidebandReceiver:
         self._rest = np.array(iq[2 * (n - n % D):2 * n], np.int16)
         for s0 in range(0, n - n % D, self.chunk):
             x = iq[2 * s0:2 * min(n - n % D, s0 + self.chunk)]
-            self.scanner.process_host(x, shared=True)
-            for d in self.scanner.fetch():
-                if d["type"] == "RS41" and d["score"] > 0:
-                    self._start(self.raster[d["channel"]] + d["df"], "RS41")
-                elif d["type"] == "DFM9":                                   # either polarity: the decoder runs with --auto
-                    self._start(self.raster[d["channel"]] + d["df"], "DFM")
-                elif d["type"] in ("M10", "M20"):                           # differential code: polarity does not matter
-                    self._start(self.raster[d["channel"]] + d["df"], d["type"])
-                elif d["type"] in IMET_AFSK:                                # the scanner's AFSK check decided the variant
-                    self._start(self.raster[d["channel"]] + d["df"], d["type"])
-                elif d["type"] == MK2LMS:
-                    self.add_channel(MK2LMS, self.raster[d["channel"]] + d["df"])
-                elif d["type"] in WXR:                                      # WXR301: the offset estimate is dropped, as auto_rx's scan.py does (not accurate without whitening)
-                    self.add_channel(d["type"], self.raster[d["channel"]] + (d["df"] if d["type"] == "WXRPN9" else 0.0))
-                elif d["type"] == DROP[0]:                                  # either polarity: a negative score starts the decoder with -i
-                    self._start(self.raster[d["channel"]] + d["df"], DROP[0], invert=d["score"] < 0)
-                elif d["type"] in FAMILY and (d["score"] > 0 or FAMILY[d["type"]]["auto"]):
-                    self._start(self.raster[d["channel"]] + d["df"], d["type"])
+            if self.scanner is not None:
+                self.scanner.process_host(x, shared=True)
+                for d in self.scanner.fetch():
+                    self._on_detection(d)
+            if self.survey is not None:
+                self.survey.process_host(x)
+                self._survey_t += (len(x) // 2) / self.sr
+                now = self.t + (len(x) // 2) / self.sr
+                if self.scanner is not None and (now - self._scan_t0 >= self.dwell_s or all(self.scanner.done(c) for c in range(len(self.raster)))):
+                    self.scanner.close()
+                    self.scanner = None
+                if self.scanner is None and self._survey_t >= self.survey_s:
+                    self._survey_round(now)
             self.t += (len(x) // 2) / self.sr
             for s in list(self.sondes):
                 if s["type"] in OWN_DEC:                       # whole multiples of its decimation; the rest waits for the next piece
@@ -228,7 +281,10 @@ class WidebandReceiver:
         return out
 
     def close(self):
-        self.scanner.close()
+        if self.scanner is not None:
+            self.scanner.close()
+        if self.survey is not None:
+            self.survey.close()
         for s in self.sondes:
             s["engine"].close(); s["telemetry"].close()
 
@@ -430,6 +486,7 @@ def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--cfreq", type=int, default=0, help="centre frequency of the stream in Hz (for the JSON freq field)")
     ap.add_argument("--raster", type=int, default=10_000, help="scanner raster in Hz")
+    ap.add_argument("--survey", type=float, default=None, metavar="SECONDS", help="auto_rx's cycle instead of the raster: a spectrum survey of that many seconds, peak pick, a scanner channel per peak")
     ap.add_argument("--channelize", action="store_true", help="polyphase channelizer front end (256 channels at sr / 200): for streams of several Msps")
     ap.add_argument("--rs92-ephem", help="RINEX navigation file for RS92 positions (rs92mod -e)")
     ap.add_argument("--rs92-alm", help="SEM almanac for RS92 positions (rs92mod -a)")
@@ -440,7 +497,9 @@ def main(argv=None):
         set_rs92_orbits(ephemeris=a.rs92_ephem, almanac=a.rs92_alm)
     if a.dash != "-" or a.bits != 16:
         ap.error("input is `- <sr> 16` (cs16 on stdin)")
-    rx = ChannelizedReceiver(a.sr, cfreq_hz=a.cfreq) if a.channelize else WidebandReceiver(a.sr, cfreq_hz=a.cfreq, raster_hz=a.raster)
+    if a.channelize and a.survey is not None:
+        ap.error("--survey belongs to the raster receiver (the channelized one scans all its channels)")
+    rx = ChannelizedReceiver(a.sr, cfreq_hz=a.cfreq) if a.channelize else WidebandReceiver(a.sr, cfreq_hz=a.cfreq, raster_hz=a.raster, survey_s=a.survey)
     inp = sys.stdin.buffer
     while True:
         buf = inp.read(rx.chunk * 4)
