@@ -4,6 +4,7 @@
 // float/double evaluation order, because the taps, the mixer table and the header template are *data* the
 // GPU kernels must share with the reference to stay inside the soft-bit tolerance:
 //   design_lowpass   Blackman x sinc, 1-norm, float accumulate            demod_mod.c:555-587
+//   dup_taps         a tap set twice in a row (+ one 0): the form the single-sonde kernels' ring FIRs read
 //   design_decimator IF rate / decM / tap count                            demod_mod.c:1222-1259
 //   design_mixer     16-Hz-snapped mixer frequency + table period           demod_mod.c:1262-1296
 //   design_match     Gaussian-pulse header template, 2-norm                demod_mod.c:1190-1195,1398-1421
@@ -33,6 +34,12 @@ std::vector<float> design_lowpass(float f, int taps) {
     }
     for (int n = 0; n < taps; n++) ws[n] = (float)(ws[n] / norm);
     return ws;
+}
+
+std::vector<float> dup_taps(const std::vector<float> &w) {
+    std::vector<float> d(2 * w.size() + 1, 0.f);
+    for (size_t i = 0; i < w.size(); i++) d[i] = d[w.size() + i] = w[i];
+    return d;
 }
 
 Decimator design_decimator(int sr_base, bool if_min) {

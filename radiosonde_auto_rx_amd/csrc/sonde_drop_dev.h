@@ -2,28 +2,18 @@
 // k_softin_drop (sonde_softin_dev.hip) share: the per-channel state records, the frame record, and the completion of a frame on the device.
 #ifndef SONDE_DROP_DEV_H
 #define SONDE_DROP_DEV_H
-#include <hip/hip_runtime.h>
-#include <cstdint>
+#include "sonde_slice_dev.h"
 
 #define DROP_RAWBITS 2400           // RAWBITFRAME_LEN
 #define DROP_FRAME_LEN 120
-#define DROP_HEADLEN 40
+#define DROP_HEADLEN SLICE_HEADLEN
 #define DROP_HDR40 0xA9555995A9ULL  // FC 1D as Manchester-coded 8N1 (header[HEADOFS..] of rd94rd41drop.c), first raw bit highest
 #define DROP_IN_RING 0              // FM samples in a power-of-two float ring by absolute sample (the iq_dec front end's fm tap), read
                                     // through iq_dec's 16-bit output conversion
 #define DROP_IN_S16 1               // FM samples of the call, channel-major: int16 / uint8
 #define DROP_IN_U8 2
 
-// per-channel state between calls: the globals and main() locals of rd94rd41drop.c that outlive a sample
-struct DropChan {
-    unsigned long long total;          // sample_count
-    unsigned long long t_hdr;          // sample_count when the open header matched
-    unsigned long long hist, valid;    // buf[40]: bit values, and which positions hold a bit at all (the initial "x" and NULs do not)
-    uint32_t n_run;                    // read_bits_fsk's n of the run in progress
-    uint32_t scount;                   // read_rawbit: samples read since bitstart
-    int32_t sum;                       // read_rawbit: sum of the bit in progress
-    int32_t par, found, bit_count, raw, raw_i;   // raw: inside the -b loop; raw_i: bits it has finished since bitstart
-};
+typedef SliceChan<int32_t> DropChan;
 
 struct DropFrame {
     int32_t channel, nraw, complete, err94, err41, pad;
@@ -31,17 +21,7 @@ struct DropFrame {
     uint8_t bytes[DROP_FRAME_LEN];
 };
 
-struct DropArgs {
-    DropChan *chan;
-    uint8_t *frames;                   // [n_ch][DROP_RAWBITS]: frame_rawbits of every channel between calls
-    DropFrame *q;
-    int *q_count;
-    const void *in;
-    long long ch_stride;               // samples between two channels of `in`
-    uint32_t first, mask;              // sample i of the call is in[(first + i) & mask]
-    int q_cap, n_ch, n, kind, inv, opt_b, finish;
-    float spb;
-};
+typedef SliceArgs<int32_t, DropFrame> DropArgs;
 
 extern "C" int sonde_launch_drop(const DropArgs *a, hipStream_t s);
 

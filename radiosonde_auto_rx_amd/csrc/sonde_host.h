@@ -13,6 +13,7 @@ namespace sonde {
 struct Decimator { int if_sr = 0, decM = 1; std::vector<float> taps; };
 
 std::vector<float> design_lowpass(float f, int taps);
+std::vector<float> dup_taps(const std::vector<float> &w);
 Decimator design_decimator(int sr_base, bool if_min);
 Decimator design_decimator_scan(int sr_base, bool if_min, float set_lpIQ);
 Decimator design_decimator_if(int sr_base, int if_target, bool narrow);

@@ -1,57 +1,31 @@
 // sonde_mk2a.cpp — host side of the LMS6-1680 / MkIIa engine behind include/sonde_mk2a.h (the reference's mk2a/mk2a1680mod.c).
 // Design (sonde_design.cpp: design_mk2a, design_mixer, design_lowpass), device state, one k_mk2a_mix + k_mk2a launch per call, the frame queue.
-#include "../../include/sonde_hip.h"
 #include "../../include/sonde_mk2a.h"
-#include "sonde_host.h"
+#include "sonde_frame_engine.h"
 #include "sonde_mk2a_dev.h"
-#include <algorithm>
 #include <cmath>
-#include <cstdio>
-#include <cstring>
-#include <new>
-#include <vector>
-
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "libsonde_hip: %s failed: %s\n", #x, hipGetErrorString(e_)); return SONDE_E_NOGPU; } } while (0)
 
 using namespace sonde;
 
-struct sonde_mk2a {
+static sonde_mk2a_frame_t host_frame(const Mk2aFrame &g) {
+    sonde_mk2a_frame_t h;
+    memset(&h, 0, sizeof h);
+    h.channel = g.channel; h.nbits = g.nbits; h.inv = g.inv; h.mv = g.mv; h.df = g.Df; h.mv_pos = g.mv_pos; h.sample = g.sample;
+    memcpy(h.bits, g.bits, sizeof h.bits);
+    return h;
+}
+
+struct sonde_mk2a : FrameEngine<sonde_mk2a_frame_t> {
     Mk2aArgs a{};
     sonde_mk2a_info_t info{};
-    hipStream_t stream = nullptr;
-    int max_chunk = 0, in_bytes = 0, finished = 0;
-    void *d_in = nullptr;
-    std::vector<void *> allocs;
-    std::vector<sonde_mk2a_frame_t> pending;   // fetched from the device, not yet handed out
-    size_t pending_pos = 0;
-    int overflowed = 0;
 
-    template <class T> int dalloc(T **p, size_t n) {
-        HIPCHK(hipMalloc((void **)p, (n ? n : 1) * sizeof(T)));
-        allocs.push_back(*p);
-        HIPCHK(hipMemsetAsync(*p, 0, (n ? n : 1) * sizeof(T), stream));
-        return 0;
-    }
-    template <class T> int upload(const T **p, const std::vector<T> &v) {
-        T *q = nullptr;
-        int rc = dalloc(&q, v.size());
-        if (rc) return rc;
-        if (!v.empty()) HIPCHK(hipMemcpyAsync(q, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, stream));
-        HIPCHK(hipStreamSynchronize(stream));                      // v may be a temporary
-        *p = q;
-        return 0;
-    }
-    ~sonde_mk2a() {
-        if (stream) { (void)hipStreamSynchronize(stream); (void)hipStreamDestroy(stream); }
-        for (void *p : allocs) (void)hipFree(p);
+    // one launch pair over n samples per channel at dev_in
+    int run(const void *dev_in, int32_t n) {
+        Mk2aArgs c = a;
+        c.in = dev_in; c.n_base = n; c.n_if = n / c.decM;
+        return launch_drain(c, sonde_launch_mk2a, host_frame);
     }
 };
-
-static std::vector<float> dup_taps(const std::vector<float> &w) {
-    std::vector<float> d(2 * w.size() + 1, 0.f);
-    for (size_t i = 0; i < w.size(); i++) d[i] = d[w.size() + i] = w[i];
-    return d;
-}
 
 static Mk2aDesign design_of(const sonde_mk2a_cfg_t *cfg) {
     const float lpbw = cfg->lpbw_hz > 0 ? (float)cfg->lpbw_hz : 180e3f;
@@ -93,14 +67,8 @@ extern "C" int sonde_mk2a_create(const sonde_mk2a_cfg_t *cfg, int32_t n_ch, cons
     if (bring > (1 << 20)) return SONDE_E_ARG;
     max_chunk -= max_chunk % d.decM;                                            // calls take whole IF samples
     if (max_chunk < 1) return SONDE_E_RANGE;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { (void)hipGetLastError(); return SONDE_E_NOGPU; }
-
-    auto *e = new (std::nothrow) sonde_mk2a();
-    if (!e) return SONDE_E_NOMEM;
-    int rc = 0;
-#define TRY(x) do { rc = (x); if (rc) { delete e; return rc; } } while (0)
-    if (hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess) { delete e; return SONDE_E_NOGPU; }
+    std::unique_ptr<sonde_mk2a> e;
+    TRY(engine_new(e));
     Mk2aArgs &a = e->a;
     a.n_ch = n_ch; a.bits = cfg->bits; a.opt_iq = cfg->opt_iq; a.lp = d.lp; a.dc = cfg->dc ? 1 : 0; a.decFM = d.decFM; a.sr = d.if_sr;
     a.K = d.K; a.L = d.L; a.delay = d.delay; a.bitofs = d.bitofs; a.mp_ofs = d.mp_ofs;
@@ -108,7 +76,7 @@ extern "C" int sonde_mk2a_create(const sonde_mk2a_cfg_t *cfg, int32_t n_ch, cons
     a.slice_cap = std::max(1, std::min(MK2A_THREADS, (int)(4096 / d.sps)));     // bits sliced together stay inside half the sample ring
     a.decM = d.decM; a.taps_dec = (int)d.lp_dec.size(); a.taps_iq = (int)d.lp_iq0.size(); a.taps_fm = (int)d.lp_fm.size(); a.taps_iqfm = (int)d.lp_iqfm.size();
     a.ring = ring; a.bring_len = (int)bring; a.if_stride = max_chunk / d.decM;
-    e->max_chunk = max_chunk;
+    e->n_ch = n_ch; e->max_chunk = max_chunk; e->dec_m = d.decM;
     e->in_bytes = (cfg->bits / 8) * 2;
     // frames per channel and call: at most one per correlation window, plus one that was under way
     a.q_cap = n_ch * (a.if_stride / d.decFM / (d.K - 4) + 2);
@@ -155,7 +123,7 @@ extern "C" int sonde_mk2a_create(const sonde_mk2a_cfg_t *cfg, int32_t n_ch, cons
     }
     a.n_tone = (int)tone.size();
 
-    TRY(e->dalloc(&a.chan, n_ch));
+    TRY(e->upload(&a.chan, ch));
     TRY(e->dalloc(&a.zrot, (size_t)n_ch * a.ring));
     TRY(e->dalloc(&a.zlp, (size_t)n_ch * a.ring));
     TRY(e->dalloc(&a.fmr, (size_t)n_ch * a.ring));
@@ -165,7 +133,7 @@ extern "C" int sonde_mk2a_create(const sonde_mk2a_cfg_t *cfg, int32_t n_ch, cons
     TRY(e->dalloc(&a.bufs, (size_t)n_ch * MK2A_M));
     TRY(e->dalloc(&a.fmbuf, (size_t)n_ch * MK2A_M));
     TRY(e->dalloc(&a.Xg, (size_t)n_ch * MK2A_M));
-    TRY(e->dalloc(&a.frames, frames.size()));
+    TRY(e->upload(&a.frames, frames));
     TRY(e->dalloc(&a.q, (size_t)a.q_cap));
     TRY(e->dalloc(&a.q_count, 1));
     TRY(e->upload(&a.ws_iq0, dup_taps(d.lp_iq0)));
@@ -176,14 +144,8 @@ extern "C" int sonde_mk2a_create(const sonde_mk2a_cfg_t *cfg, int32_t n_ch, cons
     TRY(e->upload(&a.Fm, Fm));
     TRY(e->upload(&a.tws, tw));
     TRY(e->upload(&a.tone, tone));
-    uint8_t *din;
-    TRY(e->dalloc(&din, (size_t)n_ch * max_chunk * e->in_bytes));
-    e->d_in = din;
-    if (hipMemcpyAsync(a.chan, ch.data(), ch.size() * sizeof(Mk2aChan), hipMemcpyHostToDevice, e->stream) != hipSuccess ||
-        hipMemcpyAsync(a.frames, frames.data(), frames.size(), hipMemcpyHostToDevice, e->stream) != hipSuccess ||
-        hipStreamSynchronize(e->stream) != hipSuccess) { delete e; return SONDE_E_NOGPU; }
-#undef TRY
-    *out = e;
+    TRY(e->alloc_input());
+    *out = e.release();
     return 0;
 }
 
@@ -195,49 +157,9 @@ extern "C" int sonde_mk2a_info(const sonde_mk2a_t *e, sonde_mk2a_info_t *info) {
     return 0;
 }
 
-static void queue_frame(sonde_mk2a_t *e, const Mk2aFrame &g) {
-    sonde_mk2a_frame_t h;
-    memset(&h, 0, sizeof h);
-    h.channel = g.channel; h.nbits = g.nbits; h.inv = g.inv; h.mv = g.mv; h.df = g.Df; h.mv_pos = g.mv_pos; h.sample = g.sample;
-    memcpy(h.bits, g.bits, sizeof h.bits);
-    e->pending.push_back(h);
-}
+extern "C" int sonde_mk2a_process_host(sonde_mk2a_t *e, const void *samples, int32_t n) { return engine_process_host(e, samples, n, false); }
 
-// one launch pair over n samples per channel at dev_in, then the frames it completed into the host queue
-static int run(sonde_mk2a_t *e, const void *dev_in, int32_t n) {
-    Mk2aArgs a = e->a;
-    a.in = dev_in; a.n_base = n; a.n_if = n / a.decM;
-    HIPCHK(hipMemsetAsync(a.q_count, 0, sizeof(int), e->stream));
-    if (sonde_launch_mk2a(&a, e->stream)) return SONDE_E_NOGPU;
-    int cnt = 0;
-    HIPCHK(hipMemcpyAsync(&cnt, a.q_count, sizeof(int), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    if (cnt > a.q_cap) { e->overflowed = 1; cnt = a.q_cap; }
-    if (cnt > 0) {
-        std::vector<Mk2aFrame> f(cnt);
-        HIPCHK(hipMemcpy(f.data(), a.q, cnt * sizeof(Mk2aFrame), hipMemcpyDeviceToHost));
-        std::sort(f.begin(), f.end(), [](const Mk2aFrame &x, const Mk2aFrame &y) {
-            return x.channel != y.channel ? x.channel < y.channel : x.sample < y.sample; });
-        for (const Mk2aFrame &g : f) queue_frame(e, g);
-    }
-    if (e->overflowed) { e->overflowed = 0; return SONDE_E_OVERFLOW; }     // reported once: frames of this call were lost
-    return 0;
-}
-
-extern "C" int sonde_mk2a_process_host(sonde_mk2a_t *e, const void *samples, int32_t n) {
-    if (!e || (!samples && n) || e->finished) return SONDE_E_ARG;
-    if (n < 0 || n > e->max_chunk || n % e->a.decM) return SONDE_E_RANGE;
-    if (n == 0) return 0;
-    HIPCHK(hipMemcpyAsync(e->d_in, samples, (size_t)e->a.n_ch * n * e->in_bytes, hipMemcpyHostToDevice, e->stream));
-    return run(e, e->d_in, n);
-}
-
-extern "C" int sonde_mk2a_process_device(sonde_mk2a_t *e, const void *dev_samples, int32_t n) {
-    if (!e || (!dev_samples && n) || e->finished) return SONDE_E_ARG;
-    if (n < 0 || n > e->max_chunk || n % e->a.decM) return SONDE_E_RANGE;
-    if (n == 0) return 0;
-    return run(e, dev_samples, n);
-}
+extern "C" int sonde_mk2a_process_device(sonde_mk2a_t *e, const void *dev_samples, int32_t n) { return engine_process_device(e, dev_samples, n); }
 
 // EOF inside a frame: read_softbit2p returns EOF, the loop of main breaks and print_frame gets the bits so far (:2409-2424)
 extern "C" int sonde_mk2a_finish(sonde_mk2a_t *e) {
@@ -256,15 +178,9 @@ extern "C" int sonde_mk2a_finish(sonde_mk2a_t *e) {
         memset(&g, 0, sizeof g);
         g.channel = c; g.nbits = MK2A_FRMSTART + ch[c].bitpos; g.inv = ch[c].inv; g.mv = ch[c].mv; g.Df = ch[c].Df; g.mv_pos = ch[c].mv_pos; g.sample = ch[c].N;
         memcpy(g.bits, &frames[(size_t)c * MK2A_FRAME_STRIDE], (size_t)g.nbits);
-        queue_frame(e, g);
+        e->pending.push_back(host_frame(g));
     }
     return 0;
 }
 
-extern "C" int sonde_mk2a_fetch_frames(sonde_mk2a_t *e, sonde_mk2a_frame_t *out, int32_t max) {
-    if (!e || (!out && max > 0) || max < 0) return SONDE_E_ARG;
-    int k = 0;
-    while (k < max && e->pending_pos < e->pending.size()) out[k++] = e->pending[e->pending_pos++];
-    if (e->pending_pos == e->pending.size()) { e->pending.clear(); e->pending_pos = 0; }
-    return k;
-}
+extern "C" int sonde_mk2a_fetch_frames(sonde_mk2a_t *e, sonde_mk2a_frame_t *out, int32_t max) { return engine_fetch_frames(e, out, max); }

@@ -16,6 +16,7 @@ import ctypes as C
 
 import numpy as np
 
+from ._frame_engine import EngineHandle, PrinterHandle, SoftinHandle
 from .engine import SondeError, lib
 
 FRAME_LEN, RAWBITS = 120, 2400
@@ -131,92 +132,51 @@ def _frame_dict(f) -> dict:
             "bytes": bytes(f.bytes)}
 
 
-class DropPrinter:
+class DropPrinter(PrinterHandle):
     """frame bytes -> the reference's text / -r / -R / JSON lines (host code, no GPU); keeps the fields that persist between frames."""
+    _prefix = "sonde_drop"
 
     def __init__(self, *, raw: int = 0, vbs: int = 0, json: bool = False, type: int = 0, jsn_freq_khz: int = 0, version: str = ""):
-        self._L = _sigs(lib())
         o = DropOpts(raw=int(raw), vbs=int(vbs), json=int(json), type=int(type), jsn_freq_khz=int(jsn_freq_khz), version=version.encode())
-        self._p = C.c_void_p()
-        rc = self._L.sonde_drop_printer_create(C.byref(o), C.byref(self._p))
-        if rc:
-            raise SondeError(rc, "sonde_drop_printer_create")
-        self._out = C.create_string_buffer(1 << 12)
+        self._open_printer(_sigs(lib()), o, 1 << 12)
 
     def frame(self, data) -> str:
         if len(data) != FRAME_LEN:
             raise ValueError("a frame has %d bytes" % FRAME_LEN)
-        n = self._L.sonde_drop_print_frame(self._p, _u8(data), self._out, len(self._out))
-        if n < 0:
-            raise SondeError(n, "sonde_drop_print_frame")
-        return self._out.raw[:n].decode("utf-8")
+        return self._print("utf-8", _u8(data))
 
     @property
     def last(self) -> tuple[int, bool]:
         """(type of the last frame: 41 / 94, whether its JSON was printed)"""
         t, j = C.c_int32(), C.c_int32()
-        self._L.sonde_drop_printer_last(self._p, C.byref(t), C.byref(j))
+        self._L.sonde_drop_printer_last(self._h, C.byref(t), C.byref(j))
         return t.value, bool(j.value)
 
-    def close(self):
-        if self._p:
-            self._L.sonde_drop_printer_destroy(self._p)
-            self._p = C.c_void_p()
 
-    __del__ = close
-
-
-class DropSoftin:
+class DropSoftin(SoftinHandle):
     """the --softin / --softinv bit loop: float32 soft bits -> frames (host code, no GPU); invert = (--softinv) xor (-i)"""
+    _prefix, _Frame, _frame_dict = "sonde_drop", DropFrame, staticmethod(_frame_dict)
 
     def __init__(self, *, invert: bool = False):
-        self._L = _sigs(lib())
-        self._s = C.c_void_p()
-        rc = self._L.sonde_drop_softin_create(int(invert), C.byref(self._s))
-        if rc:
-            raise SondeError(rc, "sonde_drop_softin_create")
-        self._buf = (DropFrame * 16)()
-
-    def push(self, soft) -> list[dict]:
-        x = np.ascontiguousarray(soft, dtype=np.float32)
-        out, n, p = [], len(x), x.ctypes.data_as(C.POINTER(C.c_float))
-        while True:
-            k = self._L.sonde_drop_softin_push(self._s, p, n, self._buf, len(self._buf))
-            if k < 0:
-                raise SondeError(k, "sonde_drop_softin_push")
-            out += [_frame_dict(f) for f in self._buf[:k]]
-            n, p = 0, None
-            if k < len(self._buf):
-                return out
-
-    def close(self):
-        if self._s:
-            self._L.sonde_drop_softin_destroy(self._s)
-            self._s = C.c_void_p()
-
-    __del__ = close
+        self._open(_sigs(lib()), "softin_create", int(invert), nbuf=16)
 
 
-class DropEngine:
+class DropEngine(EngineHandle):
     """the iq_dec front end + k_drop_slice behind sonde_drop_create: one channel per entry of fqs, all at sample rate sr."""
+    _prefix, _Frame, _frame_dict = "sonde_drop", DropFrame, staticmethod(_frame_dict)
 
     def __init__(self, fqs, sr: int, *, bits: int = 16, invert: bool = False, opt_b: bool = True, baud: float = 0.0, max_chunk: int | None = None,
                  input: int = IN_IQ, n_channels: int | None = None):
-        self._L = _sigs(lib())
         self.n_ch = len(fqs) if input == IN_IQ else int(n_channels or 1)
         self.bits, self.input = bits, input
         self.max_chunk = int(max_chunk or sr // 4)
         cfg = _cfg(sr, input, bits, invert, opt_b, baud)
         fq = (C.c_double * self.n_ch)(*[float(f) for f in fqs]) if input == IN_IQ else None
-        self._e = C.c_void_p()
-        rc = self._L.sonde_drop_create(C.byref(cfg), self.n_ch, fq, self.max_chunk, C.byref(self._e))
-        if rc:
-            raise SondeError(rc, "sonde_drop_create")
+        self._open(_sigs(lib()), "create", C.byref(cfg), self.n_ch, fq, self.max_chunk, nbuf=32)
         inf = DropInfo()
-        self._L.sonde_drop_info(self._e, C.byref(inf))
+        self._L.sonde_drop_info(self._h, C.byref(inf))
         self.info = {n: getattr(inf, n) for n, _ in DropInfo._fields_ if n != "reserved"}
         self.if_rate, self.dec_m = inf.if_rate, inf.dec_m
-        self._buf = (DropFrame * 32)()
 
     @classmethod
     def fm(cls, n_channels: int, sr: int, *, bits: int = 16, **kw):
@@ -231,33 +191,6 @@ class DropEngine:
     def process_host(self, x: np.ndarray):
         per = 2 if self.input == IN_IQ else 1
         x = np.ascontiguousarray(x, dtype=np.int16 if self.bits == 16 else np.uint8).reshape(self.n_ch, -1)
-        rc = self._L.sonde_drop_process_host(self._e, x.ctypes.data, x.shape[1] // per)
-        if rc:
-            raise SondeError(rc, "sonde_drop_process_host")
+        self._call("process_host", self._h, x.ctypes.data, x.shape[1] // per)
 
-    def process_device(self, ptr: int, n: int):
-        rc = self._L.sonde_drop_process_device(self._e, C.c_void_p(ptr), n)
-        if rc:
-            raise SondeError(rc, "sonde_drop_process_device")
-
-    def finish(self):
-        rc = self._L.sonde_drop_finish(self._e)
-        if rc:
-            raise SondeError(rc, "sonde_drop_finish")
-
-    def fetch_frames(self) -> list[dict]:
-        out = []
-        while True:
-            k = self._L.sonde_drop_fetch_frames(self._e, self._buf, len(self._buf))
-            if k < 0:
-                raise SondeError(k, "sonde_drop_fetch_frames")
-            out += [_frame_dict(f) for f in self._buf[:k]]
-            if k < len(self._buf):
-                return out
-
-    def close(self):
-        if self._e:
-            self._L.sonde_drop_destroy(self._e)
-            self._e = C.c_void_p()
-
-    __del__ = close
+    finish = EngineHandle._finish

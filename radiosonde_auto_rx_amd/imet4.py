@@ -12,6 +12,7 @@ import ctypes as C
 
 import numpy as np
 
+from ._frame_engine import EngineHandle, PrinterHandle
 from .engine import SondeError, lib
 
 FRAME_BITS = 1000
@@ -55,35 +56,26 @@ def crc16(data: bytes) -> int:
     return _sigs(lib()).sonde_imet4_crc16(b, len(data))
 
 
-class Imet4Printer:
+def _frame_dict(f) -> dict:
+    return {"channel": f.channel, "sample": int(f.sample), "bits": np.frombuffer(bytes(f.bits), np.uint8)[:f.nbits].copy()}
+
+
+class Imet4Printer(PrinterHandle):
     """bits -> the reference's text / -r / --rawbits / JSON lines (host code, no GPU)."""
+    _prefix = "sonde_imet4"
 
     def __init__(self, *, raw: bool = False, rawbits: bool = False, json: bool = False, jsn_freq_khz: int = 0, version: str = ""):
-        self._L = _sigs(lib())
         o = Imet4Opts(raw=int(raw), rawbits=int(rawbits), json=int(json), jsn_freq_khz=int(jsn_freq_khz), version=version.encode())
-        self._p = C.c_void_p()
-        rc = self._L.sonde_imet4_printer_create(C.byref(o), C.byref(self._p))
-        if rc:
-            raise SondeError(rc, "sonde_imet4_printer_create")
-        self._out = C.create_string_buffer(1 << 16)
+        self._open_printer(_sigs(lib()), o, 1 << 16)
 
     def frame(self, bits) -> str:
         b = np.ascontiguousarray(bits, dtype=np.uint8)
-        n = self._L.sonde_imet4_print_frame(self._p, b.ctypes.data_as(C.POINTER(C.c_uint8)), len(b), self._out, len(self._out))
-        if n < 0:
-            raise SondeError(n, "sonde_imet4_print_frame")
-        return self._out.raw[:n].decode("latin-1")
-
-    def close(self):
-        if self._p:
-            self._L.sonde_imet4_printer_destroy(self._p)
-            self._p = C.c_void_p()
-
-    __del__ = close
+        return self._print("latin-1", b.ctypes.data_as(C.POINTER(C.c_uint8)), len(b))
 
 
-class Imet4Engine:
+class Imet4Engine(EngineHandle):
     """k_imet4_afsk behind sonde_imet4_create: one channel per entry of fqs (ignored for FM audio), all at sample rate sr."""
+    _prefix, _Frame, _frame_dict = "sonde_imet4", Imet4Frame, staticmethod(_frame_dict)
 
     def __init__(self, fqs, sr: int, *, bits: int = 16, iq: bool = True, lp_iq: bool = True, lpbw_hz: int = 0, lp_fm: bool = False,
                  dc: bool = True, min: bool = False, imet1: bool = False, max_chunk: int | None = None):
@@ -94,41 +86,15 @@ class Imet4Engine:
         cfg = Imet4Cfg(sample_rate=sr, bits=bits, iq=int(iq), lp_iq=int(lp_iq), lpbw_hz=int(lpbw_hz), lp_fm=int(lp_fm), dc=int(dc),
                        min=int(min), imet1=int(imet1))
         fq = (C.c_double * self.n_ch)(*[float(f) for f in fqs])
-        self._e = C.c_void_p()
+        self._h, self._buf = C.c_void_p(), (Imet4Frame * 64)()
         ifr, dec = C.c_int32(), C.c_int32()
-        rc = self._L.sonde_imet4_create(C.byref(cfg), self.n_ch, fq, self.max_chunk, C.byref(self._e), C.byref(ifr), C.byref(dec))
+        rc = self._L.sonde_imet4_create(C.byref(cfg), self.n_ch, fq, self.max_chunk, C.byref(self._h), C.byref(ifr), C.byref(dec))
         self.if_rate, self.dec_m = ifr.value, dec.value
         if rc:
             raise SondeError(rc, "sonde_imet4_create")
-        self._buf = (Imet4Frame * 64)()
 
     def process_host(self, x: np.ndarray):
         dt = np.int16 if self.bits == 16 else np.uint8
         x = np.ascontiguousarray(x, dtype=dt).reshape(self.n_ch, -1)
         n = x.shape[1] // (2 if self.iq else 1)
-        rc = self._L.sonde_imet4_process_host(self._e, x.ctypes.data, n)
-        if rc:
-            raise SondeError(rc, "sonde_imet4_process_host")
-
-    def process_device(self, ptr: int, n: int):
-        rc = self._L.sonde_imet4_process_device(self._e, C.c_void_p(ptr), n)
-        if rc:
-            raise SondeError(rc, "sonde_imet4_process_device")
-
-    def fetch_frames(self) -> list[dict]:
-        out = []
-        while True:
-            k = self._L.sonde_imet4_fetch_frames(self._e, self._buf, len(self._buf))
-            if k < 0:
-                raise SondeError(k, "sonde_imet4_fetch_frames")
-            for f in self._buf[:k]:
-                out.append({"channel": f.channel, "sample": int(f.sample), "bits": np.frombuffer(bytes(f.bits), np.uint8)[:f.nbits].copy()})
-            if k < len(self._buf):
-                return out
-
-    def close(self):
-        if self._e:
-            self._L.sonde_imet4_destroy(self._e)
-            self._e = C.c_void_p()
-
-    __del__ = close
+        self._call("process_host", self._h, x.ctypes.data, n)

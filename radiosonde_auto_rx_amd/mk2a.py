@@ -13,6 +13,7 @@ import ctypes as C
 
 import numpy as np
 
+from ._frame_engine import EngineHandle, PrinterHandle
 from .engine import SondeError, lib
 
 MAX_BITS = 1760
@@ -81,56 +82,43 @@ def design(sr: int, *, bits: int = 16, opt_iq: int = 6, lp_iq: bool = True, lpbw
     return {n: getattr(inf, n) for n, _ in Mk2aInfo._fields_ if n != "reserved"}
 
 
-class Mk2aPrinter:
+def _frame_dict(f) -> dict:
+    return {"channel": f.channel, "sample": int(f.sample), "mv": float(f.mv), "df": float(f.df), "inv": f.inv, "mv_pos": f.mv_pos,
+            "bits": np.frombuffer(bytes(f.bits), np.uint8)[:f.nbits].copy()}
+
+
+class Mk2aPrinter(PrinterHandle):
     """frame bits -> the reference's text / -r / -v.. / JSON lines (host code, no GPU)."""
+    _prefix = "sonde_mk2a"
 
     def __init__(self, *, raw: bool = False, crc: bool = False, vbs: int = 0, json: bool = False, jsn_freq_khz: int = 0, show_df: bool = False,
                  if_rate: int = 240000, sample_rate: int = 240000, version: str = ""):
-        self._L = _sigs(lib())
         o = Mk2aOpts(raw=int(raw), crc=int(crc), vbs=int(vbs), json=int(json), jsn_freq_khz=int(jsn_freq_khz), show_df=int(show_df),
                      if_rate=int(if_rate), sample_rate=int(sample_rate), version=version.encode())
-        self._p = C.c_void_p()
-        rc = self._L.sonde_mk2a_printer_create(C.byref(o), C.byref(self._p))
-        if rc:
-            raise SondeError(rc, "sonde_mk2a_printer_create")
-        self._out = C.create_string_buffer(1 << 16)
+        self._open_printer(_sigs(lib()), o, 1 << 16)
 
     def frame(self, bits, mv: float = 0.0, df: float = 0.0) -> str:
         b = np.ascontiguousarray(bits, dtype=np.uint8)
-        n = self._L.sonde_mk2a_print_frame(self._p, b.ctypes.data_as(C.POINTER(C.c_uint8)), len(b), mv, df, self._out, len(self._out))
-        if n < 0:
-            raise SondeError(n, "sonde_mk2a_print_frame")
-        return self._out.raw[:n].decode("latin-1")
-
-    def close(self):
-        if self._p:
-            self._L.sonde_mk2a_printer_destroy(self._p)
-            self._p = C.c_void_p()
-
-    __del__ = close
+        return self._print("latin-1", b.ctypes.data_as(C.POINTER(C.c_uint8)), len(b), mv, df)
 
 
-class Mk2aEngine:
+class Mk2aEngine(EngineHandle):
     """k_mk2a_mix + k_mk2a behind sonde_mk2a_create: one channel per entry of fqs, all at sample rate sr."""
+    _prefix, _Frame, _frame_dict = "sonde_mk2a", Mk2aFrame, staticmethod(_frame_dict)
 
     def __init__(self, fqs, sr: int, *, bits: int = 16, opt_iq: int = 6, lp_iq: bool = True, lpbw_hz: int = 160000, lp_fm: bool = False, dec_fm: int = 4,
                  dc: bool = True, min: bool = False, invert: bool = False, shift: int = 0, thres: float = 0.0, baud: float = 0.0,
                  max_chunk: int | None = None):
-        self._L = _sigs(lib())
         self.n_ch = len(fqs)
         self.bits = bits
         self.max_chunk = int(max_chunk or sr // 4)
         cfg = _cfg(sr, bits, opt_iq, lp_iq, lpbw_hz, lp_fm, dec_fm, dc, min, invert, shift, thres, baud)
         fq = (C.c_double * self.n_ch)(*[float(f) for f in fqs])
-        self._e = C.c_void_p()
-        rc = self._L.sonde_mk2a_create(C.byref(cfg), self.n_ch, fq, self.max_chunk, C.byref(self._e))
-        if rc:
-            raise SondeError(rc, "sonde_mk2a_create")
+        self._open(_sigs(lib()), "create", C.byref(cfg), self.n_ch, fq, self.max_chunk, nbuf=32)
         inf = Mk2aInfo()
-        self._L.sonde_mk2a_info(self._e, C.byref(inf))
+        self._L.sonde_mk2a_info(self._h, C.byref(inf))
         self.info = {n: getattr(inf, n) for n, _ in Mk2aInfo._fields_ if n != "reserved"}
         self.if_rate, self.dec_m = inf.if_rate, inf.dec_m
-        self._buf = (Mk2aFrame * 32)()
 
     @staticmethod
     def dec_m_of(sr: int) -> int:
@@ -140,35 +128,6 @@ class Mk2aEngine:
     def process_host(self, x: np.ndarray):
         dt = np.int16 if self.bits == 16 else np.uint8
         x = np.ascontiguousarray(x, dtype=dt).reshape(self.n_ch, -1)
-        rc = self._L.sonde_mk2a_process_host(self._e, x.ctypes.data, x.shape[1] // 2)
-        if rc:
-            raise SondeError(rc, "sonde_mk2a_process_host")
+        self._call("process_host", self._h, x.ctypes.data, x.shape[1] // 2)
 
-    def process_device(self, ptr: int, n: int):
-        rc = self._L.sonde_mk2a_process_device(self._e, C.c_void_p(ptr), n)
-        if rc:
-            raise SondeError(rc, "sonde_mk2a_process_device")
-
-    def finish(self):
-        rc = self._L.sonde_mk2a_finish(self._e)
-        if rc:
-            raise SondeError(rc, "sonde_mk2a_finish")
-
-    def fetch_frames(self) -> list[dict]:
-        out = []
-        while True:
-            k = self._L.sonde_mk2a_fetch_frames(self._e, self._buf, len(self._buf))
-            if k < 0:
-                raise SondeError(k, "sonde_mk2a_fetch_frames")
-            for f in self._buf[:k]:
-                out.append({"channel": f.channel, "sample": int(f.sample), "mv": float(f.mv), "df": float(f.df), "inv": f.inv, "mv_pos": f.mv_pos,
-                            "bits": np.frombuffer(bytes(f.bits), np.uint8)[:f.nbits].copy()})
-            if k < len(self._buf):
-                return out
-
-    def close(self):
-        if self._e:
-            self._L.sonde_mk2a_destroy(self._e)
-            self._e = C.c_void_p()
-
-    __del__ = close
+    finish = EngineHandle._finish

@@ -16,6 +16,7 @@ import ctypes as C
 
 import numpy as np
 
+from ._frame_engine import EngineHandle, PrinterHandle, SoftinHandle
 from .engine import SondeError, lib
 
 BITS = 552
@@ -91,92 +92,48 @@ def _frame_dict(f) -> dict:
             "bits": np.frombuffer(bytes(f.bits), np.uint8).copy()}
 
 
-class WxrPrinter:
+class WxrPrinter(PrinterHandle):
     """frame bits -> the reference's text / -r / -R / JSON lines (host code, no GPU); remembers the id-1 frame the JSON of an id-2 frame needs."""
+    _prefix = "sonde_wxr"
 
     def __init__(self, *, raw: int = 0, vbs: bool = False, json: bool = False, pn9: bool = False, jsn_freq_khz: int = 0, version: str = ""):
-        self._L = _sigs(lib())
         o = WxrOpts(raw=int(raw), vbs=int(vbs), json=int(json), pn9=int(pn9), jsn_freq_khz=int(jsn_freq_khz), version=version.encode())
-        self._p = C.c_void_p()
-        rc = self._L.sonde_wxr_printer_create(C.byref(o), C.byref(self._p))
-        if rc:
-            raise SondeError(rc, "sonde_wxr_printer_create")
-        self._out = C.create_string_buffer(1 << 12)
+        self._open_printer(_sigs(lib()), o, 1 << 12)
 
     def frame(self, bits) -> str:
         b = np.ascontiguousarray(bits, dtype=np.uint8)
         if len(b) != BITS:
             raise ValueError("a frame has %d bit values" % BITS)
-        n = self._L.sonde_wxr_print_frame(self._p, b.ctypes.data_as(C.POINTER(C.c_uint8)), self._out, len(self._out))
-        if n < 0:
-            raise SondeError(n, "sonde_wxr_print_frame")
-        return self._out.raw[:n].decode("latin-1")
-
-    def close(self):
-        if self._p:
-            self._L.sonde_wxr_printer_destroy(self._p)
-            self._p = C.c_void_p()
-
-    __del__ = close
+        return self._print("latin-1", b.ctypes.data_as(C.POINTER(C.c_uint8)))
 
 
-class WxrSoftin:
+class WxrSoftin(SoftinHandle):
     """the --softin bit loop: float32 soft bits -> frames (host code, no GPU)"""
+    _prefix, _Frame, _frame_dict = "sonde_wxr", WxrFrame, staticmethod(_frame_dict)
 
     def __init__(self, *, pn9: bool = False, invert: bool = False):
-        self._L = _sigs(lib())
-        self._s = C.c_void_p()
-        rc = self._L.sonde_wxr_softin_create(int(pn9), int(invert), C.byref(self._s))
-        if rc:
-            raise SondeError(rc, "sonde_wxr_softin_create")
-        self._buf = (WxrFrame * 16)()
-
-    def push(self, soft) -> list[dict]:
-        x = np.ascontiguousarray(soft, dtype=np.float32)
-        out, n, p = [], len(x), x.ctypes.data_as(C.POINTER(C.c_float))
-        while True:
-            k = self._L.sonde_wxr_softin_push(self._s, p, n, self._buf, len(self._buf))
-            if k < 0:
-                raise SondeError(k, "sonde_wxr_softin_push")
-            out += [_frame_dict(f) for f in self._buf[:k]]
-            n, p = 0, None
-            if k < len(self._buf):
-                return out
+        self._open(_sigs(lib()), "softin_create", int(pn9), int(invert), nbuf=16)
 
     def finish(self) -> list[dict]:
-        k = self._L.sonde_wxr_softin_finish(self._s, self._buf)
-        if k < 0:
-            raise SondeError(k, "sonde_wxr_softin_finish")
-        return [_frame_dict(f) for f in self._buf[:k]]
-
-    def close(self):
-        if self._s:
-            self._L.sonde_wxr_softin_destroy(self._s)
-            self._s = C.c_void_p()
-
-    __del__ = close
+        return [_frame_dict(f) for f in self._buf[:self._call("softin_finish", self._h, self._buf)]]
 
 
-class WxrEngine:
+class WxrEngine(EngineHandle):
     """the iq_dec front end + k_wxr_slice behind sonde_wxr_create: one channel per entry of fqs, all at sample rate sr."""
+    _prefix, _Frame, _frame_dict = "sonde_wxr", WxrFrame, staticmethod(_frame_dict)
 
     def __init__(self, fqs, sr: int, *, bits: int = 16, pn9: bool = False, invert: bool = False, opt_b: bool = True, if_bw_khz: int = 64,
                  baud: float = 0.0, max_chunk: int | None = None, input: int = IN_IQ, n_channels: int | None = None):
-        self._L = _sigs(lib())
         self.n_ch = len(fqs) if input == IN_IQ else int(n_channels or 1)
         self.bits, self.input = bits, input
         self.max_chunk = int(max_chunk or sr // 4)
         cfg = _cfg(sr, input, bits, pn9, invert, opt_b, if_bw_khz, baud)
         fq = (C.c_double * self.n_ch)(*[float(f) for f in fqs]) if input == IN_IQ else None
-        self._e = C.c_void_p()
-        rc = self._L.sonde_wxr_create(C.byref(cfg), self.n_ch, fq, self.max_chunk, C.byref(self._e))
-        if rc:
-            raise SondeError(rc, "sonde_wxr_create")
+        self._open(_sigs(lib()), "create", C.byref(cfg), self.n_ch, fq, self.max_chunk, nbuf=32)
         inf = WxrInfo()
-        self._L.sonde_wxr_info(self._e, C.byref(inf))
+        self._L.sonde_wxr_info(self._h, C.byref(inf))
         self.info = {n: getattr(inf, n) for n, _ in WxrInfo._fields_ if n != "reserved"}
         self.if_rate, self.dec_m = inf.if_rate, inf.dec_m
-        self._buf = (WxrFrame * 32)()
 
     @classmethod
     def fm(cls, n_channels: int, sr: int, *, bits: int = 32, **kw):
@@ -194,33 +151,6 @@ class WxrEngine:
         else:
             dt, per = {8: np.uint8, 16: np.int16, 32: np.float32}[self.bits], 1
         x = np.ascontiguousarray(x, dtype=dt).reshape(self.n_ch, -1)
-        rc = self._L.sonde_wxr_process_host(self._e, x.ctypes.data, x.shape[1] // per)
-        if rc:
-            raise SondeError(rc, "sonde_wxr_process_host")
+        self._call("process_host", self._h, x.ctypes.data, x.shape[1] // per)
 
-    def process_device(self, ptr: int, n: int):
-        rc = self._L.sonde_wxr_process_device(self._e, C.c_void_p(ptr), n)
-        if rc:
-            raise SondeError(rc, "sonde_wxr_process_device")
-
-    def finish(self):
-        rc = self._L.sonde_wxr_finish(self._e)
-        if rc:
-            raise SondeError(rc, "sonde_wxr_finish")
-
-    def fetch_frames(self) -> list[dict]:
-        out = []
-        while True:
-            k = self._L.sonde_wxr_fetch_frames(self._e, self._buf, len(self._buf))
-            if k < 0:
-                raise SondeError(k, "sonde_wxr_fetch_frames")
-            out += [_frame_dict(f) for f in self._buf[:k]]
-            if k < len(self._buf):
-                return out
-
-    def close(self):
-        if self._e:
-            self._L.sonde_wxr_destroy(self._e)
-            self._e = C.c_void_p()
-
-    __del__ = close
+    finish = EngineHandle._finish

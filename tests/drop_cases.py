@@ -3,7 +3,8 @@
 Each case: gen = keyword arguments of tools.synth.drop_capture plus
     "form": "cs16" | "cu8" (IQ through iq_dec --bo 16), "wav16" | "wav8" | "wav32" | "wav2ch" (FM samples straight into rd94rd41drop),
             "soft" (IQ through fsk_demod, soft bits into rd94rd41drop --softin / --softinv), "rawhex" (the -r lines of another golden:
-            "source" = its name, "index" = the argument list whose stdout is fed to --rawhex), and "cut": IQ samples kept;
+            "source" = its name, "index" = the argument list whose stdout is fed to --rawhex), "cut": IQ samples kept, and "split_runs": raw bit
+            indices for tests/wxr_cases.py's split_runs();
 front = the iq_dec (or fsk_demod) argument list in front of the decoder; argv = the rd94rd41drop argument lists whose stdout and stderr
 the golden holds; rc = the exit code expected (0 when absent)."""
 from __future__ import annotations
@@ -59,6 +60,11 @@ CASES = {
     "wav8": dict(gen=dict(seed=56, kind=94, form="wav8"), front=None, argv=[B, ["-r"]]),
     "wav2ch": dict(gen=dict(seed=57, kind=94, form="wav2ch"), front=None, argv=[B, J]),
     "wav32": dict(gen=dict(seed=58, kind=41, form="wav32"), front=None, argv=[B], rc=255),
+    # runs of 0 bits where the two FM slicers differ: three frames, and one sample of the other sign in the middle of a two-bit run (10, 1
+    # and 9 samples: 1, 0 and 1 raw bits) in the payload of the first frame, in the 40 header bits of the second and in the payload of the
+    # third.  rd94rd41drop skips a run of 0 bits, so the golden has all three frames, with and without -b.
+    "zero_runs": dict(gen=dict(seed=64, kind=41, form="wav16", n_frames=3, lead_s=0.02, split_runs=[40 + 540, 40 + 2400 + 8, 40 + 4800 + 540]), front=None,
+                      argv=[["-r"], ["-b", "-r"]]),
     # one 2.4 Msps stream with the signal at +240 kHz: IF 48 kHz, dec 50 (the one-stream receiver's test; 4.8 kHz deviation, which the
     # detector's template answers with 0.98 — at 9.6 kHz the reference's dft_detect reports nothing)
     "wide41_2400k": dict(gen=dict(sr=2400000, seed=59, kind=41, fq=0.1, noise=15.0), front=iq_dec_args(2400000, 16, "0.1"),
@@ -91,7 +97,7 @@ def capture(case) -> bytes:
     """stdin bytes of the first program of a case's pipeline"""
     from tools import synth
     g = dict(case["gen"])
-    form, cut = g.pop("form", "cs16"), g.pop("cut", None)
+    form, cut, splits = g.pop("form", "cs16"), g.pop("cut", None), g.pop("split_runs", None)
     if form == "rawhex":
         src = load(g["source"])
         return src["stdout"][g["index"]]
@@ -105,7 +111,11 @@ def capture(case) -> bytes:
         return x.astype("<i2").tobytes()
     s = _fm(x)
     if form == "wav16":
-        return synth.wav_bytes(np.round(s * 60000).astype(np.int16), sr, 1, 16)
+        p = np.round(s * 60000).astype(np.int16)
+        if splits:                                                  # (the raw bits as drop_capture sends them)
+            from tests.wxr_cases import split_runs
+            split_runs(p, synth.drop_rawbits([b"\x1A\xCF"] + frames_in(case)), sr // 4800, int(g["lead_s"] * sr), splits)
+        return synth.wav_bytes(p, sr, 1, 16)
     if form == "wav8":
         return synth.wav_bytes(np.clip(np.round(s * 120) + 128, 0, 255).astype(np.uint8), sr, 1, 8)
     if form == "wav32":

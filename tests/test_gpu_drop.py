@@ -184,12 +184,12 @@ def test_chunkings_give_identical_frames(argv):
 def test_fm_form_chunkings_on_integer_samples():
     """the slicer alone (FM form, 16 and 8 bits) in pieces down to 7 samples a call against the reference's text on the same WAV"""
     from radiosonde_auto_rx_amd.drop import DropEngine
-    for name, dt in (("wav16", "<i2"), ("wav8", np.uint8)):
+    for name, dt, chunks in (("wav16", "<i2", (12000, 4099, 7)), ("wav8", np.uint8, (12000, 4099, 7)), ("zero_runs", "<i2", (4099, 7))):
         data = cases.capture(cases.CASES[name])
         g = cases.load(name)
         s = np.frombuffer(data[44:], dt)[None, :]
         for argv, ref in zip(g["argv"], g["stdout"]):
-            for chunk in (12000, 4099, 7):
+            for chunk in chunks:
                 s1, want = s, ref.decode()
                 if chunk == 7:                                                   # a quarter of the stream is enough at 7 samples a call
                     s1 = s[:, :60000]

@@ -180,24 +180,27 @@ def test_chunkings_give_identical_frames(argv):
 
 
 def test_fm_form_chunkings_on_float_samples():
-    """the slicer alone (FM form, float32) in pieces down to 7 samples a call against the one-call CLI run on the same WAV"""
+    """the slicer alone (FM form; float32, and the 16-bit capture with runs of 0 bits) in pieces down to 7 samples a call against the
+    one-call CLI run on the same WAV"""
     from radiosonde_auto_rx_amd.wxr import WxrEngine
-    data = cases.capture(cases.CASES["wav32"])
-    g = cases.load("wav32")
-    s = np.frombuffer(data[44:], "<f4")[None, :]
-    for argv, ref in zip(g["argv"], g["stdout"]):
-        for chunk in (24000, 4099, 7):
-            if chunk == 7:
-                s1 = s[:, :40000]
-                eng = WxrEngine.fm(1, 96000, bits=32, opt_b="-b" in argv, max_chunk=24000)
-                want = _engine_text(eng, [_printer(argv)], argv, 1, s1, 24000, per=1)[0]
+    for name, dt, chunks in (("wav32", "<f4", (24000, 4099, 7)), ("zero_runs", "<i2", (4099, 7))):
+        data = cases.capture(cases.CASES[name])
+        g = cases.load(name)
+        s = np.frombuffer(data[44:], dt)[None, :]
+        bits = s.dtype.itemsize * 8
+        for argv, ref in zip(g["argv"], g["stdout"]):
+            for chunk in chunks:
+                if chunk == 7:
+                    s1 = s[:, :40000]
+                    eng = WxrEngine.fm(1, 96000, bits=bits, opt_b="-b" in argv, max_chunk=24000)
+                    want = _engine_text(eng, [_printer(argv)], argv, 1, s1, 24000, per=1)[0]
+                    eng.close()
+                else:
+                    s1, want = s, ref.decode("latin-1")
+                eng = WxrEngine.fm(1, 96000, bits=bits, opt_b="-b" in argv, max_chunk=chunk)
+                got = _engine_text(eng, [_printer(argv)], argv, 1, s1, chunk, per=1)[0]
                 eng.close()
-            else:
-                s1, want = s, ref.decode("latin-1")
-            eng = WxrEngine.fm(1, 96000, bits=32, opt_b="-b" in argv, max_chunk=chunk)
-            got = _engine_text(eng, [_printer(argv)], argv, 1, s1, chunk, per=1)[0]
-            eng.close()
-            assert got == want, (argv, chunk)
+                assert got == want, (name, argv, chunk)
 
 
 @pytest.mark.parametrize("typ,name", [("WXR301", "wide_2400k"), ("WXRPN9", "wide_2400k_pn9")])

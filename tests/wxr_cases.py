@@ -2,7 +2,7 @@
 
 Each case: gen = keyword arguments of tools.synth.wxr_capture plus
     "form": "cs16" | "cu8" (IQ through iq_dec), "wav16" | "wav8" | "wav32" | "wav2ch" (FM samples straight into weathex301d), "soft" (IQ
-            through fsk_demod, soft bits into weathex301d --softin), and "cut": IQ samples kept;
+            through fsk_demod, soft bits into weathex301d --softin), "cut": IQ samples kept, and "split_runs": bit indices for split_runs();
 front = the iq_dec (or fsk_demod) argument list of auto_rx in front of the decoder; argv = the weathex301d argument lists whose stdout and
 stderr the golden holds."""
 from __future__ import annotations
@@ -52,6 +52,12 @@ CASES = {
     "wav8": dict(gen=dict(seed=24, form="wav8", pn9=True), front=None, argv=[B + PN, ["-r"] + PN]),
     "wav32": dict(gen=dict(seed=25, form="wav32", noise=8.0), front=None, argv=[["-b", "-r", "-t"], ["-r"]]),
     "wav2ch": dict(gen=dict(seed=26, form="wav2ch"), front=None, argv=[B, ["--json"]]),
+    # runs of 0 bits where the two FM slicers differ: three frames, and one sample of the other sign in the middle of a two-bit run (20, 1
+    # and 19 samples: 1, 0 and 1 bits) in the payload of the first frame, in the header of the second (bits 28 and 29 of its 40) and in the
+    # payload of the third.  weathex301d puts an 'x' into its header ring for the run of 0 bits, so the golden has frames 1 and 3 and not
+    # frame 2, with and without -b; in a payload the 'x' changes nothing.
+    "zero_runs": dict(gen=dict(seed=31, form="wav16", n_frames=3, lead_s=0.02, split_runs=[96 + 300, 648 + 96 + 24, 2 * 648 + 96 + 300]), front=None,
+                      argv=[["-r"], ["-b", "-r"]]),
     # one 2.4 Msps stream with the signal at +240 kHz: IF 75 kHz, dec 32 (the one-stream receiver's test, tests/test_gpu_wxr.py)
     "wide_2400k": dict(gen=dict(sr=2400000, seed=27, fq=0.1, noise=15.0, n_frames=12), front=iq_dec_args(2400000, 16, "0.1"),
                        argv=[B + ["--jsn_cfq", "403240000"]]),
@@ -73,11 +79,21 @@ def _fm(iq: np.ndarray) -> np.ndarray:
     return np.convolve(s, np.ones(9) / 9.0, mode="same")
 
 
+def split_runs(p: np.ndarray, bits: np.ndarray, spb: int, lead: int, at) -> np.ndarray:
+    """p with one sample of the other sign in the middle of the first two-bit run of `bits` at or behind each bit index of `at` (bit k of
+    the stream lies at lead + k * spb): the run falls into pieces of spb, 1 and spb - 1 samples, and the middle one rounds to 0 bits"""
+    for k0 in at:
+        k = next(k for k in range(k0, len(bits) - 2) if bits[k - 1] != bits[k] == bits[k + 1] != bits[k + 2])
+        i = lead + (k + 1) * spb
+        p[i] = -p[i] - (p[i] >= 0)
+    return p
+
+
 def capture(case) -> bytes:
     """stdin bytes of the first program of a case's pipeline"""
     from tools import synth
     g = dict(case["gen"])
-    form, cut = g.pop("form", "cs16"), g.pop("cut", None)
+    form, cut, splits = g.pop("form", "cs16"), g.pop("cut", None), g.pop("split_runs", None)
     g["corrupt"] = tuple(g.get("corrupt", ()))
     x = synth.wxr_capture(**g)
     sr = g.get("sr", 96000)
@@ -89,7 +105,11 @@ def capture(case) -> bytes:
         return x.astype("<i2").tobytes()
     s = _fm(x)
     if form == "wav16":
-        return synth.wav_bytes(np.round(s * 30000).astype(np.int16), sr, 1, 16)
+        p = np.round(s * 30000).astype(np.int16)
+        if splits:                                                  # (4800 Bd, 12 bytes AA in front of every frame: wxr_capture's defaults)
+            stream = b"".join(b"\xAA" * 12 + f for f in synth.wxr_frames(g["n_frames"])) + b"\xAA" * 12
+            split_runs(p, np.unpackbits(np.frombuffer(stream, np.uint8)), sr // 4800, int(g["lead_s"] * sr), splits)
+        return synth.wav_bytes(p, sr, 1, 16)
     if form == "wav8":
         return synth.wav_bytes(np.clip(np.round(s * 120) + 128, 0, 255).astype(np.uint8), sr, 1, 8)
     if form == "wav32":
