@@ -13,6 +13,7 @@
 
 #include "sonde_hip.h"
 #include "sonde_drop.h"
+#include "sonde_lms6.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -138,7 +139,34 @@ int  sonde_softin_dev_fetch_dfm(sonde_softin_dev_t *s, sonde_dfm_frame_t *out, i
 int  sonde_softin_dev_fetch_m10(sonde_softin_dev_t *s, sonde_m10_frame_t *out, int32_t max);
 /* SONDE_RD94RD41 consumers: the frame record of include/sonde_drop.h (sample = soft bits read when the header matched) */
 int  sonde_softin_dev_fetch_drop(sonde_softin_dev_t *s, sonde_drop_frame_t *out, int32_t max);
-/* tallies since creation: frames completed, frames accepted (RS41: rs41_ecc() >= 0; DFM: no block uncorrectable; M10: checksum good; RD94RD41: every block of the type print_frame chooses good), frames repaired, symbols / codewords repaired, frames lost to a full buffer */
+
+/* ---- SONDE_LMS6 consumers: `lms6Xmod --softin --vit | --vit2 [--ecc] [-r] [--json] [--lms6 | --lmsX]` for every channel (auto_rx's pipe
+ * `fsk_demod ... | lms6Xmod --json --softin --vit2 -i`, auto_rx/autorx/decode.py:1209).  Header search, block assembly, the K = 7 Viterbi decoder (one wavefront per
+ * channel, a trellis state per lane), deconv and bits2bytes run in device memory (lms6Xmod.c:1352-1433, :232-441); per completed block 308 bytes come to the host, where
+ * the consumer's own sonde_lms6_dec_t of that channel does RS(255,223), frame sync, CRC and the text (sonde_lms6_dec_block_bytes).  opts as for sonde_lms6_dec_create,
+ * except: vit must be 1 or 2 after the --json rule (the algebraic decoder alone has no device form) and ecc 0 or 1: SONDE_E_ARG otherwise.  invert_stream = --softinv.
+ * With opts->typ == 0 (auto detection) the length of a block depends on what the host made of the block before it (lms6Xmod.c:1436-1462): a channel stops at every
+ * completed block, and the push call launches the channels with input left again until the call is consumed — the result is the reference's for any cut of the stream.
+ * Every one of those launches reads the modem's soft decisions, so with auto detection submit_fsk / submit_fsk_behind complete the call before they tell the modem
+ * that its buffer has been read (collect then only hands over the result): any order of calls stays right, the overlap with the modem's next launch is given up.  With
+ * a forced type submit queues the one launch and collect waits for it, as for the other kinds.
+ * A push call holds at most 4 * n_channels + 16 blocks over all channels (a channel completes one per 4176 / 4800 soft bits, two at most in a second): calls of up to
+ * two seconds of soft bits never reach that; blocks beyond it are decoded, not delivered, and counted as dropped (sonde_softin_dev_counts). */
+int  sonde_softin_dev_create_lms6(int32_t n_channels, const sonde_lms6_opts_t *opts, int32_t invert_stream, sonde_softin_dev_t **out);
+#define SONDE_LMS6_TEXT_MAX 2048   /* the text of a block: at most two frames end in one (their `-r` lines are the longest: 223 x 3 + 6 characters each) */
+typedef struct {
+    int32_t  channel;
+    int32_t  type;           /* the type in effect after the block (6, 0x0206, 10)                                         */
+    float    mv;             /* score of the header in front of the block                                                   */
+    int32_t  text_len;
+    uint64_t hdr_bit;        /* the header's bit index in the channel's stream (soft bits read when it matched)             */
+    int32_t  blen, err;      /* bytes the block gave, deconv's error index                                                  */
+    char     text[SONDE_LMS6_TEXT_MAX];   /* what the reference prints for this block, NUL-terminated                       */
+} sonde_lms6_softin_t;
+/* blocks completed by the push calls since the last fetch (per channel in stream order); returns the count (<= max) */
+int  sonde_softin_dev_fetch_lms6(sonde_softin_dev_t *s, sonde_lms6_softin_t *out, int32_t max);
+
+/* tallies since creation: frames completed (SONDE_LMS6: blocks; accepted = the frames with a good CRC-16 that ended in them, the decoders' own count), frames accepted (RS41: rs41_ecc() >= 0; DFM: no block uncorrectable; M10: checksum good; RD94RD41: every block of the type print_frame chooses good), frames repaired, symbols / codewords repaired, frames lost to a full buffer */
 int  sonde_softin_dev_counts(sonde_softin_dev_t *s, int64_t *frames, int64_t *ecc_ok, int64_t *repaired, int64_t *symbols, int64_t *dropped);
 
 #ifdef __cplusplus

@@ -38,6 +38,11 @@ typedef struct {
 int  sonde_lms6_dec_create(const sonde_lms6_opts_t *opts, sonde_lms6_dec_t **out);
 void sonde_lms6_dec_destroy(sonde_lms6_dec_t *d);
 
+/* The 64 raw header bits as '0' / '1' characters, NUL-terminated: (c0, inv(c1)) of 58 f3 3f b8, what a header search correlates with. */
+const char *sonde_lms6_raw_header(void);
+/* Tallies since creation: 223-byte frames completed (printed or not), and those of them whose CRC-16 was good. */
+int  sonde_lms6_dec_counts(const sonde_lms6_dec_t *d, int64_t *frames, int64_t *crc_ok);
+
 /* Raw bits the decoder reads behind a header for the type currently in effect: 4096 (LMS6) or 4720 (LMS-X). */
 int  sonde_lms6_dec_block_bits(const sonde_lms6_dec_t *d);
 /* 6 or 10 (| 0x0200 for the LMS6-403-2 frame sync): the type in effect; *symbol_rate_changed = 1 when the last block made the auto
@@ -50,6 +55,12 @@ int  sonde_lms6_dec_type(const sonde_lms6_dec_t *d, int32_t *symbol_rate_changed
  * Writes what the reference prints for this block NUL-terminated into out; returns its length or a negative SONDE_E_* code. */
 int  sonde_lms6_dec_block(sonde_lms6_dec_t *d, const float *soft0, const float *soft1, int32_t nbits, float mv, float frm_rate,
                           double t_elapsed, char *out, size_t outlen);
+
+/* The same from block_bytes on (proc_frame, lms6Xmod.c:881-989): for a caller that has decoded the convolutional code itself (the device consumer of
+ * include/sonde_fsk.h).  bytes = blen (<= 300) bytes as bits2bytes cut them, len = raw positions of the block that were read (sync positions included), the other
+ * arguments and the output as above.  RS(255,223), frame sync, CRC, auto detection and the text run on exactly the state sonde_lms6_dec_block keeps.  Host only. */
+int  sonde_lms6_dec_block_bytes(sonde_lms6_dec_t *d, const uint8_t *bytes, int32_t blen, int32_t len, float mv, float frm_rate, double t_elapsed,
+                                char *out, size_t outlen);
 
 /* Soft-bit input (`lms6Xmod --softin`, the consumer of `fsk_demod -s`): n float32 soft bits in, header search and block assembly
  * inside; finish != 0 at end of input (a block in progress is decoded with the bits that exist).  Output as above. */

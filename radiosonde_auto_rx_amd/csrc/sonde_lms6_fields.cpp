@@ -70,6 +70,7 @@ struct sonde_lms6_dec {
     std::vector<HS> vraw; std::vector<St> vstate; St vd[NST];
     // main loop
     int rawblk_len = RAWBLK6, rate_changed = 0;
+    long long n_frames = 0, n_crc_ok = 0;      // frames that went through emit(), and those of them with a good CRC
     // soft input framer
     float sbuf[64]; int bufpos = -1; int in_block = 0, pos = 0; unsigned bc = 0;
 
@@ -242,6 +243,7 @@ struct sonde_lms6_dec {
         }
     }
     void emit(Out &w, int crc_err) {
+        n_frames++; if (crc_err == 0) n_crc_ok++;
         if (o.raw == 1) {
             for (int i = 0; i < FRM_LEN; i++) w.f("%02x ", frame[i]);
             w.f(crc_err == 0 ? " [OK]" : " [NO]");
@@ -292,6 +294,11 @@ struct sonde_lms6_dec {
             blen = n;
         }
         for (int j = blen; j < FRAME_LEN + 8; j++) bb[j] = 0;
+        proc_bytes(w, bb, blen);
+    }
+
+    // ---- proc_frame from block_bytes on (:881-989): bb[FRAME_LEN + 8], zero behind blen ---------------------------------------------------
+    void proc_bytes(Out &w, uint8_t *bb, const int blen) {
         int p = SYNC_LEN;
         if ((typ & 0xFF) == 6) {
             if (o.ecc) rs_block(bb, SYNC_LEN);
@@ -397,6 +404,15 @@ int sonde_lms6_dec_type(const sonde_lms6_dec_t *d, int32_t *changed) {
     return d->typ;
 }
 
+const char *sonde_lms6_raw_header(void) { return kRawHeader; }
+
+int sonde_lms6_dec_counts(const sonde_lms6_dec_t *d, int64_t *frames, int64_t *crc_ok) {
+    if (!d) return SONDE_E_ARG;
+    if (frames) *frames = d->n_frames;
+    if (crc_ok) *crc_ok = d->n_crc_ok;
+    return 0;
+}
+
 static int finish_out(const Out &w, char *out, size_t outlen) {
     if (w.s.size() + 1 > outlen) return SONDE_E_ARG;
     memcpy(out, w.s.c_str(), w.s.size() + 1);
@@ -412,6 +428,21 @@ int sonde_lms6_dec_block(sonde_lms6_dec_t *d, const float *soft0, const float *s
     d->time_elapsed = t_elapsed;
     Out w;
     d->proc_frame(w, d->pos);
+    d->after_block();
+    return finish_out(w, out, outlen);
+}
+
+int sonde_lms6_dec_block_bytes(sonde_lms6_dec_t *d, const uint8_t *bytes, int32_t blen, int32_t len, float mv, float frm_rate, double t_elapsed,
+                               char *out, size_t outlen) {
+    if (!d || !out || !bytes || blen < 0 || blen > FRAME_LEN || len < 0 || len > d->rawblk_len) return SONDE_E_ARG;
+    (void)mv;                                                   // (the header's sign went into the raw bits; nothing behind block_bytes reads it)
+    uint8_t bb[FRAME_LEN + 8];
+    memcpy(bb, bytes, (size_t)blen);
+    for (int j = blen; j < FRAME_LEN + 8; j++) bb[j] = 0;
+    d->frm_rate = frm_rate;
+    d->time_elapsed = t_elapsed;
+    Out w;
+    d->proc_bytes(w, bb, blen);
     d->after_block();
     return finish_out(w, out, outlen);
 }

@@ -17,6 +17,8 @@
 #include "sonde_host.h"
 #include "sonde_pinned.h"
 #include "sonde_drop_dev.h"
+#include "sonde_softhdr_dev.h"
+#include "sonde_vit_dev.h"
 #include "../../include/sonde_drop.h"
 #include <cstdio>
 #include <cstring>
@@ -77,19 +79,7 @@ void k_softin_rs41(const SoftinArgs a) {
             for (; base < nb && !found; base += 64) {
                 const int q = base + lane;
                 float mv = 0.f;
-                if (q < nb) {
-                    double sum = 0.0, normx = 0.0;
-                    const int e = 64 + (q - cur);                       // window = elements e-63 .. e
-                    for (int i = 0; i < 64; i++) {
-                        const int k = e - 63 + i;
-                        const float v = k < 64 ? s_hist[k] : sgn * x[cur + (k - 64)];
-                        const float y = (a.hdr[i] & 1) ? 1.f : -1.f;
-                        sum += (double)(y * v);
-                        normx += (double)(v * v);
-                    }
-                    sum /= sqrt(normx * 64.0);
-                    mv = (float)sum;
-                }
+                if (q < nb) mv = softhdr_corr64(s_hist, x, sgn, cur, q, a.hdr);
                 unsigned long long hits = __ballot(q < nb && fabsf(mv) > a.ths);
                 while (hits) {
                     const int l = __builtin_ctzll(hits);
@@ -100,8 +90,7 @@ void k_softin_rs41(const SoftinArgs a) {
                     found = true;
                     const int qs = base + l;
                     // the ring as the header leaves it: the 64 elements up to the hit
-                    const int e = 64 + (qs - cur), k = e - 63 + lane;
-                    const float v = k < 64 ? s_hist[k] : sgn * x[cur + (k - 64)];
+                    const float v = softhdr_ring64(s_hist, x, sgn, cur, qs, lane);
                     __builtin_amdgcn_wave_barrier();
                     s_hist[lane] = v;
                     __builtin_amdgcn_wave_barrier();
@@ -111,8 +100,7 @@ void k_softin_rs41(const SoftinArgs a) {
                 }
             }
             if (!found) {
-                const int e = 64 + (nb - 1 - cur), k = e - 63 + lane;
-                const float v = k < 64 ? s_hist[k] : sgn * x[cur + (k - 64)];
+                const float v = softhdr_ring64(s_hist, x, sgn, cur, nb - 1, lane);
                 __builtin_amdgcn_wave_barrier();
                 s_hist[lane] = v;
                 __builtin_amdgcn_wave_barrier();
@@ -575,6 +563,26 @@ void k_softin_drop(const SoftinDropArgs A) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// LMS6 / LMS-X: lms6Xmod --softin --vit | --vit2 (lms6Xmod.c:1352-1433, :232-441) — the 64-symbol raw header at 0.7 in either polarity, 4096 / 4720 raw bits with
+// every second one inverted behind 80 sync positions, then the K = 7 Viterbi decoder on the wave (a trellis state per lane), deconv and bits2bytes: sonde_vit_dev.h.
+// A record per completed block (block_bytes); RS(255,223), frame sync, CRC and the text are the host's (sonde_lms6_dec_block_bytes).  39 KB of LDS per wave
+// (block 19.2 KB + decision words 19.2 KB + ring: 38 656 B): four waves per CU.
+// ------------------------------------------------------------------------------------------------
+struct SoftinLms6Args { SoftinArgs base; Lms6Chan *chan; Lms6Block *out; int vit, stop_at_block; };
+
+__global__ __launch_bounds__(64)
+void k_softin_lms6(const SoftinLms6Args A) {
+    const SoftinArgs &a = A.base;
+    __shared__ Lms6Lds s_l;
+    const int ch = a.ch_list ? a.ch_list[blockIdx.x] : (int)blockIdx.x, lane = threadIdx.x;
+    if (ch >= a.n_ch || ch < 0) return;
+    int nb = a.nbits;
+    if (a.nbits_ch) nb = a.nbits_ch[ch];
+    nb = __builtin_amdgcn_readfirstlane(nb);
+    lms6_wave_channel(A.chan + ch, a.sd + (size_t)ch * a.ch_stride, nb, a.inv_in ? -1.f : 1.f, A.vit, A.stop_at_block, a.hdr, &s_l, A.out, a.count, a.cap, ch, lane);
+}
+
+// ------------------------------------------------------------------------------------------------
 // The same block codes for the BASE-RATE engine's hits (sonde_engine.cpp): what sonde_engine_fetch_dfm / _m10 used to do per frame on one host thread
 // now runs over the records a process call has queued, behind its frame-sync kernel on the same stream.  Only decoded frames come to the host (DFM: 8 x 104 bytes
 // a hit instead of 2224 soft bits).
@@ -713,6 +721,9 @@ struct sonde_softin_dev {
     SoftinDfmChan *d_dfm_chan = nullptr; sonde_dfm_frame_t *d_dfm_out = nullptr; std::vector<sonde_dfm_frame_t> qdfm; Pinned<sonde_dfm_frame_t> h_dfm;
     SoftinM10Chan *d_m10_chan = nullptr; sonde_m10_frame_t *d_m10_out = nullptr; std::vector<sonde_m10_frame_t> qm10; Pinned<sonde_m10_frame_t> h_m10;
     SoftinDropChan *d_drop_chan = nullptr; DropFrame *d_drop_out = nullptr; std::vector<sonde_drop_frame_t> qdrop; Pinned<DropFrame> h_drop; int drop_inv = 0;
+    // SONDE_LMS6: a host decoder per channel (what follows block_bytes), the channels of a relaunch, the block length each channel has on the device
+    Lms6Chan *d_l6_chan = nullptr; Lms6Block *d_l6_out = nullptr; Pinned<Lms6Block> h_l6; std::vector<sonde_lms6_softin_t> ql6; std::vector<sonde_lms6_dec_t *> l6_dec;
+    int l6_vit = 0, l6_auto = 0; int *d_l6_list = nullptr; Pinned<int> h_l6_list, h_l6_len; std::vector<int> l6_len; std::vector<int64_t> l6_ok;
     SoftinArgs args{};
     hipStream_t stream = nullptr; bool own_stream = false;
     SoftinChan *d_chan = nullptr; unsigned char *d_frames = nullptr, *d_hdr = nullptr, *d_gf = nullptr, *d_synd = nullptr;
@@ -789,6 +800,50 @@ int sonde_softin_dev_create(int32_t n_channels, int32_t sonde_type, int32_t ecc_
     return 0;
 }
 
+int sonde_softin_dev_create_lms6(int32_t n_channels, const sonde_lms6_opts_t *opts, int32_t invert_stream, sonde_softin_dev_t **out) {
+    if (!out || n_channels < 1 || !opts) return SONDE_E_ARG;
+    sonde_lms6_opts_t o = *opts;
+    if (o.json) { if (!o.ecc) o.ecc = 1; if (!o.vit) o.vit = 1; }                              // lms6Xmod.c:1153-1157
+    if (o.vit != 1 && o.vit != 2) return SONDE_E_ARG;                                          // the algebraic decoder alone has no device form
+    if (o.ecc == 3) return SONDE_E_ARG;                                                        // --ecc3 needs the second soft value of a sample-rate demodulator
+    {   sonde_lms6_dec_t *probe = nullptr;                                                     // the option checks of the host decoder, before the device is touched
+        const int rc = sonde_lms6_dec_create(&o, &probe);
+        if (rc) return rc;
+        sonde_lms6_dec_destroy(probe);
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { fprintf(stderr, "libsonde_hip: no usable HIP device (the batched soft-bit framer has no CPU fallback)\n"); return SONDE_E_NOGPU; }
+    sonde_softin_dev *s = new sonde_softin_dev();
+    s->C = n_channels; s->type = SONDE_LMS6; s->l6_vit = o.vit; s->l6_auto = o.typ == 0;
+    s->cap = 4 * n_channels + 16;                              // blocks a call can hold over all channels (sonde_fsk.h): a channel completes at most two in a second of 4800 soft bits
+    const size_t C = (size_t)n_channels, cap = (size_t)s->cap;
+    for (size_t c = 0; c < C; c++) {
+        sonde_lms6_dec_t *d = nullptr;
+        if (sonde_lms6_dec_create(&o, &d)) { sonde_softin_dev_destroy(s); return SONDE_E_NOMEM; }
+        s->l6_dec.push_back(d);
+    }
+    const int len0 = sonde_lms6_dec_block_bits(s->l6_dec[0]) + LMS6_BLOCKSTART;
+    s->l6_len.assign(C, len0); s->l6_ok.assign(C, 0);
+    bool ok = hipMalloc((void **)&s->d_l6_chan, C * sizeof(Lms6Chan)) == hipSuccess && hipMalloc((void **)&s->d_l6_out, cap * sizeof(Lms6Block)) == hipSuccess
+           && hipMalloc((void **)&s->d_l6_list, C * sizeof(int)) == hipSuccess && hipMalloc((void **)&s->d_hdr, 64) == hipSuccess
+           && hipMalloc((void **)&s->d_count, 8) == hipSuccess && hipHostMalloc((void **)&s->h_count, 8) == hipSuccess
+           && s->h_l6.alloc(cap) && s->h_l6_list.alloc(C) && s->h_l6_len.alloc(C);
+    if (ok) {
+        std::vector<Lms6Chan> init(C);
+        memset((void *)init.data(), 0, C * sizeof(Lms6Chan));
+        for (auto &c : init) { c.pos = LMS6_BLOCKSTART; c.rawblk_len = len0; }
+        ok = hipMemcpy(s->d_l6_chan, init.data(), C * sizeof(Lms6Chan), hipMemcpyHostToDevice) == hipSuccess
+          && hipMemcpy(s->d_hdr, sonde_lms6_raw_header(), 64, hipMemcpyHostToDevice) == hipSuccess;
+    }
+    if (!ok) { sonde_softin_dev_destroy(s); return SONDE_E_NOMEM; }
+    SoftinArgs &a = s->args;
+    a.n_ch = n_channels; a.inv_in = invert_stream ? 1 : 0; a.ths = 0.7f; a.count = s->d_count; a.cap = s->cap; a.hdr = s->d_hdr;
+    s->head = std::min(s->cap, n_channels + 16);
+    (void)hipGetLastError();
+    *out = s;
+    return 0;
+}
+
 void sonde_softin_dev_destroy(sonde_softin_dev_t *s) {
     if (!s) return;
     if (s->pending && s->pend_stream) (void)hipStreamSynchronize(s->pend_stream);
@@ -797,16 +852,19 @@ void sonde_softin_dev_destroy(sonde_softin_dev_t *s) {
     if (s->h_nbits) hipHostFree(s->h_nbits);
     if (s->d_nbits) hipFree(s->d_nbits);
     (void)hipGetLastError();
-    void *p[] = { s->d_chan, s->d_frames, s->d_hdr, s->d_gf, s->d_synd, s->d_flen, s->d_ecc, s->d_codes, s->d_meta, s->d_count, s->d_dfm_chan, s->d_dfm_out, s->d_m10_chan, s->d_m10_out, s->d_drop_chan, s->d_drop_out };
+    void *p[] = { s->d_chan, s->d_frames, s->d_hdr, s->d_gf, s->d_synd, s->d_flen, s->d_ecc, s->d_codes, s->d_meta, s->d_count, s->d_dfm_chan, s->d_dfm_out, s->d_m10_chan, s->d_m10_out, s->d_drop_chan, s->d_drop_out, s->d_l6_chan, s->d_l6_out, s->d_l6_list };
     for (void *q : p) if (q) hipFree(q);
+    for (sonde_lms6_dec_t *d : s->l6_dec) sonde_lms6_dec_destroy(d);
     delete s;
 }
 
 // one pass of the framer (and rs41_ecc() over the frames it completes) over the channels of ch_list (null: all), its records behind the `off` records the
 // call already has; counter `which` of d_count
+static int softin_finish_lms6(sonde_softin_dev *s, hipStream_t st, long long n);
 static int softin_pass(sonde_softin_dev *s, hipStream_t st, const int off, const int nblocks, const int *ch_list, const int which) {
     SoftinArgs a = s->args;
-    a.frames += (size_t)off * 518; a.flen += off; a.meta += off; a.cap = s->cap - off; a.count = s->d_count + which; a.ch_list = ch_list;
+    if (s->type != SONDE_LMS6) { a.frames += (size_t)off * 518; a.flen += off; a.meta += off; }
+    a.cap = s->cap - off; a.count = s->d_count + which; a.ch_list = ch_list;
     HIPCHK(hipMemsetAsync(a.count, 0, 4, st));
     if (s->type == SONDE_DFM09) { SoftinDfmArgs d{a, s->d_dfm_chan, s->d_dfm_out + off, s->ecc_level}; hipLaunchKernelGGL(k_softin_dfm, dim3(nblocks), dim3(64), 0, st, d); }
     else if (s->type == SONDE_M10) {
@@ -820,6 +878,7 @@ static int softin_pass(sonde_softin_dev *s, hipStream_t st, const int off, const
         hipLaunchKernelGGL(k_softin_m10, dim3(nblocks), dim3(64), m.stage_cap ? lds : 0, st, m);
     }
     else if (s->type == SONDE_RD94RD41) { SoftinDropArgs d{a, s->d_drop_chan, s->d_drop_out + off, s->drop_inv}; hipLaunchKernelGGL(k_softin_drop, dim3(nblocks), dim3(64), 0, st, d); }
+    else if (s->type == SONDE_LMS6) { SoftinLms6Args d{a, s->d_l6_chan, s->d_l6_out + off, s->l6_vit, s->l6_auto}; hipLaunchKernelGGL(k_softin_lms6, dim3(nblocks), dim3(64), 0, st, d); }
     else {
         hipLaunchKernelGGL(k_softin_rs41, dim3(nblocks), dim3(64), 0, st, a);
         if (s->ecc_level > 0)
@@ -836,6 +895,7 @@ static int softin_copy(sonde_softin_dev *s, hipStream_t st, const int from, cons
     if (s->type == SONDE_DFM09) HIPCHK(hipMemcpyAsync(s->h_dfm.data() + from, s->d_dfm_out + from, n * sizeof(sonde_dfm_frame_t), hipMemcpyDeviceToHost, st));
     else if (s->type == SONDE_M10) HIPCHK(hipMemcpyAsync(s->h_m10.data() + from, s->d_m10_out + from, n * sizeof(sonde_m10_frame_t), hipMemcpyDeviceToHost, st));
     else if (s->type == SONDE_RD94RD41) HIPCHK(hipMemcpyAsync(s->h_drop.data() + from, s->d_drop_out + from, n * sizeof(DropFrame), hipMemcpyDeviceToHost, st));
+    else if (s->type == SONDE_LMS6) HIPCHK(hipMemcpyAsync(s->h_l6.data() + from, s->d_l6_out + from, n * sizeof(Lms6Block), hipMemcpyDeviceToHost, st));
     else {
         HIPCHK(hipMemcpyAsync(s->h_meta.data() + from, s->d_meta + from, n * sizeof(SoftinMeta), hipMemcpyDeviceToHost, st));
         HIPCHK(hipMemcpyAsync(s->h_ecc.data() + from, s->d_ecc + from, n * 4, hipMemcpyDeviceToHost, st));
@@ -843,6 +903,42 @@ static int softin_copy(sonde_softin_dev *s, hipStream_t st, const int from, cons
     }
     return 0;
 }
+// LMS6: every block of the round goes through its channel's host decoder (RS(255,223), frame sync, CRC, text).  With auto detection a channel stopped at its block
+// (Lms6Block.more): the decoder says how long the next block is (lms6Xmod.c:1436-1462), the channel's rawblk_len on the device follows, and the channels with input
+// left are launched again until the call is consumed.
+static int softin_finish_lms6(sonde_softin_dev *s, hipStream_t st, long long n) {
+    for (;;) {
+        int nlist = 0;
+        for (long long i = 0; i < n; i++) {
+            const Lms6Block &b = s->h_l6[i];
+            if (b.channel < 0 || b.channel >= s->C) continue;
+            sonde_lms6_dec_t *d = s->l6_dec[(size_t)b.channel];
+            sonde_lms6_softin_t r; memset(&r, 0, sizeof r);
+            const float nanv = __builtin_nanf("");             // dsp_t stays zeroed with soft input: frm_rate and the elapsed time are 0 / 0
+            const int len = sonde_lms6_dec_block_bytes(d, b.bytes, b.blen, b.pos, b.mv, nanv, (double)nanv, r.text, sizeof r.text);
+            if (len < 0) return len;
+            r.channel = b.channel; r.type = sonde_lms6_dec_type(d, nullptr); r.mv = b.mv; r.text_len = len; r.hdr_bit = b.hdr_bit; r.blen = b.blen; r.err = b.err;
+            s->ql6.push_back(r);
+            s->frames_total++;
+            int64_t ok = 0;
+            (void)sonde_lms6_dec_counts(d, nullptr, &ok);                 // the decoder's own tally of CRC-good frames, whatever the output form
+            s->ecc_ok_total += ok - s->l6_ok[(size_t)b.channel]; s->l6_ok[(size_t)b.channel] = ok;
+            const int want = sonde_lms6_dec_block_bits(d) + LMS6_BLOCKSTART;
+            if (want != s->l6_len[(size_t)b.channel]) {
+                s->l6_len[(size_t)b.channel] = want; s->h_l6_len[(size_t)b.channel] = want;
+                HIPCHK(hipMemcpyAsync(&s->d_l6_chan[b.channel].rawblk_len, &s->h_l6_len[(size_t)b.channel], sizeof(int), hipMemcpyHostToDevice, st));
+            }
+            if (b.more && nlist < s->C) s->h_l6_list[(size_t)nlist++] = b.channel;
+        }
+        if (!nlist) return 0;
+        HIPCHK(hipMemcpyAsync(s->d_l6_list, s->h_l6_list.data(), (size_t)nlist * sizeof(int), hipMemcpyHostToDevice, st));
+        { const int rc = softin_pass(s, st, 0, nlist, s->d_l6_list, 0); if (rc) return rc; }
+        { const int rc = softin_copy(s, st, 0, std::min(nlist, s->cap)); if (rc) return rc; }
+        HIPCHK(hipStreamSynchronize(st));
+        n = std::min<long long>(s->h_count[0], std::min(nlist, s->cap));
+    }
+}
+
 // enqueue a call: the framer over what args.sd / nbits describe, the block code, the counter and the records a call normally completes (`head`) on their way to the host
 static int softin_enqueue(sonde_softin_dev *s, hipStream_t st) {
     if (s->pending) return SONDE_E_ARG;
@@ -861,6 +957,7 @@ static int softin_finish(sonde_softin_dev *s) {
     if (n > s->cap) { s->dropped += n - s->cap; n = s->cap; }
     const int have = (int)std::min<long long>(n, s->head);
     if (n > have) { const int rc = softin_copy(s, st, have, (int)n); if (rc) return rc; HIPCHK(hipStreamSynchronize(st)); }
+    if (s->type == SONDE_LMS6) return softin_finish_lms6(s, st, n);
     if (s->type == SONDE_DFM09) {
         // (frames of one channel in order: the slots of a call are handed out in completion order per channel, channels interleave)
         for (long long i = 0; i < n; i++) {
@@ -938,6 +1035,9 @@ int sonde_softin_dev_submit_fsk(sonde_softin_dev_t *s, sonde_fsk_t *modem) {
     { const int rc = softin_own_stream(s); if (rc) return rc; }
     { const int rc = softin_bind_fsk(s, modem, s->stream); if (rc) return rc; }
     { const int rc = softin_enqueue(s, s->stream); if (rc) return rc; }
+    // LMS6 with auto detection launches again per completed block and reads the soft decisions each time: the call is completed here, so that the point of the
+    // stream the modem is told about below lies behind every read — whatever the caller does before sonde_softin_dev_collect
+    if (s->type == SONDE_LMS6 && s->l6_auto) { const int rc = softin_finish(s); if (rc) return rc; }
     // the modem's launch that reuses this buffer of soft decisions (the next but one) waits for the consumer's kernels: submitting the modem twice before
     // sonde_softin_dev_collect is slower, not wrong
     return sonde_fsk_dev_reader_done(modem, s->stream);
@@ -962,6 +1062,8 @@ int sonde_softin_dev_submit_fsk_behind(sonde_softin_dev_t *s, sonde_fsk_t *modem
     SoftinArgs &a = s->args;
     a.sd = d_sd; a.ch_stride = cap; a.fsk_chan = nullptr; a.bits_per_frame = bpf; a.nbits_ch = s->d_nbits; a.nbits = 0;
     { const int rc = softin_enqueue(s, s->stream); if (rc) return rc; }
+    // (LMS6 with auto detection reads the soft decisions again in its later rounds, and the modem's launch in flight is the one that overwrites them next)
+    if (s->type == SONDE_LMS6 && s->l6_auto) { const int rc = softin_finish(s); if (rc) return rc; }
     return sonde_fsk_dev_reader_done_prev(modem, s->stream);
 }
 int sonde_softin_dev_collect(sonde_softin_dev_t *s) {
@@ -1012,6 +1114,15 @@ int sonde_softin_dev_fetch_drop(sonde_softin_dev_t *s, sonde_drop_frame_t *out, 
     const int n = (int)std::min<size_t>(s->qdrop.size(), (size_t)(max < 0 ? 0 : max));
     for (int i = 0; i < n; i++) out[i] = s->qdrop[i];
     s->qdrop.erase(s->qdrop.begin(), s->qdrop.begin() + n);
+    return n;
+}
+
+int sonde_softin_dev_fetch_lms6(sonde_softin_dev_t *s, sonde_lms6_softin_t *out, int32_t max) {
+    if (s && s->pending) { const int rc_ = softin_finish(s); if (rc_) return rc_; }
+    if (!s || (!out && max > 0)) return SONDE_E_ARG;
+    const int n = (int)std::min<size_t>(s->ql6.size(), (size_t)(max < 0 ? 0 : max));
+    for (int i = 0; i < n; i++) out[i] = s->ql6[i];
+    s->ql6.erase(s->ql6.begin(), s->ql6.begin() + n);
     return n;
 }
 

@@ -29,6 +29,21 @@ class FskFrame(C.Structure):
                 ("ppm", C.c_float), ("EbNodB", C.c_float), ("snr_est", C.c_float)]
 
 
+class Lms6Opts(C.Structure):
+    """sonde_lms6_opts_t (include/sonde_lms6.h)"""
+    _fields_ = [("raw", C.c_int32), ("ecc", C.c_int32), ("vit", C.c_int32), ("json", C.c_int32), ("typ", C.c_int32), ("gpsweek", C.c_int32),
+                ("jsn_freq_khz", C.c_int32), ("version", C.c_char * 32), ("reserved", C.c_int32 * 4)]
+
+
+LMS6_TEXT_MAX = 2048
+
+
+class Lms6SoftinRec(C.Structure):
+    """sonde_lms6_softin_t (include/sonde_fsk.h)"""
+    _fields_ = [("channel", C.c_int32), ("type", C.c_int32), ("mv", C.c_float), ("text_len", C.c_int32), ("hdr_bit", C.c_uint64),
+                ("blen", C.c_int32), ("err", C.c_int32), ("text", C.c_char * LMS6_TEXT_MAX)]
+
+
 _proto = False
 
 
@@ -62,6 +77,8 @@ def _lib():
         L.sonde_softin_dev_fetch_dfm.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
         L.sonde_softin_dev_fetch_m10.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
         L.sonde_softin_dev_fetch_drop.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+        L.sonde_softin_dev_create_lms6.argtypes = [C.c_int32, C.POINTER(Lms6Opts), C.c_int32, C.POINTER(C.c_void_p)]
+        L.sonde_softin_dev_fetch_lms6.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
         _proto = True
     return L
 
@@ -168,12 +185,19 @@ class SoftinDev:
     engine's soft decisions where they lie — auto_rx's pipe `fsk_demod ... | rs41mod --softin -i` (auto_rx/autorx/decode.py:901-909)
     without the soft-decision stream crossing to the host.  No CPU fallback."""
 
-    def __init__(self, n_channels: int, *, ecc: int = 2, softinv: bool = False, inv: bool = True, auto: bool = False, kind: str = "rs41"):
-        """kind: "rs41" (rs41mod --softin), "dfm" (dfm09mod --softin: ecc 0 / 1 = --ecc / 2 = --ecc2), "m10" (m10mod --softin) or "drop" (rd94rd41drop --softin /
-        --softinv [-i]: auto_rx runs it as softinv=True, inv=False; ecc and auto are ignored)"""
+    def __init__(self, n_channels: int, *, ecc: int = 2, softinv: bool = False, inv: bool = True, auto: bool = False, kind: str = "rs41",
+                 vit: int = 2, typ: int = 0, json: bool = False, raw: bool = False, gpsweek: int = 0, freq_khz: int = 0, version: str = ""):
+        """kind: "rs41" (rs41mod --softin), "dfm" (dfm09mod --softin: ecc 0 / 1 = --ecc / 2 = --ecc2), "m10" (m10mod --softin), "drop" (rd94rd41drop --softin /
+        --softinv [-i]: auto_rx runs it as softinv=True, inv=False; ecc and auto are ignored) or "lms6" (lms6Xmod --softin: vit 1 = --vit / 2 = --vit2, typ 0 = auto
+        detection / 6 = --lms6 / 10 = --lmsX, ecc != 0 = --ecc, json, raw = -r, gpsweek, freq_khz and version as sonde_lms6_opts_t; inv (-i) means nothing to it)"""
         from .engine import SONDE_RS41, SONDE_DFM09, SONDE_M10, SONDE_RD94RD41
         h = C.c_void_p()
         self.kind, self.ecc = kind, ecc
+        if kind == "lms6":
+            o = Lms6Opts(raw=int(raw), ecc=1 if ecc else 0, vit=vit, json=int(json), typ=typ, gpsweek=gpsweek, jsn_freq_khz=freq_khz, version=version.encode())
+            _chk(_lib().sonde_softin_dev_create_lms6(n_channels, C.byref(o), int(softinv), C.byref(h)))
+            self._h, self.n_channels = h, n_channels
+            return
         _chk(_lib().sonde_softin_dev_create(n_channels, {"rs41": SONDE_RS41, "dfm": SONDE_DFM09, "m10": SONDE_M10, "drop": SONDE_RD94RD41}[kind], ecc, int(softinv), int(inv), int(auto), C.byref(h)))
         self._h, self.n_channels = h, n_channels
 
@@ -249,6 +273,18 @@ class SoftinDev:
         buf = (DropFrame * max_frames)()
         n = _chk(_lib().sonde_softin_dev_fetch_drop(self._h, buf, max_frames))
         return [_frame_dict(buf[i]) for i in range(n)]
+
+    def fetch_lms6(self, max_blocks: int = 1024):
+        """LMS6 consumers: a dict per completed block — channel, hdr_bit (the header's bit index in the channel's stream), mv, type (6 / 0x0206 / 10 in effect
+        after the block), blen, err, text = what `lms6Xmod` prints for the block, lines = its non-empty lines"""
+        buf = (Lms6SoftinRec * max_blocks)()
+        n = _chk(_lib().sonde_softin_dev_fetch_lms6(self._h, buf, max_blocks))
+        out = []
+        for i in range(n):
+            r = buf[i]
+            text = r.text.decode()
+            out.append(dict(channel=r.channel, hdr_bit=r.hdr_bit, mv=r.mv, type=r.type, blen=r.blen, err=r.err, text=text, lines=[l for l in text.splitlines() if l]))
+        return out
 
     def counts(self):
         v = [C.c_int64(0) for _ in range(5)]
