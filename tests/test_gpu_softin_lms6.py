@@ -11,6 +11,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import lms6_vit_model as M
 from golden_cases import need_ref
 from tools import synth
 
@@ -176,3 +177,120 @@ def test_the_algebraic_decoder_alone_is_refused():
     with pytest.raises(SondeError, match=r"\(-1\)"):
         SoftinDev(1, kind="lms6", vit=0, ecc=1)
     SoftinDev(1, kind="lms6", vit=0, json=True).close()      # --json implies --vit (lms6Xmod.c:1153-1157)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------------------
+# The decoder where it works (tests/lms6_vit_model.py, tests/test_softin_lms6_emu.py): streams whose noise the wave Viterbi has to correct, printed with -r and
+# without --ecc — every frame line is the decoder's output as it stands, nothing repairs a survivor path that differs from the reference's.
+# ------------------------------------------------------------------------------------------------------------------------------------------------
+def _model_recs(s, vit, typ, types):
+    """(hdr_bit, mv > 0, blen, err) per block of the numpy model; types = the decoder's type after each block (the length of the next one)"""
+    first = M.RAWBLKX if typ == 10 else M.RAWBLK6
+    lens = [first] + [M.RAWBLKX if t == 10 else M.RAWBLK6 for t in types]
+    out = []
+    for hb, mv, raw in M.frame_stream(s, lambda k: lens[min(k, len(lens) - 1)] - M.BLOCKSTART):
+        _, blen, err = M.decode_block(M.block_sb(raw, mv, vit))
+        out.append((hb, bool(mv > 0), blen, err))
+    return out
+
+
+@pytest.mark.parametrize("vit", [1, 2])
+@pytest.mark.parametrize("tn", list(M.NOISY_TYPES))
+def test_noisy_streams_raw_text_equals_reference_and_records_equal_model(tn, vit):
+    """four blocks per channel at sigma 0.7 (--vit), 0.9 (--vit2), on the 0.5 grid, with 15 % erasures, inverted; LMS6 forced, LMS-X forced, auto detection:
+    the reference prints at least three frame lines of which at least three differ from the noiseless stream's; the device prints the same lines, and blen / err
+    of every record are the model's"""
+    need_ref()
+    kinds = [k for k, (v, _) in M.NOISY_KINDS.items() if v == vit]
+    built = [M.noisy_stream(tn, k) for k in kinds]
+    typ = built[0][2]
+    S = _stack([b[0] for b in built], 31)
+    got, recs, cnt = _run(S, np.random.default_rng(40 + vit), vit=vit, ecc=0, raw=True, typ=typ)
+    for c, (s, clean, _, _, ropt) in enumerate(built):
+        ref, base = _ref_lines(S[c], ["--softin", "-r"] + ropt), _ref_lines(clean, ["--softin", "-r"] + ropt)
+        assert len(ref) >= 3 and sum(l not in base for l in ref) >= 3, (kinds[c], len(ref))
+        assert _same(got[c], ref), (kinds[c], len(got[c]), len(ref))
+        mine = [r for r in recs if r["channel"] == c]
+        assert [(r["hdr_bit"], r["mv"] > 0, r["blen"], r["err"]) for r in mine] == _model_recs(S[c], vit, typ, [r["type"] for r in mine]), kinds[c]
+    assert cnt["dropped"] == 0
+
+
+@pytest.mark.parametrize("call", [1, 63, 64, 65])
+def test_calls_shorter_than_the_header_window(call):
+    """one block in calls of 1, 63, 64 and 65 soft bits: the header window lies in the ring the channel keeps in device memory between calls"""
+    need_ref()
+    s, _, typ, vit, ropt = M.noisy_stream("lms6", "vit_s07", n_blocks=1)
+    ref = _ref_lines(s, ["--softin", "-r"] + ropt)
+    assert len(ref) >= 1
+    got, recs, cnt = _run(s[None, :], np.random.default_rng(1), cuts=(call,), vit=vit, ecc=0, raw=True, typ=typ)
+    assert _same(got[0], ref)
+    assert [(r["hdr_bit"], r["mv"] > 0, r["blen"], r["err"]) for r in recs] == _model_recs(s, vit, typ, [6])
+
+
+def test_header_at_the_threshold():
+    """9 and 10 flips among the 64 header bits (0.71875 / 0.6875) and scores within 1e-3 of 0.7 on either side, both polarities, a channel each: the reference
+    decides whether a block is found; the device agrees, with the header's bit index and the sign of the score"""
+    need_ref()
+    cases = [(n, inv) + M.threshold_stream(f, t, inv) for n, (f, t) in M.THRESHOLD_CASES.items() for inv in (False, True)]
+    S = _stack([c[2] for c in cases], 32)
+    got, recs, cnt = _run(S, np.random.default_rng(51), vit=1, ecc=0, raw=True, typ=6)
+    found = 0
+    for c, (name, inv, s, score, hdr_bit) in enumerate(cases):
+        ref = _ref_lines(S[c], ["--softin", "-r", "--lms6", "--vit"])
+        assert bool(ref) == (score > 0.7), (name, inv, score)
+        assert _same(got[c], ref), (name, inv)
+        mine = [(r["hdr_bit"], r["mv"] < 0) for r in recs if r["channel"] == c]
+        assert mine == ([(hdr_bit, inv)] if ref else []), (name, inv, mine)
+        found += bool(ref)
+    assert found == 6 and cnt["frames"] == 6
+
+
+def test_many_waves_in_one_launch():
+    """320 channels (more than one wave per CU at 38.6 KB of LDS each) from 8 distinct noisy two-block streams, each channel behind its own lead of 0 .. 127 noise
+    samples, pushed in uneven calls: every channel prints its stream's reference text, its headers are found `lead` bits later, nothing is dropped and the
+    number of records is exact"""
+    need_ref()
+    kw = [dict(sigma=0.9, seed=301), dict(sigma=0.9, seed=302), dict(sigma=0.8, grid=True, seed=303), dict(sigma=0.8, grid=True, seed=304),
+          dict(sigma=0.75, erase=0.15, seed=305), dict(sigma=0.75, erase=0.15, seed=306), dict(sigma=0.9, invert=True, seed=307), dict(sigma=0.7, seed=308)]
+    base = [M.soft_stream(2, lead=0, **k) for k in kw]
+    ref = [_ref_lines(b, ["--softin", "-r", "--lms6", "--vit2"]) for b in base]
+    model = [_model_recs(b, 2, 6, [6]) for b in base]
+    assert sum(len(r) for r in ref) >= 12 and all(len(m) >= 1 for m in model)
+    rng = np.random.default_rng(33)
+    C = 320
+    leads = rng.permutation(np.arange(C) % 128)
+    S = _stack([np.concatenate([rng.normal(0, 0.3, leads[c]).astype(np.float32), base[c % 8]]) for c in range(C)], 34)
+    got, recs, cnt = _run(S, np.random.default_rng(35), vit=2, ecc=0, raw=True, typ=6)
+    for c in range(C):
+        assert _same(got[c], ref[c % 8]), (c, leads[c], len(got[c]), len(ref[c % 8]))
+        mine = [(r["hdr_bit"], r["mv"] > 0, r["blen"], r["err"]) for r in recs if r["channel"] == c]
+        assert mine == [(hb + int(leads[c]), p, bl, er) for hb, p, bl, er in model[c % 8]], (c, leads[c])
+    assert cnt["dropped"] == 0 and cnt["frames"] == len(recs) == sum(len(model[c % 8]) for c in range(C))
+
+
+def test_blocks_beyond_the_record_buffer_are_dropped_and_the_channel_goes_on():
+    """the documented overflow: one channel holds 4 * 1 + 16 = 20 records a call.  22 blocks in one push_device call: 20 records with the reference's text for
+    those blocks, two counted as dropped (decoded into the tail of the wave's LDS); three more blocks in the next call come back whole"""
+    need_ref()
+    import torch
+    from radiosonde_auto_rx_amd.fsk import SoftinDev
+    lead = 37
+    s = M.soft_stream(25, sigma=0.6, seed=60, lead=lead)
+    ref = _ref_lines(s, ["--softin", "-r", "--lms6", "--vit"])
+    assert len(ref) == 25 and sum(a != b for a, b in zip(ref, _ref_lines(M.soft_stream(25, seed=60, lead=lead), ["--softin", "-r", "--lms6", "--vit"]))) >= 3
+    cut = lead + 22 * 4160 + 16                                  # block 22 is complete (its last 16 positions are the head of block 23), the header of block 23 is not
+    d = torch.from_numpy(s).cuda()
+    sf = SoftinDev(1, kind="lms6", vit=1, ecc=0, raw=True, typ=6)
+    sf.push_device(d[:cut].contiguous().data_ptr(), cut, cut)
+    a = sf.fetch_lms6()
+    assert len(a) == 20 and sf.counts()["dropped"] == 2
+    assert "".join(r["text"] for r in a).splitlines() == ref[:20]
+    assert [r["hdr_bit"] for r in a] == [lead + 80 + 4160 * k for k in range(20)]
+    rest = d[cut:].contiguous()
+    sf.push_device(rest.data_ptr(), len(s) - cut, len(s) - cut)
+    b = sf.fetch_lms6()
+    assert [r["hdr_bit"] for r in b] == [lead + 80 + 4160 * k for k in (22, 23, 24)]
+    assert "".join(r["text"] for r in b).splitlines() == ref[22:] and "[OK]" in b[-1]["text"] and b[-1]["text"].splitlines()[-1] == ref[-1]
+    cnt = sf.counts()
+    assert cnt["dropped"] == 2 and cnt["frames"] == 23
+    sf.close()
