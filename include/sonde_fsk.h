@@ -137,6 +137,16 @@ int  sonde_softin_dev_fetch(sonde_softin_dev_t *s, sonde_frame_t *out, int32_t m
 /* SONDE_DFM09 / SONDE_M10 consumers: their frames (ecc[3] = hamming()'s value per block; cs_ok / cs_calc = the frame checksum) */
 int  sonde_softin_dev_fetch_dfm(sonde_softin_dev_t *s, sonde_dfm_frame_t *out, int32_t max);
 int  sonde_softin_dev_fetch_m10(sonde_softin_dev_t *s, sonde_m10_frame_t *out, int32_t max);
+/* SONDE_M20 = `m20mod --softin` (m20mod.c:1276-1377; auto_rx's pipe `fsk_demod ... 2 48000 9600 - - | m20mod --json --ptu -vvv --softin -i`, auto_rx/autorx/decode.py:1131-1167):
+ * the 32 raw header symbols of m20mod.c:81 at 0.8 in either polarity, two soft symbols per bit, differential decoding with bit0 = '0' at the frame's first bit,
+ * (101 + 64) * 8 bits, bits2bytes, and what print_frame derives (:875-907, blk_checkM10 :548-560, checkM10 :562-596): len with its clamp, fw, cs_calc / cs_ok, blk_ok — a
+ * length byte of 0 as sonde_m20_frame_finish has it.  ecc_level is ignored, opt_inv / opt_auto mean nothing to the differential code.  A push call holds at most
+ * 4 * n_channels + 16 frames over all channels (without the skip a channel completes one per 2672 symbols); frames beyond that are decoded, not delivered, and counted
+ * as dropped.
+ * set_m20_skip: 1 (default) = verbosity below 3, one symbol per counted bit dropped behind a frame up to 5 * 808 (m20mod.c:1361-1373); 0 = -vvv, auto_rx's form: the
+ * search resumes right behind the frame's 2640 symbols.  Takes effect with the next push call.  SONDE_E_ARG for consumers of another kind; so is fetch_m20. */
+int  sonde_softin_dev_set_m20_skip(sonde_softin_dev_t *s, int32_t skip);
+int  sonde_softin_dev_fetch_m20(sonde_softin_dev_t *s, sonde_m20_frame_t *out, int32_t max);
 /* SONDE_RD94RD41 consumers: the frame record of include/sonde_drop.h (sample = soft bits read when the header matched) */
 int  sonde_softin_dev_fetch_drop(sonde_softin_dev_t *s, sonde_drop_frame_t *out, int32_t max);
 
@@ -166,7 +176,7 @@ typedef struct {
 /* blocks completed by the push calls since the last fetch (per channel in stream order); returns the count (<= max) */
 int  sonde_softin_dev_fetch_lms6(sonde_softin_dev_t *s, sonde_lms6_softin_t *out, int32_t max);
 
-/* tallies since creation: frames completed (SONDE_LMS6: blocks; accepted = the frames with a good CRC-16 that ended in them, the decoders' own count), frames accepted (RS41: rs41_ecc() >= 0; DFM: no block uncorrectable; M10: checksum good; RD94RD41: every block of the type print_frame chooses good), frames repaired, symbols / codewords repaired, frames lost to a full buffer */
+/* tallies since creation: frames completed (SONDE_LMS6: blocks; accepted = the frames with a good CRC-16 that ended in them, the decoders' own count), frames accepted (RS41: rs41_ecc() >= 0; DFM: no block uncorrectable; M10 / M20: checksum good; RD94RD41: every block of the type print_frame chooses good), frames repaired, symbols / codewords repaired, frames lost to a full buffer */
 int  sonde_softin_dev_counts(sonde_softin_dev_t *s, int64_t *frames, int64_t *ecc_ok, int64_t *repaired, int64_t *symbols, int64_t *dropped);
 
 #ifdef __cplusplus

@@ -19,6 +19,7 @@
 #include "sonde_drop_dev.h"
 #include "sonde_softhdr_dev.h"
 #include "sonde_vit_dev.h"
+#include "sonde_softin_mxx_dev.h"
 #include "../../include/sonde_drop.h"
 #include <cstdio>
 #include <cstring>
@@ -337,7 +338,7 @@ struct SoftinM10Chan {
     char  mbits[976];
 };
 struct SoftinM10Args { SoftinArgs base; SoftinM10Chan *chan; sonde_m10_frame_t *out; int stage_cap; };
-#define M10_STAGE_MAX 12288            // soft decisions of a call the kernel keeps in LDS (48 KB); longer calls read them from global memory
+// (M10_STAGE_MAX, the soft decisions of a call the kernel keeps in LDS: sonde_softin_mxx_dev.h)
 
 // The header search (find_softbinhead / corr_softhdb, demod_mod.c:1692-1762) evaluates at EVERY symbol the normalised correlation of the last 32 with the header, in
 // double.  Round 5 did exactly that on a lane per position — 64 dependent double adds and 32 global loads each, 0.37 ms for 341 channels.  Now the call's soft decisions
@@ -489,6 +490,28 @@ void k_softin_m10(const SoftinM10Args A) {
     if (lane < 32) st->hist[lane] = s_hist[lane];
     for (int i = lane; i < 976; i += 64) st->mbits[i] = s_mb[i];
     if (lane == 0) { st->mode = mode; st->inv = inv; st->mpos = mpos; st->mhalf = mhalf; st->mbit0 = mbit0; st->mskip = mskip; st->ms1 = ms1; st->mv = mv_hdr; st->hdr_bit = hdr_bit; st->bits_in = bits0 + (unsigned long long)nb; }
+}
+
+// ------------------------------------------------------------------------------------------------
+// M20: m20mod --softin (m20mod.c:1276-1377) — as M10 with 1320 bits a frame, the verdicts of m20mod's print_frame (:875-907: length byte with its clamp, firmware
+// byte, frame checksum, block checksum) and the skip as an option (-vvv, auto_rx's form, searches on right behind the frame): sonde_softin_mxx_dev.h, which the
+// CPU wave emulator compiles as well.  The call's soft decisions are staged in LDS as for M10 (a second at 9600 Bd: 38.4 KB + 1.6 KB of state, four waves per CU).
+// ------------------------------------------------------------------------------------------------
+struct SoftinM20Args { SoftinArgs base; SoftinM20Chan *chan; sonde_m20_frame_t *out; int stage_cap, doskip; };
+
+__global__ __launch_bounds__(64)
+void k_softin_m20(const SoftinM20Args A) {
+    const SoftinArgs &a = A.base;
+    extern __shared__ float s_x[];                     // [stage_cap] sgn * x of this call (staged: nb <= stage_cap)
+    __shared__ SoftinM20Lds s_l;
+    const int ch = a.ch_list ? a.ch_list[blockIdx.x] : (int)blockIdx.x, lane = threadIdx.x;
+    if (ch >= a.n_ch || ch < 0) return;
+    int nb = a.nbits;
+    if (a.fsk_chan) { const int fr = a.fsk_chan[ch].frames; nb = fr > 0 ? fr * a.bits_per_frame : 0; }
+    else if (a.nbits_ch) nb = a.nbits_ch[ch];
+    nb = __builtin_amdgcn_readfirstlane(nb);
+    if ((long long)nb > a.ch_stride) return;                                     // (never: a channel's count lies within its stride)
+    m20_wave_channel(A.chan + ch, a.sd + (size_t)ch * a.ch_stride, nb, a.inv_in ? -1.f : 1.f, a.ths, A.doskip, &s_l, s_x, A.stage_cap, A.out, a.count, a.cap, ch, lane);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -720,6 +743,7 @@ struct sonde_softin_dev {
     int C = 0, ecc_level = 0, cap = 0, type = SONDE_RS41;
     SoftinDfmChan *d_dfm_chan = nullptr; sonde_dfm_frame_t *d_dfm_out = nullptr; std::vector<sonde_dfm_frame_t> qdfm; Pinned<sonde_dfm_frame_t> h_dfm;
     SoftinM10Chan *d_m10_chan = nullptr; sonde_m10_frame_t *d_m10_out = nullptr; std::vector<sonde_m10_frame_t> qm10; Pinned<sonde_m10_frame_t> h_m10;
+    SoftinM20Chan *d_m20_chan = nullptr; sonde_m20_frame_t *d_m20_out = nullptr; std::vector<sonde_m20_frame_t> qm20; Pinned<sonde_m20_frame_t> h_m20; int m20_skip = 1;
     SoftinDropChan *d_drop_chan = nullptr; DropFrame *d_drop_out = nullptr; std::vector<sonde_drop_frame_t> qdrop; Pinned<DropFrame> h_drop; int drop_inv = 0;
     // SONDE_LMS6: a host decoder per channel (what follows block_bytes), the channels of a relaunch, the block length each channel has on the device
     Lms6Chan *d_l6_chan = nullptr; Lms6Block *d_l6_out = nullptr; Pinned<Lms6Block> h_l6; std::vector<sonde_lms6_softin_t> ql6; std::vector<sonde_lms6_dec_t *> l6_dec;
@@ -740,14 +764,14 @@ struct sonde_softin_dev {
 extern "C" {
 
 int sonde_softin_dev_create(int32_t n_channels, int32_t sonde_type, int32_t ecc_level, int32_t invert_stream, int32_t opt_inv, int32_t opt_auto, sonde_softin_dev_t **out) {
-    if (!out || n_channels < 1 || (sonde_type != SONDE_RS41 && sonde_type != SONDE_DFM09 && sonde_type != SONDE_M10 && sonde_type != SONDE_RD94RD41) || ecc_level < 0 || ecc_level > 2) return SONDE_E_ARG;
+    if (!out || n_channels < 1 || (sonde_type != SONDE_RS41 && sonde_type != SONDE_DFM09 && sonde_type != SONDE_M10 && sonde_type != SONDE_M20 && sonde_type != SONDE_RD94RD41) || ecc_level < 0 || ecc_level > 2) return SONDE_E_ARG;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { fprintf(stderr, "libsonde_hip: no usable HIP device (the batched soft-bit framer has no CPU fallback)\n"); return SONDE_E_NOGPU; }
     sonde_softin_dev *s = new sonde_softin_dev();
     s->C = n_channels; s->ecc_level = ecc_level; s->type = sonde_type;
     // frames a call of about a second can complete per channel: RS41 two, DFM09 six (280 bits at 1250 b/s), M10 two (one per second; the rest of the second is skipped),
-    // dropsondes three (two a second)
-    s->cap = (sonde_type == SONDE_DFM09 ? 8 : sonde_type == SONDE_RD94RD41 ? 4 : 2) * n_channels + 16;
+    // dropsondes three (two a second), M20 four (without the skip a frame can complete every 32 + 2640 symbols of the 9600 a second)
+    s->cap = (sonde_type == SONDE_DFM09 ? 8 : sonde_type == SONDE_RD94RD41 || sonde_type == SONDE_M20 ? 4 : 2) * n_channels + 16;
     const size_t C = (size_t)n_channels, cap = (size_t)s->cap;
     std::vector<SoftinChan> init(C);
     memset(init.data(), 0, C * sizeof(SoftinChan));
@@ -780,6 +804,14 @@ int sonde_softin_dev_create(int32_t n_channels, int32_t sonde_type, int32_t ecc_
           && hipMemcpy(s->d_m10_chan, mi.data(), C * sizeof(SoftinM10Chan), hipMemcpyHostToDevice) == hipSuccess;
         ok = ok && s->h_m10.alloc(cap);
     }
+    if (ok && sonde_type == SONDE_M20) {
+        std::vector<SoftinM20Chan> mi(C);
+        memset((void *)mi.data(), 0, C * sizeof(SoftinM20Chan));
+        for (auto &c : mi) { c.inv = opt_inv ? 1 : 0; c.mbit0 = '0'; }
+        ok = hipMalloc((void **)&s->d_m20_chan, C * sizeof(SoftinM20Chan)) == hipSuccess && hipMalloc((void **)&s->d_m20_out, cap * sizeof(sonde_m20_frame_t)) == hipSuccess
+          && hipMemcpy(s->d_m20_chan, mi.data(), C * sizeof(SoftinM20Chan), hipMemcpyHostToDevice) == hipSuccess;
+        ok = ok && s->h_m20.alloc(cap);
+    }
     if (ok && sonde_type == SONDE_RD94RD41) {
         std::vector<SoftinDropChan> di(C);
         memset(di.data(), 0, C * sizeof(SoftinDropChan));
@@ -791,7 +823,7 @@ int sonde_softin_dev_create(int32_t n_channels, int32_t sonde_type, int32_t ecc_
     }
     if (!ok) { sonde_softin_dev_destroy(s); return SONDE_E_NOMEM; }
     SoftinArgs &a = s->args;
-    a.n_ch = n_channels; a.inv_in = invert_stream ? 1 : 0; a.opt_auto = opt_auto ? 1 : 0; a.ths = sonde_type == SONDE_M10 ? 0.8f : 0.7f;
+    a.n_ch = n_channels; a.inv_in = invert_stream ? 1 : 0; a.opt_auto = opt_auto ? 1 : 0; a.ths = sonde_type == SONDE_M10 || sonde_type == SONDE_M20 ? 0.8f : 0.7f;
     a.chan = s->d_chan; a.frames = s->d_frames; a.flen = s->d_flen; a.meta = s->d_meta; a.count = s->d_count; a.cap = s->cap; a.hdr = s->d_hdr;
     if (!s->h_ecc.alloc(cap) || !s->h_meta.alloc(cap) || !s->h_frames.alloc(cap * 518)) { sonde_softin_dev_destroy(s); return SONDE_E_NOMEM; }
     s->head = std::min(s->cap, (sonde_type == SONDE_DFM09 ? 5 : sonde_type == SONDE_RD94RD41 ? 2 : 1) * n_channels + 16);
@@ -852,7 +884,7 @@ void sonde_softin_dev_destroy(sonde_softin_dev_t *s) {
     if (s->h_nbits) hipHostFree(s->h_nbits);
     if (s->d_nbits) hipFree(s->d_nbits);
     (void)hipGetLastError();
-    void *p[] = { s->d_chan, s->d_frames, s->d_hdr, s->d_gf, s->d_synd, s->d_flen, s->d_ecc, s->d_codes, s->d_meta, s->d_count, s->d_dfm_chan, s->d_dfm_out, s->d_m10_chan, s->d_m10_out, s->d_drop_chan, s->d_drop_out, s->d_l6_chan, s->d_l6_out, s->d_l6_list };
+    void *p[] = { s->d_chan, s->d_frames, s->d_hdr, s->d_gf, s->d_synd, s->d_flen, s->d_ecc, s->d_codes, s->d_meta, s->d_count, s->d_dfm_chan, s->d_dfm_out, s->d_m10_chan, s->d_m10_out, s->d_m20_chan, s->d_m20_out, s->d_drop_chan, s->d_drop_out, s->d_l6_chan, s->d_l6_out, s->d_l6_list };
     for (void *q : p) if (q) hipFree(q);
     for (sonde_lms6_dec_t *d : s->l6_dec) sonde_lms6_dec_destroy(d);
     delete s;
@@ -877,6 +909,16 @@ static int softin_pass(sonde_softin_dev *s, hipStream_t st, const int off, const
         if (lds > attr) { if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_softin_m10), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess) attr = lds; else m.stage_cap = 0; }
         hipLaunchKernelGGL(k_softin_m10, dim3(nblocks), dim3(64), m.stage_cap ? lds : 0, st, m);
     }
+    else if (s->type == SONDE_M20) {
+        // (LDS for the call's soft decisions as for M10)
+        long long need = a.fsk_chan || a.nbits_ch ? a.ch_stride : a.nbits;
+        if (need > M10_STAGE_MAX || need < 0) need = 0;
+        SoftinM20Args m{a, s->d_m20_chan, s->d_m20_out + off, (int)need, s->m20_skip};
+        static size_t attr = 0;
+        const size_t lds = (size_t)need * sizeof(float);
+        if (lds > attr) { if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_softin_m20), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess) attr = lds; else m.stage_cap = 0; }
+        hipLaunchKernelGGL(k_softin_m20, dim3(nblocks), dim3(64), m.stage_cap ? lds : 0, st, m);
+    }
     else if (s->type == SONDE_RD94RD41) { SoftinDropArgs d{a, s->d_drop_chan, s->d_drop_out + off, s->drop_inv}; hipLaunchKernelGGL(k_softin_drop, dim3(nblocks), dim3(64), 0, st, d); }
     else if (s->type == SONDE_LMS6) { SoftinLms6Args d{a, s->d_l6_chan, s->d_l6_out + off, s->l6_vit, s->l6_auto}; hipLaunchKernelGGL(k_softin_lms6, dim3(nblocks), dim3(64), 0, st, d); }
     else {
@@ -894,6 +936,7 @@ static int softin_copy(sonde_softin_dev *s, hipStream_t st, const int from, cons
     const size_t n = (size_t)(to - from);
     if (s->type == SONDE_DFM09) HIPCHK(hipMemcpyAsync(s->h_dfm.data() + from, s->d_dfm_out + from, n * sizeof(sonde_dfm_frame_t), hipMemcpyDeviceToHost, st));
     else if (s->type == SONDE_M10) HIPCHK(hipMemcpyAsync(s->h_m10.data() + from, s->d_m10_out + from, n * sizeof(sonde_m10_frame_t), hipMemcpyDeviceToHost, st));
+    else if (s->type == SONDE_M20) HIPCHK(hipMemcpyAsync(s->h_m20.data() + from, s->d_m20_out + from, n * sizeof(sonde_m20_frame_t), hipMemcpyDeviceToHost, st));
     else if (s->type == SONDE_RD94RD41) HIPCHK(hipMemcpyAsync(s->h_drop.data() + from, s->d_drop_out + from, n * sizeof(DropFrame), hipMemcpyDeviceToHost, st));
     else if (s->type == SONDE_LMS6) HIPCHK(hipMemcpyAsync(s->h_l6.data() + from, s->d_l6_out + from, n * sizeof(Lms6Block), hipMemcpyDeviceToHost, st));
     else {
@@ -969,6 +1012,8 @@ static int softin_finish(sonde_softin_dev *s) {
         }
     } else if (s->type == SONDE_M10) {
         for (long long i = 0; i < n; i++) { s->qm10.push_back(s->h_m10[i]); s->frames_total++; if (s->h_m10[i].cs_ok) s->ecc_ok_total++; }
+    } else if (s->type == SONDE_M20) {
+        for (long long i = 0; i < n; i++) { s->qm20.push_back(s->h_m20[i]); s->frames_total++; if (s->h_m20[i].cs_ok) s->ecc_ok_total++; }
     } else if (s->type == SONDE_RD94RD41) {
         for (long long i = 0; i < n; i++) {
             const DropFrame &g = s->h_drop[i];
@@ -1105,6 +1150,21 @@ int sonde_softin_dev_fetch_m10(sonde_softin_dev_t *s, sonde_m10_frame_t *out, in
     const int n = (int)std::min<size_t>(s->qm10.size(), (size_t)(max < 0 ? 0 : max));
     for (int i = 0; i < n; i++) out[i] = s->qm10[i];
     s->qm10.erase(s->qm10.begin(), s->qm10.begin() + n);
+    return n;
+}
+
+int sonde_softin_dev_set_m20_skip(sonde_softin_dev_t *s, int32_t skip) {
+    if (!s || s->type != SONDE_M20) return SONDE_E_ARG;
+    s->m20_skip = skip != 0;                       // (takes effect with the next call; a call in flight has its own copy)
+    return 0;
+}
+
+int sonde_softin_dev_fetch_m20(sonde_softin_dev_t *s, sonde_m20_frame_t *out, int32_t max) {
+    if (!s || s->type != SONDE_M20 || (!out && max > 0)) return SONDE_E_ARG;
+    if (s->pending) { const int rc_ = softin_finish(s); if (rc_) return rc_; }
+    const int n = (int)std::min<size_t>(s->qm20.size(), (size_t)(max < 0 ? 0 : max));
+    for (int i = 0; i < n; i++) out[i] = s->qm20[i];
+    s->qm20.erase(s->qm20.begin(), s->qm20.begin() + n);
     return n;
 }
 

@@ -76,6 +76,8 @@ def _lib():
         L.sonde_softin_dev_counts.argtypes = [C.c_void_p] + [C.POINTER(C.c_int64)] * 5
         L.sonde_softin_dev_fetch_dfm.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
         L.sonde_softin_dev_fetch_m10.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+        L.sonde_softin_dev_fetch_m20.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+        L.sonde_softin_dev_set_m20_skip.argtypes = [C.c_void_p, C.c_int32]
         L.sonde_softin_dev_fetch_drop.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
         L.sonde_softin_dev_create_lms6.argtypes = [C.c_int32, C.POINTER(Lms6Opts), C.c_int32, C.POINTER(C.c_void_p)]
         L.sonde_softin_dev_fetch_lms6.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
@@ -186,11 +188,12 @@ class SoftinDev:
     without the soft-decision stream crossing to the host.  No CPU fallback."""
 
     def __init__(self, n_channels: int, *, ecc: int = 2, softinv: bool = False, inv: bool = True, auto: bool = False, kind: str = "rs41",
-                 vit: int = 2, typ: int = 0, json: bool = False, raw: bool = False, gpsweek: int = 0, freq_khz: int = 0, version: str = ""):
-        """kind: "rs41" (rs41mod --softin), "dfm" (dfm09mod --softin: ecc 0 / 1 = --ecc / 2 = --ecc2), "m10" (m10mod --softin), "drop" (rd94rd41drop --softin /
+                 vit: int = 2, typ: int = 0, json: bool = False, raw: bool = False, gpsweek: int = 0, freq_khz: int = 0, version: str = "", skip: bool = True):
+        """kind: "rs41" (rs41mod --softin), "dfm" (dfm09mod --softin: ecc 0 / 1 = --ecc / 2 = --ecc2), "m10" (m10mod --softin), "m20" (m20mod --softin: skip = the rest of
+        the second behind a frame is dropped, as m20mod does below -vvv; auto_rx runs `m20mod --json --ptu -vvv --softin -i`: skip=False; ecc, inv and auto mean nothing to it), "drop" (rd94rd41drop --softin /
         --softinv [-i]: auto_rx runs it as softinv=True, inv=False; ecc and auto are ignored) or "lms6" (lms6Xmod --softin: vit 1 = --vit / 2 = --vit2, typ 0 = auto
         detection / 6 = --lms6 / 10 = --lmsX, ecc != 0 = --ecc, json, raw = -r, gpsweek, freq_khz and version as sonde_lms6_opts_t; inv (-i) means nothing to it)"""
-        from .engine import SONDE_RS41, SONDE_DFM09, SONDE_M10, SONDE_RD94RD41
+        from .engine import SONDE_RS41, SONDE_DFM09, SONDE_M10, SONDE_M20, SONDE_RD94RD41
         h = C.c_void_p()
         self.kind, self.ecc = kind, ecc
         if kind == "lms6":
@@ -198,8 +201,14 @@ class SoftinDev:
             _chk(_lib().sonde_softin_dev_create_lms6(n_channels, C.byref(o), int(softinv), C.byref(h)))
             self._h, self.n_channels = h, n_channels
             return
-        _chk(_lib().sonde_softin_dev_create(n_channels, {"rs41": SONDE_RS41, "dfm": SONDE_DFM09, "m10": SONDE_M10, "drop": SONDE_RD94RD41}[kind], ecc, int(softinv), int(inv), int(auto), C.byref(h)))
+        _chk(_lib().sonde_softin_dev_create(n_channels, {"rs41": SONDE_RS41, "dfm": SONDE_DFM09, "m10": SONDE_M10, "m20": SONDE_M20, "drop": SONDE_RD94RD41}[kind], ecc, int(softinv), int(inv), int(auto), C.byref(h)))
         self._h, self.n_channels = h, n_channels
+        if kind == "m20":
+            self.set_m20_skip(skip)
+
+    def set_m20_skip(self, skip: bool):
+        """M20 consumers: True = the rest of the second behind a frame is dropped (m20mod below -vvv), False = -vvv; from the next push on"""
+        _chk(_lib().sonde_softin_dev_set_m20_skip(self._h, int(bool(skip))))
 
     def close(self):
         if getattr(self, "_h", None):
@@ -265,6 +274,21 @@ class SoftinDev:
             f = buf[i]
             ll = lib().sonde_m10_rawline(C.byref(f), verbose, line, 420)
             out.append(dict(channel=f.channel, nbits=f.nbits, len=f.len, cs_ok=f.cs_ok, cs_calc=f.cs_calc, mv=f.mv, mv_pos=f.mv_pos, frame=bytes(f.frame), line=line.raw[:ll].decode()))
+        return out
+
+    def fetch_m20(self, max_frames: int = 4096, verbose: int = 1):
+        """M20 consumers: dicts with the fields of SondeM20Frame (channel, nbits, len, cs_ok, cs_calc, blk_ok, fw, mv_pos, mv, frame — what telemetry.M20Telemetry.decode
+        takes) and line = the `m20mod -r [-v]` text"""
+        from .engine import SondeM20Frame, lib
+        buf = (SondeM20Frame * max_frames)()
+        n = _chk(_lib().sonde_softin_dev_fetch_m20(self._h, buf, max_frames))
+        out = []
+        line = C.create_string_buffer(420)
+        for i in range(n):
+            f = buf[i]
+            ll = lib().sonde_m20_rawline(C.byref(f), verbose, line, 420)
+            out.append(dict(channel=f.channel, nbits=f.nbits, len=f.len, cs_ok=f.cs_ok, cs_calc=f.cs_calc, blk_ok=f.blk_ok, fw=f.fw, mv_pos=f.mv_pos, mv=f.mv,
+                            frame=bytes(f.frame), line=line.raw[:ll].decode()))
         return out
 
     def fetch_drop(self, max_frames: int = 4096):

@@ -8,7 +8,12 @@ sigma 0.3, repeated, so that every push continues the stream of the one before. 
 alone comes from a run of its own under `rocprofv3 --kernel-trace --stats -- python tools/bench_softin.py --channels 1024`.  The host tier is timed on
 --host-channels channels of the same stream (one thread; the figure is per channel and second, and scales linearly).  One JSON line per channel count.
 
-    python tools/bench_softin.py [--channels 1,64,341,1024] [--pushes 39] [--vit 2] [--typ 0] [--out profiles/softin_bench.json]"""
+--kind m20 (or all): the M20 consumer (SoftinDev(kind="m20", skip=False): k_softin_m20, auto_rx's form `m20mod --json --ptu -vvv --softin -i`) the same way — N channels x
+one second (9600 symbols) per push in device memory, a 13 s stream with one frame per second at sigma 0.3, repeated; the same warm-up and timed counts; beside it the host
+framer on the same stream (sonde_softin_push + sonde_softin_fetch_m20, one thread).  Only completed frames cross to the host: 38.4 KB of soft decisions per channel and
+second stay where the modem left them.  --out keeps the rows of the kinds that were not run.
+
+    python tools/bench_softin.py [--kind lms6|m20|all] [--channels 1,64,341,1024] [--pushes 39] [--vit 2] [--typ 0] [--out profiles/softin_bench.json]"""
 import argparse
 import ctypes as C
 import json
@@ -61,8 +66,90 @@ def host_tier(s, pushes, nch, vit, typ):
     return walls, ok
 
 
+def m20_stream(sigma=0.3, seed=2):
+    """13 s at 9600 Bd: per second the 1001 idle pattern, the header and one frame (tools/synth.py m20_frame), noise on everything"""
+    from tools import synth
+    rng = np.random.default_rng(seed)
+    out = []
+    for k in range(13):
+        sym = synth.m10_symbols(data=synth.m20_frame(k))
+        out += [np.tile(np.array([1, 0, 0, 1], np.uint8), 250), sym, np.tile(np.array([1, 0, 0, 1], np.uint8), (9600 - 1000 - len(sym)) // 4)]
+    s = 2.0 * np.concatenate(out).astype(np.float64) - 1.0
+    assert len(s) == 13 * 9600
+    return (s + rng.normal(0.0, sigma, len(s))).astype(np.float32)
+
+
+def m20_host_tier(s, pushes, nch):
+    """ms per push of one channel through the host framer (no-skip), frames with a good checksum of one channel"""
+    from radiosonde_auto_rx_amd.engine import lib, SondeM20Frame, SONDE_M20
+    L = lib()
+    L.sonde_softin_create.argtypes = [C.c_int32] * 5 + [C.POINTER(C.c_void_p)]
+    L.sonde_softin_destroy.argtypes = [C.c_void_p]
+    L.sonde_softin_push.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+    L.sonde_softin_set_m10_skip.argtypes = [C.c_void_p, C.c_int32]
+    L.sonde_softin_fetch_m20.argtypes = [C.c_void_p, C.POINTER(SondeM20Frame), C.c_int32]
+    hs = []
+    for _ in range(nch):
+        h = C.c_void_p()
+        assert L.sonde_softin_create(SONDE_M20, 0, 0, 1, 0, C.byref(h)) == 0 and L.sonde_softin_set_m10_skip(h, 0) == 0
+        hs.append(h)
+    buf = (SondeM20Frame * 8)()
+    walls, ok = [], 0
+    for k in range(13 + pushes):
+        p = s.ctypes.data + (k % 13) * 9600 * 4
+        t0 = time.perf_counter()
+        n = 0
+        for h in hs:
+            assert L.sonde_softin_push(h, p, 9600) == 0
+            n = L.sonde_softin_fetch_m20(h, buf, 8)
+            assert n >= 0
+        dt = (time.perf_counter() - t0) * 1e3
+        if k >= 13:
+            walls.append(dt / nch)
+            ok += sum(buf[i].cs_ok for i in range(n))
+    for h in hs:
+        L.sonde_softin_destroy(h)
+    return walls, ok
+
+
+def m20_rows(a):
+    import torch
+    from radiosonde_auto_rx_amd.fsk import SoftinDev
+    s = m20_stream()
+    hw, hok = m20_host_tier(s, a.pushes, a.host_channels)
+    host_ms = statistics.median(hw)
+    rows = []
+    for nch in [int(c) for c in a.channels.split(",")]:
+        d = torch.from_numpy(s).to("cuda").repeat(nch, 1).contiguous()
+        torch.cuda.synchronize()
+        sf = SoftinDev(nch, kind="m20", skip=False)
+        walls, ok, frames = [], 0, 0
+        for k in range(13 + a.pushes):
+            p = d.data_ptr() + (k % 13) * 9600 * 4
+            t0 = time.perf_counter()
+            sf.push_device(p, d.shape[1], 9600)
+            dt = (time.perf_counter() - t0) * 1e3
+            recs = sf.fetch_m20(4 * nch + 16)
+            if k >= 13:
+                walls.append(dt)
+                frames += len(recs)
+                ok += sum(r["cs_ok"] for r in recs if r["channel"] == 0)
+        cnt = sf.counts()
+        sf.close()
+        wall = statistics.median(walls)
+        row = {"kind": "m20", "skip": 0, "channels": nch, "pushes": a.pushes, "push_ms": round(wall, 3), "min_ms": round(min(walls), 3), "max_ms": round(max(walls), 3),
+               "channel_seconds_per_second": round(nch * 1e3 / wall, 1), "frames": frames, "ok_channel0": ok, "dropped": cnt["dropped"],
+               "soft_bytes_per_channel_second_left_on_device": 9600 * 4,
+               "host_tier_ms_per_channel_second": round(host_ms, 4), "host_tier_min_ms": round(min(hw), 4), "host_tier_max_ms": round(max(hw), 4),
+               "host_tier_ms_for_these_channels": round(host_ms * nch, 2), "host_tier_ok_one_channel": hok}
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--kind", default="lms6", choices=["lms6", "m20", "all"])
     ap.add_argument("--channels", default="1,64,341,1024")
     ap.add_argument("--pushes", type=int, default=39)
     ap.add_argument("--vit", type=int, default=2)
@@ -71,6 +158,19 @@ def main():
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     assert a.pushes >= 30
+    rows = (lms6_rows(a) if a.kind in ("lms6", "all") else []) + (m20_rows(a) if a.kind in ("m20", "all") else [])
+    if a.out:
+        kinds = {r["kind"] for r in rows}
+        if os.path.exists(a.out):
+            with open(a.out) as f:
+                rows = [r for r in json.load(f) if r.get("kind") not in kinds] + rows
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(rows, f, indent=1)
+            f.write("\n")
+
+
+def lms6_rows(a):
     import torch
     from radiosonde_auto_rx_amd.fsk import SoftinDev
     s = lms6_stream()
@@ -101,11 +201,7 @@ def main():
                "host_tier_ms_for_these_channels": round(host_ms * nch, 1), "host_tier_ok_one_channel": hok}
         rows.append(row)
         print(json.dumps(row), flush=True)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            json.dump(rows, f, indent=1)
-            f.write("\n")
+    return rows
 
 
 if __name__ == "__main__":
