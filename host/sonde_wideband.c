@@ -487,7 +487,8 @@ int main(int argc, char **argv) {
         else break;
     }
     if (argc - ai != 3 || strcmp(argv[ai], "-") || atoi(argv[ai + 2]) != 16 || atoi(argv[ai + 1]) < 48000 || g_raster < 100 || g_slots < 1 || g_slots > 256) {
-        fprintf(stderr, "usage: %s [--channelize [--chan-M 256] [--chan-D 200] [--chan-P 16]] [--cfreq Hz] [--raster Hz] [--slots N] [--release-s S] [--rs92-ephem rinex_nav] [--rs92-alm sem_almanac] [--device D] [-v] - <sr> 16   (cs16 on stdin)\n", argv[0]);
+        fprintf(stderr, "usage: %s [--channelize [--chan-M 256] [--chan-D 200] [--chan-P 16]] [--cfreq Hz] [--raster Hz] [--slots N] [--release-s S] [--rs92-ephem rinex_nav] [--rs92-alm sem_almanac] [--device D] [-v] - <sr> 16   (cs16 on stdin)\n"
+                        "       --chan-M 16..1024 (power of two), --chan-D 1..M, --chan-P 4..32, and 4 (M P + 15 D) + 128 M bytes must fit the LDS of a compute unit (160 KB)\n", argv[0]);
         return 255;
     }
     g_sr = atoi(argv[ai + 1]);

@@ -31,6 +31,9 @@ typedef struct {
     int32_t M;               /* channels: power of two, 16 .. 1024                                      */
     int32_t D;               /* decimation: output rate = sample_rate / D, D <= M                       */
     int32_t P;               /* prototype taps per branch (filter length M * P), 4 .. 32                */
+                             /* and together: 4 * (M P + 15 D, rounded up to even) + 128 M bytes of LDS */
+                             /* per workgroup must fit the device's (160 KB on gfx950: M = 1024 with    */
+                             /* D = 128, P = 4 fits, with D = 800, P = 8 it does not), else SONDE_E_ARG  */
     int32_t max_chunk;       /* largest n_samples per process call                                      */
     int32_t reserved[5];
 } sonde_chan_cfg_t;

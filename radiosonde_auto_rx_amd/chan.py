@@ -34,6 +34,9 @@ def _lib():
         L.sonde_chan_sync.argtypes = [C.c_void_p]
         L.sonde_chan_stream.argtypes = [C.c_void_p]; L.sonde_chan_stream.restype = C.c_void_p
         L.sonde_chan_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
+        L.sonde_chan_output.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
+        L.sonde_chan_rows_alloc.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]
+        L.sonde_chan_gather.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_void_p]
         _proto = True
     return L
 
@@ -70,6 +73,24 @@ class Channelizer:
     def stream(self) -> int:
         """The hipStream_t the channelizer queues its work on (for Scanner.wait_stream / an engine's wait)."""
         return int(_lib().sonde_chan_stream(self._h) or 0)
+
+    def output(self):
+        """-> (device pointer, row stride) of the [M][max_frames] complex64 output array the channelizer owns (freed with it)"""
+        p, stride = C.c_void_p(), C.c_int64()
+        _chk(_lib().sonde_chan_output(self._h, C.byref(p), C.byref(stride)))
+        return int(p.value or 0), stride.value
+
+    def rows_alloc(self, n_rows: int) -> int:
+        """-> device pointer of a zeroed [n_rows][max_frames] complex64 array (freed with the channelizer)"""
+        p = C.c_void_p()
+        _chk(_lib().sonde_chan_rows_alloc(self._h, n_rows, C.byref(p)))
+        return int(p.value or 0)
+
+    def gather(self, out_ptr: int, out_stride: int, channels, n_frames: int, rows_ptr: int):
+        """rows r of rows_ptr ([len(channels)][max_frames]) <- the first n_frames samples of channel channels[r] of out_ptr; a channel < 0
+        leaves its row alone.  Queued on the channelizer's stream: sync() before another stream reads the rows."""
+        ch = (C.c_int32 * len(channels))(*channels)
+        _chk(_lib().sonde_chan_gather(self._h, C.c_void_p(out_ptr), out_stride, ch, len(channels), n_frames, C.c_void_p(rows_ptr)))
 
     def kernel_ms(self):
         ms, n = C.c_double(), C.c_int64()

@@ -110,10 +110,17 @@ struct sonde_chan {
     float2 *d_own = nullptr;            // sonde_chan_output(): [M][max_frames] owned by the channelizer (callers without a device allocator of their own)
     std::vector<void *> rows;           // sonde_chan_rows_alloc()
     int T = 0, log2M = 0, hist = 0;
+    size_t lds = 0;                     // dynamic LDS of every launch (chan_lds_bytes)
     long long n_in = 0, m_out = 0;      // stream samples consumed, output samples produced (per channel)
     double ms = 0; int64_t launches = 0;
     hipEvent_t ev_a = nullptr, ev_b = nullptr;
 };
+
+// [span, rounded up to even] raw cs16 words and CH_F transforms of M complex floats: what k_channelize carves out of its dynamic LDS
+static size_t chan_lds_bytes(int M, int D, int P) {
+    const size_t span = (size_t)M * P + (size_t)(CH_F - 1) * D;
+    return ((span + 1) & ~(size_t)1) * sizeof(uint32_t) + (size_t)CH_F * M * sizeof(float2);
+}
 
 extern "C" {
 
@@ -127,8 +134,19 @@ int sonde_chan_create(const sonde_chan_cfg_t *cfg, sonde_chan_t **out) {
         return SONDE_E_NOGPU;
     }
     HIPCHK(hipSetDevice(cfg->device));
+    // a shape inside the M, D, P ranges can still ask for more LDS than a workgroup may have: refused here, not at the first launch.  Above 64 KB
+    // the launch has to be announced, per (function, device): done for every such channelizer on the device it lives on, and with the device's
+    // limit rather than its own need, so that a smaller channelizer created later does not lower what an earlier one launches with
+    const size_t lds = chan_lds_bytes(cfg->M, cfg->D, cfg->P);
+    int lds_max = 0;
+    HIPCHK(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, cfg->device));
+    if (lds > (size_t)lds_max) {
+        fprintf(stderr, "libsonde_hip: channelizer M = %d, D = %d, P = %d needs %zu bytes of LDS per workgroup (4 (M P + 15 D) + 128 M), the device has %d\n", cfg->M, cfg->D, cfg->P, lds, lds_max);
+        return SONDE_E_ARG;
+    }
+    if (lds > 64 * 1024) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_channelize), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
     sonde_chan *c = new sonde_chan();
-    c->cfg = *cfg;
+    c->cfg = *cfg; c->lds = lds;
     const int M = cfg->M, T = M * cfg->P;
     c->T = T; c->hist = T - 1;
     while ((1 << c->log2M) < M) c->log2M++;
@@ -193,10 +211,8 @@ int sonde_chan_process_device(sonde_chan_t *c, const void *d_iq, int32_t n_sampl
         ChanArgs a{};
         a.x = c->d_x; a.h = c->d_h; a.tw = c->d_tw; a.out = (float2 *)d_out; a.out_stride = out_stride;
         a.M = c->cfg.M; a.log2M = c->log2M; a.D = D; a.P = c->cfg.P; a.T = c->T; a.m0 = c->m_out; a.n0 = c->n_in; a.hist = c->hist; a.n_frames = n_frames;
-        const int span = c->T + (CH_F - 1) * D;
-        const size_t lds = (size_t)((span + 1) & ~1) * sizeof(uint32_t) + (size_t)CH_F * c->cfg.M * sizeof(float2);
         hipEventRecord(c->ev_a, c->stream);
-        hipLaunchKernelGGL(k_channelize, dim3((n_frames + CH_F - 1) / CH_F), dim3(CH_THREADS), lds, c->stream, a);
+        hipLaunchKernelGGL(k_channelize, dim3((n_frames + CH_F - 1) / CH_F), dim3(CH_THREADS), c->lds, c->stream, a);
         hipEventRecord(c->ev_b, c->stream);
         c->launches++;
     }
