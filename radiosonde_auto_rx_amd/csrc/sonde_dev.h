@@ -238,5 +238,10 @@ void sonde_launch_search_sync(const SearchSyncArgs *a, hipStream_t s);
 // workgroups of k_if_chain (with the dynamic LDS a launch with these arguments asks for) / of k_search_sync that one CU holds at a time; -1: the runtime refused
 int  sonde_if_chain_residency(const IfArgs *a);
 int  sonde_search_sync_residency(void);
+// dynamic LDS of a full tile of k_if_chain / k_if_chain_multi and the layout it runs in (*overlay: 1 = layout B), from the tap counts (1 = filter off), the tone
+// window and the two switches alone: a pure host function, the rule the launches use (tests/test_if_chain_cases_design.py holds its case table to it)
+size_t sonde_if_chain_lds_bytes(int T1, int T2, int nwin, int tone_on, int fm_on, int *overlay);
+// at engine create: 0 = a launch with these arguments fits (and is announced where it needs more than 64 KB), -1 = it needs more LDS than the device has (said on stderr), -2 = runtime error
+int  sonde_if_chain_reserve(const IfArgs *a, int device);
 }
 #endif

@@ -10,7 +10,7 @@
 //   find_header / read_softbit2p counters              SyncState per channel in HBM
 //   AFC of --dc (dsp.Df / locked / dc, demod_mod.c:1553-1600)   AfcState per channel; optimistic chunk + per-channel restart loop (process_device)
 // Returns SONDE_E_ARG for what is not mirrored: --ecc3/4, --noLUT together with --dc, decimators of more than 8 tap columns on a mixed engine (single-type engines run
-// those through the float32 mixer / FIR kernels, create_impl).
+// those through the float32 mixer / FIR kernels, create_impl), and for an IF rate whose filters need more LDS per workgroup of k_if_chain than the device has.
 #include "../../include/sonde_hip.h"
 #include "sonde_dev.h"
 #include "sonde_host.h"
@@ -303,6 +303,7 @@ int sonde_engine_create_generic(const sonde_cfg_t *cfg, const double *fq, const 
 
 }  // extern "C"
 
+static IfArgs fill_if(sonde_engine *e, int n_if, uint32_t m_first);
 static int create_impl(const sonde_cfg_t *cfg, const double *fq, const sonde_generic_t *gen, const CreateLink *lk, sonde_engine_t **out) {
     if (!cfg || !fq || !out || cfg->abi_version != SONDE_ABI_VERSION) return SONDE_E_ARG;
     if (cfg->sonde_type == SONDE_GENERIC && !gen) return SONDE_E_ARG;
@@ -417,6 +418,13 @@ static int create_impl(const sonde_cfg_t *cfg, const double *fq, const sonde_gen
         // (bits up to 5 x 808 are read and dropped, m10mod.c:1494-1507)
         const int last = skip_last >= 0 ? skip_last : ((cfg->sonde_type == SONDE_M10 || cfg->sonde_type == SONDE_M20) && !cfg->m10_noskip) ? 5 * 808 - 1 : e->nbits - 1;
         uint32_t q0, q1; double mid; bit_window(last, e->symlen - 1, e->symlen, e->sps, q0, q1, mid); e->frame_samples = q1;
+    }
+
+    // the IF chain's LDS need grows with the IF rate (both low-passes are 1 / 1000 s and 1 / 500 s long): decided here, for a full tile, not at the first launch
+    if (!audio && !front_only) {
+        const IfArgs ia = fill_if(e, 0, 0);
+        const int rc = sonde_if_chain_reserve(&ia, cfg->device);
+        if (rc) { delete e; return rc == -1 ? SONDE_E_ARG : SONDE_E_NOGPU; }
     }
 
     const int max_if = (cfg->max_chunk + D - 1) / D;

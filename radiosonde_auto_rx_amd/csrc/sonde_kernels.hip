@@ -24,6 +24,7 @@
 #include "md_fast_gen.h"
 #include "sonde_rs_dev.h"
 #include <cstdlib>
+#include <cstdio>
 #include <algorithm>
 
 typedef short  short2v __attribute__((ext_vector_type(2)));
@@ -2728,6 +2729,31 @@ extern "C" void sonde_launch_search_sync(const SearchSyncArgs *a, hipStream_t s)
 extern "C" int sonde_if_chain_residency(const IfArgs *a) {
     int n = 0;
     return hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_if_chain, IF_THREADS, if_chain_lds(*a)) == hipSuccess ? n : -1;
+}
+// What if_chain_lds / if_chain_overlay give for a full tile, from the numbers alone (no device): T1 / T2 = taps of the IF / FM low-pass (1 = off)
+extern "C" size_t sonde_if_chain_lds_bytes(int T1, int T2, int nwin, int tone_on, int fm_on, int *overlay) {
+    IfArgs a{};
+    a.lpiq_on = 1; a.lpiq_taps = T1; a.lpfm_on = 1; a.lpfm_taps = T2; a.nwin = nwin; a.tone_on = tone_on; a.fm_on = fm_on;
+    if (overlay) *overlay = if_chain_overlay(tone_on, T2, (T2 - 1) + std::max(1, nwin - 1) + (tone_on ? IF_RUN - 1 : 0)) ? 1 : 0;
+    return if_chain_lds(a);
+}
+// An engine's need is known when it is created: more than a workgroup may have is refused there (-1), not at the first launch.  Above 64 KB the launch has to be
+// announced, per (function, device): with the device's limit rather than the engine's own need, so that a smaller engine created later does not lower what an
+// earlier one launches with (as sonde_chan_create does for k_channelize)
+extern "C" int sonde_if_chain_reserve(const IfArgs *a, int device) {
+    const size_t lds = if_chain_lds(*a);
+    int lds_max = 0;
+    if (hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, device) != hipSuccess) return -2;
+    if (lds > (size_t)lds_max) {
+        fprintf(stderr, "libsonde_hip: the IF chain with %d IF low-pass taps, %d FM low-pass taps and a tone window of %d samples needs %zu bytes of LDS per workgroup, the device has %d\n",
+                a->lpiq_on ? a->lpiq_taps : 1, a->lpfm_on ? a->lpfm_taps : 1, a->nwin, lds, lds_max);
+        return -1;
+    }
+    if (lds > 64 * 1024) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_if_chain), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max) != hipSuccess) return -2;
+        if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_if_chain_multi), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max) != hipSuccess) return -2;
+    }
+    return 0;
 }
 extern "C" int sonde_search_sync_residency(void) {
     int n = 0;
