@@ -14,6 +14,7 @@
 #include "sonde_hip.h"
 #include "sonde_drop.h"
 #include "sonde_lms6.h"
+#include "sonde_rs92.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -176,7 +177,40 @@ typedef struct {
 /* blocks completed by the push calls since the last fetch (per channel in stream order); returns the count (<= max) */
 int  sonde_softin_dev_fetch_lms6(sonde_softin_dev_t *s, sonde_lms6_softin_t *out, int32_t max);
 
-/* tallies since creation: frames completed (SONDE_LMS6: blocks; accepted = the frames with a good CRC-16 that ended in them, the decoders' own count), frames accepted (RS41: rs41_ecc() >= 0; DFM: no block uncorrectable; M10 / M20: checksum good; RD94RD41: every block of the type print_frame chooses good), frames repaired, symbols / codewords repaired, frames lost to a full buffer */
+/* ---- SONDE_RS92 consumers: `rs92mod --softin [-i] --ecc ...` for every channel (auto_rx's pipe `fsk_demod --cs16 -b -20000 -u 20000 -s --stats=N 2 48000 4800 - - |
+ * rs92mod -vx -v --crc --ecc --vel --json --softin -i -e <rinex> --ptu`, auto_rx/autorx/decode.py:976-987).  On the device, one wavefront per channel
+ * (rs92mod.c:1959-2050, :183-196, :1360-1385): the 60 raw header symbols of 2A 2A 10 at 0.8 (a score of exactly 0.8f and the NaN of an all-zero window are no hits; the
+ * ring is emptied on every hit; a hit of the other polarity is dropped, rs92mod has no --auto), 234 bytes of 10 bits from two soft symbols per bit, and RS(255,231) of
+ * the finished frame — always on, as --json and the host tier force it.  Per completed frame 264 bytes come to the host, where the consumer's own sonde_rs92_dec_t of
+ * that channel (its calibration rows are per sonde) checks the CRCs, solves the position and prints (sonde_rs92_dec_corrected) when the record is fetched.  Only
+ * complete frames are delivered: the reference prints a partial frame at end of input alone, and a consumer behind a live modem has none.
+ * opts as for sonde_rs92_dec_create; opts->inv = -i, invert_stream = --softinv.  SONDE_E_ARG for what would leave a record's text without a bound: gps_verbose == 8
+ * (-gg) and dbg.  sonde_softin_dev_create with SONDE_RS92 is SONDE_E_ARG (the kind needs its options); the other kinds' fetch calls refuse an RS92 consumer and
+ * fetch_rs92 / the load calls refuse the other kinds.  One launch per push call: submit_fsk / collect keep the overlap with the modem's next second.
+ * A push call holds at most 4 * n_channels + 16 frames over all channels (a channel completes one per 4740 symbols at the least); frames beyond that are decoded, not
+ * delivered, and counted as dropped. */
+int  sonde_softin_dev_create_rs92(int32_t n_channels, const sonde_rs92_opts_t *opts, int32_t invert_stream, sonde_softin_dev_t **out);
+/* orbit data for every channel's decoder; SONDE_E_ARG as sonde_rs92_dec_load_ephemeris / _almanac return it */
+int  sonde_softin_dev_rs92_load_ephemeris(sonde_softin_dev_t *s, const char *path);
+int  sonde_softin_dev_rs92_load_almanac(sonde_softin_dev_t *s, const char *path);
+/* The text of a frame under the accepted options.  Its line: "[%5d] (id) (date) day time" 52, position / (d:) / velocity / a DOP list of 12 PRNs 190, three PTU
+ * values 60, aux 22, "  # [crc]" (n) 15, the -vv calibration row with its aux bytes and frequency / kill timer 160: below 500 for values in their physical range;
+ * a %f field of a float without one (a temperature from corrupt calibration rows) can take 47 characters, eight of them 380 more.  The JSON object: 360 of fixed
+ * text and bounded fields, the same six %f fields again, version 31: below 800.  2048 leaves room for both at their worst. */
+#define SONDE_RS92_TEXT_MAX 2048
+typedef struct {
+    int32_t  channel;
+    int32_t  ec;             /* rs_decode's value for the frame: 0, the number of repaired bytes, -1 / -2 / -3 = left as received */
+    float    mv;             /* score of the header in front of the frame                                                         */
+    int32_t  text_len;       /* SONDE_E_ARG (negative) if the text did not fit: text is "" then                                   */
+    uint64_t hdr_bit;        /* symbols read when the header matched                                                             */
+    uint8_t  frame[SONDE_RS92_FRAME_LEN];     /* the frame behind rs92_ecc                                                       */
+    char     text[SONDE_RS92_TEXT_MAX];       /* what the reference prints for this frame, NUL-terminated                        */
+} sonde_rs92_softin_t;
+/* frames completed by the push calls since the last fetch (per channel in stream order); returns the count (<= max) */
+int  sonde_softin_dev_fetch_rs92(sonde_softin_dev_t *s, sonde_rs92_softin_t *out, int32_t max);
+
+/* tallies since creation: frames completed (SONDE_LMS6: blocks; accepted = the frames with a good CRC-16 that ended in them, the decoders' own count), frames accepted (RS41: rs41_ecc() >= 0; DFM: no block uncorrectable; M10 / M20: checksum good; RD94RD41: every block of the type print_frame chooses good; RS92: rs_decode >= 0), frames repaired (RS92: rs_decode > 0), symbols / codewords repaired (RS92: the sum of the positive rs_decode values), frames lost to a full buffer */
 int  sonde_softin_dev_counts(sonde_softin_dev_t *s, int64_t *frames, int64_t *ecc_ok, int64_t *repaired, int64_t *symbols, int64_t *dropped);
 
 #ifdef __cplusplus

@@ -75,6 +75,11 @@ int  sonde_rs92_dec_frame(sonde_rs92_dec_t *d, const float *soft, int32_t n, cha
 /* One frame as bytes (`rs92mod --rawhex`, :2075-2081): len bytes from the start of the frame (header included). */
 int  sonde_rs92_dec_bytes(sonde_rs92_dec_t *d, const uint8_t *frame, int32_t len, char *out, size_t outlen);
 
+/* print_frame for a frame that has ALREADY been through rs92_ecc (the device soft-bit consumer, include/sonde_fsk.h): the 240 bytes as rs92_ecc left them and its
+ * value ec (0, the repaired count, negative = not correctable, bytes as received).  The text is what sonde_rs92_dec_bytes gives on the uncorrected frame, the
+ * (n) / (-) of --ecc2 / --json and [OK] / [NO] of -r -v included. */
+int  sonde_rs92_dec_corrected(sonde_rs92_dec_t *d, const uint8_t frame[SONDE_RS92_FRAME_LEN], int32_t ec, char *out, size_t outlen);
+
 /* Soft-symbol input (`rs92mod --softin`): raw symbols at 4800 per second (two per bit); header search, polarity check against opts.inv and the bit loop
  * inside; finish != 0 at end of input (a frame in progress is printed with the bytes that exist). */
 int  sonde_rs92_dec_push_soft(sonde_rs92_dec_t *d, const float *soft, int32_t n, int32_t invert, int32_t finish, char *out, size_t outlen);

@@ -665,8 +665,12 @@ struct sonde_rs92_dec {
     }
 
     void print_frame(Out &w, int len) {
-        crc = 0;
         const int ec = rs_correct(len);                         // (ecc is at least 1, :1866)
+        print_corrected(w, len, ec);
+    }
+    // print_frame behind rs92_ecc: frame holds what the decoder left, ec its value
+    void print_corrected(Out &w, int len, int ec) {
+        crc = 0;
         for (int i = len; i < FRAME_LEN; i++) frame[i] = 0;
         if (o.raw) {
             for (int i = 0; i < len; i++) w.f("%02x", frame[i]);
@@ -755,6 +759,14 @@ int sonde_rs92_dec_bytes(sonde_rs92_dec_t *d, const uint8_t *frame, int32_t len,
     Out w;
     memcpy(d->frame, frame, (size_t)len);
     d->print_frame(w, len);
+    return finish_out(w, out, outlen);
+}
+
+int sonde_rs92_dec_corrected(sonde_rs92_dec_t *d, const uint8_t frame[SONDE_RS92_FRAME_LEN], int32_t ec, char *out, size_t outlen) {
+    if (!d || !frame || !out) return SONDE_E_ARG;
+    Out w;
+    memcpy(d->frame, frame, FRAME_LEN);
+    d->print_corrected(w, FRAME_LEN, ec);
     return finish_out(w, out, outlen);
 }
 

@@ -6,6 +6,7 @@ channels at once.  No CPU fallback: the constructor raises without the in-tree H
 from __future__ import annotations
 
 import ctypes as C
+import os
 
 import numpy as np
 
@@ -44,6 +45,18 @@ class Lms6SoftinRec(C.Structure):
                 ("blen", C.c_int32), ("err", C.c_int32), ("text", C.c_char * LMS6_TEXT_MAX)]
 
 
+RS92_TEXT_MAX = 2048
+
+
+class Rs92SoftinRec(C.Structure):
+    """sonde_rs92_softin_t (include/sonde_fsk.h)"""
+    _fields_ = [("channel", C.c_int32), ("ec", C.c_int32), ("mv", C.c_float), ("text_len", C.c_int32), ("hdr_bit", C.c_uint64),
+                ("frame", C.c_uint8 * 240), ("text", C.c_char * RS92_TEXT_MAX)]
+
+
+# auto_rx's `rs92mod -vx -v --crc --ecc --vel --json --softin -i` (auto_rx/autorx/decode.py:976-987; --json makes --ecc an --ecc2)
+RS92_DEFAULTS = dict(verbose=1, aux=1, ecc=2, gps_vel=4, json=1, inv=1, gpsepoch=-1)
+
 _proto = False
 
 
@@ -81,6 +94,11 @@ def _lib():
         L.sonde_softin_dev_fetch_drop.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
         L.sonde_softin_dev_create_lms6.argtypes = [C.c_int32, C.POINTER(Lms6Opts), C.c_int32, C.POINTER(C.c_void_p)]
         L.sonde_softin_dev_fetch_lms6.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+        from .family import Rs92Opts
+        L.sonde_softin_dev_create_rs92.argtypes = [C.c_int32, C.POINTER(Rs92Opts), C.c_int32, C.POINTER(C.c_void_p)]
+        L.sonde_softin_dev_rs92_load_ephemeris.argtypes = [C.c_void_p, C.c_char_p]
+        L.sonde_softin_dev_rs92_load_almanac.argtypes = [C.c_void_p, C.c_char_p]
+        L.sonde_softin_dev_fetch_rs92.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
         _proto = True
     return L
 
@@ -188,14 +206,31 @@ class SoftinDev:
     without the soft-decision stream crossing to the host.  No CPU fallback."""
 
     def __init__(self, n_channels: int, *, ecc: int = 2, softinv: bool = False, inv: bool = True, auto: bool = False, kind: str = "rs41",
-                 vit: int = 2, typ: int = 0, json: bool = False, raw: bool = False, gpsweek: int = 0, freq_khz: int = 0, version: str = "", skip: bool = True):
+                 vit: int = 2, typ: int = 0, json: bool = False, raw: bool = False, gpsweek: int = 0, freq_khz: int = 0, version: str = "", skip: bool = True,
+                 rs92_opts: dict | None = None, ephemeris: str | None = None, almanac: str | None = None):
         """kind: "rs41" (rs41mod --softin), "dfm" (dfm09mod --softin: ecc 0 / 1 = --ecc / 2 = --ecc2), "m10" (m10mod --softin), "m20" (m20mod --softin: skip = the rest of
         the second behind a frame is dropped, as m20mod does below -vvv; auto_rx runs `m20mod --json --ptu -vvv --softin -i`: skip=False; ecc, inv and auto mean nothing to it), "drop" (rd94rd41drop --softin /
         --softinv [-i]: auto_rx runs it as softinv=True, inv=False; ecc and auto are ignored) or "lms6" (lms6Xmod --softin: vit 1 = --vit / 2 = --vit2, typ 0 = auto
-        detection / 6 = --lms6 / 10 = --lmsX, ecc != 0 = --ecc, json, raw = -r, gpsweek, freq_khz and version as sonde_lms6_opts_t; inv (-i) means nothing to it)"""
+        detection / 6 = --lms6 / 10 = --lmsX, ecc != 0 = --ecc, json, raw = -r, gpsweek, freq_khz and version as sonde_lms6_opts_t; inv (-i) means nothing to it) or
+        "rs92" (rs92mod --softin: rs92_opts = fields of family.Rs92Opts over auto_rx's defaults verbose 1, aux 1, ecc 2, gps_vel 4, json 1, inv 1 — inv there is -i;
+        ephemeris = a RINEX navigation file (-e), almanac = an SEM almanac (-a) for every channel's decoder; ecc, inv and auto of this call mean nothing to it)"""
         from .engine import SONDE_RS41, SONDE_DFM09, SONDE_M10, SONDE_M20, SONDE_RD94RD41
         h = C.c_void_p()
         self.kind, self.ecc = kind, ecc
+        if kind == "rs92":
+            from .family import Rs92Opts
+            kw = dict(RS92_DEFAULTS)
+            kw.update(rs92_opts or {})
+            if isinstance(kw.get("version"), str):
+                kw["version"] = kw["version"].encode()
+            o = Rs92Opts(**kw)
+            _chk(_lib().sonde_softin_dev_create_rs92(n_channels, C.byref(o), int(softinv), C.byref(h)))
+            self._h, self.n_channels = h, n_channels
+            if ephemeris:
+                self.load_rs92_ephemeris(ephemeris)
+            if almanac:
+                self.load_rs92_almanac(almanac)
+            return
         if kind == "lms6":
             o = Lms6Opts(raw=int(raw), ecc=1 if ecc else 0, vit=vit, json=int(json), typ=typ, gpsweek=gpsweek, jsn_freq_khz=freq_khz, version=version.encode())
             _chk(_lib().sonde_softin_dev_create_lms6(n_channels, C.byref(o), int(softinv), C.byref(h)))
@@ -309,6 +344,21 @@ class SoftinDev:
             text = r.text.decode()
             out.append(dict(channel=r.channel, hdr_bit=r.hdr_bit, mv=r.mv, type=r.type, blen=r.blen, err=r.err, text=text, lines=[l for l in text.splitlines() if l]))
         return out
+
+    def load_rs92_ephemeris(self, path: str):
+        """RS92 consumers: a RINEX navigation file (rs92mod -e) for every channel's decoder"""
+        _chk(_lib().sonde_softin_dev_rs92_load_ephemeris(self._h, os.fsencode(path)))
+
+    def load_rs92_almanac(self, path: str):
+        """RS92 consumers: an SEM almanac (rs92mod -a) for every channel's decoder"""
+        _chk(_lib().sonde_softin_dev_rs92_load_almanac(self._h, os.fsencode(path)))
+
+    def fetch_rs92(self, max_frames: int = 1024):
+        """RS92 consumers: a dict per completed frame — channel, ec (rs_decode's value: 0, repaired bytes, negative = left as received), mv, hdr_bit (symbols read when
+        the header matched), frame = the 240 bytes behind rs92_ecc, text = what `rs92mod` prints for it (the channel's own decoder: calibration rows, orbit data)"""
+        buf = (Rs92SoftinRec * max_frames)()
+        n = _chk(_lib().sonde_softin_dev_fetch_rs92(self._h, buf, max_frames))
+        return [dict(channel=r.channel, ec=r.ec, mv=r.mv, hdr_bit=r.hdr_bit, frame=bytes(r.frame), text=r.text[:max(r.text_len, 0)].decode()) for r in buf[:n]]
 
     def counts(self):
         v = [C.c_int64(0) for _ in range(5)]

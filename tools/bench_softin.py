@@ -13,7 +13,13 @@ one second (9600 symbols) per push in device memory, a 13 s stream with one fram
 framer on the same stream (sonde_softin_push + sonde_softin_fetch_m20, one thread).  Only completed frames cross to the host: 38.4 KB of soft decisions per channel and
 second stay where the modem left them.  --out keeps the rows of the kinds that were not run.
 
-    python tools/bench_softin.py [--kind lms6|m20|all] [--channels 1,64,341,1024] [--pushes 39] [--vit 2] [--typ 0] [--out profiles/softin_bench.json]"""
+--kind rs92 (or all): the RS92 consumer (SoftinDev(kind="rs92"): k_softin_rs92 with RS(255,231) on the wave, auto_rx's form `rs92mod -vx -v --crc --ecc --vel --json
+--softin -i -e <rinex> --ptu`) — N channels x one second (4800 symbols) per push in device memory, a 13 s flight of tools/synth_rs92.py (inverted, as -i wants it) at sigma
+0.3, repeated.  A push is the kernel and the copies of its records (push_ms); the text is made when the records are fetched, by the channel's host decoder, and is timed
+apart: text_ms with the synthetic RINEX file loaded (CRCs, PTU, the GPS solution of every frame, JSON) and text_no_gps_ms without orbit data (no solution, no JSON): the
+difference is the GPS solve, which stays on the host.  Beside it the host tier (sonde_rs92_dec_push_soft, one thread) with and without orbit data.
+
+    python tools/bench_softin.py [--kind lms6|m20|rs92|all] [--channels 1,64,341,1024] [--pushes 39] [--vit 2] [--typ 0] [--out profiles/softin_bench.json]"""
 import argparse
 import ctypes as C
 import json
@@ -112,6 +118,101 @@ def m20_host_tier(s, pushes, nch):
     return walls, ok
 
 
+def rs92_stream(sigma=0.3, seed=3):
+    """13 s at 4800 symbols: 13 frames of one flight back to back (a frame is a second on air), inverted, noise on everything; the flight's RINEX file as bytes"""
+    from tools import synth_rs92 as R
+    eph = R.constellation()
+    sym = R.onair_symbols(R.flight(13, eph), lead=0)
+    assert len(sym) == 13 * 4800
+    rng = np.random.default_rng(seed)
+    return (-(2.0 * sym.astype(np.float64) - 1.0) + rng.normal(0.0, sigma, len(sym))).astype(np.float32), R.rinex_nav(eph, extra_toe=(-7200.0,))
+
+
+RS92_OPTS = dict(verbose=1, aux=1, ecc=2, gps_vel=4, json=1, inv=1, ptu=1, gpsepoch=-1)
+
+
+def rs92_host_tier(s, pushes, nch, rinex):
+    """ms per push of one channel through sonde_rs92_dec_push_soft (rinex: with orbit data, else without), frames with a position of one channel"""
+    from radiosonde_auto_rx_amd.engine import lib
+    from radiosonde_auto_rx_amd.family import Rs92Opts
+    L = lib()
+    L.sonde_rs92_dec_create.argtypes = [C.POINTER(Rs92Opts), C.POINTER(C.c_void_p)]
+    L.sonde_rs92_dec_destroy.argtypes = [C.c_void_p]
+    L.sonde_rs92_dec_load_ephemeris.argtypes = [C.c_void_p, C.c_char_p]
+    L.sonde_rs92_dec_push_soft.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_char_p, C.c_size_t]
+    o = Rs92Opts(**RS92_OPTS)
+    decs = []
+    for _ in range(nch):
+        d = C.c_void_p()
+        assert L.sonde_rs92_dec_create(C.byref(o), C.byref(d)) == 0
+        if rinex:
+            assert L.sonde_rs92_dec_load_ephemeris(d, os.fsencode(rinex)) == 0
+        decs.append(d)
+    out = C.create_string_buffer(1 << 16)
+    walls, ok = [], 0
+    for k in range(13 + pushes):
+        p = s.ctypes.data + (k % 13) * 4800 * 4
+        t0 = time.perf_counter()
+        for d in decs:
+            n = L.sonde_rs92_dec_push_soft(d, p, 4800, 0, 0, out, len(out))
+            assert n >= 0
+        dt = (time.perf_counter() - t0) * 1e3
+        if k >= 13:
+            walls.append(dt / nch)
+            ok += out.value.count(b'"lat"')
+    for d in decs:
+        L.sonde_rs92_dec_destroy(d)
+    return walls, ok
+
+
+def rs92_rows(a):
+    import tempfile
+    import torch
+    from radiosonde_auto_rx_amd.fsk import SoftinDev
+    s, nav = rs92_stream()
+    rows = []
+    with tempfile.TemporaryDirectory() as tmp:
+        rinex = os.path.join(tmp, "brdc.nav")
+        with open(rinex, "wb") as f:
+            f.write(nav)
+        hw, hok = rs92_host_tier(s, a.pushes, a.host_channels, rinex)
+        hw0, _ = rs92_host_tier(s, a.pushes, a.host_channels, None)
+        host_ms, host0_ms = statistics.median(hw), statistics.median(hw0)
+        for nch in [int(c) for c in a.channels.split(",")]:
+            d = torch.from_numpy(s).to("cuda").repeat(nch, 1).contiguous()
+            torch.cuda.synchronize()
+            res = {}
+            for orbit in (True, False):
+                sf = SoftinDev(nch, kind="rs92", rs92_opts=dict(ptu=1), ephemeris=rinex if orbit else None)
+                walls, texts, ok, frames, repaired = [], [], 0, 0, 0
+                for k in range(13 + a.pushes):
+                    p = d.data_ptr() + (k % 13) * 4800 * 4
+                    t0 = time.perf_counter()
+                    sf.push_device(p, d.shape[1], 4800)
+                    t1 = time.perf_counter()
+                    recs = sf.fetch_rs92(nch + 16)
+                    t2 = time.perf_counter()
+                    if k >= 13:
+                        walls.append((t1 - t0) * 1e3); texts.append((t2 - t1) * 1e3)
+                        frames += len(recs)
+                        ok += sum(r["text"].count('"lat"') for r in recs if r["channel"] == 0)
+                        repaired += sum(r["ec"] > 0 for r in recs)
+                res[orbit] = (walls, texts, ok, frames, repaired, sf.counts())
+                sf.close()
+            walls, texts, ok, frames, repaired, cnt = res[True]
+            wall, text, text0 = statistics.median(walls), statistics.median(texts), statistics.median(res[False][1])
+            row = {"kind": "rs92", "channels": nch, "pushes": a.pushes, "push_ms": round(wall, 3), "min_ms": round(min(walls), 3), "max_ms": round(max(walls), 3),
+                   "text_ms": round(text, 3), "text_min_ms": round(min(texts), 3), "text_max_ms": round(max(texts), 3), "text_no_gps_ms": round(text0, 3),
+                   "push_plus_text_ms": round(wall + text, 3), "channel_seconds_per_second": round(nch * 1e3 / (wall + text), 1), "frames": frames, "repaired": repaired,
+                   "positions_channel0": ok, "dropped": cnt["dropped"], "soft_bytes_per_channel_second_left_on_device": 4800 * 4,
+                   "host_tier_ms_per_channel_second": round(host_ms, 4), "host_tier_min_ms": round(min(hw), 4), "host_tier_max_ms": round(max(hw), 4),
+                   "host_tier_no_gps_ms_per_channel_second": round(host0_ms, 4), "host_tier_ms_for_these_channels": round(host_ms * nch, 2),
+                   "host_tier_positions_one_channel": hok}
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+    return rows
+
+
 def m20_rows(a):
     import torch
     from radiosonde_auto_rx_amd.fsk import SoftinDev
@@ -149,7 +250,7 @@ def m20_rows(a):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--kind", default="lms6", choices=["lms6", "m20", "all"])
+    ap.add_argument("--kind", default="lms6", choices=["lms6", "m20", "rs92", "all"])
     ap.add_argument("--channels", default="1,64,341,1024")
     ap.add_argument("--pushes", type=int, default=39)
     ap.add_argument("--vit", type=int, default=2)
@@ -158,7 +259,7 @@ def main():
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     assert a.pushes >= 30
-    rows = (lms6_rows(a) if a.kind in ("lms6", "all") else []) + (m20_rows(a) if a.kind in ("m20", "all") else [])
+    rows = (lms6_rows(a) if a.kind in ("lms6", "all") else []) + (m20_rows(a) if a.kind in ("m20", "all") else []) + (rs92_rows(a) if a.kind in ("rs92", "all") else [])
     if a.out:
         kinds = {r["kind"] for r in rows}
         if os.path.exists(a.out):
