@@ -15,6 +15,7 @@
 #include "sonde_drop.h"
 #include "sonde_lms6.h"
 #include "sonde_rs92.h"
+#include "sonde_imet54.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -210,7 +211,39 @@ typedef struct {
 /* frames completed by the push calls since the last fetch (per channel in stream order); returns the count (<= max) */
 int  sonde_softin_dev_fetch_rs92(sonde_softin_dev_t *s, sonde_rs92_softin_t *out, int32_t max);
 
-/* tallies since creation: frames completed (SONDE_LMS6: blocks; accepted = the frames with a good CRC-16 that ended in them, the decoders' own count), frames accepted (RS41: rs41_ecc() >= 0; DFM: no block uncorrectable; M10 / M20: checksum good; RD94RD41: every block of the type print_frame chooses good; RS92: rs_decode >= 0), frames repaired (RS92: rs_decode > 0), symbols / codewords repaired (RS92: the sum of the positive rs_decode values), frames lost to a full buffer */
+/* ---- SONDE_IMET54 consumers: `imet54mod --softin [-i] [--auto] [--ecc] ...` for every channel (auto_rx's pipe `fsk_demod --cs16 -b -10000 -u 10000 -s --stats=N 2 48000
+ * 4800 - - | imet54mod --ecc --json --softin -i --ptu`, auto_rx/autorx/decode.py:1215-1250).  On the device, one wavefront per channel (imet54mod.c:1007-1063,
+ * :107-133, :162-303, :350-360, :618-660): the 40 header symbols of 00 AA 24 24 at 0.8 (a score of exactly 0.8f and the NaN of an all-zero window are no hits; the ring
+ * is left as it is on a hit and frame symbols never enter it; a hit of the other polarity is dropped, or with --auto flips the polarity for good), 220 8N1
+ * characters, the 8 x 8 de-interleave, 216 Hamming(8,4) codewords (single errors repaired with --ecc only), the three ecc sums of print_frame and both check sums.
+ * Per completed frame 152 bytes come to the host, where the consumer's own sonde_imet54_dec_t of that channel prints from the device's values
+ * (sonde_imet54_dec_decoded) when the record is fetched.  Only complete frames are delivered: the reference prints a partial frame at end of input alone, and a
+ * consumer behind a live modem has none.
+ * opts as for sonde_imet54_dec_create (SONDE_E_ARG as it returns it); opts->inv = -i, opts->aut = --auto, json implies ecc; invert_stream = --softinv.
+ * sonde_softin_dev_create with SONDE_IMET54 is SONDE_E_ARG (the kind needs its options); the other kinds' fetch calls refuse an iMet-54 consumer and fetch_imet54
+ * refuses the other kinds.  One launch per push call: submit_fsk / collect keep the overlap with the modem's next second.
+ * A push call holds at most 4 * n_channels + 16 frames over all channels (a channel completes at most one per 2240 symbols); frames beyond that are decoded, not
+ * delivered, and counted as dropped. */
+int  sonde_softin_dev_create_imet54(int32_t n_channels, const sonde_imet54_opts_t *opts, int32_t invert_stream, sonde_softin_dev_t **out);
+/* The text of a frame under any options.  The -r4 line: 108 x "XX " and a blank per four bytes 351, the tag 5, " # (-1) [-1]" with counts of three digits at most
+ * 16, the newline: below 380.  The position line (with -r only beside --json, where --silent suppresses it; counted all the same): serial 15, time 17, lat / lon /
+ * alt 49 (printed only inside their ranges, get_GPS), four PTU fields inside theirs 50, tag 5, status 10, ecc 16: below 170.  The JSON object: 250 of fixed text and
+ * bounded fields, freq 11, version 31: below 300.  1024 leaves room for all three. */
+#define SONDE_IMET54_TEXT_MAX 1024
+typedef struct {
+    int32_t  channel;
+    int32_t  ecc_frm, ecc_tlm, ecc_std;   /* print_frame's sums over the first 104 codewords (ecc_tlm: 88): repaired codewords, -1 behind an uncorrectable one */
+    int32_t  crc;            /* 0 neither check sum good, 1 the standard frame's (crc32ok), 2 the continuous frame's (crc32ok_cont)      */
+    float    mv;             /* score of the header in front of the frame                                                         */
+    uint64_t hdr_bit;        /* symbols read when the header matched                                                             */
+    int32_t  text_len;       /* SONDE_E_ARG (negative) if the text did not fit: text is "" then                                   */
+    uint8_t  frame[SONDE_IMET54_FRAME_LEN];   /* the frame behind Hamming(8,4)                                                   */
+    char     text[SONDE_IMET54_TEXT_MAX];     /* what the reference prints for this frame, NUL-terminated                        */
+} sonde_imet54_softin_t;
+/* frames completed by the push calls since the last fetch (per channel in stream order); returns the count (<= max) */
+int  sonde_softin_dev_fetch_imet54(sonde_softin_dev_t *s, sonde_imet54_softin_t *out, int32_t max);
+
+/* tallies since creation: frames completed (SONDE_LMS6: blocks; accepted = the frames with a good CRC-16 that ended in them, the decoders' own count), frames accepted (RS41: rs41_ecc() >= 0; DFM: no block uncorrectable; M10 / M20: checksum good; RD94RD41: every block of the type print_frame chooses good; RS92: rs_decode >= 0; iMet-54: ecc_frm >= 0 and a check sum good, or ecc_std == 0 — the JSON rule without the status bits), frames repaired (RS92: rs_decode > 0; iMet-54: ecc_frm > 0), symbols / codewords repaired (RS92: the sum of the positive rs_decode values; iMet-54: of the positive ecc_frm), frames lost to a full buffer */
 int  sonde_softin_dev_counts(sonde_softin_dev_t *s, int64_t *frames, int64_t *ecc_ok, int64_t *repaired, int64_t *symbols, int64_t *dropped);
 
 #ifdef __cplusplus

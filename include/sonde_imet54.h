@@ -25,6 +25,7 @@ extern "C" {
 #endif
 
 #define SONDE_IMET54_FRAME_BITS 2200     /* 220 8N1 characters, imet54mod.c:59-62 */
+#define SONDE_IMET54_FRAME_LEN  108      /* frame bytes behind de8n1, deinter64 and Hamming(8,4): 216 nibbles */
 
 typedef struct sonde_imet54_dec sonde_imet54_dec_t;
 
@@ -51,6 +52,11 @@ int  sonde_imet54_dec_frame(sonde_imet54_dec_t *d, const float *soft, int32_t n,
 int  sonde_imet54_dec_rawhex(sonde_imet54_dec_t *d, const char *line, char *out, size_t outlen);
 /* Soft-bit input (`imet54mod --softin`, decode.py:1250): header search, polarity and frame assembly inside; finish != 0 at end of input. */
 int  sonde_imet54_dec_push_soft(sonde_imet54_dec_t *d, const float *soft, int32_t n, int32_t invert, int32_t finish, char *out, size_t outlen);
+/* A complete frame that is decoded already (the device consumer, include/sonde_fsk.h): the 108 frame bytes behind Hamming(8,4), the three ecc sums of print_frame
+ * (:651-659) and the verdicts of crc32ok / crc32ok_cont.  Prints what print_frame prints behind its b2B branch — the -r / -r4 line with its tag [OK] / [ok] /
+ * [oo] / [NO] / [no] and `# (n) [m]`, print_position, JSON — from the values given: neither check sum is computed again. */
+int  sonde_imet54_dec_decoded(sonde_imet54_dec_t *d, const uint8_t *frame108, int32_t ecc_frm, int32_t ecc_tlm, int32_t ecc_std, int32_t crc_std, int32_t crc_cont,
+                              char *out, size_t outlen);
 
 #ifdef __cplusplus
 }

@@ -106,6 +106,10 @@ struct sonde_imet54_dec {
     uint8_t nib[FRAME_LEN] = { 0 }, ec[FRAME_LEN] = { 0 };
     int inv = 0;
     float sbuf[40]; int bufpos = -1, in_frame = 0, pos = 0;
+    // sonde_imet54_dec_decoded: the verdicts of both check sums as the caller found them (-1: computed here from the frame bytes)
+    int given_std = -1, given_cont = -1;
+    int chk_std(int len) const { return given_std >= 0 ? given_std : crc32ok(frame, len); }
+    int chk_cont() const { return given_cont >= 0 ? given_cont : crc32ok_cont(frame); }
 
     int get_GPS() {
         int val = (int)u4be(frame + P_TIME);
@@ -148,7 +152,7 @@ struct sonde_imet54_dec {
     }
     void crc_tag(Out &w, int &crc_ok, int ecc_std, int *std_ok) {
         if (crc_ok) { w.f(" [OK]"); return; }
-        crc_ok = crc32ok_cont(frame);
+        crc_ok = chk_cont();
         if (crc_ok) w.f(" [ok]");
         else if (ecc_std == 0) { w.f(" [oo]"); if (std_ok) *std_ok = 1; }
         else if (frame[P_F8] == 0xF8) w.f(" [NO]");
@@ -157,7 +161,7 @@ struct sonde_imet54_dec {
 
     void print_position(Out &w, int len, int ecc_frm, int ecc_tlm, int ecc_std) {
         int prnGPS = 0, prnPTU = 0, prnSTS = 0, ptu1e9 = 0, std_ok = 0, rs_type = 54;
-        int crc_ok = crc32ok(frame, len);
+        int crc_ok = chk_std(len);
         int frm_ok = (ecc_frm >= 0 && len > P_F8);
         SNu32 = 0; timems = 0; std_ = 0; min_ = 0; sek = 0.0f; lat = lon = alt = 0.0; T = -273.15f; Trh = -273.15f; _RH = -1.0f; RH = -1.0f; status = 0;
         if (len > P_ALT + 4) {
@@ -236,8 +240,12 @@ struct sonde_imet54_dec {
             }
             if (j < 2 * P_CRC32CONT) ecc_std = -1;
         } else ecc_frm = -2;
+        print_decoded(w, len, ecc_frm, ecc_tlm, ecc_std);
+    }
+    // what print_frame prints (:662-707) once frame[] and the ecc sums stand; len = bits of the frame (16 a byte)
+    void print_decoded(Out &w, int len, int ecc_frm, int ecc_tlm, int ecc_std) {
         if (o.raw) {
-            int crc_ok = crc32ok(frame, len / 16);
+            int crc_ok = chk_std(len / 16);
             for (int i = 0; i < len / 16; i++) {
                 w.f("%02X", frame[i]);
                 if (o.raw > 1) { w.f(" "); if (o.raw == 4 && i % 4 == 3) w.f(" "); }
@@ -278,6 +286,17 @@ int sonde_imet54_dec_frame(sonde_imet54_dec_t *d, const float *soft, int32_t n, 
     Out w;
     for (int j = 0; j < n; j++) d->frame_bits[j] = (uint8_t)(soft[j] >= 0.0f);
     d->print_frame(w, n, 1);
+    return finish_out(w, out, outlen);
+}
+
+int sonde_imet54_dec_decoded(sonde_imet54_dec_t *d, const uint8_t *frame108, int32_t ecc_frm, int32_t ecc_tlm, int32_t ecc_std, int32_t crc_std, int32_t crc_cont,
+                             char *out, size_t outlen) {
+    if (!d || !frame108 || !out) return SONDE_E_ARG;
+    Out w;
+    memcpy(d->frame, frame108, 108);
+    d->given_std = crc_std != 0; d->given_cont = crc_cont != 0;
+    d->print_decoded(w, 108 * 16, ecc_frm, ecc_tlm, ecc_std);
+    d->given_std = d->given_cont = -1;
     return finish_out(w, out, outlen);
 }
 

@@ -21,8 +21,10 @@
 #include "sonde_vit_dev.h"
 #include "sonde_softin_mxx_dev.h"
 #include "sonde_softin_rs92_dev.h"
+#include "sonde_softin_imet54_dev.h"
 #include "../../include/sonde_drop.h"
 #include "../../include/sonde_rs92.h"
+#include "../../include/sonde_imet54.h"
 #include <cstdio>
 #include <cstring>
 #include <vector>
@@ -540,6 +542,30 @@ void k_softin_rs92(const SoftinRs92Args A) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// iMet-54: imet54mod --softin [-i] [--auto] [--ecc] (imet54mod.c:1007-1063, :107-133, :162-303, :350-360, :618-660) — the 40 header symbols at 0.8 with the ring left
+// as it is, 220 8N1 characters on a lane per character, then de-interleave + Hamming(8,4) on a lane per codeword, the ecc sums by ballot and both check sums as XOR
+// sums of per-bit contribution words on the same wave: sonde_softin_imet54_dev.h, which the CPU wave emulator compiles as well.  The call's soft decisions are
+// staged in LDS as for M10 / M20 / RS92 (a second at 4800 symbols: 19.2 KB + 0.75 KB of state).  A record per completed frame; the fields and the text are the
+// host's (sonde_imet54_dec_decoded).
+// ------------------------------------------------------------------------------------------------
+struct SoftinImet54Args { SoftinArgs base; SoftinImet54Chan *chan; SoftinImet54Rec *out; const uint32_t *tab; int stage_cap, ecc; };
+
+__global__ __launch_bounds__(64)
+void k_softin_imet54(const SoftinImet54Args A) {
+    const SoftinArgs &a = A.base;
+    extern __shared__ float s_x[];                     // [stage_cap] sgn * x of this call (staged: nb <= stage_cap)
+    __shared__ SoftinImet54Lds s_l;
+    const int ch = a.ch_list ? a.ch_list[blockIdx.x] : (int)blockIdx.x, lane = threadIdx.x;
+    if (ch >= a.n_ch || ch < 0) return;
+    int nb = a.nbits;
+    if (a.fsk_chan) { const int fr = a.fsk_chan[ch].frames; nb = fr > 0 ? fr * a.bits_per_frame : 0; }
+    else if (a.nbits_ch) nb = a.nbits_ch[ch];
+    nb = __builtin_amdgcn_readfirstlane(nb);
+    if ((long long)nb > a.ch_stride) return;                                     // (never: a channel's count lies within its stride)
+    imet54_wave_channel(A.chan + ch, a.sd + (size_t)ch * a.ch_stride, nb, a.inv_in ? -1.f : 1.f, a.opt_auto, A.ecc, a.ths, A.tab, &s_l, s_x, A.stage_cap, A.out, a.count, a.cap, ch, lane);
+}
+
+// ------------------------------------------------------------------------------------------------
 // RD94 / RD41 dropsondes: rd94rd41drop --softin / --softinv [-i] (rd94rd41drop.c:1357-1386) — no correlation: the sign of every soft bit (s >= 0 after the two
 // inversions, which cancel each other) goes into the 40-bit ring, a frame is the 2360 raw bits behind a ring that equals FC 1D as Manchester-coded 8N1, and the
 // bits of a frame enter the ring too.  64 soft bits a pass: signs by ballot, every lane tests the ring as it stands behind its bit (values and "holds a bit"
@@ -775,6 +801,9 @@ struct sonde_softin_dev {
     int l6_vit = 0, l6_auto = 0; int *d_l6_list = nullptr; Pinned<int> h_l6_list, h_l6_len; std::vector<int> l6_len; std::vector<int64_t> l6_ok;
     // SONDE_RS92: a host decoder per channel (the calibration rows a channel collects are per sonde); the text of a record is made when it is fetched
     SoftinRs92Chan *d_r92_chan = nullptr; SoftinRs92Rec *d_r92_out = nullptr; Pinned<SoftinRs92Rec> h_r92; std::vector<SoftinRs92Rec> qr92; std::vector<sonde_rs92_dec_t *> r92_dec; int r92_inv = 0;
+    // SONDE_IMET54: a host decoder per channel (print_position keeps its fields in the object); the text of a record is made when it is fetched
+    SoftinImet54Chan *d_i54_chan = nullptr; SoftinImet54Rec *d_i54_out = nullptr; uint32_t *d_i54_tab = nullptr; Pinned<SoftinImet54Rec> h_i54; std::vector<SoftinImet54Rec> qi54;
+    std::vector<sonde_imet54_dec_t *> i54_dec; int i54_ecc = 0;
     SoftinArgs args{};
     hipStream_t stream = nullptr; bool own_stream = false;
     SoftinChan *d_chan = nullptr; unsigned char *d_frames = nullptr, *d_hdr = nullptr, *d_gf = nullptr, *d_synd = nullptr;
@@ -936,6 +965,43 @@ int sonde_softin_dev_create_rs92(int32_t n_channels, const sonde_rs92_opts_t *op
     return 0;
 }
 
+int sonde_softin_dev_create_imet54(int32_t n_channels, const sonde_imet54_opts_t *opts, int32_t invert_stream, sonde_softin_dev_t **out) {
+    if (!out || n_channels < 1 || !opts) return SONDE_E_ARG;
+    {   sonde_imet54_dec_t *probe = nullptr;                                                   // the option checks of the host decoder, before the device is touched
+        const int rc = sonde_imet54_dec_create(opts, &probe);
+        if (rc) return rc;
+        sonde_imet54_dec_destroy(probe);
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { fprintf(stderr, "libsonde_hip: no usable HIP device (the batched soft-bit framer has no CPU fallback)\n"); return SONDE_E_NOGPU; }
+    sonde_softin_dev *s = new sonde_softin_dev();
+    s->C = n_channels; s->type = SONDE_IMET54; s->i54_ecc = (opts->ecc || opts->json) ? 1 : 0;     // --json implies --ecc (imet54mod.c:899)
+    s->cap = 4 * n_channels + 16;                              // frames a call can hold over all channels (sonde_fsk.h): a channel completes one per 2240 symbols at the most
+    const size_t C = (size_t)n_channels, cap = (size_t)s->cap;
+    for (size_t c = 0; c < C; c++) {
+        sonde_imet54_dec_t *d = nullptr;
+        if (sonde_imet54_dec_create(opts, &d)) { sonde_softin_dev_destroy(s); return SONDE_E_NOMEM; }
+        s->i54_dec.push_back(d);
+    }
+    std::vector<SoftinImet54Chan> init(C);
+    memset((void *)init.data(), 0, C * sizeof(SoftinImet54Chan));
+    for (auto &c : init) c.inv = opts->inv ? 1 : 0;
+    std::vector<uint32_t> tab(IMET54_TAB_N);
+    imet54_crc_table(tab.data());
+    bool ok = hipMalloc((void **)&s->d_i54_chan, C * sizeof(SoftinImet54Chan)) == hipSuccess && hipMalloc((void **)&s->d_i54_out, cap * sizeof(SoftinImet54Rec)) == hipSuccess
+           && hipMalloc((void **)&s->d_i54_tab, IMET54_TAB_N * sizeof(uint32_t)) == hipSuccess && hipMalloc((void **)&s->d_count, 8) == hipSuccess
+           && hipHostMalloc((void **)&s->h_count, 8) == hipSuccess && s->h_i54.alloc(cap);
+    ok = ok && hipMemcpy(s->d_i54_chan, init.data(), C * sizeof(SoftinImet54Chan), hipMemcpyHostToDevice) == hipSuccess
+            && hipMemcpy(s->d_i54_tab, tab.data(), IMET54_TAB_N * sizeof(uint32_t), hipMemcpyHostToDevice) == hipSuccess;
+    if (!ok) { sonde_softin_dev_destroy(s); return SONDE_E_NOMEM; }
+    SoftinArgs &a = s->args;
+    a.n_ch = n_channels; a.inv_in = invert_stream ? 1 : 0; a.opt_auto = opts->aut ? 1 : 0; a.ths = 0.8f; a.count = s->d_count; a.cap = s->cap;
+    s->head = std::min(s->cap, n_channels + 16);               // (a frame a second and channel)
+    (void)hipGetLastError();
+    *out = s;
+    return 0;
+}
+
 int sonde_softin_dev_rs92_load_ephemeris(sonde_softin_dev_t *s, const char *path) {
     if (!s || s->type != SONDE_RS92 || !path) return SONDE_E_ARG;
     for (sonde_rs92_dec_t *d : s->r92_dec) { const int rc = sonde_rs92_dec_load_ephemeris(d, path); if (rc) return rc; }
@@ -955,10 +1021,11 @@ void sonde_softin_dev_destroy(sonde_softin_dev_t *s) {
     if (s->h_nbits) hipHostFree(s->h_nbits);
     if (s->d_nbits) hipFree(s->d_nbits);
     (void)hipGetLastError();
-    void *p[] = { s->d_chan, s->d_frames, s->d_hdr, s->d_gf, s->d_synd, s->d_flen, s->d_ecc, s->d_codes, s->d_meta, s->d_count, s->d_dfm_chan, s->d_dfm_out, s->d_m10_chan, s->d_m10_out, s->d_m20_chan, s->d_m20_out, s->d_drop_chan, s->d_drop_out, s->d_l6_chan, s->d_l6_out, s->d_l6_list, s->d_r92_chan, s->d_r92_out };
+    void *p[] = { s->d_chan, s->d_frames, s->d_hdr, s->d_gf, s->d_synd, s->d_flen, s->d_ecc, s->d_codes, s->d_meta, s->d_count, s->d_dfm_chan, s->d_dfm_out, s->d_m10_chan, s->d_m10_out, s->d_m20_chan, s->d_m20_out, s->d_drop_chan, s->d_drop_out, s->d_l6_chan, s->d_l6_out, s->d_l6_list, s->d_r92_chan, s->d_r92_out, s->d_i54_chan, s->d_i54_out, s->d_i54_tab };
     for (void *q : p) if (q) hipFree(q);
     for (sonde_lms6_dec_t *d : s->l6_dec) sonde_lms6_dec_destroy(d);
     for (sonde_rs92_dec_t *d : s->r92_dec) sonde_rs92_dec_destroy(d);
+    for (sonde_imet54_dec_t *d : s->i54_dec) sonde_imet54_dec_destroy(d);
     delete s;
 }
 
@@ -967,7 +1034,7 @@ void sonde_softin_dev_destroy(sonde_softin_dev_t *s) {
 static int softin_finish_lms6(sonde_softin_dev *s, hipStream_t st, long long n);
 static int softin_pass(sonde_softin_dev *s, hipStream_t st, const int off, const int nblocks, const int *ch_list, const int which) {
     SoftinArgs a = s->args;
-    if (s->type != SONDE_LMS6 && s->type != SONDE_RS92) { a.frames += (size_t)off * 518; a.flen += off; a.meta += off; }
+    if (s->type != SONDE_LMS6 && s->type != SONDE_RS92 && s->type != SONDE_IMET54) { a.frames += (size_t)off * 518; a.flen += off; a.meta += off; }
     a.cap = s->cap - off; a.count = s->d_count + which; a.ch_list = ch_list;
     HIPCHK(hipMemsetAsync(a.count, 0, 4, st));
     if (s->type == SONDE_DFM09) { SoftinDfmArgs d{a, s->d_dfm_chan, s->d_dfm_out + off, s->ecc_level}; hipLaunchKernelGGL(k_softin_dfm, dim3(nblocks), dim3(64), 0, st, d); }
@@ -1001,6 +1068,16 @@ static int softin_pass(sonde_softin_dev *s, hipStream_t st, const int off, const
         if (lds > attr) { if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_softin_rs92), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess) attr = lds; else m.stage_cap = 0; }
         hipLaunchKernelGGL(k_softin_rs92, dim3(nblocks), dim3(64), m.stage_cap ? lds : 0, st, m);
     }
+    else if (s->type == SONDE_IMET54) {
+        // (LDS for the call's soft decisions as for M10)
+        long long need = a.fsk_chan || a.nbits_ch ? a.ch_stride : a.nbits;
+        if (need > M10_STAGE_MAX || need < 0) need = 0;
+        SoftinImet54Args m{a, s->d_i54_chan, s->d_i54_out + off, s->d_i54_tab, (int)need, s->i54_ecc};
+        static size_t attr = 0;
+        const size_t lds = (size_t)need * sizeof(float);
+        if (lds > attr) { if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_softin_imet54), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess) attr = lds; else m.stage_cap = 0; }
+        hipLaunchKernelGGL(k_softin_imet54, dim3(nblocks), dim3(64), m.stage_cap ? lds : 0, st, m);
+    }
     else if (s->type == SONDE_RD94RD41) { SoftinDropArgs d{a, s->d_drop_chan, s->d_drop_out + off, s->drop_inv}; hipLaunchKernelGGL(k_softin_drop, dim3(nblocks), dim3(64), 0, st, d); }
     else if (s->type == SONDE_LMS6) { SoftinLms6Args d{a, s->d_l6_chan, s->d_l6_out + off, s->l6_vit, s->l6_auto}; hipLaunchKernelGGL(k_softin_lms6, dim3(nblocks), dim3(64), 0, st, d); }
     else {
@@ -1021,6 +1098,7 @@ static int softin_copy(sonde_softin_dev *s, hipStream_t st, const int from, cons
     else if (s->type == SONDE_M20) HIPCHK(hipMemcpyAsync(s->h_m20.data() + from, s->d_m20_out + from, n * sizeof(sonde_m20_frame_t), hipMemcpyDeviceToHost, st));
     else if (s->type == SONDE_RD94RD41) HIPCHK(hipMemcpyAsync(s->h_drop.data() + from, s->d_drop_out + from, n * sizeof(DropFrame), hipMemcpyDeviceToHost, st));
     else if (s->type == SONDE_RS92) HIPCHK(hipMemcpyAsync(s->h_r92.data() + from, s->d_r92_out + from, n * sizeof(SoftinRs92Rec), hipMemcpyDeviceToHost, st));
+    else if (s->type == SONDE_IMET54) HIPCHK(hipMemcpyAsync(s->h_i54.data() + from, s->d_i54_out + from, n * sizeof(SoftinImet54Rec), hipMemcpyDeviceToHost, st));
     else if (s->type == SONDE_LMS6) HIPCHK(hipMemcpyAsync(s->h_l6.data() + from, s->d_l6_out + from, n * sizeof(Lms6Block), hipMemcpyDeviceToHost, st));
     else {
         HIPCHK(hipMemcpyAsync(s->h_meta.data() + from, s->d_meta + from, n * sizeof(SoftinMeta), hipMemcpyDeviceToHost, st));
@@ -1092,6 +1170,17 @@ static int softin_finish(sonde_softin_dev *s) {
             s->qr92.push_back(r); s->frames_total++;
             if (r.ec >= 0) s->ecc_ok_total++;
             if (r.ec > 0) { s->repaired_total++; s->symbols_total += r.ec; }
+        }
+        return 0;
+    }
+    if (s->type == SONDE_IMET54) {
+        for (long long i = 0; i < n; i++) {
+            const SoftinImet54Rec &r = s->h_i54[i];
+            if (r.channel < 0 || r.channel >= s->C) continue;
+            s->qi54.push_back(r); s->frames_total++;
+            // the JSON rule without the status bits (imet54mod.c:583): frm_ok and a check sum good, or every codeword of the standard frame clean
+            if (r.ecc_frm >= 0 && (r.crc_std || r.crc_cont || r.ecc_std == 0)) s->ecc_ok_total++;
+            if (r.ecc_frm > 0) { s->repaired_total++; s->symbols_total += r.ecc_frm; }
         }
         return 0;
     }
@@ -1221,7 +1310,7 @@ int sonde_softin_dev_push_device(sonde_softin_dev_t *s, const float *d_soft, int
 }
 
 int sonde_softin_dev_fetch(sonde_softin_dev_t *s, sonde_frame_t *out, int32_t max) {
-    if (s && s->type == SONDE_RS92) return SONDE_E_ARG;
+    if (s && (s->type == SONDE_RS92 || s->type == SONDE_IMET54)) return SONDE_E_ARG;
     if (s && s->pending) { const int rc_ = softin_finish(s); if (rc_) return rc_; }
     if (!s || (!out && max > 0)) return SONDE_E_ARG;
     const int n = (int)std::min<size_t>(s->queue.size(), (size_t)(max < 0 ? 0 : max));
@@ -1231,7 +1320,7 @@ int sonde_softin_dev_fetch(sonde_softin_dev_t *s, sonde_frame_t *out, int32_t ma
 }
 
 int sonde_softin_dev_fetch_dfm(sonde_softin_dev_t *s, sonde_dfm_frame_t *out, int32_t max) {
-    if (s && s->type == SONDE_RS92) return SONDE_E_ARG;
+    if (s && (s->type == SONDE_RS92 || s->type == SONDE_IMET54)) return SONDE_E_ARG;
     if (s && s->pending) { const int rc_ = softin_finish(s); if (rc_) return rc_; }
     if (!s || (!out && max > 0)) return SONDE_E_ARG;
     const int n = (int)std::min<size_t>(s->qdfm.size(), (size_t)(max < 0 ? 0 : max));
@@ -1241,7 +1330,7 @@ int sonde_softin_dev_fetch_dfm(sonde_softin_dev_t *s, sonde_dfm_frame_t *out, in
 }
 
 int sonde_softin_dev_fetch_m10(sonde_softin_dev_t *s, sonde_m10_frame_t *out, int32_t max) {
-    if (s && s->type == SONDE_RS92) return SONDE_E_ARG;
+    if (s && (s->type == SONDE_RS92 || s->type == SONDE_IMET54)) return SONDE_E_ARG;
     if (s && s->pending) { const int rc_ = softin_finish(s); if (rc_) return rc_; }
     if (!s || (!out && max > 0)) return SONDE_E_ARG;
     const int n = (int)std::min<size_t>(s->qm10.size(), (size_t)(max < 0 ? 0 : max));
@@ -1266,7 +1355,7 @@ int sonde_softin_dev_fetch_m20(sonde_softin_dev_t *s, sonde_m20_frame_t *out, in
 }
 
 int sonde_softin_dev_fetch_drop(sonde_softin_dev_t *s, sonde_drop_frame_t *out, int32_t max) {
-    if (s && s->type == SONDE_RS92) return SONDE_E_ARG;
+    if (s && (s->type == SONDE_RS92 || s->type == SONDE_IMET54)) return SONDE_E_ARG;
     if (s && s->pending) { const int rc_ = softin_finish(s); if (rc_) return rc_; }
     if (!s || (!out && max > 0)) return SONDE_E_ARG;
     const int n = (int)std::min<size_t>(s->qdrop.size(), (size_t)(max < 0 ? 0 : max));
@@ -1276,7 +1365,7 @@ int sonde_softin_dev_fetch_drop(sonde_softin_dev_t *s, sonde_drop_frame_t *out, 
 }
 
 int sonde_softin_dev_fetch_lms6(sonde_softin_dev_t *s, sonde_lms6_softin_t *out, int32_t max) {
-    if (s && s->type == SONDE_RS92) return SONDE_E_ARG;
+    if (s && (s->type == SONDE_RS92 || s->type == SONDE_IMET54)) return SONDE_E_ARG;
     if (s && s->pending) { const int rc_ = softin_finish(s); if (rc_) return rc_; }
     if (!s || (!out && max > 0)) return SONDE_E_ARG;
     const int n = (int)std::min<size_t>(s->ql6.size(), (size_t)(max < 0 ? 0 : max));
@@ -1300,6 +1389,24 @@ int sonde_softin_dev_fetch_rs92(sonde_softin_dev_t *s, sonde_rs92_softin_t *out,
         if (len < 0) o.text[0] = 0;
     }
     s->qr92.erase(s->qr92.begin(), s->qr92.begin() + n);
+    return n;
+}
+
+int sonde_softin_dev_fetch_imet54(sonde_softin_dev_t *s, sonde_imet54_softin_t *out, int32_t max) {
+    if (!s || s->type != SONDE_IMET54 || (!out && max > 0)) return SONDE_E_ARG;
+    if (s->pending) { const int rc_ = softin_finish(s); if (rc_) return rc_; }
+    const int n = (int)std::min<size_t>(s->qi54.size(), (size_t)(max < 0 ? 0 : max));
+    for (int i = 0; i < n; i++) {
+        // print_frame behind the Hamming step, by the channel's own decoder and from the device's verdicts: here, not in the push call, so that collect stays short
+        const SoftinImet54Rec &r = s->qi54[i];
+        sonde_imet54_softin_t &o = out[i];
+        o.channel = r.channel; o.ecc_frm = r.ecc_frm; o.ecc_tlm = r.ecc_tlm; o.ecc_std = r.ecc_std; o.crc = r.crc_std ? 1 : r.crc_cont ? 2 : 0; o.mv = r.mv; o.hdr_bit = r.hdr_bit;
+        memcpy(o.frame, r.frame, sizeof o.frame);
+        const int len = sonde_imet54_dec_decoded(s->i54_dec[(size_t)r.channel], r.frame, r.ecc_frm, r.ecc_tlm, r.ecc_std, r.crc_std, r.crc_cont, o.text, sizeof o.text);
+        o.text_len = len;                                      // (negative: the text did not fit; the frame is delivered all the same)
+        if (len < 0) o.text[0] = 0;
+    }
+    s->qi54.erase(s->qi54.begin(), s->qi54.begin() + n);
     return n;
 }
 

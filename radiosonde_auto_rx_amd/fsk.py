@@ -57,6 +57,18 @@ class Rs92SoftinRec(C.Structure):
 # auto_rx's `rs92mod -vx -v --crc --ecc --vel --json --softin -i` (auto_rx/autorx/decode.py:976-987; --json makes --ecc an --ecc2)
 RS92_DEFAULTS = dict(verbose=1, aux=1, ecc=2, gps_vel=4, json=1, inv=1, gpsepoch=-1)
 
+IMET54_TEXT_MAX = 1024
+
+
+class Imet54SoftinRec(C.Structure):
+    """sonde_imet54_softin_t (include/sonde_fsk.h)"""
+    _fields_ = [("channel", C.c_int32), ("ecc_frm", C.c_int32), ("ecc_tlm", C.c_int32), ("ecc_std", C.c_int32), ("crc", C.c_int32), ("mv", C.c_float),
+                ("hdr_bit", C.c_uint64), ("text_len", C.c_int32), ("frame", C.c_uint8 * 108), ("text", C.c_char * IMET54_TEXT_MAX)]
+
+
+# auto_rx's `imet54mod --ecc --json --softin -i --ptu` (auto_rx/autorx/decode.py:1215-1250)
+IMET54_DEFAULTS = dict(ecc=1, json=1, ptu=1, inv=1)
+
 _proto = False
 
 
@@ -99,6 +111,9 @@ def _lib():
         L.sonde_softin_dev_rs92_load_ephemeris.argtypes = [C.c_void_p, C.c_char_p]
         L.sonde_softin_dev_rs92_load_almanac.argtypes = [C.c_void_p, C.c_char_p]
         L.sonde_softin_dev_fetch_rs92.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+        from .family import Imet54Opts
+        L.sonde_softin_dev_create_imet54.argtypes = [C.c_int32, C.POINTER(Imet54Opts), C.c_int32, C.POINTER(C.c_void_p)]
+        L.sonde_softin_dev_fetch_imet54.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
         _proto = True
     return L
 
@@ -207,13 +222,15 @@ class SoftinDev:
 
     def __init__(self, n_channels: int, *, ecc: int = 2, softinv: bool = False, inv: bool = True, auto: bool = False, kind: str = "rs41",
                  vit: int = 2, typ: int = 0, json: bool = False, raw: bool = False, gpsweek: int = 0, freq_khz: int = 0, version: str = "", skip: bool = True,
-                 rs92_opts: dict | None = None, ephemeris: str | None = None, almanac: str | None = None):
+                 rs92_opts: dict | None = None, ephemeris: str | None = None, almanac: str | None = None, imet54_opts: dict | None = None):
         """kind: "rs41" (rs41mod --softin), "dfm" (dfm09mod --softin: ecc 0 / 1 = --ecc / 2 = --ecc2), "m10" (m10mod --softin), "m20" (m20mod --softin: skip = the rest of
         the second behind a frame is dropped, as m20mod does below -vvv; auto_rx runs `m20mod --json --ptu -vvv --softin -i`: skip=False; ecc, inv and auto mean nothing to it), "drop" (rd94rd41drop --softin /
         --softinv [-i]: auto_rx runs it as softinv=True, inv=False; ecc and auto are ignored) or "lms6" (lms6Xmod --softin: vit 1 = --vit / 2 = --vit2, typ 0 = auto
         detection / 6 = --lms6 / 10 = --lmsX, ecc != 0 = --ecc, json, raw = -r, gpsweek, freq_khz and version as sonde_lms6_opts_t; inv (-i) means nothing to it) or
         "rs92" (rs92mod --softin: rs92_opts = fields of family.Rs92Opts over auto_rx's defaults verbose 1, aux 1, ecc 2, gps_vel 4, json 1, inv 1 — inv there is -i;
-        ephemeris = a RINEX navigation file (-e), almanac = an SEM almanac (-a) for every channel's decoder; ecc, inv and auto of this call mean nothing to it)"""
+        ephemeris = a RINEX navigation file (-e), almanac = an SEM almanac (-a) for every channel's decoder; ecc, inv and auto of this call mean nothing to it) or
+        "imet54" (imet54mod --softin: imet54_opts = fields of family.Imet54Opts over auto_rx's defaults ecc 1, json 1, ptu 1, inv 1 — inv there is -i, aut is --auto, json
+        implies ecc; ecc, inv and auto of this call mean nothing to it)"""
         from .engine import SONDE_RS41, SONDE_DFM09, SONDE_M10, SONDE_M20, SONDE_RD94RD41
         h = C.c_void_p()
         self.kind, self.ecc = kind, ecc
@@ -230,6 +247,16 @@ class SoftinDev:
                 self.load_rs92_ephemeris(ephemeris)
             if almanac:
                 self.load_rs92_almanac(almanac)
+            return
+        if kind == "imet54":
+            from .family import Imet54Opts
+            kw = dict(IMET54_DEFAULTS)
+            kw.update(imet54_opts or {})
+            if isinstance(kw.get("version"), str):
+                kw["version"] = kw["version"].encode()
+            o = Imet54Opts(**kw)
+            _chk(_lib().sonde_softin_dev_create_imet54(n_channels, C.byref(o), int(softinv), C.byref(h)))
+            self._h, self.n_channels = h, n_channels
             return
         if kind == "lms6":
             o = Lms6Opts(raw=int(raw), ecc=1 if ecc else 0, vit=vit, json=int(json), typ=typ, gpsweek=gpsweek, jsn_freq_khz=freq_khz, version=version.encode())
@@ -359,6 +386,15 @@ class SoftinDev:
         buf = (Rs92SoftinRec * max_frames)()
         n = _chk(_lib().sonde_softin_dev_fetch_rs92(self._h, buf, max_frames))
         return [dict(channel=r.channel, ec=r.ec, mv=r.mv, hdr_bit=r.hdr_bit, frame=bytes(r.frame), text=r.text[:max(r.text_len, 0)].decode()) for r in buf[:n]]
+
+    def fetch_imet54(self, max_frames: int = 1024):
+        """iMet-54 consumers: a dict per completed frame — channel, ecc_frm / ecc_tlm / ecc_std (print_frame's sums: repaired codewords, -1 behind an uncorrectable
+        one), crc (0 neither check sum, 1 the standard frame's, 2 the continuous frame's), mv, hdr_bit (symbols read when the header matched), frame = the 108 bytes
+        behind Hamming(8,4), text = what `imet54mod` prints for it from the device's verdicts"""
+        buf = (Imet54SoftinRec * max_frames)()
+        n = _chk(_lib().sonde_softin_dev_fetch_imet54(self._h, buf, max_frames))
+        return [dict(channel=r.channel, ecc_frm=r.ecc_frm, ecc_tlm=r.ecc_tlm, ecc_std=r.ecc_std, crc=r.crc, mv=r.mv, hdr_bit=r.hdr_bit, frame=bytes(r.frame),
+                     text=r.text[:max(r.text_len, 0)].decode()) for r in buf[:n]]
 
     def counts(self):
         v = [C.c_int64(0) for _ in range(5)]
