@@ -16,6 +16,7 @@
 #include "sonde_lms6.h"
 #include "sonde_rs92.h"
 #include "sonde_imet54.h"
+#include "sonde_meisei.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -243,7 +244,40 @@ typedef struct {
 /* frames completed by the push calls since the last fetch (per channel in stream order); returns the count (<= max) */
 int  sonde_softin_dev_fetch_imet54(sonde_softin_dev_t *s, sonde_imet54_softin_t *out, int32_t max);
 
-/* tallies since creation: frames completed (SONDE_LMS6: blocks; accepted = the frames with a good CRC-16 that ended in them, the decoders' own count), frames accepted (RS41: rs41_ecc() >= 0; DFM: no block uncorrectable; M10 / M20: checksum good; RD94RD41: every block of the type print_frame chooses good; RS92: rs_decode >= 0; iMet-54: ecc_frm >= 0 and a check sum good, or ecc_std == 0 — the JSON rule without the status bits), frames repaired (RS92: rs_decode > 0; iMet-54: ecc_frm > 0), symbols / codewords repaired (RS92: the sum of the positive rs_decode values; iMet-54: of the positive ecc_frm), frames lost to a full buffer */
+/* ---- SONDE_MEISEI consumers: `meisei100mod --softin [--ecc] ...` for every channel (auto_rx's pipe `fsk_demod --cs16 -s -b -15000 -u 15000 --stats=N 2 48000 2400 - - |
+ * meisei100mod --softin --json --ptu --ecc`, auto_rx/autorx/decode.py:1343-1379).  On the device, one wavefront per channel (meisei100mod.c:654-776, :213-229;
+ * bch_ecc_mod.c:968-1043): the 48 header half symbols at 0.8 in either polarity (a score of exactly 0.8f and the NaN of an all-zero window are no hits; there is no
+ * polarity rule and no -i, biphase-S compares neighbours; the ring is left as it is on a hit and frame symbols never enter it), 576 biphase-S bits behind the 24
+ * known header bits, and with --ecc the 12 BCH(63,51) blocks with the padding and word-parity rules, corrected bits written back only where the block is accepted.
+ * Per completed frame 104 bytes come to the host, where the consumer's own sonde_meisei_dec_t of that channel (the variant in effect, the 64-word configuration, the
+ * counters) prints from the device's bits and verdicts (sonde_meisei_dec_decoded) when the record is fetched.  Only complete frames are delivered: a consumer
+ * behind a live modem has no end of input.
+ * opts as for sonde_meisei_dec_create (SONDE_E_ARG as it returns it); json implies ecc; invert_stream = --softinv (it changes the sign of mv, and bits only at exact
+ * zeros).  sonde_softin_dev_create with SONDE_MEISEI is SONDE_E_ARG (the kind needs its options); the other kinds' fetch calls refuse a Meisei consumer and
+ * fetch_meisei refuses the other kinds.  One launch per push call: submit_fsk / collect keep the overlap with the modem's next second.
+ * A push call holds at most 4 * n_channels + 16 frames over all channels (a channel completes at most one per 1200 half symbols — 48 of the header and 1152 behind
+ * it — so two seconds at 2400 Bd fit); frames beyond that are decoded, not delivered, and counted as dropped. */
+int  sonde_softin_dev_create_meisei(int32_t n_channels, const sonde_meisei_opts_t *opts, int32_t invert_stream, sonde_softin_dev_t **out);
+/* The text of a frame under any options.  The -r line: per subframe the header word 7, 12 words of 5 and `#......#  ` 10, the newline: below 160.  The two printers:
+ * a counter 8, `--dbg` 30, time 15, date 13, T / RH 20, position 55 (lat / lon / alt are 32-bit integers over 1e7 / 1e2), speeds 45, (ok)[OK] 8, sn 28, fq 15 and
+ * the newlines of a hand-over: below 260 for the frame.  The JSON object: 330 of fixed text and bounded fields, freq 11, tx_frequency 25, version 31: below 400.
+ * 1024 leaves room for all three. */
+#define SONDE_MEISEI_TEXT_MAX 1024
+typedef struct {
+    int32_t  channel;
+    uint8_t  block_err[12];  /* per block, subframe 0 first: 0 / 1 / 2 corrected bits, 0xF padding or word parity failed, 0xE uncorrectable; all 0 without --ecc */
+    int32_t  err_frm;        /* blocks 0xE / 0xF                                                                                  */
+    int32_t  err_blks;       /* blocks that are not 0                                                                             */
+    float    mv;             /* score of the header in front of the frame, with its sign                                          */
+    uint64_t hdr_bit;        /* half symbols read when the header matched                                                         */
+    int32_t  text_len;       /* SONDE_E_ARG (negative) if the text did not fit: text is "" then                                   */
+    uint8_t  bits[SONDE_MEISEI_FRAME_BYTES];  /* the 600 frame bits behind BCH, MSB first: bits2val positions map directly         */
+    char     text[SONDE_MEISEI_TEXT_MAX];     /* what the reference prints for this frame, NUL-terminated                          */
+} sonde_meisei_softin_t;
+/* frames completed by the push calls since the last fetch (per channel in stream order); returns the count (<= max) */
+int  sonde_softin_dev_fetch_meisei(sonde_softin_dev_t *s, sonde_meisei_softin_t *out, int32_t max);
+
+/* tallies since creation: frames completed (SONDE_LMS6: blocks; accepted = the frames with a good CRC-16 that ended in them, the decoders' own count), frames accepted (RS41: rs41_ecc() >= 0; DFM: no block uncorrectable; M10 / M20: checksum good; RD94RD41: every block of the type print_frame chooses good; RS92: rs_decode >= 0; iMet-54: ecc_frm >= 0 and a check sum good, or ecc_std == 0 — the JSON rule without the status bits; Meisei: no block 0xE / 0xF), frames repaired (RS92: rs_decode > 0; iMet-54: ecc_frm > 0; Meisei: any block 1 or 2), symbols / codewords repaired (RS92: the sum of the positive rs_decode values; iMet-54: of the positive ecc_frm; Meisei: the sum of the corrected bits), frames lost to a full buffer */
 int  sonde_softin_dev_counts(sonde_softin_dev_t *s, int64_t *frames, int64_t *ecc_ok, int64_t *repaired, int64_t *symbols, int64_t *dropped);
 
 #ifdef __cplusplus

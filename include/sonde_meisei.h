@@ -26,6 +26,7 @@ extern "C" {
 #endif
 
 #define SONDE_MEISEI_FRAME_SYMBOLS 1152     /* half symbols behind the header: 2 * 600 - 48 (meisei100mod.c:707) */
+#define SONDE_MEISEI_FRAME_BYTES   75       /* the 600 frame bits, MSB first */
 
 typedef struct sonde_meisei_dec sonde_meisei_dec_t;
 
@@ -54,6 +55,13 @@ int  sonde_meisei_dec_frame(sonde_meisei_dec_t *d, const float *soft, int32_t n,
 /* Soft-bit input (`meisei100mod --softin`, decode.py:1379): n float32 soft half symbols in, header search and frame assembly inside;
  * finish != 0 at end of input appends the newline the reference prints before it exits (:1320). */
 int  sonde_meisei_dec_push_soft(sonde_meisei_dec_t *d, const float *soft, int32_t n, int32_t invert, int32_t finish, char *out, size_t outlen);
+
+/* A complete frame that is decoded already (the device consumer, include/sonde_fsk.h): the 600 frame bits, MSB first in 75 bytes (subframe 0 at bit 0, subframe 1
+ * at bit 300, the header bits included), and the 12 block verdicts — 0 / 1 / 2 corrected bits, 0xF padding or word parity, 0xE uncorrectable; subframe 0 first.
+ * Prints what the frame loop prints behind its block loop — the -r words with #......# under -v, or the RS-11G / iMS-100 lines with their hand-over, the
+ * configuration cycle and JSON — from the values given: no block is decoded again, err_frm and err_blks are counted from the verdicts.  Without --ecc the
+ * verdicts are not looked at. */
+int  sonde_meisei_dec_decoded(sonde_meisei_dec_t *d, const uint8_t *bits75, const uint8_t *block_err12, char *out, size_t outlen);
 
 #ifdef __cplusplus
 }

@@ -161,23 +161,50 @@ struct sonde_meisei_dec {
                     err_blks += (errors != 0);
                 }
             }
-            if (o.raw) {
-                w.f("%06X ", bits2val(sf, HEADLEN) & 0xFFFFFF);
-                for (int j = 0; j < 6; j++) {
-                    w.f("%04X ", bits2val(sf + HEADLEN + 46 * j, 16) & 0xFFFF);
-                    w.f("%04X ", bits2val(sf + HEADLEN + 46 * j + 17, 16) & 0xFFFF);
-                }
-                if (o.ecc && o.verbose) { w.f("#"); for (int b = 0; b < 6; b++) w.f("%X", block_err[b]); w.f("#  "); }
-                if (subframe > 0) w.f("\n");
-            } else {
-                int ims = option_ims100;
-                for (;;) {                                         // at most one hand-over: the two conditions exclude each other
-                    if (rst_gpx) { reset_gpx(); sn = -1; freq = -1; rst_gpx = 0; }
-                    if (!ims) { if (rs11g(w, sf, header_found, err_frm, err_blks)) { ims = 1; continue; } }
-                    else      { if (ims100(w, sf, header_found, err_frm, gps_chk_sum, gps_err)) { ims = 0; continue; } }
-                    break;
+            print_subframe(w, sf, subframe, header_found, err_frm, err_blks, gps_chk_sum, gps_err);
+            header_found += 1;
+        }
+    }
+
+    // what the frame loop prints for one subframe once its bits and block verdicts stand (:779-1310): the -r words (with #......# under -v), or the RS-11G /
+    // iMS-100 printer with the hand-over between them
+    void print_subframe(Out &w, const uint8_t *sf, int subframe, int header_found, int err_frm, int err_blks, int &gps_chk_sum, int &gps_err) {
+        if (o.raw) {
+            w.f("%06X ", bits2val(sf, HEADLEN) & 0xFFFFFF);
+            for (int j = 0; j < 6; j++) {
+                w.f("%04X ", bits2val(sf + HEADLEN + 46 * j, 16) & 0xFFFF);
+                w.f("%04X ", bits2val(sf + HEADLEN + 46 * j + 17, 16) & 0xFFFF);
+            }
+            if (o.ecc && o.verbose) { w.f("#"); for (int b = 0; b < 6; b++) w.f("%X", block_err[b]); w.f("#  "); }
+            if (subframe > 0) w.f("\n");
+        } else {
+            int ims = option_ims100;
+            for (;;) {                                         // at most one hand-over: the two conditions exclude each other
+                if (rst_gpx) { reset_gpx(); sn = -1; freq = -1; rst_gpx = 0; }
+                if (!ims) { if (rs11g(w, sf, header_found, err_frm, err_blks)) { ims = 1; continue; } }
+                else      { if (ims100(w, sf, header_found, err_frm, gps_chk_sum, gps_err)) { ims = 0; continue; } }
+                break;
+            }
+        }
+    }
+
+    // a frame that is decoded already: 600 bits and the 12 block verdicts (sonde_meisei_dec_decoded).  The counts are what the block loop of frame() derives from
+    // its own verdicts, accumulated over both subframes; without --ecc the verdicts are not looked at, as frame() leaves block_err alone then.
+    void decoded(Out &w, const uint8_t *bits75, const uint8_t *be12) {
+        for (int j = 0; j < 2 * (BITFRAME_LEN / 4); j++) frame_bits[j] = (uint8_t)((bits75[j >> 3] >> (7 - (j & 7))) & 1);
+        frame_bits[HEADLEN + NSYM / 2] = 0;
+        int gps_chk_sum = 0, gps_err = 0, err_frm = 0, err_blks = 0, header_found = 1;
+        for (int subframe = 0; subframe < 2; subframe++) {
+            const uint8_t *sf = frame_bits + (subframe ? BITFRAME_LEN / 4 : 0);
+            if (o.ecc) {
+                for (int block = 0; block < 6; block++) {
+                    const uint8_t e = be12[6 * subframe + block];
+                    block_err[block] = e;
+                    if (e >= 0xE) err_frm += 1;
+                    err_blks += (e != 0);
                 }
             }
+            print_subframe(w, sf, subframe, header_found, err_frm, err_blks, gps_chk_sum, gps_err);
             header_found += 1;
         }
     }
@@ -373,6 +400,13 @@ int sonde_meisei_dec_frame(sonde_meisei_dec_t *d, const float *soft, int32_t n, 
     if (!d || !out || n < 0 || n > NSYM || (n > 0 && !soft)) return SONDE_E_ARG;
     Out w;
     if (n == NSYM) d->frame(w, soft);
+    return finish_out(w, out, outlen);
+}
+
+int sonde_meisei_dec_decoded(sonde_meisei_dec_t *d, const uint8_t *bits75, const uint8_t *block_err12, char *out, size_t outlen) {
+    if (!d || !bits75 || !block_err12 || !out) return SONDE_E_ARG;
+    Out w;
+    d->decoded(w, bits75, block_err12);
     return finish_out(w, out, outlen);
 }
 

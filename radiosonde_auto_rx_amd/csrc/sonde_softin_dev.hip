@@ -22,9 +22,11 @@
 #include "sonde_softin_mxx_dev.h"
 #include "sonde_softin_rs92_dev.h"
 #include "sonde_softin_imet54_dev.h"
+#include "sonde_softin_meisei_dev.h"
 #include "../../include/sonde_drop.h"
 #include "../../include/sonde_rs92.h"
 #include "../../include/sonde_imet54.h"
+#include "../../include/sonde_meisei.h"
 #include <cstdio>
 #include <cstring>
 #include <vector>
@@ -566,6 +568,30 @@ void k_softin_imet54(const SoftinImet54Args A) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// Meisei iMS-100 / RS-11G: meisei100mod --softin [--ecc] (meisei100mod.c:654-776) — the 48 header half symbols at 0.8 in either polarity with the ring left as it
+// is, biphase-S bits on a lane per bit packed by ballot, then the 12 BCH(63,51) blocks one at a time on the same wave (syndromes as an XOR sum, the error positions
+// as one ballot of the locator's values, padding and word parities as population counts): sonde_softin_meisei_dev.h, which the CPU wave emulator compiles as well.
+// The call's soft decisions are staged in LDS as for M10 / M20 / RS92 / iMet-54 (a second at 2400 half symbols: 9.6 KB + 0.27 KB of state).  A record per completed
+// frame; the fields and the text are the host's (sonde_meisei_dec_decoded).
+// ------------------------------------------------------------------------------------------------
+struct SoftinMeiseiArgs { SoftinArgs base; SoftinMeiseiChan *chan; SoftinMeiseiRec *out; int stage_cap, ecc; };
+
+__global__ __launch_bounds__(64)
+void k_softin_meisei(const SoftinMeiseiArgs A) {
+    const SoftinArgs &a = A.base;
+    extern __shared__ float s_x[];                     // [stage_cap] sgn * x of this call (staged: nb <= stage_cap)
+    __shared__ SoftinMeiseiLds s_l;
+    const int ch = a.ch_list ? a.ch_list[blockIdx.x] : (int)blockIdx.x, lane = threadIdx.x;
+    if (ch >= a.n_ch || ch < 0) return;
+    int nb = a.nbits;
+    if (a.fsk_chan) { const int fr = a.fsk_chan[ch].frames; nb = fr > 0 ? fr * a.bits_per_frame : 0; }
+    else if (a.nbits_ch) nb = a.nbits_ch[ch];
+    nb = __builtin_amdgcn_readfirstlane(nb);
+    if ((long long)nb > a.ch_stride) return;                                     // (never: a channel's count lies within its stride)
+    meisei_wave_channel(A.chan + ch, a.sd + (size_t)ch * a.ch_stride, nb, a.inv_in ? -1.f : 1.f, A.ecc, a.ths, &s_l, s_x, A.stage_cap, A.out, a.count, a.cap, ch, lane);
+}
+
+// ------------------------------------------------------------------------------------------------
 // RD94 / RD41 dropsondes: rd94rd41drop --softin / --softinv [-i] (rd94rd41drop.c:1357-1386) — no correlation: the sign of every soft bit (s >= 0 after the two
 // inversions, which cancel each other) goes into the 40-bit ring, a frame is the 2360 raw bits behind a ring that equals FC 1D as Manchester-coded 8N1, and the
 // bits of a frame enter the ring too.  64 soft bits a pass: signs by ballot, every lane tests the ring as it stands behind its bit (values and "holds a bit"
@@ -804,6 +830,9 @@ struct sonde_softin_dev {
     // SONDE_IMET54: a host decoder per channel (print_position keeps its fields in the object); the text of a record is made when it is fetched
     SoftinImet54Chan *d_i54_chan = nullptr; SoftinImet54Rec *d_i54_out = nullptr; uint32_t *d_i54_tab = nullptr; Pinned<SoftinImet54Rec> h_i54; std::vector<SoftinImet54Rec> qi54;
     std::vector<sonde_imet54_dec_t *> i54_dec; int i54_ecc = 0;
+    // SONDE_MEISEI: a host decoder per channel (the variant in effect, the 64-word configuration, the counters); the text of a record is made when it is fetched
+    SoftinMeiseiChan *d_mei_chan = nullptr; SoftinMeiseiRec *d_mei_out = nullptr; Pinned<SoftinMeiseiRec> h_mei; std::vector<SoftinMeiseiRec> qmei;
+    std::vector<sonde_meisei_dec_t *> mei_dec; int mei_ecc = 0;
     SoftinArgs args{};
     hipStream_t stream = nullptr; bool own_stream = false;
     SoftinChan *d_chan = nullptr; unsigned char *d_frames = nullptr, *d_hdr = nullptr, *d_gf = nullptr, *d_synd = nullptr;
@@ -1002,6 +1031,38 @@ int sonde_softin_dev_create_imet54(int32_t n_channels, const sonde_imet54_opts_t
     return 0;
 }
 
+int sonde_softin_dev_create_meisei(int32_t n_channels, const sonde_meisei_opts_t *opts, int32_t invert_stream, sonde_softin_dev_t **out) {
+    if (!out || n_channels < 1 || !opts) return SONDE_E_ARG;
+    {   sonde_meisei_dec_t *probe = nullptr;                                                   // the option checks of the host decoder, before the device is touched
+        const int rc = sonde_meisei_dec_create(opts, &probe);
+        if (rc) return rc;
+        sonde_meisei_dec_destroy(probe);
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { fprintf(stderr, "libsonde_hip: no usable HIP device (the batched soft-bit framer has no CPU fallback)\n"); return SONDE_E_NOGPU; }
+    sonde_softin_dev *s = new sonde_softin_dev();
+    s->C = n_channels; s->type = SONDE_MEISEI; s->mei_ecc = (opts->ecc || opts->json) ? 1 : 0;     // --json implies --ecc (sonde_meisei.h)
+    s->cap = 4 * n_channels + 16;                              // frames a call can hold over all channels (sonde_fsk.h): a channel completes one per 1200 half symbols at the most
+    const size_t C = (size_t)n_channels, cap = (size_t)s->cap;
+    for (size_t c = 0; c < C; c++) {
+        sonde_meisei_dec_t *d = nullptr;
+        if (sonde_meisei_dec_create(opts, &d)) { sonde_softin_dev_destroy(s); return SONDE_E_NOMEM; }
+        s->mei_dec.push_back(d);
+    }
+    std::vector<SoftinMeiseiChan> init(C);
+    memset((void *)init.data(), 0, C * sizeof(SoftinMeiseiChan));
+    bool ok = hipMalloc((void **)&s->d_mei_chan, C * sizeof(SoftinMeiseiChan)) == hipSuccess && hipMalloc((void **)&s->d_mei_out, cap * sizeof(SoftinMeiseiRec)) == hipSuccess
+           && hipMalloc((void **)&s->d_count, 8) == hipSuccess && hipHostMalloc((void **)&s->h_count, 8) == hipSuccess && s->h_mei.alloc(cap);
+    ok = ok && hipMemcpy(s->d_mei_chan, init.data(), C * sizeof(SoftinMeiseiChan), hipMemcpyHostToDevice) == hipSuccess;
+    if (!ok) { sonde_softin_dev_destroy(s); return SONDE_E_NOMEM; }
+    SoftinArgs &a = s->args;
+    a.n_ch = n_channels; a.inv_in = invert_stream ? 1 : 0; a.ths = 0.8f; a.count = s->d_count; a.cap = s->cap;
+    s->head = std::min(s->cap, 2 * n_channels + 16);           // (two frames a second and channel)
+    (void)hipGetLastError();
+    *out = s;
+    return 0;
+}
+
 int sonde_softin_dev_rs92_load_ephemeris(sonde_softin_dev_t *s, const char *path) {
     if (!s || s->type != SONDE_RS92 || !path) return SONDE_E_ARG;
     for (sonde_rs92_dec_t *d : s->r92_dec) { const int rc = sonde_rs92_dec_load_ephemeris(d, path); if (rc) return rc; }
@@ -1021,11 +1082,12 @@ void sonde_softin_dev_destroy(sonde_softin_dev_t *s) {
     if (s->h_nbits) hipHostFree(s->h_nbits);
     if (s->d_nbits) hipFree(s->d_nbits);
     (void)hipGetLastError();
-    void *p[] = { s->d_chan, s->d_frames, s->d_hdr, s->d_gf, s->d_synd, s->d_flen, s->d_ecc, s->d_codes, s->d_meta, s->d_count, s->d_dfm_chan, s->d_dfm_out, s->d_m10_chan, s->d_m10_out, s->d_m20_chan, s->d_m20_out, s->d_drop_chan, s->d_drop_out, s->d_l6_chan, s->d_l6_out, s->d_l6_list, s->d_r92_chan, s->d_r92_out, s->d_i54_chan, s->d_i54_out, s->d_i54_tab };
+    void *p[] = { s->d_chan, s->d_frames, s->d_hdr, s->d_gf, s->d_synd, s->d_flen, s->d_ecc, s->d_codes, s->d_meta, s->d_count, s->d_dfm_chan, s->d_dfm_out, s->d_m10_chan, s->d_m10_out, s->d_m20_chan, s->d_m20_out, s->d_drop_chan, s->d_drop_out, s->d_l6_chan, s->d_l6_out, s->d_l6_list, s->d_r92_chan, s->d_r92_out, s->d_i54_chan, s->d_i54_out, s->d_i54_tab, s->d_mei_chan, s->d_mei_out };
     for (void *q : p) if (q) hipFree(q);
     for (sonde_lms6_dec_t *d : s->l6_dec) sonde_lms6_dec_destroy(d);
     for (sonde_rs92_dec_t *d : s->r92_dec) sonde_rs92_dec_destroy(d);
     for (sonde_imet54_dec_t *d : s->i54_dec) sonde_imet54_dec_destroy(d);
+    for (sonde_meisei_dec_t *d : s->mei_dec) sonde_meisei_dec_destroy(d);
     delete s;
 }
 
@@ -1034,7 +1096,7 @@ void sonde_softin_dev_destroy(sonde_softin_dev_t *s) {
 static int softin_finish_lms6(sonde_softin_dev *s, hipStream_t st, long long n);
 static int softin_pass(sonde_softin_dev *s, hipStream_t st, const int off, const int nblocks, const int *ch_list, const int which) {
     SoftinArgs a = s->args;
-    if (s->type != SONDE_LMS6 && s->type != SONDE_RS92 && s->type != SONDE_IMET54) { a.frames += (size_t)off * 518; a.flen += off; a.meta += off; }
+    if (s->type != SONDE_LMS6 && s->type != SONDE_RS92 && s->type != SONDE_IMET54 && s->type != SONDE_MEISEI) { a.frames += (size_t)off * 518; a.flen += off; a.meta += off; }
     a.cap = s->cap - off; a.count = s->d_count + which; a.ch_list = ch_list;
     HIPCHK(hipMemsetAsync(a.count, 0, 4, st));
     if (s->type == SONDE_DFM09) { SoftinDfmArgs d{a, s->d_dfm_chan, s->d_dfm_out + off, s->ecc_level}; hipLaunchKernelGGL(k_softin_dfm, dim3(nblocks), dim3(64), 0, st, d); }
@@ -1078,6 +1140,16 @@ static int softin_pass(sonde_softin_dev *s, hipStream_t st, const int off, const
         if (lds > attr) { if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_softin_imet54), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess) attr = lds; else m.stage_cap = 0; }
         hipLaunchKernelGGL(k_softin_imet54, dim3(nblocks), dim3(64), m.stage_cap ? lds : 0, st, m);
     }
+    else if (s->type == SONDE_MEISEI) {
+        // (LDS for the call's soft decisions as for M10)
+        long long need = a.fsk_chan || a.nbits_ch ? a.ch_stride : a.nbits;
+        if (need > M10_STAGE_MAX || need < 0) need = 0;
+        SoftinMeiseiArgs m{a, s->d_mei_chan, s->d_mei_out + off, (int)need, s->mei_ecc};
+        static size_t attr = 0;
+        const size_t lds = (size_t)need * sizeof(float);
+        if (lds > attr) { if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_softin_meisei), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess) attr = lds; else m.stage_cap = 0; }
+        hipLaunchKernelGGL(k_softin_meisei, dim3(nblocks), dim3(64), m.stage_cap ? lds : 0, st, m);
+    }
     else if (s->type == SONDE_RD94RD41) { SoftinDropArgs d{a, s->d_drop_chan, s->d_drop_out + off, s->drop_inv}; hipLaunchKernelGGL(k_softin_drop, dim3(nblocks), dim3(64), 0, st, d); }
     else if (s->type == SONDE_LMS6) { SoftinLms6Args d{a, s->d_l6_chan, s->d_l6_out + off, s->l6_vit, s->l6_auto}; hipLaunchKernelGGL(k_softin_lms6, dim3(nblocks), dim3(64), 0, st, d); }
     else {
@@ -1099,6 +1171,7 @@ static int softin_copy(sonde_softin_dev *s, hipStream_t st, const int from, cons
     else if (s->type == SONDE_RD94RD41) HIPCHK(hipMemcpyAsync(s->h_drop.data() + from, s->d_drop_out + from, n * sizeof(DropFrame), hipMemcpyDeviceToHost, st));
     else if (s->type == SONDE_RS92) HIPCHK(hipMemcpyAsync(s->h_r92.data() + from, s->d_r92_out + from, n * sizeof(SoftinRs92Rec), hipMemcpyDeviceToHost, st));
     else if (s->type == SONDE_IMET54) HIPCHK(hipMemcpyAsync(s->h_i54.data() + from, s->d_i54_out + from, n * sizeof(SoftinImet54Rec), hipMemcpyDeviceToHost, st));
+    else if (s->type == SONDE_MEISEI) HIPCHK(hipMemcpyAsync(s->h_mei.data() + from, s->d_mei_out + from, n * sizeof(SoftinMeiseiRec), hipMemcpyDeviceToHost, st));
     else if (s->type == SONDE_LMS6) HIPCHK(hipMemcpyAsync(s->h_l6.data() + from, s->d_l6_out + from, n * sizeof(Lms6Block), hipMemcpyDeviceToHost, st));
     else {
         HIPCHK(hipMemcpyAsync(s->h_meta.data() + from, s->d_meta + from, n * sizeof(SoftinMeta), hipMemcpyDeviceToHost, st));
@@ -1181,6 +1254,18 @@ static int softin_finish(sonde_softin_dev *s) {
             // the JSON rule without the status bits (imet54mod.c:583): frm_ok and a check sum good, or every codeword of the standard frame clean
             if (r.ecc_frm >= 0 && (r.crc_std || r.crc_cont || r.ecc_std == 0)) s->ecc_ok_total++;
             if (r.ecc_frm > 0) { s->repaired_total++; s->symbols_total += r.ecc_frm; }
+        }
+        return 0;
+    }
+    if (s->type == SONDE_MEISEI) {
+        for (long long i = 0; i < n; i++) {
+            const SoftinMeiseiRec &r = s->h_mei[i];
+            if (r.channel < 0 || r.channel >= s->C) continue;
+            s->qmei.push_back(r); s->frames_total++;
+            int bad = 0, fixed = 0;
+            for (int k = 0; k < MEISEI_BLOCKS; k++) { if (r.block_err[k] >= 0xE) bad++; else fixed += r.block_err[k]; }
+            if (!bad) s->ecc_ok_total++;
+            if (fixed) { s->repaired_total++; s->symbols_total += fixed; }
         }
         return 0;
     }
@@ -1310,7 +1395,7 @@ int sonde_softin_dev_push_device(sonde_softin_dev_t *s, const float *d_soft, int
 }
 
 int sonde_softin_dev_fetch(sonde_softin_dev_t *s, sonde_frame_t *out, int32_t max) {
-    if (s && (s->type == SONDE_RS92 || s->type == SONDE_IMET54)) return SONDE_E_ARG;
+    if (s && (s->type == SONDE_RS92 || s->type == SONDE_IMET54 || s->type == SONDE_MEISEI)) return SONDE_E_ARG;
     if (s && s->pending) { const int rc_ = softin_finish(s); if (rc_) return rc_; }
     if (!s || (!out && max > 0)) return SONDE_E_ARG;
     const int n = (int)std::min<size_t>(s->queue.size(), (size_t)(max < 0 ? 0 : max));
@@ -1320,7 +1405,7 @@ int sonde_softin_dev_fetch(sonde_softin_dev_t *s, sonde_frame_t *out, int32_t ma
 }
 
 int sonde_softin_dev_fetch_dfm(sonde_softin_dev_t *s, sonde_dfm_frame_t *out, int32_t max) {
-    if (s && (s->type == SONDE_RS92 || s->type == SONDE_IMET54)) return SONDE_E_ARG;
+    if (s && (s->type == SONDE_RS92 || s->type == SONDE_IMET54 || s->type == SONDE_MEISEI)) return SONDE_E_ARG;
     if (s && s->pending) { const int rc_ = softin_finish(s); if (rc_) return rc_; }
     if (!s || (!out && max > 0)) return SONDE_E_ARG;
     const int n = (int)std::min<size_t>(s->qdfm.size(), (size_t)(max < 0 ? 0 : max));
@@ -1330,7 +1415,7 @@ int sonde_softin_dev_fetch_dfm(sonde_softin_dev_t *s, sonde_dfm_frame_t *out, in
 }
 
 int sonde_softin_dev_fetch_m10(sonde_softin_dev_t *s, sonde_m10_frame_t *out, int32_t max) {
-    if (s && (s->type == SONDE_RS92 || s->type == SONDE_IMET54)) return SONDE_E_ARG;
+    if (s && (s->type == SONDE_RS92 || s->type == SONDE_IMET54 || s->type == SONDE_MEISEI)) return SONDE_E_ARG;
     if (s && s->pending) { const int rc_ = softin_finish(s); if (rc_) return rc_; }
     if (!s || (!out && max > 0)) return SONDE_E_ARG;
     const int n = (int)std::min<size_t>(s->qm10.size(), (size_t)(max < 0 ? 0 : max));
@@ -1355,7 +1440,7 @@ int sonde_softin_dev_fetch_m20(sonde_softin_dev_t *s, sonde_m20_frame_t *out, in
 }
 
 int sonde_softin_dev_fetch_drop(sonde_softin_dev_t *s, sonde_drop_frame_t *out, int32_t max) {
-    if (s && (s->type == SONDE_RS92 || s->type == SONDE_IMET54)) return SONDE_E_ARG;
+    if (s && (s->type == SONDE_RS92 || s->type == SONDE_IMET54 || s->type == SONDE_MEISEI)) return SONDE_E_ARG;
     if (s && s->pending) { const int rc_ = softin_finish(s); if (rc_) return rc_; }
     if (!s || (!out && max > 0)) return SONDE_E_ARG;
     const int n = (int)std::min<size_t>(s->qdrop.size(), (size_t)(max < 0 ? 0 : max));
@@ -1365,7 +1450,7 @@ int sonde_softin_dev_fetch_drop(sonde_softin_dev_t *s, sonde_drop_frame_t *out, 
 }
 
 int sonde_softin_dev_fetch_lms6(sonde_softin_dev_t *s, sonde_lms6_softin_t *out, int32_t max) {
-    if (s && (s->type == SONDE_RS92 || s->type == SONDE_IMET54)) return SONDE_E_ARG;
+    if (s && (s->type == SONDE_RS92 || s->type == SONDE_IMET54 || s->type == SONDE_MEISEI)) return SONDE_E_ARG;
     if (s && s->pending) { const int rc_ = softin_finish(s); if (rc_) return rc_; }
     if (!s || (!out && max > 0)) return SONDE_E_ARG;
     const int n = (int)std::min<size_t>(s->ql6.size(), (size_t)(max < 0 ? 0 : max));
@@ -1407,6 +1492,25 @@ int sonde_softin_dev_fetch_imet54(sonde_softin_dev_t *s, sonde_imet54_softin_t *
         if (len < 0) o.text[0] = 0;
     }
     s->qi54.erase(s->qi54.begin(), s->qi54.begin() + n);
+    return n;
+}
+
+int sonde_softin_dev_fetch_meisei(sonde_softin_dev_t *s, sonde_meisei_softin_t *out, int32_t max) {
+    if (!s || s->type != SONDE_MEISEI || (!out && max > 0)) return SONDE_E_ARG;
+    if (s->pending) { const int rc_ = softin_finish(s); if (rc_) return rc_; }
+    const int n = (int)std::min<size_t>(s->qmei.size(), (size_t)(max < 0 ? 0 : max));
+    for (int i = 0; i < n; i++) {
+        // the printers behind the block loop, by the channel's own decoder and from the device's bits and verdicts: here, not in the push call, so that collect stays short
+        const SoftinMeiseiRec &r = s->qmei[i];
+        sonde_meisei_softin_t &o = out[i];
+        o.channel = r.channel; o.mv = r.mv; o.hdr_bit = r.hdr_bit; o.err_frm = 0; o.err_blks = 0;
+        for (int k = 0; k < MEISEI_BLOCKS; k++) { o.block_err[k] = r.block_err[k]; o.err_frm += r.block_err[k] >= 0xE; o.err_blks += r.block_err[k] != 0; }
+        memcpy(o.bits, r.bits, sizeof o.bits);
+        const int len = sonde_meisei_dec_decoded(s->mei_dec[(size_t)r.channel], r.bits, r.block_err, o.text, sizeof o.text);
+        o.text_len = len;                                      // (negative: the text did not fit; the frame is delivered all the same)
+        if (len < 0) o.text[0] = 0;
+    }
+    s->qmei.erase(s->qmei.begin(), s->qmei.begin() + n);
     return n;
 }
 

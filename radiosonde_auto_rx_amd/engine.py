@@ -22,6 +22,7 @@ SONDE_M20 = 20
 SONDE_LMS6 = 6
 SONDE_RS92 = 92
 SONDE_IMET54 = 54
+SONDE_MEISEI = 11
 LP_IQ, LP_FM = 1, 2
 TAP_DECIM, TAP_IFIQ, TAP_FM, TAP_BUFS, TAP_CORR = range(5)
 ABI_VERSION = 3

@@ -69,6 +69,18 @@ class Imet54SoftinRec(C.Structure):
 # auto_rx's `imet54mod --ecc --json --softin -i --ptu` (auto_rx/autorx/decode.py:1215-1250)
 IMET54_DEFAULTS = dict(ecc=1, json=1, ptu=1, inv=1)
 
+MEISEI_TEXT_MAX = 1024
+
+
+class MeiseiSoftinRec(C.Structure):
+    """sonde_meisei_softin_t (include/sonde_fsk.h)"""
+    _fields_ = [("channel", C.c_int32), ("block_err", C.c_uint8 * 12), ("err_frm", C.c_int32), ("err_blks", C.c_int32), ("mv", C.c_float), ("hdr_bit", C.c_uint64),
+                ("text_len", C.c_int32), ("bits", C.c_uint8 * 75), ("text", C.c_char * MEISEI_TEXT_MAX)]
+
+
+# auto_rx's `meisei100mod --softin --json --ptu --ecc` (auto_rx/autorx/decode.py:1343-1379)
+MEISEI_DEFAULTS = dict(ecc=1, json=1, ptu=1)
+
 _proto = False
 
 
@@ -114,6 +126,9 @@ def _lib():
         from .family import Imet54Opts
         L.sonde_softin_dev_create_imet54.argtypes = [C.c_int32, C.POINTER(Imet54Opts), C.c_int32, C.POINTER(C.c_void_p)]
         L.sonde_softin_dev_fetch_imet54.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+        from .family import MeiseiOpts
+        L.sonde_softin_dev_create_meisei.argtypes = [C.c_int32, C.POINTER(MeiseiOpts), C.c_int32, C.POINTER(C.c_void_p)]
+        L.sonde_softin_dev_fetch_meisei.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
         _proto = True
     return L
 
@@ -222,7 +237,8 @@ class SoftinDev:
 
     def __init__(self, n_channels: int, *, ecc: int = 2, softinv: bool = False, inv: bool = True, auto: bool = False, kind: str = "rs41",
                  vit: int = 2, typ: int = 0, json: bool = False, raw: bool = False, gpsweek: int = 0, freq_khz: int = 0, version: str = "", skip: bool = True,
-                 rs92_opts: dict | None = None, ephemeris: str | None = None, almanac: str | None = None, imet54_opts: dict | None = None):
+                 rs92_opts: dict | None = None, ephemeris: str | None = None, almanac: str | None = None, imet54_opts: dict | None = None,
+                 meisei_opts: dict | None = None):
         """kind: "rs41" (rs41mod --softin), "dfm" (dfm09mod --softin: ecc 0 / 1 = --ecc / 2 = --ecc2), "m10" (m10mod --softin), "m20" (m20mod --softin: skip = the rest of
         the second behind a frame is dropped, as m20mod does below -vvv; auto_rx runs `m20mod --json --ptu -vvv --softin -i`: skip=False; ecc, inv and auto mean nothing to it), "drop" (rd94rd41drop --softin /
         --softinv [-i]: auto_rx runs it as softinv=True, inv=False; ecc and auto are ignored) or "lms6" (lms6Xmod --softin: vit 1 = --vit / 2 = --vit2, typ 0 = auto
@@ -230,7 +246,9 @@ class SoftinDev:
         "rs92" (rs92mod --softin: rs92_opts = fields of family.Rs92Opts over auto_rx's defaults verbose 1, aux 1, ecc 2, gps_vel 4, json 1, inv 1 — inv there is -i;
         ephemeris = a RINEX navigation file (-e), almanac = an SEM almanac (-a) for every channel's decoder; ecc, inv and auto of this call mean nothing to it) or
         "imet54" (imet54mod --softin: imet54_opts = fields of family.Imet54Opts over auto_rx's defaults ecc 1, json 1, ptu 1, inv 1 — inv there is -i, aut is --auto, json
-        implies ecc; ecc, inv and auto of this call mean nothing to it)"""
+        implies ecc; ecc, inv and auto of this call mean nothing to it) or "meisei" (meisei100mod --softin: meisei_opts = fields of family.MeiseiOpts over auto_rx's
+        defaults ecc 1, json 1, ptu 1 — json implies ecc; there is no -i: biphase-S compares neighbours, and a header counts in either polarity; ecc, inv and auto of
+        this call mean nothing to it)"""
         from .engine import SONDE_RS41, SONDE_DFM09, SONDE_M10, SONDE_M20, SONDE_RD94RD41
         h = C.c_void_p()
         self.kind, self.ecc = kind, ecc
@@ -256,6 +274,16 @@ class SoftinDev:
                 kw["version"] = kw["version"].encode()
             o = Imet54Opts(**kw)
             _chk(_lib().sonde_softin_dev_create_imet54(n_channels, C.byref(o), int(softinv), C.byref(h)))
+            self._h, self.n_channels = h, n_channels
+            return
+        if kind == "meisei":
+            from .family import MeiseiOpts
+            kw = dict(MEISEI_DEFAULTS)
+            kw.update(meisei_opts or {})
+            if isinstance(kw.get("version"), str):
+                kw["version"] = kw["version"].encode()
+            o = MeiseiOpts(**kw)
+            _chk(_lib().sonde_softin_dev_create_meisei(n_channels, C.byref(o), int(softinv), C.byref(h)))
             self._h, self.n_channels = h, n_channels
             return
         if kind == "lms6":
@@ -394,6 +422,15 @@ class SoftinDev:
         buf = (Imet54SoftinRec * max_frames)()
         n = _chk(_lib().sonde_softin_dev_fetch_imet54(self._h, buf, max_frames))
         return [dict(channel=r.channel, ecc_frm=r.ecc_frm, ecc_tlm=r.ecc_tlm, ecc_std=r.ecc_std, crc=r.crc, mv=r.mv, hdr_bit=r.hdr_bit, frame=bytes(r.frame),
+                     text=r.text[:max(r.text_len, 0)].decode()) for r in buf[:n]]
+
+    def fetch_meisei(self, max_frames: int = 1024):
+        """Meisei consumers: a dict per completed frame — channel, block_err (12 verdicts, subframe 0 first: 0 / 1 / 2 corrected bits, 0xF padding or word parity,
+        0xE uncorrectable), err_frm / err_blks (blocks 0xE / 0xF, blocks not 0), mv (with its sign), hdr_bit (half symbols read when the header matched), bits =
+        the 600 frame bits behind BCH in 75 bytes, MSB first, text = what `meisei100mod` prints for it from the device's bits and verdicts"""
+        buf = (MeiseiSoftinRec * max_frames)()
+        n = _chk(_lib().sonde_softin_dev_fetch_meisei(self._h, buf, max_frames))
+        return [dict(channel=r.channel, block_err=bytes(r.block_err), err_frm=r.err_frm, err_blks=r.err_blks, mv=r.mv, hdr_bit=r.hdr_bit, bits=bytes(r.bits),
                      text=r.text[:max(r.text_len, 0)].decode()) for r in buf[:n]]
 
     def counts(self):

@@ -25,7 +25,13 @@ inverted, as -i wants it) at sigma 0.3, repeated.  A push is the kernel and the 
 apart (text_ms).  Beside it the host tier (sonde_imet54_dec_push_soft, one thread) on the same stream in the same run.  No speed threshold: the rows are the measured pair
 and the 19.2 KB of soft decisions per channel and second that stay on the device.
 
-    python tools/bench_softin.py [--kind lms6|m20|rs92|imet54|all] [--channels 1,64,341,1024] [--pushes 39] [--vit 2] [--typ 0] [--out profiles/softin_bench.json]"""
+--kind meisei (or all): the Meisei consumer (SoftinDev(kind="meisei"): k_softin_meisei with BCH(63,51) on the wave, auto_rx's form `meisei100mod --softin --json --ptu
+--ecc`) — N channels x one second (2400 half symbols: two frames) per push in device memory, a 13 s stream of 26 continuous iMS-100 frames (tools/synth.py
+meisei_symbols) at sigma 0.3, repeated.  A push is the kernel and the copies of its records (push_ms); the text is made when the records are fetched and is timed apart
+(text_ms).  Beside it the host tier (sonde_meisei_dec_push_soft, one thread) on the same stream in the same run.  No speed threshold: the rows are the measured pair and
+the 9.6 KB of soft decisions per channel and second that stay on the device.
+
+    python tools/bench_softin.py [--kind lms6|m20|rs92|imet54|meisei|all] [--channels 1,64,341,1024] [--pushes 39] [--vit 2] [--typ 0] [--out profiles/softin_bench.json]"""
 import argparse
 import ctypes as C
 import json
@@ -305,6 +311,87 @@ def imet54_rows(a):
     return rows
 
 
+def meisei_stream(sigma=0.3, seed=5):
+    """13 s at 2400 half symbols: 26 continuous iMS-100 frames (tools/synth.py meisei_symbols), noise on everything"""
+    from tools import synth
+    rng = np.random.default_rng(seed)
+    s = 2.0 * synth.meisei_symbols(26, "ims100").astype(np.float64) - 1.0
+    assert len(s) == 13 * 2400
+    return (s + rng.normal(0.0, sigma, len(s))).astype(np.float32)
+
+
+MEISEI_OPTS = dict(ecc=1, json=1, ptu=1)
+
+
+def meisei_host_tier(s, pushes, nch):
+    """ms per push of one channel through sonde_meisei_dec_push_soft, JSON objects of one channel"""
+    from radiosonde_auto_rx_amd.engine import lib
+    from radiosonde_auto_rx_amd.family import MeiseiOpts
+    L = lib()
+    L.sonde_meisei_dec_create.argtypes = [C.POINTER(MeiseiOpts), C.POINTER(C.c_void_p)]
+    L.sonde_meisei_dec_destroy.argtypes = [C.c_void_p]
+    L.sonde_meisei_dec_push_soft.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_char_p, C.c_size_t]
+    o = MeiseiOpts(**MEISEI_OPTS)
+    decs = []
+    for _ in range(nch):
+        d = C.c_void_p()
+        assert L.sonde_meisei_dec_create(C.byref(o), C.byref(d)) == 0
+        decs.append(d)
+    out = C.create_string_buffer(1 << 16)
+    walls, ok = [], 0
+    for k in range(13 + pushes):
+        p = s.ctypes.data + (k % 13) * 2400 * 4
+        t0 = time.perf_counter()
+        for d in decs:
+            n = L.sonde_meisei_dec_push_soft(d, p, 2400, 0, 0, out, len(out))
+            assert n >= 0
+        dt = (time.perf_counter() - t0) * 1e3
+        if k >= 13:
+            walls.append(dt / nch)
+            ok += out.value.count(b'"type": "MEISEI"')
+    for d in decs:
+        L.sonde_meisei_dec_destroy(d)
+    return walls, ok
+
+
+def meisei_rows(a):
+    import torch
+    from radiosonde_auto_rx_amd.fsk import SoftinDev
+    s = meisei_stream()
+    hw, hok = meisei_host_tier(s, a.pushes, a.host_channels)
+    host_ms = statistics.median(hw)
+    rows = []
+    for nch in [int(c) for c in a.channels.split(",")]:
+        d = torch.from_numpy(s).to("cuda").repeat(nch, 1).contiguous()
+        torch.cuda.synchronize()
+        sf = SoftinDev(nch, kind="meisei", meisei_opts=dict(MEISEI_OPTS))
+        walls, texts, ok, frames, repaired = [], [], 0, 0, 0
+        for k in range(13 + a.pushes):
+            p = d.data_ptr() + (k % 13) * 2400 * 4
+            t0 = time.perf_counter()
+            sf.push_device(p, d.shape[1], 2400)
+            t1 = time.perf_counter()
+            recs = sf.fetch_meisei(4 * nch + 16)
+            t2 = time.perf_counter()
+            if k >= 13:
+                walls.append((t1 - t0) * 1e3); texts.append((t2 - t1) * 1e3)
+                frames += len(recs)
+                ok += sum(r["text"].count('"type": "MEISEI"') for r in recs if r["channel"] == 0)
+                repaired += sum(any(e in (1, 2) for e in r["block_err"]) for r in recs)
+        cnt = sf.counts()
+        sf.close()
+        wall, text = statistics.median(walls), statistics.median(texts)
+        row = {"kind": "meisei", "channels": nch, "pushes": a.pushes, "push_ms": round(wall, 3), "min_ms": round(min(walls), 3), "max_ms": round(max(walls), 3),
+               "text_ms": round(text, 3), "text_min_ms": round(min(texts), 3), "text_max_ms": round(max(texts), 3), "push_plus_text_ms": round(wall + text, 3),
+               "channel_seconds_per_second": round(nch * 1e3 / (wall + text), 1), "frames": frames, "repaired": repaired, "json_channel0": ok, "dropped": cnt["dropped"],
+               "soft_bytes_per_channel_second_left_on_device": 2400 * 4,
+               "host_tier_ms_per_channel_second": round(host_ms, 4), "host_tier_min_ms": round(min(hw), 4), "host_tier_max_ms": round(max(hw), 4),
+               "host_tier_ms_for_these_channels": round(host_ms * nch, 2), "host_tier_json_one_channel": hok}
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    return rows
+
+
 def m20_rows(a):
     import torch
     from radiosonde_auto_rx_amd.fsk import SoftinDev
@@ -342,7 +429,7 @@ def m20_rows(a):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--kind", default="lms6", choices=["lms6", "m20", "rs92", "imet54", "all"])
+    ap.add_argument("--kind", default="lms6", choices=["lms6", "m20", "rs92", "imet54", "meisei", "all"])
     ap.add_argument("--channels", default="1,64,341,1024")
     ap.add_argument("--pushes", type=int, default=39)
     ap.add_argument("--vit", type=int, default=2)
@@ -352,7 +439,7 @@ def main():
     a = ap.parse_args()
     assert a.pushes >= 30
     rows = (lms6_rows(a) if a.kind in ("lms6", "all") else []) + (m20_rows(a) if a.kind in ("m20", "all") else []) + (rs92_rows(a) if a.kind in ("rs92", "all") else []) \
-        + (imet54_rows(a) if a.kind in ("imet54", "all") else [])
+        + (imet54_rows(a) if a.kind in ("imet54", "all") else []) + (meisei_rows(a) if a.kind in ("meisei", "all") else [])
     if a.out:
         kinds = {r["kind"] for r in rows}
         if os.path.exists(a.out):
