@@ -62,6 +62,32 @@ int  sonde_imet4_process_device(sonde_imet4_t *e, const void *dev_samples, int32
  * nothing is handed out for it. */
 int  sonde_imet4_fetch_frames(sonde_imet4_t *e, sonde_imet4_frame_t *out, int32_t max);
 
+/* ------------------------------------------------------------------ testing taps (host code; not part of the decoding interface)
+ * Read-only views of what the kernels left in device memory, for tests that compare every sample with a reference.  Each call waits for the
+ * engine's stream and copies from the device; nothing the kernels compute depends on them. */
+#define SONDE_IMET4_TAP_IF      0   /* cf32: IF samples of the last process call (behind IQ-dc removal, mixer and decimator); decimation > 1 */
+#define SONDE_IMET4_TAP_ZRING   1   /* cf32: the sample the IF low-pass takes in (behind the AFC rotation); with the IF low-pass only         */
+#define SONDE_IMET4_TAP_FMRING  2   /* f32:  the sample the FM low-pass takes in (discriminator output or FM audio); with lp_fm only          */
+#define SONDE_IMET4_TAP_XRING   3   /* f32:  the front-end sample the sliding two-tone DFT takes (the reference's f32_sample output)          */
+
+typedef struct {                         /* one channel's state between calls, as the kernels keep it                                        */
+    double   df, dc, sum_x, sum_y, f0;   /* AFC offset (Hz), its last mean; IQ-dc block sums; mixer frequency (cycles per input sample)      */
+    double   f1_re, f1_im, f2_re, f2_im; /* the sliding DFT sums of the 2200 Hz and 1200 Hz tones                                            */
+    double   pos_bit;                    /* slicer: position of the last bit decision                                                        */
+    uint64_t sample_hi, base;            /* upper part of the IF sample count; input samples taken by the decimator                         */
+    float    xsum, avg_x, avg_y, prev_re, prev_im;   /* AFC running sum; IQ-dc average in effect; the last IF sample (discriminator)         */
+    uint32_t sample, pre_pos, cnt, maxcnt, maxlim, hreg;   /* IF samples done (low 32 bits); AFC phase; IQ-dc block position / length / limit */
+    int32_t  lut_len, locked, bit0, pos, hf, bitpos, hcount, bb0, bb1, bb2;   /* mixer table length; tap set; slicer                         */
+} sonde_imet4_state_t;
+
+/* copy `count` samples of one channel's tap starting at absolute IF sample index `first`; they must still be inside the history ring, which
+ * keeps the last (ring - 64) samples (SONDE_IMET4_TAP_IF: inside the last call), SONDE_E_RANGE otherwise; SONDE_E_ARG for a tap the
+ * configuration does not have.  out: count floats (x2 for the cf32 taps).  Returns count. */
+int  sonde_imet4_read_tap(sonde_imet4_t *e, int32_t channel, int32_t tap, int64_t first, int32_t count, float *out);
+int  sonde_imet4_read_state(sonde_imet4_t *e, int32_t channel, sonde_imet4_state_t *out);
+/* length of the history rings behind taps 1-3 (a power of two) */
+int  sonde_imet4_tap_ring(sonde_imet4_t *e);
+
 /* ------------------------------------------------------------------ printer (host code) */
 typedef struct sonde_imet4_printer sonde_imet4_printer_t;
 

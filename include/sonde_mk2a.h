@@ -81,6 +81,34 @@ int  sonde_mk2a_finish(sonde_mk2a_t *e);
 /* completed frames in channel / time order; returns their number (<= max) or a SONDE_E_* code.  Frames not fetched stay queued. */
 int  sonde_mk2a_fetch_frames(sonde_mk2a_t *e, sonde_mk2a_frame_t *out, int32_t max);
 
+/* ------------------------------------------------------------------ testing taps (host code; not part of the decoding interface)
+ * Read-only views of what the kernels left in device memory, for tests that compare every sample with a reference.  Each call waits for the
+ * engine's stream and copies from the device; nothing the kernels compute depends on them. */
+#define SONDE_MK2A_TAP_IF     0   /* cf32: IF samples of the last process call (behind IQ-dc removal, mixer and decimator)        */
+#define SONDE_MK2A_TAP_ZROT   1   /* cf32: behind the AFC rotation                                                               */
+#define SONDE_MK2A_TAP_ZLP    2   /* cf32: behind the IF low-pass (the reference's rot_iqbuf)                                    */
+#define SONDE_MK2A_TAP_FMR    3   /* f32:  discriminator output per IF sample                                                    */
+#define SONDE_MK2A_TAP_SRAW   4   /* f32:  tone correlator output per IF sample (--IQ only)                                      */
+#define SONDE_MK2A_TAP_BUFS   5   /* f32:  dsp->bufs, output rate (IF rate / dec_fm), ring of 8192                               */
+#define SONDE_MK2A_TAP_FMBUF  6   /* f32:  dsp->fm_buffer, output rate, ring of 8192                                             */
+
+typedef struct {                         /* one channel's state between calls, as the kernels keep it                            */
+    double   df, ddf, dc;                /* AFC offset (Hz), its last step, the header's dc                                      */
+    double   sum_x, sum_y, f0;           /* IQ-dc block sums; mixer frequency (cycles per input sample)                          */
+    uint64_t base;                       /* input samples taken                                                                  */
+    uint64_t if_samples, out_samples;    /* IF samples through the front end; output samples written (sample_in)                 */
+    uint64_t n_start, n_hdr;             /* sample_in when the header search last restarted / at the header of the frame         */
+    float    avg_x, avg_y, mv;           /* IQ-dc average in effect; last correlation score                                      */
+    uint32_t cnt, maxcnt, maxlim, mv_pos;/* IQ-dc block position, length, limit; position of the last correlation peak           */
+    int32_t  lut_len, locked, mode, inv, buffered0, bitpos;   /* mode 0: searching, 1: in a frame                                */
+} sonde_mk2a_state_t;
+
+/* copy `count` samples of one channel's tap starting at absolute sample index `first` (IF-rate index for taps 0-4, output-rate index for
+ * 5 and 6); they must still be inside the ring (SONDE_MK2A_TAP_IF: inside the last call), SONDE_E_RANGE otherwise.
+ * out: count floats (x2 for the cf32 taps).  Returns count. */
+int  sonde_mk2a_read_tap(sonde_mk2a_t *e, int32_t channel, int32_t tap, int64_t first, int32_t count, float *out);
+int  sonde_mk2a_read_state(sonde_mk2a_t *e, int32_t channel, sonde_mk2a_state_t *out);
+
 /* ------------------------------------------------------------------ printer (host code) */
 typedef struct sonde_mk2a_printer sonde_mk2a_printer_t;
 

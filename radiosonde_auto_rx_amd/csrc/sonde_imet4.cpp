@@ -9,11 +9,17 @@ using namespace sonde;
 
 struct sonde_imet4 : FrameEngine<sonde_imet4_frame_t> {
     Imet4Args a{};
+    int32_t if_last = 0;                 // IF samples per channel of the last call whose kernels ran (the range of the testing tap on ifbuf)
 
     // one launch over n samples per channel at dev_in
     int run(const void *dev_in, int32_t n) {
         Imet4Args c = a;
         c.in = dev_in; c.n = n / c.decM;
+        const int rc = drain(c);
+        if (rc == 0 || rc == SONDE_E_OVERFLOW) if_last = c.n;                    // (an overflow loses frames, the samples are written)
+        return rc;
+    }
+    int drain(const Imet4Args &c) {
         return launch_drain(c, sonde_launch_imet4, [](const Imet4Frame &g) {
             sonde_imet4_frame_t h;
             h.channel = g.channel; h.nbits = g.nbits; h.sample = g.sample;
@@ -110,3 +116,52 @@ extern "C" int sonde_imet4_process_host(sonde_imet4_t *e, const void *samples, i
 extern "C" int sonde_imet4_process_device(sonde_imet4_t *e, const void *dev_samples, int32_t n) { return engine_process_device(e, dev_samples, n); }
 
 extern "C" int sonde_imet4_fetch_frames(sonde_imet4_t *e, sonde_imet4_frame_t *out, int32_t max) { return engine_fetch_frames(e, out, max); }
+
+// ---- testing taps: host code only, the kernels and their arguments are as without them
+static_assert(sizeof(sonde_imet4_state_t) == sizeof(Imet4Chan), "sonde_imet4_state_t mirrors Imet4Chan field by field");
+
+extern "C" int sonde_imet4_tap_ring(sonde_imet4_t *e) { return e ? e->a.ring : SONDE_E_ARG; }
+
+extern "C" int sonde_imet4_read_tap(sonde_imet4_t *e, int32_t channel, int32_t tap, int64_t first, int32_t count, float *out) {
+    if (!e || !out || channel < 0 || channel >= e->a.n_ch || count < 0 || first < 0) return SONDE_E_ARG;
+    const Imet4Args &a = e->a;
+    HIPCHK(hipStreamSynchronize(e->stream));
+    Imet4Chan st;                                                               // what the kernels have written, from their own record
+    HIPCHK(hipMemcpy(&st, a.chan + channel, sizeof st, hipMemcpyDeviceToHost));
+    const int64_t U = (int64_t)(st.sample_hi + st.sample);
+    const char *row; size_t esz;
+    switch (tap) {
+        case SONDE_IMET4_TAP_IF:     if (!a.pre) return SONDE_E_ARG;
+                                     row = (const char *)(a.ifbuf + (size_t)channel * a.if_stride); esz = 8; break;
+        case SONDE_IMET4_TAP_ZRING:  if (!a.lp_iq) return SONDE_E_ARG;
+                                     row = (const char *)(a.zring + (size_t)channel * a.ring); esz = 8; break;
+        case SONDE_IMET4_TAP_FMRING: if (!a.lp_fm) return SONDE_E_ARG;
+                                     row = (const char *)(a.fmring + (size_t)channel * a.ring); esz = 4; break;
+        case SONDE_IMET4_TAP_XRING:  row = (const char *)(a.xring + (size_t)channel * a.ring); esz = 4; break;
+        default: return SONDE_E_ARG;
+    }
+    if (tap == SONDE_IMET4_TAP_IF) {                                            // the call's buffer: index from the call's first IF sample
+        const int64_t lo = U - e->if_last;
+        if (first < lo || first + count > U) return SONDE_E_RANGE;
+        if (count) HIPCHK(hipMemcpy(out, row + (size_t)(first - lo) * esz, (size_t)count * esz, hipMemcpyDeviceToHost));
+        return count;
+    }
+    // a tile cut short at a header has written up to 63 samples past U, over the oldest entries: those no longer count as history
+    const int64_t ring = a.ring, lo = U - (ring - 64);
+    if (first < lo || first + count > U) return SONDE_E_RANGE;
+    int32_t done = 0;
+    while (done < count) {
+        const int64_t idx = (first + done) & (ring - 1);
+        const int32_t run = (int32_t)std::min<int64_t>(count - done, ring - idx);
+        HIPCHK(hipMemcpy((char *)out + (size_t)done * esz, row + (size_t)idx * esz, (size_t)run * esz, hipMemcpyDeviceToHost));
+        done += run;
+    }
+    return count;
+}
+
+extern "C" int sonde_imet4_read_state(sonde_imet4_t *e, int32_t channel, sonde_imet4_state_t *out) {
+    if (!e || !out || channel < 0 || channel >= e->a.n_ch) return SONDE_E_ARG;
+    HIPCHK(hipStreamSynchronize(e->stream));
+    HIPCHK(hipMemcpy(out, e->a.chan + channel, sizeof *out, hipMemcpyDeviceToHost));
+    return 0;
+}

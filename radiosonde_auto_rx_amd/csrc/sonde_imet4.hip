@@ -140,8 +140,10 @@ __global__ __launch_bounds__(64) void k_imet4_afsk(const Imet4Args a) {
             }
             float pr = __shfl_up(zr, 1), pi_ = __shfl_up(zi, 1);
             if (lane == 0) { pr = st.prevr; pi_ = st.previ; }
-            const float cr = pr, ci = -pi_;                           // w = z * conj(z0)
-            const float wr = zr * cr - zi * ci, wi = zr * ci + zi * cr;
+            // w = z * conj(z0): conj() is the double function, so the reference forms the product in double (the float products are exact
+            // there) and rounds each part once to float (:505-507); float products rounded one by one differ from that in the last bit
+            const float wr = (float)((double)zr * (double)pr + (double)zi * (double)pi_);
+            const float wi = (float)((double)zi * (double)pr - (double)zr * (double)pi_);
             v = (float)(0.8 * atan2((double)wi, (double)wr) / kPi);
         } else if (act) {
             if (a.bits == 16) v = (float)((float)(in16[ix] / 128.0) / 256.0);

@@ -18,12 +18,15 @@ static sonde_mk2a_frame_t host_frame(const Mk2aFrame &g) {
 struct sonde_mk2a : FrameEngine<sonde_mk2a_frame_t> {
     Mk2aArgs a{};
     sonde_mk2a_info_t info{};
+    int32_t if_last = 0;                 // IF samples per channel of the last call whose kernels ran (the range of the testing tap on ifbuf)
 
     // one launch pair over n samples per channel at dev_in
     int run(const void *dev_in, int32_t n) {
         Mk2aArgs c = a;
         c.in = dev_in; c.n_base = n; c.n_if = n / c.decM;
-        return launch_drain(c, sonde_launch_mk2a, host_frame);
+        const int rc = launch_drain(c, sonde_launch_mk2a, host_frame);
+        if (rc == 0 || rc == SONDE_E_OVERFLOW) if_last = c.n_if;                 // (an overflow loses frames, the samples are written)
+        return rc;
     }
 };
 
@@ -184,3 +187,47 @@ extern "C" int sonde_mk2a_finish(sonde_mk2a_t *e) {
 }
 
 extern "C" int sonde_mk2a_fetch_frames(sonde_mk2a_t *e, sonde_mk2a_frame_t *out, int32_t max) { return engine_fetch_frames(e, out, max); }
+
+// ---- testing taps: host code only, the kernels and their arguments are as without them
+static_assert(sizeof(sonde_mk2a_state_t) == sizeof(Mk2aChan), "sonde_mk2a_state_t mirrors Mk2aChan field by field");
+
+extern "C" int sonde_mk2a_read_tap(sonde_mk2a_t *e, int32_t channel, int32_t tap, int64_t first, int32_t count, float *out) {
+    if (!e || !out || channel < 0 || channel >= e->a.n_ch || count < 0 || first < 0) return SONDE_E_ARG;
+    const Mk2aArgs &a = e->a;
+    const char *row; size_t esz; int64_t ring, lo, hi;                          // valid absolute indices: [lo, hi)
+    HIPCHK(hipStreamSynchronize(e->stream));
+    Mk2aChan st;                                                                // what the kernels have written, from their own record
+    HIPCHK(hipMemcpy(&st, a.chan + channel, sizeof st, hipMemcpyDeviceToHost));
+    const int64_t U = (int64_t)st.U, N = (int64_t)st.N;
+    switch (tap) {
+        case SONDE_MK2A_TAP_IF:    row = (const char *)(a.ifbuf + (size_t)channel * a.if_stride); esz = 8; ring = 0; lo = U - e->if_last; hi = U; break;
+        case SONDE_MK2A_TAP_ZROT:  row = (const char *)(a.zrot + (size_t)channel * a.ring); esz = 8; ring = a.ring; lo = U - ring; hi = U; break;
+        case SONDE_MK2A_TAP_ZLP:   row = (const char *)(a.zlp + (size_t)channel * a.ring); esz = 8; ring = a.ring; lo = U - ring; hi = U; break;
+        case SONDE_MK2A_TAP_FMR:   row = (const char *)(a.fmr + (size_t)channel * a.ring); esz = 4; ring = a.ring; lo = U - ring; hi = U; break;
+        case SONDE_MK2A_TAP_SRAW:  if (a.opt_iq != 5) return SONDE_E_ARG;
+                                   row = (const char *)(a.sraw + (size_t)channel * a.ring); esz = 4; ring = a.ring; lo = U - ring; hi = U; break;
+        case SONDE_MK2A_TAP_BUFS:  row = (const char *)(a.bufs + (size_t)channel * MK2A_M); esz = 4; ring = MK2A_M; lo = N - ring; hi = N; break;
+        case SONDE_MK2A_TAP_FMBUF: row = (const char *)(a.fmbuf + (size_t)channel * MK2A_M); esz = 4; ring = MK2A_M; lo = N - ring; hi = N; break;
+        default: return SONDE_E_ARG;
+    }
+    if (first < lo || first + count > hi) return SONDE_E_RANGE;
+    if (ring == 0) {                                                            // the call's buffer: index from the call's first IF sample
+        if (count) HIPCHK(hipMemcpy(out, row + (size_t)(first - lo) * esz, (size_t)count * esz, hipMemcpyDeviceToHost));
+        return count;
+    }
+    int32_t done = 0;
+    while (done < count) {
+        const int64_t idx = (first + done) & (ring - 1);
+        const int32_t run = (int32_t)std::min<int64_t>(count - done, ring - idx);
+        HIPCHK(hipMemcpy((char *)out + (size_t)done * esz, row + (size_t)idx * esz, (size_t)run * esz, hipMemcpyDeviceToHost));
+        done += run;
+    }
+    return count;
+}
+
+extern "C" int sonde_mk2a_read_state(sonde_mk2a_t *e, int32_t channel, sonde_mk2a_state_t *out) {
+    if (!e || !out || channel < 0 || channel >= e->a.n_ch) return SONDE_E_ARG;
+    HIPCHK(hipStreamSynchronize(e->stream));
+    HIPCHK(hipMemcpy(out, e->a.chan + channel, sizeof *out, hipMemcpyDeviceToHost));
+    return 0;
+}

@@ -216,7 +216,11 @@ __global__ __launch_bounds__(MK2A_THREADS) void k_mk2a(const Mk2aArgs a) {
             for (u64 u = Ua + tid; u < Ub; u += MK2A_THREADS) {
                 const float2 z = zlp[u & rm];
                 const float2 z0 = u ? zlp[(u - 1) & rm] : make_float2(0.f, 0.f);
-                const float wr = z.x * z0.x + z.y * z0.y, wi = z.y * z0.x - z.x * z0.y;      // w = z * conj(z0)
+                // w = z * conj(z0): conj() is the double function, so the reference forms the product in double (the float products are
+                // exact there) and rounds each part once to float (:842-844); float products rounded one by one flip the sign of a
+                // cancelling imaginary part, and with it the discriminator from -0.8 to +0.8
+                const float wr = (float)((double)z.x * (double)z0.x + (double)z.y * (double)z0.y);
+                const float wi = (float)((double)z.y * (double)z0.x - (double)z.x * (double)z0.y);
                 fmr[u & rm] = (float)(0.8 * atan2((double)wi, (double)wr) / kPi);
                 if (iq5) {                                                          // tone correlator over the middle of the bit (:881-907)
                     float x1r = 0.f, x1i = 0.f, x2r = 0.f, x2i = 0.f;

@@ -31,6 +31,19 @@ class Imet4Opts(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("raw", "rawbits", "json", "jsn_freq_khz")] + [("version", C.c_char * 32), ("reserved", C.c_int32 * 4)]
 
 
+class Imet4State(C.Structure):
+    """sonde_imet4_state_t: one channel's state between calls (testing tap)"""
+    _fields_ = [(n, C.c_double) for n in ("df", "dc", "sum_x", "sum_y", "f0", "f1_re", "f1_im", "f2_re", "f2_im", "pos_bit")] + \
+               [(n, C.c_uint64) for n in ("sample_hi", "base")] + \
+               [(n, C.c_float) for n in ("xsum", "avg_x", "avg_y", "prev_re", "prev_im")] + \
+               [(n, C.c_uint32) for n in ("sample", "pre_pos", "cnt", "maxcnt", "maxlim", "hreg")] + \
+               [(n, C.c_int32) for n in ("lut_len", "locked", "bit0", "pos", "hf", "bitpos", "hcount", "bb0", "bb1", "bb2")]
+
+
+# testing taps (SONDE_IMET4_TAP_*): name -> (number, floats per sample)
+TAPS = {"if": (0, 2), "zring": (1, 2), "fmring": (2, 1), "xring": (3, 1)}
+
+
 def _sigs(L):
     if getattr(L, "_imet4_sigs", False):
         return L
@@ -42,6 +55,9 @@ def _sigs(L):
     L.sonde_imet4_process_host.argtypes = [P, P, C.c_int32]
     L.sonde_imet4_process_device.argtypes = [P, P, C.c_int32]
     L.sonde_imet4_fetch_frames.argtypes = [P, C.POINTER(Imet4Frame), C.c_int32]
+    L.sonde_imet4_read_tap.argtypes = [P, C.c_int32, C.c_int32, C.c_int64, C.c_int32, P]
+    L.sonde_imet4_read_state.argtypes = [P, C.c_int32, C.POINTER(Imet4State)]
+    L.sonde_imet4_tap_ring.argtypes = [P]
     L.sonde_imet4_printer_create.argtypes = [C.POINTER(Imet4Opts), C.POINTER(P)]
     L.sonde_imet4_printer_destroy.argtypes = [P]
     L.sonde_imet4_printer_destroy.restype = None
@@ -98,3 +114,21 @@ class Imet4Engine(EngineHandle):
         x = np.ascontiguousarray(x, dtype=dt).reshape(self.n_ch, -1)
         n = x.shape[1] // (2 if self.iq else 1)
         self._call("process_host", self._h, x.ctypes.data, n)
+
+    def read_tap(self, channel: int, tap: str, first: int, count: int) -> np.ndarray:
+        """testing tap: `count` samples of TAPS[tap] from absolute IF sample `first`, which must still be inside the history ring (the last
+        tap_ring - 64 samples; "if": inside the last call).  complex64 for the IQ taps, float32 otherwise"""
+        num, width = TAPS[tap]
+        out = np.empty(count * width, np.float32)
+        self._call("read_tap", self._h, channel, num, first, count, out.ctypes.data)
+        return out.view(np.complex64) if width == 2 else out
+
+    def read_state(self, channel: int = 0) -> dict:
+        """testing tap: the channel's state record between calls"""
+        st = Imet4State()
+        self._call("read_state", self._h, channel, C.byref(st))
+        return {n: getattr(st, n) for n, _ in Imet4State._fields_}
+
+    @property
+    def tap_ring(self) -> int:
+        return int(self._L.sonde_imet4_tap_ring(self._h))

@@ -34,6 +34,18 @@ class Mk2aFrame(C.Structure):
                 ("reserved", C.c_uint32), ("sample", C.c_uint64), ("bits", C.c_uint8 * MAX_BITS)]
 
 
+class Mk2aState(C.Structure):
+    """sonde_mk2a_state_t: one channel's state between calls (testing tap)"""
+    _fields_ = [(n, C.c_double) for n in ("df", "ddf", "dc", "sum_x", "sum_y", "f0")] + \
+               [(n, C.c_uint64) for n in ("base", "if_samples", "out_samples", "n_start", "n_hdr")] + \
+               [(n, C.c_float) for n in ("avg_x", "avg_y", "mv")] + [(n, C.c_uint32) for n in ("cnt", "maxcnt", "maxlim", "mv_pos")] + \
+               [(n, C.c_int32) for n in ("lut_len", "locked", "mode", "inv", "buffered0", "bitpos")]
+
+
+# testing taps (SONDE_MK2A_TAP_*): name -> (number, floats per sample)
+TAPS = {"if": (0, 2), "zrot": (1, 2), "zlp": (2, 2), "fmr": (3, 1), "sraw": (4, 1), "bufs": (5, 1), "fmbuf": (6, 1)}
+
+
 class Mk2aOpts(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("raw", "crc", "vbs", "json", "jsn_freq_khz", "show_df", "if_rate", "sample_rate")] + \
                [("version", C.c_char * 32), ("reserved", C.c_int32 * 4)]
@@ -52,6 +64,8 @@ def _sigs(L):
     L.sonde_mk2a_process_device.argtypes = [P, P, C.c_int32]
     L.sonde_mk2a_finish.argtypes = [P]
     L.sonde_mk2a_fetch_frames.argtypes = [P, C.POINTER(Mk2aFrame), C.c_int32]
+    L.sonde_mk2a_read_tap.argtypes = [P, C.c_int32, C.c_int32, C.c_int64, C.c_int32, P]
+    L.sonde_mk2a_read_state.argtypes = [P, C.c_int32, C.POINTER(Mk2aState)]
     L.sonde_mk2a_printer_create.argtypes = [C.POINTER(Mk2aOpts), C.POINTER(P)]
     L.sonde_mk2a_printer_destroy.argtypes = [P]
     L.sonde_mk2a_printer_destroy.restype = None
@@ -131,3 +145,17 @@ class Mk2aEngine(EngineHandle):
         self._call("process_host", self._h, x.ctypes.data, x.shape[1] // 2)
 
     finish = EngineHandle._finish
+
+    def read_tap(self, channel: int, tap: str, first: int, count: int) -> np.ndarray:
+        """testing tap: `count` samples of TAPS[tap] from absolute sample `first` (IF rate; output rate for bufs / fmbuf), which must still
+        be inside the ring ("if": inside the last call).  complex64 for the IQ taps, float32 otherwise"""
+        num, width = TAPS[tap]
+        out = np.empty(count * width, np.float32)
+        self._call("read_tap", self._h, channel, num, first, count, out.ctypes.data)
+        return out.view(np.complex64) if width == 2 else out
+
+    def read_state(self, channel: int = 0) -> dict:
+        """testing tap: the channel's state record between calls"""
+        st = Mk2aState()
+        self._call("read_state", self._h, channel, C.byref(st))
+        return {n: getattr(st, n) for n, _ in Mk2aState._fields_}
