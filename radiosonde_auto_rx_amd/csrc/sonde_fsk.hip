@@ -984,9 +984,7 @@ void k_fsk_wave(const FskArgs a) {
     fsk_wave_channel<M, LOG2N, SPLIT, FMT>(a, ch, (int)threadIdx.x, lds, ctl);
 }
 
-// hipFuncSetAttribute(MaxDynamicSharedMemorySize) is a property of (function, device): the launchers remember what each device has been given
-#define FSK_MAX_DEV 16
-static int fsk_cur_dev() { int d = 0; if (hipGetDevice(&d) != hipSuccess || d < 0) d = 0; return d % FSK_MAX_DEV; }
+// (FSK_MAX_DEV / fsk_cur_dev, sonde_fsk_dev.h: the launchers remember the dynamic LDS each device has been given)
 
 template <int M, int LOG2N, bool SPLIT, int FMT>
 static int launch_wave_f(const FskArgs &b, const size_t lds_bytes, hipStream_t s) {

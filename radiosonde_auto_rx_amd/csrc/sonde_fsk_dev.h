@@ -10,6 +10,10 @@ typedef void *hipStream_t;
 #else
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+// hipFuncSetAttribute(MaxDynamicSharedMemorySize) is a property of (function, device): a launcher that raises it keeps one high-water mark per device
+// (sonde_fsk.hip, sonde_softin_dev.hip: static size_t attr[FSK_MAX_DEV], indexed by fsk_cur_dev())
+#define FSK_MAX_DEV 16
+static inline int fsk_cur_dev() { int d = 0; if (hipGetDevice(&d) != hipSuccess || d < 0) d = 0; return d % FSK_MAX_DEV; }
 #endif
 
 #define FSK_THREADS 256

@@ -15,10 +15,10 @@
 #include "../../include/sonde_fsk.h"
 #include "sonde_fsk_dev.h"
 #include "sonde_host.h"
-#include "sonde_pinned.h"
 #include "sonde_drop_dev.h"
 #include "sonde_softhdr_dev.h"
 #include "sonde_vit_dev.h"
+#include "sonde_softin_wave_dev.h"
 #include "sonde_softin_mxx_dev.h"
 #include "sonde_softin_rs92_dev.h"
 #include "sonde_softin_imet54_dev.h"
@@ -49,26 +49,33 @@ struct SoftinMeta { int channel, len, nbytes; float mv; unsigned long long hdr_b
 struct SoftinArgs {
     const float *sd; long long ch_stride;          // soft decisions of channel c at sd + c * ch_stride
     const int *nbits_ch; int nbits;                // per channel (device) or one count for all
-    const FskChan *fsk_chan; int bits_per_frame;   // or: frames of the modem's last launch x bits per frame
     const int *ch_list;                            // the channels of this launch (one workgroup each); null: all of them
     int n_ch, inv_in, opt_auto; float ths;
     SoftinChan *chan;
     unsigned char *frames; int *flen; SoftinMeta *meta; unsigned *count; int cap;
     const unsigned char *hdr;                      // 64 header bits ('0'/'1'), 8 header bytes, 64 mask bytes
 };
+// what every kernel begins with: the channel of this workgroup, its share of the call (nb symbols at x, wave-uniform) and the sign --softinv gives them;
+// false = nothing to do (a channel the launch does not have; a count beyond the stride never comes from the host)
+struct SoftinIn { int ch, nb; const float *x; float sgn; };
+__device__ __forceinline__ bool softin_input(const SoftinArgs &a, SoftinIn &in) {
+    in.ch = a.ch_list ? a.ch_list[blockIdx.x] : (int)blockIdx.x;
+    if (in.ch >= a.n_ch || in.ch < 0) return false;
+    in.nb = __builtin_amdgcn_readfirstlane(a.nbits_ch ? a.nbits_ch[in.ch] : a.nbits);
+    in.x = a.sd + (size_t)in.ch * a.ch_stride; in.sgn = a.inv_in ? -1.f : 1.f;
+    return (long long)in.nb <= a.ch_stride;
+}
 
 __global__ __launch_bounds__(64)
 void k_softin_rs41(const SoftinArgs a) {
     __shared__ float s_hist[64];
     __shared__ unsigned char s_frame[520];
     __shared__ float s_carry[8];
-    const int ch = a.ch_list ? a.ch_list[blockIdx.x] : (int)blockIdx.x, lane = threadIdx.x;
-    if (ch >= a.n_ch) return;
+    SoftinIn in;
+    if (!softin_input(a, in)) return;
+    const int ch = in.ch, nb = in.nb, lane = threadIdx.x;
+    const float *x = in.x; const float sgn = in.sgn;
     SoftinChan *st = a.chan + ch;
-    int nb = a.nbits;
-    if (a.fsk_chan) { const int fr = a.fsk_chan[ch].frames; nb = fr > 0 ? fr * a.bits_per_frame : 0; }
-    else if (a.nbits_ch) nb = a.nbits_ch[ch];
-    const float *x = a.sd + (size_t)ch * a.ch_stride;
     int mode = st->mode, inv = st->inv, body_done = st->body_done, carry_n = st->carry_n;
     float mv_hdr = st->mv; unsigned long long hdr_bit = st->hdr_bit; const unsigned long long bits0 = st->bits_in;
     s_hist[lane] = st->hist[lane];
@@ -76,7 +83,6 @@ void k_softin_rs41(const SoftinArgs a) {
     if (lane < 8) s_carry[lane] = st->carry[lane];
     // the header as +-1, one element per lane (for the dot products every lane needs all 64: from LDS-free registers via the constant array)
     __builtin_amdgcn_wave_barrier();
-    const float sgn = a.inv_in ? -1.f : 1.f;
     int cur = 0;
     while (cur < nb) {
         if (mode == 0) {
@@ -139,9 +145,7 @@ void k_softin_rs41(const SoftinArgs a) {
             carry_n = rest; body_done += take; cur += take;
             if (body_done == 4080) {
                 // print_frame(): the frame goes out (header bytes in front), rs41_ecc() follows in k_rs41_ecc_batch
-                unsigned slot = 0;
-                if (lane == 0) slot = atomicAdd(a.count, 1u);
-                slot = __shfl(slot, 0);
+                const unsigned slot = softin_wave_slot(a.count, lane);
                 if ((int)slot < a.cap) {
                     unsigned char *o = a.frames + (size_t)slot * 518;
                     for (int i = lane; i < 518; i += 64) o[i] = i < 8 ? a.hdr[64 + i] : s_frame[i];
@@ -220,19 +224,16 @@ void k_softin_dfm(const SoftinDfmArgs A) {
     __shared__ float s_hist[32];
     __shared__ unsigned char s_hb[280];
     __shared__ float s_sf[280];
-    const int ch = a.ch_list ? a.ch_list[blockIdx.x] : (int)blockIdx.x, lane = threadIdx.x;
-    if (ch >= a.n_ch) return;
+    SoftinIn in;
+    if (!softin_input(a, in)) return;
+    const int ch = in.ch, nb = in.nb, lane = threadIdx.x;
+    const float *x = in.x; const float sgn = in.sgn;
     SoftinDfmChan *st = A.chan + ch;
-    int nb = a.nbits;
-    if (a.fsk_chan) { const int fr = a.fsk_chan[ch].frames; nb = fr > 0 ? fr * a.bits_per_frame : 0; }
-    else if (a.nbits_ch) nb = a.nbits_ch[ch];
-    const float *x = a.sd + (size_t)ch * a.ch_stride;
     int mode = st->mode, inv = st->inv, dpos = st->dpos, dfrm = st->dfrm, dhalf = st->dhalf;
     float ds1 = st->ds1, mv_hdr = st->mv; unsigned hdrcnt = st->hdrcnt; unsigned long long hdr_bit = st->hdr_bit; const unsigned long long bits0 = st->bits_in;
     if (lane < 32) s_hist[lane] = st->hist[lane];
     for (int i = lane; i < 280; i += 64) { s_hb[i] = st->dhb[i]; s_sf[i] = st->dsf[i]; }
     __builtin_amdgcn_wave_barrier();
-    const float sgn = a.inv_in ? -1.f : 1.f;
     int cur = 0;
     while (cur < nb) {
         if (mode == 0) {
@@ -293,9 +294,7 @@ void k_softin_dfm(const SoftinDfmArgs A) {
             if ((dhalf + take) & 1) { ds1 = sgn * x[cur + take - 1]; dhalf = 1; } else dhalf = 0;
             dpos += nbits; cur += take;
             if (dpos == 280) {
-                unsigned slot = 0;
-                if (lane == 0) slot = atomicAdd(a.count, 1u);
-                slot = __shfl(slot, 0);
+                const unsigned slot = softin_wave_slot(a.count, lane);
                 // de-interleave + Hamming: lanes 0..6 conf (block at bit 16, 7 codewords), 7..19 dat1 (72, 13), 20..32 dat2 (176, 13)
                 int e = 0; unsigned char nib = 0;
                 const int blk = lane < 7 ? 0 : lane < 20 ? 1 : 2, i = lane < 7 ? lane : lane < 20 ? lane - 7 : lane - 20;
@@ -344,7 +343,7 @@ struct SoftinM10Chan {
     char  mbits[976];
 };
 struct SoftinM10Args { SoftinArgs base; SoftinM10Chan *chan; sonde_m10_frame_t *out; int stage_cap; };
-// (M10_STAGE_MAX, the soft decisions of a call the kernel keeps in LDS: sonde_softin_mxx_dev.h)
+// (M10_STAGE_MAX, the soft decisions of a call the kernel keeps in LDS: sonde_softin_wave_dev.h)
 
 // The header search (find_softbinhead / corr_softhdb, demod_mod.c:1692-1762) evaluates at EVERY symbol the normalised correlation of the last 32 with the header, in
 // double.  Round 5 did exactly that on a lane per position — 64 dependent double adds and 32 global loads each, 0.37 ms for 341 channels.  Now the call's soft decisions
@@ -357,47 +356,44 @@ void k_softin_m10(const SoftinM10Args A) {
     __shared__ float s_hist[32];
     __shared__ char s_mb[976];
     __shared__ unsigned char s_fr[124];
-    const int ch = a.ch_list ? a.ch_list[blockIdx.x] : (int)blockIdx.x, lane = threadIdx.x;
-    if (ch >= a.n_ch) return;
+    SoftinIn in;
+    if (!softin_input(a, in)) return;
+    const int ch = in.ch, nb = in.nb, lane = threadIdx.x;
     SoftinM10Chan *st = A.chan + ch;
-    int nb = a.nbits;
-    if (a.fsk_chan) { const int fr = a.fsk_chan[ch].frames; nb = fr > 0 ? fr * a.bits_per_frame : 0; }
-    else if (a.nbits_ch) nb = a.nbits_ch[ch];
-    const float *x = a.sd + (size_t)ch * a.ch_stride;
     constexpr int NBITS = 121 * 8;
     int mode = st->mode, inv = st->inv, mpos = st->mpos, mhalf = st->mhalf, mbit0 = st->mbit0, mskip = st->mskip;
     float ms1 = st->ms1, mv_hdr = st->mv; unsigned long long hdr_bit = st->hdr_bit; const unsigned long long bits0 = st->bits_in;
     if (lane < 32) s_hist[lane] = st->hist[lane];
     for (int i = lane; i < 976; i += 64) s_mb[i] = st->mbits[i];
-    const float sgn = a.inv_in ? -1.f : 1.f;
-    const bool staged = nb <= A.stage_cap;
-    if (staged) for (int i = lane; i < nb; i += 64) s_x[i] = sgn * x[i];
-    __builtin_amdgcn_wave_barrier();
-    auto X = [&](int p) -> float { return staged ? s_x[p] : sgn * x[p]; };       // soft decision p of this call, in the polarity in effect
+    const SoftinX X = softin_wave_stage(s_x, in.x, in.sgn, nb, A.stage_cap, lane);           // soft decision p of this call, in the polarity in effect
+    rsw_wave_sync();
     unsigned hbits = 0;                                                          // the 32 header symbols as a bit mask
     for (int i = 0; i < 32; i++) hbits |= (unsigned)(a.hdr[i] & 1) << i;
     int cur = 0;
     while (cur < nb) {
         if (mode == 0) {
+            // element k of the ring ++ the call's symbols from `cur`
+            const int cur0 = cur;
+            auto W = [&](const int k) -> float { return k < 32 ? s_hist[k] : X(cur0 + (k - 32)); };
             bool found = false;
-            for (int base = cur; base < nb && !found; base += 64) {
+            for (int base = cur0; base < nb && !found; base += 64) {
                 const int q = base + lane;
                 float mv = 0.f;
                 if (q < nb) {
-                    const int e = 32 + (q - cur);
+                    // softin_wave_score<32>, written out: with the header in a register (a.hdr, not a constant) the template's unrolled loops keep 32 condition
+                    // masks in scalar registers — 85 of them spilled, 80 vector registers for 66 and a wave less per SIMD
+                    const int k0 = q - cur0 + 1;                          // the window of position q ends with the symbol at q
                     float fs = 0.f, fn = 0.f;
                     for (int i = 0; i < 32; i++) {
-                        const int k = e - 31 + i;
-                        const float v = k < 32 ? s_hist[k] : X(cur + (k - 32));
+                        const float v = W(k0 + i);
                         fs += ((hbits >> i) & 1u) ? v : -v;
                         fn = fmaf(v, v, fn);
                     }
-                    mv = fs * __builtin_amdgcn_rsqf(fn * 32.0f);
+                    mv = fs * mxxw_rsq(fn * 32.0f);
                     if (!(fabsf(mv) < a.ths - 1e-3f)) {                   // (also NaN: an all-zero window is the reference's 0 / 0)
                         double sum = 0.0, normx = 0.0;
                         for (int i = 0; i < 32; i++) {
-                            const int k = e - 31 + i;
-                            const float v = k < 32 ? s_hist[k] : X(cur + (k - 32));
+                            const float v = W(k0 + i);
                             const float y = ((hbits >> i) & 1u) ? 1.f : -1.f;
                             sum += (double)(y * v);
                             normx += (double)(v * v);
@@ -408,25 +404,17 @@ void k_softin_m10(const SoftinM10Args A) {
                 }
                 const unsigned long long hits = __ballot(q < nb && fabsf(mv) > a.ths);
                 if (hits) {
-                    const int l = __builtin_ctzll(hits);
-                    const float mvl = __shfl(mv, l);
+                    const int l = __builtin_ctzll(hits), qs = base + l;
+                    const float mvl = mxxw_bcast_f(mv, l);
                     if ((double)mvl * (0.5 - inv) < 0) inv ^= 1;            // irrelevant for the differential code (m10mod.c:1447)
                     found = true;
-                    const int qs = base + l, e = 32 + (qs - cur), k = e - 31 + (lane & 31);
-                    const float v = k < 32 ? s_hist[k] : X(cur + (k - 32));
-                    __builtin_amdgcn_wave_barrier();
-                    if (lane < 32) s_hist[lane] = v;
-                    __builtin_amdgcn_wave_barrier();
+                    softin_wave_ring<32>(s_hist, W, qs - cur0 + 1, lane);  // the ring as the header leaves it: the 32 elements up to the hit
                     mode = 1; mpos = 0; mhalf = 0; mbit0 = '0'; mv_hdr = mvl; hdr_bit = bits0 + (unsigned long long)qs + 1ull;
                     cur = qs + 1;
                 }
             }
             if (!found) {
-                const int e = 32 + (nb - 1 - cur), k = e - 31 + (lane & 31);
-                const float v = k < 32 ? s_hist[k] : X(cur + (k - 32));
-                __builtin_amdgcn_wave_barrier();
-                if (lane < 32) s_hist[lane] = v;
-                __builtin_amdgcn_wave_barrier();
+                softin_wave_ring<32>(s_hist, W, nb - cur0, lane);          // the 32 elements up to the call's last symbol
                 cur = nb;
             }
         } else if (mode == 1) {
@@ -452,9 +440,7 @@ void k_softin_m10(const SoftinM10Args A) {
             if ((mhalf + take) & 1) { ms1 = X(cur + take - 1); mhalf = 1; } else mhalf = 0;
             mpos += nbits; cur += take;
             if (mpos == NBITS) {
-                unsigned slot = 0;
-                if (lane == 0) slot = atomicAdd(a.count, 1u);
-                slot = __shfl(slot, 0);
+                const unsigned slot = softin_wave_slot(a.count, lane);
                 for (int i = lane; i < 124; i += 64) {
                     unsigned v = 0;
                     if (i < 121) for (int k = 0; k < 8; k++) if (s_mb[8 * i + 7 - k] == '1') v |= 1u << k;
@@ -510,14 +496,9 @@ void k_softin_m20(const SoftinM20Args A) {
     const SoftinArgs &a = A.base;
     extern __shared__ float s_x[];                     // [stage_cap] sgn * x of this call (staged: nb <= stage_cap)
     __shared__ SoftinM20Lds s_l;
-    const int ch = a.ch_list ? a.ch_list[blockIdx.x] : (int)blockIdx.x, lane = threadIdx.x;
-    if (ch >= a.n_ch || ch < 0) return;
-    int nb = a.nbits;
-    if (a.fsk_chan) { const int fr = a.fsk_chan[ch].frames; nb = fr > 0 ? fr * a.bits_per_frame : 0; }
-    else if (a.nbits_ch) nb = a.nbits_ch[ch];
-    nb = __builtin_amdgcn_readfirstlane(nb);
-    if ((long long)nb > a.ch_stride) return;                                     // (never: a channel's count lies within its stride)
-    m20_wave_channel(A.chan + ch, a.sd + (size_t)ch * a.ch_stride, nb, a.inv_in ? -1.f : 1.f, a.ths, A.doskip, &s_l, s_x, A.stage_cap, A.out, a.count, a.cap, ch, lane);
+    SoftinIn in;
+    if (!softin_input(a, in)) return;
+    m20_wave_channel(A.chan + in.ch, in.x, in.nb, in.sgn, a.ths, A.doskip, &s_l, s_x, A.stage_cap, A.out, a.count, a.cap, in.ch, threadIdx.x);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -533,14 +514,9 @@ void k_softin_rs92(const SoftinRs92Args A) {
     const SoftinArgs &a = A.base;
     extern __shared__ float s_x[];                     // [stage_cap] sgn * x of this call (staged: nb <= stage_cap)
     __shared__ SoftinRs92Lds s_l;
-    const int ch = a.ch_list ? a.ch_list[blockIdx.x] : (int)blockIdx.x, lane = threadIdx.x;
-    if (ch >= a.n_ch || ch < 0) return;
-    int nb = a.nbits;
-    if (a.fsk_chan) { const int fr = a.fsk_chan[ch].frames; nb = fr > 0 ? fr * a.bits_per_frame : 0; }
-    else if (a.nbits_ch) nb = a.nbits_ch[ch];
-    nb = __builtin_amdgcn_readfirstlane(nb);
-    if ((long long)nb > a.ch_stride) return;                                     // (never: a channel's count lies within its stride)
-    rs92_wave_channel(A.chan + ch, a.sd + (size_t)ch * a.ch_stride, nb, a.inv_in ? -1.f : 1.f, A.inv, a.ths, A.gf, &s_l, s_x, A.stage_cap, A.out, a.count, a.cap, ch, lane);
+    SoftinIn in;
+    if (!softin_input(a, in)) return;
+    rs92_wave_channel(A.chan + in.ch, in.x, in.nb, in.sgn, A.inv, a.ths, A.gf, &s_l, s_x, A.stage_cap, A.out, a.count, a.cap, in.ch, threadIdx.x);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -557,14 +533,9 @@ void k_softin_imet54(const SoftinImet54Args A) {
     const SoftinArgs &a = A.base;
     extern __shared__ float s_x[];                     // [stage_cap] sgn * x of this call (staged: nb <= stage_cap)
     __shared__ SoftinImet54Lds s_l;
-    const int ch = a.ch_list ? a.ch_list[blockIdx.x] : (int)blockIdx.x, lane = threadIdx.x;
-    if (ch >= a.n_ch || ch < 0) return;
-    int nb = a.nbits;
-    if (a.fsk_chan) { const int fr = a.fsk_chan[ch].frames; nb = fr > 0 ? fr * a.bits_per_frame : 0; }
-    else if (a.nbits_ch) nb = a.nbits_ch[ch];
-    nb = __builtin_amdgcn_readfirstlane(nb);
-    if ((long long)nb > a.ch_stride) return;                                     // (never: a channel's count lies within its stride)
-    imet54_wave_channel(A.chan + ch, a.sd + (size_t)ch * a.ch_stride, nb, a.inv_in ? -1.f : 1.f, a.opt_auto, A.ecc, a.ths, A.tab, &s_l, s_x, A.stage_cap, A.out, a.count, a.cap, ch, lane);
+    SoftinIn in;
+    if (!softin_input(a, in)) return;
+    imet54_wave_channel(A.chan + in.ch, in.x, in.nb, in.sgn, a.opt_auto, A.ecc, a.ths, A.tab, &s_l, s_x, A.stage_cap, A.out, a.count, a.cap, in.ch, threadIdx.x);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -581,14 +552,9 @@ void k_softin_meisei(const SoftinMeiseiArgs A) {
     const SoftinArgs &a = A.base;
     extern __shared__ float s_x[];                     // [stage_cap] sgn * x of this call (staged: nb <= stage_cap)
     __shared__ SoftinMeiseiLds s_l;
-    const int ch = a.ch_list ? a.ch_list[blockIdx.x] : (int)blockIdx.x, lane = threadIdx.x;
-    if (ch >= a.n_ch || ch < 0) return;
-    int nb = a.nbits;
-    if (a.fsk_chan) { const int fr = a.fsk_chan[ch].frames; nb = fr > 0 ? fr * a.bits_per_frame : 0; }
-    else if (a.nbits_ch) nb = a.nbits_ch[ch];
-    nb = __builtin_amdgcn_readfirstlane(nb);
-    if ((long long)nb > a.ch_stride) return;                                     // (never: a channel's count lies within its stride)
-    meisei_wave_channel(A.chan + ch, a.sd + (size_t)ch * a.ch_stride, nb, a.inv_in ? -1.f : 1.f, A.ecc, a.ths, &s_l, s_x, A.stage_cap, A.out, a.count, a.cap, ch, lane);
+    SoftinIn in;
+    if (!softin_input(a, in)) return;
+    meisei_wave_channel(A.chan + in.ch, in.x, in.nb, in.sgn, A.ecc, a.ths, &s_l, s_x, A.stage_cap, A.out, a.count, a.cap, in.ch, threadIdx.x);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -618,14 +584,11 @@ void k_softin_drop(const SoftinDropArgs A) {
     constexpr unsigned long long M40 = (1ULL << DROP_HEADLEN) - 1;
     __shared__ unsigned char s_fb[DROP_RAWBITS];
     __shared__ unsigned char s_by[128];
-    const int ch = a.ch_list ? a.ch_list[blockIdx.x] : (int)blockIdx.x, lane = threadIdx.x;
-    if (ch >= a.n_ch) return;
+    SoftinIn in;
+    if (!softin_input(a, in)) return;
+    const int ch = in.ch, nb = in.nb, lane = threadIdx.x;
+    const float *x = in.x;                         // (both inversions are in A.inv: the sign is not applied here)
     SoftinDropChan *st = A.chan + ch;
-    int nb = a.nbits;
-    if (a.fsk_chan) { const int fr = a.fsk_chan[ch].frames; nb = fr > 0 ? fr * a.bits_per_frame : 0; }
-    else if (a.nbits_ch) nb = a.nbits_ch[ch];
-    nb = __builtin_amdgcn_readfirstlane(nb);
-    const float *x = a.sd + (size_t)ch * a.ch_stride;
     int found = __builtin_amdgcn_readfirstlane(st->found), pos = __builtin_amdgcn_readfirstlane(st->pos);
     unsigned long long hist = st->hist, valid = st->valid, t_hdr = st->t_hdr;
     const unsigned long long bits0 = st->bits_in;
@@ -674,12 +637,9 @@ __global__ __launch_bounds__(64)
 void k_softin_lms6(const SoftinLms6Args A) {
     const SoftinArgs &a = A.base;
     __shared__ Lms6Lds s_l;
-    const int ch = a.ch_list ? a.ch_list[blockIdx.x] : (int)blockIdx.x, lane = threadIdx.x;
-    if (ch >= a.n_ch || ch < 0) return;
-    int nb = a.nbits;
-    if (a.nbits_ch) nb = a.nbits_ch[ch];
-    nb = __builtin_amdgcn_readfirstlane(nb);
-    lms6_wave_channel(A.chan + ch, a.sd + (size_t)ch * a.ch_stride, nb, a.inv_in ? -1.f : 1.f, A.vit, A.stop_at_block, a.hdr, &s_l, A.out, a.count, a.cap, ch, lane);
+    SoftinIn in;
+    if (!softin_input(a, in)) return;
+    lms6_wave_channel(A.chan + in.ch, in.x, in.nb, in.sgn, A.vit, A.stop_at_block, a.hdr, &s_l, A.out, a.count, a.cap, in.ch, threadIdx.x);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -816,105 +776,273 @@ extern "C" int sonde_fsk_dev_reader_done(sonde_fsk_t *f, hipStream_t consumer_st
 extern "C" int sonde_fsk_dev_view_prev(sonde_fsk_t *f, const float **d_sd, long long *sd_cap, int *bits_per_frame, int *n_ch, int32_t *frames_out);
 extern "C" int sonde_fsk_dev_reader_done_prev(sonde_fsk_t *f, hipStream_t consumer_stream);
 
-struct sonde_softin_dev {
-    int C = 0, ecc_level = 0, cap = 0, type = SONDE_RS41;
-    SoftinDfmChan *d_dfm_chan = nullptr; sonde_dfm_frame_t *d_dfm_out = nullptr; std::vector<sonde_dfm_frame_t> qdfm; Pinned<sonde_dfm_frame_t> h_dfm;
-    SoftinM10Chan *d_m10_chan = nullptr; sonde_m10_frame_t *d_m10_out = nullptr; std::vector<sonde_m10_frame_t> qm10; Pinned<sonde_m10_frame_t> h_m10;
-    SoftinM20Chan *d_m20_chan = nullptr; sonde_m20_frame_t *d_m20_out = nullptr; std::vector<sonde_m20_frame_t> qm20; Pinned<sonde_m20_frame_t> h_m20; int m20_skip = 1;
-    SoftinDropChan *d_drop_chan = nullptr; DropFrame *d_drop_out = nullptr; std::vector<sonde_drop_frame_t> qdrop; Pinned<DropFrame> h_drop; int drop_inv = 0;
-    // SONDE_LMS6: a host decoder per channel (what follows block_bytes), the channels of a relaunch, the block length each channel has on the device
-    Lms6Chan *d_l6_chan = nullptr; Lms6Block *d_l6_out = nullptr; Pinned<Lms6Block> h_l6; std::vector<sonde_lms6_softin_t> ql6; std::vector<sonde_lms6_dec_t *> l6_dec;
-    int l6_vit = 0, l6_auto = 0; int *d_l6_list = nullptr; Pinned<int> h_l6_list, h_l6_len; std::vector<int> l6_len; std::vector<int64_t> l6_ok;
-    // SONDE_RS92: a host decoder per channel (the calibration rows a channel collects are per sonde); the text of a record is made when it is fetched
-    SoftinRs92Chan *d_r92_chan = nullptr; SoftinRs92Rec *d_r92_out = nullptr; Pinned<SoftinRs92Rec> h_r92; std::vector<SoftinRs92Rec> qr92; std::vector<sonde_rs92_dec_t *> r92_dec; int r92_inv = 0;
-    // SONDE_IMET54: a host decoder per channel (print_position keeps its fields in the object); the text of a record is made when it is fetched
-    SoftinImet54Chan *d_i54_chan = nullptr; SoftinImet54Rec *d_i54_out = nullptr; uint32_t *d_i54_tab = nullptr; Pinned<SoftinImet54Rec> h_i54; std::vector<SoftinImet54Rec> qi54;
-    std::vector<sonde_imet54_dec_t *> i54_dec; int i54_ecc = 0;
-    // SONDE_MEISEI: a host decoder per channel (the variant in effect, the 64-word configuration, the counters); the text of a record is made when it is fetched
-    SoftinMeiseiChan *d_mei_chan = nullptr; SoftinMeiseiRec *d_mei_out = nullptr; Pinned<SoftinMeiseiRec> h_mei; std::vector<SoftinMeiseiRec> qmei;
-    std::vector<sonde_meisei_dec_t *> mei_dec; int mei_ecc = 0;
-    SoftinArgs args{};
-    hipStream_t stream = nullptr; bool own_stream = false;
-    SoftinChan *d_chan = nullptr; unsigned char *d_frames = nullptr, *d_hdr = nullptr, *d_gf = nullptr, *d_synd = nullptr;
-    int *d_flen = nullptr, *d_ecc = nullptr, *d_codes = nullptr; SoftinMeta *d_meta = nullptr; unsigned *d_count = nullptr;
-    std::vector<sonde_frame_t> queue;
-    long long frames_total = 0, ecc_ok_total = 0, repaired_total = 0, symbols_total = 0, dropped = 0;
-    Pinned<int> h_ecc; Pinned<SoftinMeta> h_meta; Pinned<unsigned char> h_frames;       // page-locked landing buffers of a call's records (sonde_pinned.h)
-    unsigned *h_count = nullptr;                   // pinned: the counters of a call's two passes
-    int head = 0;                                  // records copied to the host without asking how many there are (what a call of a second normally completes)
-    bool pending = false; hipStream_t pend_stream = nullptr;
-    int *h_nbits = nullptr, *d_nbits = nullptr;    // bits per channel of the modem launch a call consumes (pinned host copy, device copy)
+// ------------------------------------------------------------------------------------------------
+// The host side.  One handle for every kind; what differs from kind to kind is a SoftinKind: the record the kernel leaves, the launch, and what a record counts for.
+// ------------------------------------------------------------------------------------------------
+struct SoftinKind {
+    size_t rec;                                    // bytes of a record in d_rec / h_rec; 0 = RS41's three arrays (frames / flen / meta + ecc: what k_rs41_ecc_batch reads)
+    void (*launch)(sonde_softin_dev *s, const SoftinArgs &a, int nblocks, hipStream_t st);
+    void (*tally)(sonde_softin_dev *s, long long n);   // the n records of a call, on the host: into the queue and the counts (null: LMS6, softin_finish_lms6)
 };
+
+struct sonde_softin_dev {
+    int C = 0, type = SONDE_RS41, cap = 0;
+    int head = 0;                                  // records copied to the host without asking how many there are (what a call of a second normally completes)
+    const SoftinKind *kind = nullptr;
+    int ecc_level = 0;                             // RS41, DFM09
+    int opt = 0;                                   // the kind's own switch: M20 skip, dropsonde / RS92 inv, iMet-54 / Meisei ecc, LMS6 vit
+    SoftinArgs args{};
+    hipStream_t stream = nullptr;                  // the consumer's own, made by its first call (softin_enqueue): behind the modem's streams, in the order of use
+    std::vector<std::pair<void *, bool>> allocs;   // every buffer below (true: page-locked host memory), freed by destroy
+    void *d_state = nullptr;                       // the channels between calls
+    unsigned char *d_rec = nullptr, *h_rec = nullptr;      // a call's records, and their page-locked landing buffer
+    unsigned *d_count = nullptr, *h_count = nullptr;
+    int *d_nbits = nullptr, *h_nbits = nullptr;    // bits per channel of the modem launch a call consumes
+    unsigned char *d_hdr = nullptr, *d_gf = nullptr; uint32_t *d_tab = nullptr;
+    // SONDE_RS41: the frames as sonde_launch_rs41_ecc_batch_n takes them
+    unsigned char *d_frames = nullptr, *d_synd = nullptr, *h_frames = nullptr; int *d_flen = nullptr, *d_ecc = nullptr, *d_codes = nullptr, *h_ecc = nullptr;
+    SoftinMeta *d_meta = nullptr, *h_meta = nullptr;
+    // SONDE_LMS6: the channels of a relaunch, the block length each channel has on the device, the decoders' tallies so far
+    int l6_auto = 0; int *d_l6_list = nullptr, *h_l6_list = nullptr, *h_l6_len = nullptr; std::vector<int> l6_len; std::vector<int64_t> l6_ok;
+    // LMS6 / RS92 / iMet-54 / Meisei: a host decoder per channel (what a sonde collects — calibration rows, configuration words, counters — is per channel)
+    std::vector<void *> dec; void (*dec_free)(void *) = nullptr;
+    std::vector<unsigned char> q;                  // the records not yet fetched, in the form the kind's tally queues
+    long long frames_total = 0, ecc_ok_total = 0, repaired_total = 0, symbols_total = 0, dropped = 0;
+    bool pending = false; hipStream_t pend_stream = nullptr;
+
+    template <class T> bool dalloc(T **p, size_t n) {
+        if (hipMalloc((void **)p, (n ? n : 1) * sizeof(T)) != hipSuccess) { *p = nullptr; return false; }
+        allocs.push_back({*p, false});
+        return true;
+    }
+    template <class T> bool halloc(T **p, size_t n) {
+        if (hipHostMalloc((void **)p, (n ? n : 1) * sizeof(T), hipHostMallocDefault) != hipSuccess) { *p = nullptr; return false; }
+        allocs.push_back({*p, true});
+        memset((void *)*p, 0, (n ? n : 1) * sizeof(T));
+        return true;
+    }
+    template <class T> T *chan() { return (T *)d_state; }
+    template <class T> T *recs() { return (T *)d_rec; }
+    template <class T> const T &landed(long long i) const { return ((const T *)h_rec)[i]; }
+    template <class T> void queue(const T &r) { const unsigned char *b = (const unsigned char *)&r; q.insert(q.end(), b, b + sizeof(T)); }
+    template <class T> T *decoder(int ch) { return (T *)dec[(size_t)ch]; }
+};
+
+// ---- the launches.  The staged kinds keep the call's soft decisions in LDS: what a call can hold (a modem launch: its capacity; a pushed stream: its length), up to
+// M10_STAGE_MAX; beyond that, or where the device refuses the dynamic LDS, the kernel reads them where they lie.  The attribute is a property of (function, device):
+// one high-water mark per kernel (Args names it) and device, as in sonde_fsk.hip.
+template <class Args>
+static void softin_launch_staged(void (*kern)(const Args), Args m, const int nblocks, hipStream_t st) {
+    const SoftinArgs &a = m.base;
+    long long need = a.nbits_ch ? a.ch_stride : a.nbits;
+    if (need > M10_STAGE_MAX || need < 0) need = 0;
+    m.stage_cap = (int)need;
+    static size_t attr[FSK_MAX_DEV] = {};
+    size_t &hw = attr[fsk_cur_dev()];
+    const size_t lds = (size_t)need * sizeof(float);
+    if (lds > hw) { if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess) hw = lds; else m.stage_cap = 0; }
+    hipLaunchKernelGGL(kern, dim3(nblocks), dim3(64), m.stage_cap ? lds : 0, st, m);
+}
+static void launch_rs41(sonde_softin_dev *s, const SoftinArgs &a, int nblocks, hipStream_t st) {
+    hipLaunchKernelGGL(k_softin_rs41, dim3(nblocks), dim3(64), 0, st, a);
+    if (s->ecc_level > 0) sonde_launch_rs41_ecc_batch_n(a.frames, a.flen, a.count, a.cap, s->ecc_level, s->d_ecc, s->d_codes, s->d_synd, s->d_gf, s->d_gf + 512, st);
+}
+static void launch_dfm(sonde_softin_dev *s, const SoftinArgs &a, int nblocks, hipStream_t st) {
+    const SoftinDfmArgs d{a, s->chan<SoftinDfmChan>(), s->recs<sonde_dfm_frame_t>(), s->ecc_level};
+    hipLaunchKernelGGL(k_softin_dfm, dim3(nblocks), dim3(64), 0, st, d);
+}
+static void launch_m10(sonde_softin_dev *s, const SoftinArgs &a, int nblocks, hipStream_t st) {
+    softin_launch_staged(k_softin_m10, SoftinM10Args{a, s->chan<SoftinM10Chan>(), s->recs<sonde_m10_frame_t>(), 0}, nblocks, st);
+}
+static void launch_m20(sonde_softin_dev *s, const SoftinArgs &a, int nblocks, hipStream_t st) {
+    softin_launch_staged(k_softin_m20, SoftinM20Args{a, s->chan<SoftinM20Chan>(), s->recs<sonde_m20_frame_t>(), 0, s->opt}, nblocks, st);
+}
+static void launch_rs92(sonde_softin_dev *s, const SoftinArgs &a, int nblocks, hipStream_t st) {
+    softin_launch_staged(k_softin_rs92, SoftinRs92Args{a, s->chan<SoftinRs92Chan>(), s->recs<SoftinRs92Rec>(), s->d_gf, 0, s->opt}, nblocks, st);
+}
+static void launch_imet54(sonde_softin_dev *s, const SoftinArgs &a, int nblocks, hipStream_t st) {
+    softin_launch_staged(k_softin_imet54, SoftinImet54Args{a, s->chan<SoftinImet54Chan>(), s->recs<SoftinImet54Rec>(), s->d_tab, 0, s->opt}, nblocks, st);
+}
+static void launch_meisei(sonde_softin_dev *s, const SoftinArgs &a, int nblocks, hipStream_t st) {
+    softin_launch_staged(k_softin_meisei, SoftinMeiseiArgs{a, s->chan<SoftinMeiseiChan>(), s->recs<SoftinMeiseiRec>(), 0, s->opt}, nblocks, st);
+}
+static void launch_drop(sonde_softin_dev *s, const SoftinArgs &a, int nblocks, hipStream_t st) {
+    const SoftinDropArgs d{a, s->chan<SoftinDropChan>(), s->recs<DropFrame>(), s->opt};
+    hipLaunchKernelGGL(k_softin_drop, dim3(nblocks), dim3(64), 0, st, d);
+}
+static void launch_lms6(sonde_softin_dev *s, const SoftinArgs &a, int nblocks, hipStream_t st) {
+    const SoftinLms6Args d{a, s->chan<Lms6Chan>(), s->recs<Lms6Block>(), s->opt, s->l6_auto};
+    hipLaunchKernelGGL(k_softin_lms6, dim3(nblocks), dim3(64), 0, st, d);
+}
+
+// ---- a call's records on the host, a rule per record.  Frames of one channel stay in order: the slots of a call are handed out in completion order per channel, channels interleave.
+template <class R, void (*One)(sonde_softin_dev *, const R &)> static void tally_all(sonde_softin_dev *s, long long n) {
+    for (long long i = 0; i < n; i++) One(s, s->landed<R>(i));
+}
+static void tally_rs41(sonde_softin_dev *s, long long n) {
+    for (long long i = 0; i < n; i++) {
+        sonde_frame_t f; memset(&f, 0, sizeof f);
+        const SoftinMeta &m = s->h_meta[i];
+        f.channel = m.channel; f.len = m.len; f.nbytes = m.nbytes; f.mv = m.mv; f.mv_pos = (uint32_t)m.hdr_bit;
+        f.ecc = s->ecc_level > 0 ? s->h_ecc[i] : 0;
+        memcpy(f.frame, s->h_frames + (size_t)i * 518, 518);
+        s->queue(f); s->frames_total++;
+        if (f.ecc >= 0) s->ecc_ok_total++;
+        if (f.ecc > 0) { s->repaired_total++; s->symbols_total += f.ecc; }
+    }
+}
+static void tally_dfm(sonde_softin_dev *s, const sonde_dfm_frame_t &f) {
+    s->queue(f); s->frames_total++;
+    const bool okf = f.ecc[0] >= 0 && f.ecc[1] >= 0 && f.ecc[2] >= 0;
+    if (okf) s->ecc_ok_total++;
+    if (okf && (f.ecc[0] > 0 || f.ecc[1] > 0 || f.ecc[2] > 0)) { s->repaired_total++; s->symbols_total += __builtin_popcount((unsigned)f.ecc[0]) + __builtin_popcount((unsigned)f.ecc[1]) + __builtin_popcount((unsigned)f.ecc[2]); }
+}
+static void tally_m10(sonde_softin_dev *s, const sonde_m10_frame_t &f) { s->queue(f); s->frames_total++; if (f.cs_ok) s->ecc_ok_total++; }
+static void tally_m20(sonde_softin_dev *s, const sonde_m20_frame_t &f) { s->queue(f); s->frames_total++; if (f.cs_ok) s->ecc_ok_total++; }
+static void tally_drop(sonde_softin_dev *s, const DropFrame &g) {
+    sonde_drop_frame_t f; memset(&f, 0, sizeof f);
+    f.channel = g.channel; f.nraw = g.nraw; f.complete = g.complete; f.err94 = g.err94; f.err41 = g.err41; f.sample = g.sample;
+    memcpy(f.bytes, g.bytes, sizeof f.bytes);
+    s->queue(f); s->frames_total++;
+    // print_frame's type choice and frm_ok (rd94rd41drop.c:1028-1038, :1213): more than two failing RD41 blocks = RD94
+    if (__builtin_popcount((unsigned)g.err41) > 2 ? g.err94 == 0 : g.err41 == 0) s->ecc_ok_total++;
+}
+static void tally_rs92(sonde_softin_dev *s, const SoftinRs92Rec &r) {
+    if (r.channel < 0 || r.channel >= s->C) return;
+    s->queue(r); s->frames_total++;
+    if (r.ec >= 0) s->ecc_ok_total++;
+    if (r.ec > 0) { s->repaired_total++; s->symbols_total += r.ec; }
+}
+static void tally_imet54(sonde_softin_dev *s, const SoftinImet54Rec &r) {
+    if (r.channel < 0 || r.channel >= s->C) return;
+    s->queue(r); s->frames_total++;
+    // the JSON rule without the status bits (imet54mod.c:583): frm_ok and a check sum good, or every codeword of the standard frame clean
+    if (r.ecc_frm >= 0 && (r.crc_std || r.crc_cont || r.ecc_std == 0)) s->ecc_ok_total++;
+    if (r.ecc_frm > 0) { s->repaired_total++; s->symbols_total += r.ecc_frm; }
+}
+static void tally_meisei(sonde_softin_dev *s, const SoftinMeiseiRec &r) {
+    if (r.channel < 0 || r.channel >= s->C) return;
+    s->queue(r); s->frames_total++;
+    int bad = 0, fixed = 0;
+    for (int k = 0; k < MEISEI_BLOCKS; k++) { if (r.block_err[k] >= 0xE) bad++; else fixed += r.block_err[k]; }
+    if (!bad) s->ecc_ok_total++;
+    if (fixed) { s->repaired_total++; s->symbols_total += fixed; }
+}
+
+static const SoftinKind *softin_kind(const int type) {
+    static const SoftinKind rs41{0, launch_rs41, tally_rs41}, dfm{sizeof(sonde_dfm_frame_t), launch_dfm, tally_all<sonde_dfm_frame_t, tally_dfm>},
+        m10{sizeof(sonde_m10_frame_t), launch_m10, tally_all<sonde_m10_frame_t, tally_m10>}, m20{sizeof(sonde_m20_frame_t), launch_m20, tally_all<sonde_m20_frame_t, tally_m20>},
+        drop{sizeof(DropFrame), launch_drop, tally_all<DropFrame, tally_drop>}, lms6{sizeof(Lms6Block), launch_lms6, nullptr},
+        rs92{sizeof(SoftinRs92Rec), launch_rs92, tally_all<SoftinRs92Rec, tally_rs92>}, imet54{sizeof(SoftinImet54Rec), launch_imet54, tally_all<SoftinImet54Rec, tally_imet54>},
+        meisei{sizeof(SoftinMeiseiRec), launch_meisei, tally_all<SoftinMeiseiRec, tally_meisei>};
+    switch (type) {
+        case SONDE_RS41: return &rs41;     case SONDE_DFM09: return &dfm;   case SONDE_M10: return &m10;       case SONDE_M20: return &m20;       case SONDE_RD94RD41: return &drop;
+        case SONDE_LMS6: return &lms6;     case SONDE_RS92: return &rs92;   case SONDE_IMET54: return &imet54; case SONDE_MEISEI: return &meisei;
+    }
+    return nullptr;
+}
+
+// A new consumer of `type`: what every kind has.  A call can hold per_cap records per channel + 16 and normally completes per_head per channel + 16 (include/sonde_fsk.h);
+// every channel starts as *init.  What only the kind has (header, tables, host decoders, options) is the caller's.
+static int softin_new(const int32_t n_channels, const int type, const int per_cap, const int per_head, const float ths, const int32_t invert_stream,
+                      const void *init, const size_t chan_bytes, sonde_softin_dev **out) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { fprintf(stderr, "libsonde_hip: no usable HIP device (the batched soft-bit framer has no CPU fallback)\n"); return SONDE_E_NOGPU; }
+    sonde_softin_dev *s = new sonde_softin_dev();
+    s->C = n_channels; s->type = type; s->kind = softin_kind(type);
+    s->cap = per_cap * n_channels + 16; s->head = std::min(s->cap, per_head * n_channels + 16);
+    const size_t C = (size_t)n_channels, cap = (size_t)s->cap;
+    std::vector<unsigned char> img(C * chan_bytes);
+    for (size_t c = 0; c < C; c++) memcpy(img.data() + c * chan_bytes, init, chan_bytes);
+    unsigned char *state = nullptr;
+    bool ok = s->dalloc(&state, img.size()) && s->dalloc(&s->d_count, 2) && s->halloc(&s->h_count, 2) && s->dalloc(&s->d_nbits, C) && s->halloc(&s->h_nbits, C)
+           && hipMemcpy(state, img.data(), img.size(), hipMemcpyHostToDevice) == hipSuccess;
+    if (ok && s->kind->rec) ok = s->dalloc(&s->d_rec, cap * s->kind->rec) && s->halloc(&s->h_rec, cap * s->kind->rec);
+    if (!ok) { sonde_softin_dev_destroy(s); return SONDE_E_NOMEM; }
+    s->d_state = state;
+    SoftinArgs &a = s->args;
+    a.n_ch = n_channels; a.inv_in = invert_stream ? 1 : 0; a.ths = ths; a.count = s->d_count; a.cap = s->cap;
+    *out = s;
+    return 0;
+}
+// the option checks of a kind's host decoder, before the device is touched; and a decoder per channel
+template <class D, class O> static int softin_probe(const O *o, int (*create)(const O *, D **), void (*destroy)(D *)) {
+    D *probe = nullptr;
+    const int rc = create(o, &probe);
+    if (!rc) destroy(probe);
+    return rc;
+}
+template <class D, class O, void (*Destroy)(D *)> static int softin_decoders(sonde_softin_dev *s, const O *o, int (*create)(const O *, D **)) {
+    s->dec_free = [](void *d) { Destroy((D *)d); };
+    for (int c = 0; c < s->C; c++) {
+        D *d = nullptr;
+        if (create(o, &d)) return SONDE_E_NOMEM;
+        s->dec.push_back(d);
+    }
+    return 0;
+}
+// the end of every create: what the kind added is in place (ok) and the handle is the caller's, or it goes
+static int softin_created(sonde_softin_dev *s, const bool ok, sonde_softin_dev **out) {
+    (void)hipGetLastError();
+    if (!ok) { sonde_softin_dev_destroy(s); return SONDE_E_NOMEM; }
+    *out = s;
+    return 0;
+}
 
 extern "C" {
 
 int sonde_softin_dev_create(int32_t n_channels, int32_t sonde_type, int32_t ecc_level, int32_t invert_stream, int32_t opt_inv, int32_t opt_auto, sonde_softin_dev_t **out) {
     if (!out || n_channels < 1 || (sonde_type != SONDE_RS41 && sonde_type != SONDE_DFM09 && sonde_type != SONDE_M10 && sonde_type != SONDE_M20 && sonde_type != SONDE_RD94RD41) || ecc_level < 0 || ecc_level > 2) return SONDE_E_ARG;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { fprintf(stderr, "libsonde_hip: no usable HIP device (the batched soft-bit framer has no CPU fallback)\n"); return SONDE_E_NOGPU; }
-    sonde_softin_dev *s = new sonde_softin_dev();
-    s->C = n_channels; s->ecc_level = ecc_level; s->type = sonde_type;
     // frames a call of about a second can complete per channel: RS41 two, DFM09 six (280 bits at 1250 b/s), M10 two (one per second; the rest of the second is skipped),
     // dropsondes three (two a second), M20 four (without the skip a frame can complete every 32 + 2640 symbols of the 9600 a second)
-    s->cap = (sonde_type == SONDE_DFM09 ? 8 : sonde_type == SONDE_RD94RD41 || sonde_type == SONDE_M20 ? 4 : 2) * n_channels + 16;
-    const size_t C = (size_t)n_channels, cap = (size_t)s->cap;
-    std::vector<SoftinChan> init(C);
-    memset(init.data(), 0, C * sizeof(SoftinChan));
-    for (auto &c : init) { c.inv = opt_inv ? 1 : 0; memcpy(c.frame, sonde::kRs41HeaderBytes, 8); }
+    const int per_cap = sonde_type == SONDE_DFM09 ? 8 : sonde_type == SONDE_RD94RD41 || sonde_type == SONDE_M20 ? 4 : 2;
+    const int per_head = sonde_type == SONDE_DFM09 ? 5 : sonde_type == SONDE_RD94RD41 ? 2 : 1;
+    const float ths = sonde_type == SONDE_M10 || sonde_type == SONDE_M20 ? 0.8f : 0.7f;
+    const int inv = opt_inv ? 1 : 0;
+    sonde_softin_dev *s = nullptr;
+    auto make = [&](const void *c, const size_t bytes) { return softin_new(n_channels, sonde_type, per_cap, per_head, ths, invert_stream, c, bytes, &s); };
+    int rc = 0;
+    if (sonde_type == SONDE_RS41) {
+        SoftinChan c; memset(&c, 0, sizeof c);
+        c.inv = inv; memcpy(c.frame, sonde::kRs41HeaderBytes, 8);
+        rc = make(&c, sizeof c);
+    } else if (sonde_type == SONDE_DFM09) {
+        SoftinDfmChan c; memset(&c, 0, sizeof c);
+        static const char kDfmHdr[] = "0100010111001111";                                 // dfm09mod.c:1503-1506: the header's 16 bits in front of the first frame of a hit
+        c.inv = inv; c.dpos = 16; for (int i = 0; i < 16; i++) c.dhb[i] = (unsigned char)(kDfmHdr[i] & 1);
+        rc = make(&c, sizeof c);
+    } else if (sonde_type == SONDE_M10) {
+        SoftinM10Chan c; memset(&c, 0, sizeof c);
+        c.inv = inv; c.mbit0 = '0';
+        rc = make(&c, sizeof c);
+    } else if (sonde_type == SONDE_M20) {
+        SoftinM20Chan c; memset((void *)&c, 0, sizeof c);
+        c.inv = inv; c.mbit0 = '0';
+        rc = make(&c, sizeof c);
+    } else {
+        SoftinDropChan c; memset(&c, 0, sizeof c);
+        c.pos = DROP_HEADLEN; for (int i = 0; i < DROP_HEADLEN; i++) c.frame[i] = (unsigned char)((DROP_HDR40 >> (DROP_HEADLEN - 1 - i)) & 1);
+        rc = make(&c, sizeof c);
+    }
+    if (rc) return rc;
+    s->ecc_level = ecc_level; s->args.opt_auto = opt_auto ? 1 : 0;
+    s->opt = sonde_type == SONDE_M20 ? 1 : sonde_type == SONDE_RD94RD41 ? (invert_stream ? 1 : 0) ^ inv : 0;
     unsigned char hdr[136];
     memset(hdr, 0, sizeof hdr);
     if (sonde_type == SONDE_RS41) { memcpy(hdr, sonde::kRs41Header, 64); memcpy(hdr + 64, sonde::kRs41HeaderBytes, 8); memcpy(hdr + 72, sonde::kRs41Mask, 64); }
     else memcpy(hdr, sonde_type == SONDE_DFM09 ? sonde::kDfmRawHeader : sonde::kM10RawHeader, 32);
-    bool ok = hipMalloc((void **)&s->d_chan, C * sizeof(SoftinChan)) == hipSuccess && hipMalloc((void **)&s->d_frames, cap * 518) == hipSuccess
-           && hipMalloc((void **)&s->d_hdr, sizeof hdr) == hipSuccess && hipMalloc((void **)&s->d_gf, 768) == hipSuccess && hipMalloc((void **)&s->d_synd, cap * 48) == hipSuccess
-           && hipMalloc((void **)&s->d_flen, cap * 4) == hipSuccess && hipMalloc((void **)&s->d_ecc, cap * 4) == hipSuccess && hipMalloc((void **)&s->d_codes, cap * 8) == hipSuccess
-           && hipMalloc((void **)&s->d_meta, cap * sizeof(SoftinMeta)) == hipSuccess && hipMalloc((void **)&s->d_count, 8) == hipSuccess && hipHostMalloc((void **)&s->h_count, 8) == hipSuccess;
-    ok = ok && hipMemcpy(s->d_chan, init.data(), C * sizeof(SoftinChan), hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(s->d_hdr, hdr, sizeof hdr, hipMemcpyHostToDevice) == hipSuccess
-            && hipMemcpy(s->d_gf, sonde::gf_exp_table(), 512, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(s->d_gf + 512, sonde::gf_log_table(), 256, hipMemcpyHostToDevice) == hipSuccess
-            && hipMemset(s->d_ecc, 0, cap * 4) == hipSuccess;
-    if (ok && sonde_type == SONDE_DFM09) {
-        std::vector<SoftinDfmChan> di(C);
-        memset(di.data(), 0, C * sizeof(SoftinDfmChan));
-        static const char kDfmHdr[] = "0100010111001111";                                 // dfm09mod.c:1503-1506: the header's 16 bits in front of the first frame of a hit
-        for (auto &c : di) { c.inv = opt_inv ? 1 : 0; c.dpos = 16; for (int i = 0; i < 16; i++) c.dhb[i] = (unsigned char)(kDfmHdr[i] & 1); }
-        ok = hipMalloc((void **)&s->d_dfm_chan, C * sizeof(SoftinDfmChan)) == hipSuccess && hipMalloc((void **)&s->d_dfm_out, cap * sizeof(sonde_dfm_frame_t)) == hipSuccess
-          && hipMemcpy(s->d_dfm_chan, di.data(), C * sizeof(SoftinDfmChan), hipMemcpyHostToDevice) == hipSuccess;
-        ok = ok && s->h_dfm.alloc(cap);
+    bool ok = s->dalloc(&s->d_hdr, sizeof hdr) && hipMemcpy(s->d_hdr, hdr, sizeof hdr, hipMemcpyHostToDevice) == hipSuccess;
+    if (ok && sonde_type == SONDE_RS41) {
+        const size_t cap = (size_t)s->cap;
+        ok = s->dalloc(&s->d_frames, cap * 518) && s->dalloc(&s->d_gf, 768) && s->dalloc(&s->d_synd, cap * 48) && s->dalloc(&s->d_flen, cap) && s->dalloc(&s->d_ecc, cap)
+          && s->dalloc(&s->d_codes, cap * 2) && s->dalloc(&s->d_meta, cap) && s->halloc(&s->h_ecc, cap) && s->halloc(&s->h_meta, cap) && s->halloc(&s->h_frames, cap * 518)
+          && hipMemcpy(s->d_gf, sonde::gf_exp_table(), 512, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(s->d_gf + 512, sonde::gf_log_table(), 256, hipMemcpyHostToDevice) == hipSuccess
+          && hipMemset(s->d_ecc, 0, cap * 4) == hipSuccess;
+        SoftinArgs &a = s->args;
+        a.chan = s->chan<SoftinChan>(); a.frames = s->d_frames; a.flen = s->d_flen; a.meta = s->d_meta;
     }
-    if (ok && sonde_type == SONDE_M10) {
-        std::vector<SoftinM10Chan> mi(C);
-        memset(mi.data(), 0, C * sizeof(SoftinM10Chan));
-        for (auto &c : mi) { c.inv = opt_inv ? 1 : 0; c.mbit0 = '0'; }
-        ok = hipMalloc((void **)&s->d_m10_chan, C * sizeof(SoftinM10Chan)) == hipSuccess && hipMalloc((void **)&s->d_m10_out, cap * sizeof(sonde_m10_frame_t)) == hipSuccess
-          && hipMemcpy(s->d_m10_chan, mi.data(), C * sizeof(SoftinM10Chan), hipMemcpyHostToDevice) == hipSuccess;
-        ok = ok && s->h_m10.alloc(cap);
-    }
-    if (ok && sonde_type == SONDE_M20) {
-        std::vector<SoftinM20Chan> mi(C);
-        memset((void *)mi.data(), 0, C * sizeof(SoftinM20Chan));
-        for (auto &c : mi) { c.inv = opt_inv ? 1 : 0; c.mbit0 = '0'; }
-        ok = hipMalloc((void **)&s->d_m20_chan, C * sizeof(SoftinM20Chan)) == hipSuccess && hipMalloc((void **)&s->d_m20_out, cap * sizeof(sonde_m20_frame_t)) == hipSuccess
-          && hipMemcpy(s->d_m20_chan, mi.data(), C * sizeof(SoftinM20Chan), hipMemcpyHostToDevice) == hipSuccess;
-        ok = ok && s->h_m20.alloc(cap);
-    }
-    if (ok && sonde_type == SONDE_RD94RD41) {
-        std::vector<SoftinDropChan> di(C);
-        memset(di.data(), 0, C * sizeof(SoftinDropChan));
-        for (auto &c : di) { c.pos = DROP_HEADLEN; for (int i = 0; i < DROP_HEADLEN; i++) c.frame[i] = (unsigned char)((DROP_HDR40 >> (DROP_HEADLEN - 1 - i)) & 1); }
-        s->drop_inv = (invert_stream ? 1 : 0) ^ (opt_inv ? 1 : 0);
-        ok = hipMalloc((void **)&s->d_drop_chan, C * sizeof(SoftinDropChan)) == hipSuccess && hipMalloc((void **)&s->d_drop_out, cap * sizeof(DropFrame)) == hipSuccess
-          && hipMemcpy(s->d_drop_chan, di.data(), C * sizeof(SoftinDropChan), hipMemcpyHostToDevice) == hipSuccess;
-        ok = ok && s->h_drop.alloc(cap);
-    }
-    if (!ok) { sonde_softin_dev_destroy(s); return SONDE_E_NOMEM; }
-    SoftinArgs &a = s->args;
-    a.n_ch = n_channels; a.inv_in = invert_stream ? 1 : 0; a.opt_auto = opt_auto ? 1 : 0; a.ths = sonde_type == SONDE_M10 || sonde_type == SONDE_M20 ? 0.8f : 0.7f;
-    a.chan = s->d_chan; a.frames = s->d_frames; a.flen = s->d_flen; a.meta = s->d_meta; a.count = s->d_count; a.cap = s->cap; a.hdr = s->d_hdr;
-    if (!s->h_ecc.alloc(cap) || !s->h_meta.alloc(cap) || !s->h_frames.alloc(cap * 518)) { sonde_softin_dev_destroy(s); return SONDE_E_NOMEM; }
-    s->head = std::min(s->cap, (sonde_type == SONDE_DFM09 ? 5 : sonde_type == SONDE_RD94RD41 ? 2 : 1) * n_channels + 16);
-    (void)hipGetLastError();
-    *out = s;
-    return 0;
+    s->args.hdr = s->d_hdr;
+    return softin_created(s, ok, out);
 }
 
 int sonde_softin_dev_create_lms6(int32_t n_channels, const sonde_lms6_opts_t *opts, int32_t invert_stream, sonde_softin_dev_t **out) {
@@ -923,260 +1051,108 @@ int sonde_softin_dev_create_lms6(int32_t n_channels, const sonde_lms6_opts_t *op
     if (o.json) { if (!o.ecc) o.ecc = 1; if (!o.vit) o.vit = 1; }                              // lms6Xmod.c:1153-1157
     if (o.vit != 1 && o.vit != 2) return SONDE_E_ARG;                                          // the algebraic decoder alone has no device form
     if (o.ecc == 3) return SONDE_E_ARG;                                                        // --ecc3 needs the second soft value of a sample-rate demodulator
-    {   sonde_lms6_dec_t *probe = nullptr;                                                     // the option checks of the host decoder, before the device is touched
-        const int rc = sonde_lms6_dec_create(&o, &probe);
-        if (rc) return rc;
-        sonde_lms6_dec_destroy(probe);
-    }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { fprintf(stderr, "libsonde_hip: no usable HIP device (the batched soft-bit framer has no CPU fallback)\n"); return SONDE_E_NOGPU; }
-    sonde_softin_dev *s = new sonde_softin_dev();
-    s->C = n_channels; s->type = SONDE_LMS6; s->l6_vit = o.vit; s->l6_auto = o.typ == 0;
-    s->cap = 4 * n_channels + 16;                              // blocks a call can hold over all channels (sonde_fsk.h): a channel completes at most two in a second of 4800 soft bits
-    const size_t C = (size_t)n_channels, cap = (size_t)s->cap;
-    for (size_t c = 0; c < C; c++) {
-        sonde_lms6_dec_t *d = nullptr;
-        if (sonde_lms6_dec_create(&o, &d)) { sonde_softin_dev_destroy(s); return SONDE_E_NOMEM; }
-        s->l6_dec.push_back(d);
-    }
-    const int len0 = sonde_lms6_dec_block_bits(s->l6_dec[0]) + LMS6_BLOCKSTART;
+    sonde_lms6_dec_t *probe = nullptr;                                                         // the option checks of the host decoder, before the device is touched
+    if (const int rc = sonde_lms6_dec_create(&o, &probe)) return rc;
+    const int len0 = sonde_lms6_dec_block_bits(probe) + LMS6_BLOCKSTART;
+    sonde_lms6_dec_destroy(probe);
+    sonde_softin_dev *s = nullptr;
+    Lms6Chan c; memset((void *)&c, 0, sizeof c);
+    c.pos = LMS6_BLOCKSTART; c.rawblk_len = len0;
+    // blocks a call can hold over all channels (sonde_fsk.h): a channel completes at most two in a second of 4800 soft bits
+    if (const int rc = softin_new(n_channels, SONDE_LMS6, 4, 1, 0.7f, invert_stream, &c, sizeof c, &s)) return rc;
+    const size_t C = (size_t)n_channels;
+    s->opt = o.vit; s->l6_auto = o.typ == 0;
     s->l6_len.assign(C, len0); s->l6_ok.assign(C, 0);
-    bool ok = hipMalloc((void **)&s->d_l6_chan, C * sizeof(Lms6Chan)) == hipSuccess && hipMalloc((void **)&s->d_l6_out, cap * sizeof(Lms6Block)) == hipSuccess
-           && hipMalloc((void **)&s->d_l6_list, C * sizeof(int)) == hipSuccess && hipMalloc((void **)&s->d_hdr, 64) == hipSuccess
-           && hipMalloc((void **)&s->d_count, 8) == hipSuccess && hipHostMalloc((void **)&s->h_count, 8) == hipSuccess
-           && s->h_l6.alloc(cap) && s->h_l6_list.alloc(C) && s->h_l6_len.alloc(C);
-    if (ok) {
-        std::vector<Lms6Chan> init(C);
-        memset((void *)init.data(), 0, C * sizeof(Lms6Chan));
-        for (auto &c : init) { c.pos = LMS6_BLOCKSTART; c.rawblk_len = len0; }
-        ok = hipMemcpy(s->d_l6_chan, init.data(), C * sizeof(Lms6Chan), hipMemcpyHostToDevice) == hipSuccess
-          && hipMemcpy(s->d_hdr, sonde_lms6_raw_header(), 64, hipMemcpyHostToDevice) == hipSuccess;
-    }
-    if (!ok) { sonde_softin_dev_destroy(s); return SONDE_E_NOMEM; }
-    SoftinArgs &a = s->args;
-    a.n_ch = n_channels; a.inv_in = invert_stream ? 1 : 0; a.ths = 0.7f; a.count = s->d_count; a.cap = s->cap; a.hdr = s->d_hdr;
-    s->head = std::min(s->cap, n_channels + 16);
-    (void)hipGetLastError();
-    *out = s;
-    return 0;
+    const bool ok = softin_decoders<sonde_lms6_dec_t, sonde_lms6_opts_t, sonde_lms6_dec_destroy>(s, &o, sonde_lms6_dec_create) == 0
+                 && s->dalloc(&s->d_l6_list, C) && s->halloc(&s->h_l6_list, C) && s->halloc(&s->h_l6_len, C) && s->dalloc(&s->d_hdr, 64)
+                 && hipMemcpy(s->d_hdr, sonde_lms6_raw_header(), 64, hipMemcpyHostToDevice) == hipSuccess;
+    s->args.hdr = s->d_hdr;
+    return softin_created(s, ok, out);
 }
 
 int sonde_softin_dev_create_rs92(int32_t n_channels, const sonde_rs92_opts_t *opts, int32_t invert_stream, sonde_softin_dev_t **out) {
     if (!out || n_channels < 1 || !opts) return SONDE_E_ARG;
     if (opts->gps_verbose == 8 || opts->dbg) return SONDE_E_ARG;                               // -gg / --dbg: lines without a bound per frame
-    {   sonde_rs92_dec_t *probe = nullptr;                                                     // the option checks of the host decoder, before the device is touched
-        const int rc = sonde_rs92_dec_create(opts, &probe);
-        if (rc) return rc;
-        sonde_rs92_dec_destroy(probe);
-    }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { fprintf(stderr, "libsonde_hip: no usable HIP device (the batched soft-bit framer has no CPU fallback)\n"); return SONDE_E_NOGPU; }
-    sonde_softin_dev *s = new sonde_softin_dev();
-    s->C = n_channels; s->type = SONDE_RS92; s->r92_inv = opts->inv ? 1 : 0;
-    s->cap = 4 * n_channels + 16;                              // frames a call can hold over all channels (sonde_fsk.h): a channel completes one per 4740 symbols at the least
-    const size_t C = (size_t)n_channels, cap = (size_t)s->cap;
-    for (size_t c = 0; c < C; c++) {
-        sonde_rs92_dec_t *d = nullptr;
-        if (sonde_rs92_dec_create(opts, &d)) { sonde_softin_dev_destroy(s); return SONDE_E_NOMEM; }
-        s->r92_dec.push_back(d);
-    }
-    bool ok = hipMalloc((void **)&s->d_r92_chan, C * sizeof(SoftinRs92Chan)) == hipSuccess && hipMalloc((void **)&s->d_r92_out, cap * sizeof(SoftinRs92Rec)) == hipSuccess
-           && hipMalloc((void **)&s->d_gf, 768) == hipSuccess && hipMalloc((void **)&s->d_count, 8) == hipSuccess && hipHostMalloc((void **)&s->h_count, 8) == hipSuccess
-           && s->h_r92.alloc(cap);
-    ok = ok && hipMemset(s->d_r92_chan, 0, C * sizeof(SoftinRs92Chan)) == hipSuccess
-            && hipMemcpy(s->d_gf, sonde::gf_exp_table(), 512, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(s->d_gf + 512, sonde::gf_log_table(), 256, hipMemcpyHostToDevice) == hipSuccess;
-    if (!ok) { sonde_softin_dev_destroy(s); return SONDE_E_NOMEM; }
-    SoftinArgs &a = s->args;
-    a.n_ch = n_channels; a.inv_in = invert_stream ? 1 : 0; a.ths = 0.8f; a.count = s->d_count; a.cap = s->cap;
-    s->head = std::min(s->cap, n_channels + 16);               // (a frame a second and channel)
-    (void)hipGetLastError();
-    *out = s;
-    return 0;
+    if (const int rc = softin_probe(opts, sonde_rs92_dec_create, sonde_rs92_dec_destroy)) return rc;
+    sonde_softin_dev *s = nullptr;
+    SoftinRs92Chan c; memset((void *)&c, 0, sizeof c);
+    // frames a call can hold over all channels (sonde_fsk.h): a channel completes one per 4740 symbols at the least; a frame a second and channel
+    if (const int rc = softin_new(n_channels, SONDE_RS92, 4, 1, 0.8f, invert_stream, &c, sizeof c, &s)) return rc;
+    s->opt = opts->inv ? 1 : 0;
+    const bool ok = softin_decoders<sonde_rs92_dec_t, sonde_rs92_opts_t, sonde_rs92_dec_destroy>(s, opts, sonde_rs92_dec_create) == 0 && s->dalloc(&s->d_gf, 768)
+                 && hipMemcpy(s->d_gf, sonde::gf_exp_table(), 512, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(s->d_gf + 512, sonde::gf_log_table(), 256, hipMemcpyHostToDevice) == hipSuccess;
+    return softin_created(s, ok, out);
 }
 
 int sonde_softin_dev_create_imet54(int32_t n_channels, const sonde_imet54_opts_t *opts, int32_t invert_stream, sonde_softin_dev_t **out) {
     if (!out || n_channels < 1 || !opts) return SONDE_E_ARG;
-    {   sonde_imet54_dec_t *probe = nullptr;                                                   // the option checks of the host decoder, before the device is touched
-        const int rc = sonde_imet54_dec_create(opts, &probe);
-        if (rc) return rc;
-        sonde_imet54_dec_destroy(probe);
-    }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { fprintf(stderr, "libsonde_hip: no usable HIP device (the batched soft-bit framer has no CPU fallback)\n"); return SONDE_E_NOGPU; }
-    sonde_softin_dev *s = new sonde_softin_dev();
-    s->C = n_channels; s->type = SONDE_IMET54; s->i54_ecc = (opts->ecc || opts->json) ? 1 : 0;     // --json implies --ecc (imet54mod.c:899)
-    s->cap = 4 * n_channels + 16;                              // frames a call can hold over all channels (sonde_fsk.h): a channel completes one per 2240 symbols at the most
-    const size_t C = (size_t)n_channels, cap = (size_t)s->cap;
-    for (size_t c = 0; c < C; c++) {
-        sonde_imet54_dec_t *d = nullptr;
-        if (sonde_imet54_dec_create(opts, &d)) { sonde_softin_dev_destroy(s); return SONDE_E_NOMEM; }
-        s->i54_dec.push_back(d);
-    }
-    std::vector<SoftinImet54Chan> init(C);
-    memset((void *)init.data(), 0, C * sizeof(SoftinImet54Chan));
-    for (auto &c : init) c.inv = opts->inv ? 1 : 0;
+    if (const int rc = softin_probe(opts, sonde_imet54_dec_create, sonde_imet54_dec_destroy)) return rc;
+    sonde_softin_dev *s = nullptr;
+    SoftinImet54Chan c; memset((void *)&c, 0, sizeof c);
+    c.inv = opts->inv ? 1 : 0;
+    // frames a call can hold over all channels (sonde_fsk.h): a channel completes one per 2240 symbols at the most; a frame a second and channel
+    if (const int rc = softin_new(n_channels, SONDE_IMET54, 4, 1, 0.8f, invert_stream, &c, sizeof c, &s)) return rc;
+    s->opt = (opts->ecc || opts->json) ? 1 : 0;                                                // --json implies --ecc (imet54mod.c:899)
+    s->args.opt_auto = opts->aut ? 1 : 0;
     std::vector<uint32_t> tab(IMET54_TAB_N);
     imet54_crc_table(tab.data());
-    bool ok = hipMalloc((void **)&s->d_i54_chan, C * sizeof(SoftinImet54Chan)) == hipSuccess && hipMalloc((void **)&s->d_i54_out, cap * sizeof(SoftinImet54Rec)) == hipSuccess
-           && hipMalloc((void **)&s->d_i54_tab, IMET54_TAB_N * sizeof(uint32_t)) == hipSuccess && hipMalloc((void **)&s->d_count, 8) == hipSuccess
-           && hipHostMalloc((void **)&s->h_count, 8) == hipSuccess && s->h_i54.alloc(cap);
-    ok = ok && hipMemcpy(s->d_i54_chan, init.data(), C * sizeof(SoftinImet54Chan), hipMemcpyHostToDevice) == hipSuccess
-            && hipMemcpy(s->d_i54_tab, tab.data(), IMET54_TAB_N * sizeof(uint32_t), hipMemcpyHostToDevice) == hipSuccess;
-    if (!ok) { sonde_softin_dev_destroy(s); return SONDE_E_NOMEM; }
-    SoftinArgs &a = s->args;
-    a.n_ch = n_channels; a.inv_in = invert_stream ? 1 : 0; a.opt_auto = opts->aut ? 1 : 0; a.ths = 0.8f; a.count = s->d_count; a.cap = s->cap;
-    s->head = std::min(s->cap, n_channels + 16);               // (a frame a second and channel)
-    (void)hipGetLastError();
-    *out = s;
-    return 0;
+    const bool ok = softin_decoders<sonde_imet54_dec_t, sonde_imet54_opts_t, sonde_imet54_dec_destroy>(s, opts, sonde_imet54_dec_create) == 0 && s->dalloc(&s->d_tab, IMET54_TAB_N)
+                 && hipMemcpy(s->d_tab, tab.data(), IMET54_TAB_N * sizeof(uint32_t), hipMemcpyHostToDevice) == hipSuccess;
+    return softin_created(s, ok, out);
 }
 
 int sonde_softin_dev_create_meisei(int32_t n_channels, const sonde_meisei_opts_t *opts, int32_t invert_stream, sonde_softin_dev_t **out) {
     if (!out || n_channels < 1 || !opts) return SONDE_E_ARG;
-    {   sonde_meisei_dec_t *probe = nullptr;                                                   // the option checks of the host decoder, before the device is touched
-        const int rc = sonde_meisei_dec_create(opts, &probe);
-        if (rc) return rc;
-        sonde_meisei_dec_destroy(probe);
-    }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { fprintf(stderr, "libsonde_hip: no usable HIP device (the batched soft-bit framer has no CPU fallback)\n"); return SONDE_E_NOGPU; }
-    sonde_softin_dev *s = new sonde_softin_dev();
-    s->C = n_channels; s->type = SONDE_MEISEI; s->mei_ecc = (opts->ecc || opts->json) ? 1 : 0;     // --json implies --ecc (sonde_meisei.h)
-    s->cap = 4 * n_channels + 16;                              // frames a call can hold over all channels (sonde_fsk.h): a channel completes one per 1200 half symbols at the most
-    const size_t C = (size_t)n_channels, cap = (size_t)s->cap;
-    for (size_t c = 0; c < C; c++) {
-        sonde_meisei_dec_t *d = nullptr;
-        if (sonde_meisei_dec_create(opts, &d)) { sonde_softin_dev_destroy(s); return SONDE_E_NOMEM; }
-        s->mei_dec.push_back(d);
-    }
-    std::vector<SoftinMeiseiChan> init(C);
-    memset((void *)init.data(), 0, C * sizeof(SoftinMeiseiChan));
-    bool ok = hipMalloc((void **)&s->d_mei_chan, C * sizeof(SoftinMeiseiChan)) == hipSuccess && hipMalloc((void **)&s->d_mei_out, cap * sizeof(SoftinMeiseiRec)) == hipSuccess
-           && hipMalloc((void **)&s->d_count, 8) == hipSuccess && hipHostMalloc((void **)&s->h_count, 8) == hipSuccess && s->h_mei.alloc(cap);
-    ok = ok && hipMemcpy(s->d_mei_chan, init.data(), C * sizeof(SoftinMeiseiChan), hipMemcpyHostToDevice) == hipSuccess;
-    if (!ok) { sonde_softin_dev_destroy(s); return SONDE_E_NOMEM; }
-    SoftinArgs &a = s->args;
-    a.n_ch = n_channels; a.inv_in = invert_stream ? 1 : 0; a.ths = 0.8f; a.count = s->d_count; a.cap = s->cap;
-    s->head = std::min(s->cap, 2 * n_channels + 16);           // (two frames a second and channel)
-    (void)hipGetLastError();
-    *out = s;
-    return 0;
+    if (const int rc = softin_probe(opts, sonde_meisei_dec_create, sonde_meisei_dec_destroy)) return rc;
+    sonde_softin_dev *s = nullptr;
+    SoftinMeiseiChan c; memset((void *)&c, 0, sizeof c);
+    // frames a call can hold over all channels (sonde_fsk.h): a channel completes one per 1200 half symbols at the most; two frames a second and channel
+    if (const int rc = softin_new(n_channels, SONDE_MEISEI, 4, 2, 0.8f, invert_stream, &c, sizeof c, &s)) return rc;
+    s->opt = (opts->ecc || opts->json) ? 1 : 0;                                                // --json implies --ecc (sonde_meisei.h)
+    const bool ok = softin_decoders<sonde_meisei_dec_t, sonde_meisei_opts_t, sonde_meisei_dec_destroy>(s, opts, sonde_meisei_dec_create) == 0;
+    return softin_created(s, ok, out);
 }
 
 int sonde_softin_dev_rs92_load_ephemeris(sonde_softin_dev_t *s, const char *path) {
     if (!s || s->type != SONDE_RS92 || !path) return SONDE_E_ARG;
-    for (sonde_rs92_dec_t *d : s->r92_dec) { const int rc = sonde_rs92_dec_load_ephemeris(d, path); if (rc) return rc; }
+    for (int c = 0; c < s->C; c++) { const int rc = sonde_rs92_dec_load_ephemeris(s->decoder<sonde_rs92_dec_t>(c), path); if (rc) return rc; }
     return 0;
 }
 int sonde_softin_dev_rs92_load_almanac(sonde_softin_dev_t *s, const char *path) {
     if (!s || s->type != SONDE_RS92 || !path) return SONDE_E_ARG;
-    for (sonde_rs92_dec_t *d : s->r92_dec) { const int rc = sonde_rs92_dec_load_almanac(d, path); if (rc) return rc; }
+    for (int c = 0; c < s->C; c++) { const int rc = sonde_rs92_dec_load_almanac(s->decoder<sonde_rs92_dec_t>(c), path); if (rc) return rc; }
     return 0;
 }
 
 void sonde_softin_dev_destroy(sonde_softin_dev_t *s) {
     if (!s) return;
     if (s->pending && s->pend_stream) (void)hipStreamSynchronize(s->pend_stream);
-    if (s->own_stream && s->stream) { hipStreamSynchronize(s->stream); hipStreamDestroy(s->stream); }
-    if (s->h_count) hipHostFree(s->h_count);
-    if (s->h_nbits) hipHostFree(s->h_nbits);
-    if (s->d_nbits) hipFree(s->d_nbits);
+    if (s->stream) { hipStreamSynchronize(s->stream); hipStreamDestroy(s->stream); }
+    for (const auto &p : s->allocs) { if (p.second) (void)hipHostFree(p.first); else (void)hipFree(p.first); }
     (void)hipGetLastError();
-    void *p[] = { s->d_chan, s->d_frames, s->d_hdr, s->d_gf, s->d_synd, s->d_flen, s->d_ecc, s->d_codes, s->d_meta, s->d_count, s->d_dfm_chan, s->d_dfm_out, s->d_m10_chan, s->d_m10_out, s->d_m20_chan, s->d_m20_out, s->d_drop_chan, s->d_drop_out, s->d_l6_chan, s->d_l6_out, s->d_l6_list, s->d_r92_chan, s->d_r92_out, s->d_i54_chan, s->d_i54_out, s->d_i54_tab, s->d_mei_chan, s->d_mei_out };
-    for (void *q : p) if (q) hipFree(q);
-    for (sonde_lms6_dec_t *d : s->l6_dec) sonde_lms6_dec_destroy(d);
-    for (sonde_rs92_dec_t *d : s->r92_dec) sonde_rs92_dec_destroy(d);
-    for (sonde_imet54_dec_t *d : s->i54_dec) sonde_imet54_dec_destroy(d);
-    for (sonde_meisei_dec_t *d : s->mei_dec) sonde_meisei_dec_destroy(d);
+    for (void *d : s->dec) s->dec_free(d);
     delete s;
 }
 
-// one pass of the framer (and rs41_ecc() over the frames it completes) over the channels of ch_list (null: all), its records behind the `off` records the
-// call already has; counter `which` of d_count
-static int softin_finish_lms6(sonde_softin_dev *s, hipStream_t st, long long n);
-static int softin_pass(sonde_softin_dev *s, hipStream_t st, const int off, const int nblocks, const int *ch_list, const int which) {
+// one pass of the framer (and rs41_ecc() over the frames it completes) over the channels of ch_list (null: all)
+static int softin_pass(sonde_softin_dev *s, hipStream_t st, const int nblocks, const int *ch_list) {
     SoftinArgs a = s->args;
-    if (s->type != SONDE_LMS6 && s->type != SONDE_RS92 && s->type != SONDE_IMET54 && s->type != SONDE_MEISEI) { a.frames += (size_t)off * 518; a.flen += off; a.meta += off; }
-    a.cap = s->cap - off; a.count = s->d_count + which; a.ch_list = ch_list;
+    a.ch_list = ch_list;
     HIPCHK(hipMemsetAsync(a.count, 0, 4, st));
-    if (s->type == SONDE_DFM09) { SoftinDfmArgs d{a, s->d_dfm_chan, s->d_dfm_out + off, s->ecc_level}; hipLaunchKernelGGL(k_softin_dfm, dim3(nblocks), dim3(64), 0, st, d); }
-    else if (s->type == SONDE_M10) {
-        // LDS for the call's soft decisions: what a call can hold (a modem launch: its capacity; a pushed stream: its length), up to M10_STAGE_MAX
-        long long need = a.fsk_chan || a.nbits_ch ? a.ch_stride : a.nbits;
-        if (need > M10_STAGE_MAX || need < 0) need = 0;
-        SoftinM10Args m{a, s->d_m10_chan, s->d_m10_out + off, (int)need};
-        static size_t attr = 0;
-        const size_t lds = (size_t)need * sizeof(float);
-        if (lds > attr) { if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_softin_m10), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess) attr = lds; else m.stage_cap = 0; }
-        hipLaunchKernelGGL(k_softin_m10, dim3(nblocks), dim3(64), m.stage_cap ? lds : 0, st, m);
-    }
-    else if (s->type == SONDE_M20) {
-        // (LDS for the call's soft decisions as for M10)
-        long long need = a.fsk_chan || a.nbits_ch ? a.ch_stride : a.nbits;
-        if (need > M10_STAGE_MAX || need < 0) need = 0;
-        SoftinM20Args m{a, s->d_m20_chan, s->d_m20_out + off, (int)need, s->m20_skip};
-        static size_t attr = 0;
-        const size_t lds = (size_t)need * sizeof(float);
-        if (lds > attr) { if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_softin_m20), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess) attr = lds; else m.stage_cap = 0; }
-        hipLaunchKernelGGL(k_softin_m20, dim3(nblocks), dim3(64), m.stage_cap ? lds : 0, st, m);
-    }
-    else if (s->type == SONDE_RS92) {
-        // (LDS for the call's soft decisions as for M10)
-        long long need = a.fsk_chan || a.nbits_ch ? a.ch_stride : a.nbits;
-        if (need > M10_STAGE_MAX || need < 0) need = 0;
-        SoftinRs92Args m{a, s->d_r92_chan, s->d_r92_out + off, s->d_gf, (int)need, s->r92_inv};
-        static size_t attr = 0;
-        const size_t lds = (size_t)need * sizeof(float);
-        if (lds > attr) { if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_softin_rs92), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess) attr = lds; else m.stage_cap = 0; }
-        hipLaunchKernelGGL(k_softin_rs92, dim3(nblocks), dim3(64), m.stage_cap ? lds : 0, st, m);
-    }
-    else if (s->type == SONDE_IMET54) {
-        // (LDS for the call's soft decisions as for M10)
-        long long need = a.fsk_chan || a.nbits_ch ? a.ch_stride : a.nbits;
-        if (need > M10_STAGE_MAX || need < 0) need = 0;
-        SoftinImet54Args m{a, s->d_i54_chan, s->d_i54_out + off, s->d_i54_tab, (int)need, s->i54_ecc};
-        static size_t attr = 0;
-        const size_t lds = (size_t)need * sizeof(float);
-        if (lds > attr) { if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_softin_imet54), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess) attr = lds; else m.stage_cap = 0; }
-        hipLaunchKernelGGL(k_softin_imet54, dim3(nblocks), dim3(64), m.stage_cap ? lds : 0, st, m);
-    }
-    else if (s->type == SONDE_MEISEI) {
-        // (LDS for the call's soft decisions as for M10)
-        long long need = a.fsk_chan || a.nbits_ch ? a.ch_stride : a.nbits;
-        if (need > M10_STAGE_MAX || need < 0) need = 0;
-        SoftinMeiseiArgs m{a, s->d_mei_chan, s->d_mei_out + off, (int)need, s->mei_ecc};
-        static size_t attr = 0;
-        const size_t lds = (size_t)need * sizeof(float);
-        if (lds > attr) { if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_softin_meisei), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess) attr = lds; else m.stage_cap = 0; }
-        hipLaunchKernelGGL(k_softin_meisei, dim3(nblocks), dim3(64), m.stage_cap ? lds : 0, st, m);
-    }
-    else if (s->type == SONDE_RD94RD41) { SoftinDropArgs d{a, s->d_drop_chan, s->d_drop_out + off, s->drop_inv}; hipLaunchKernelGGL(k_softin_drop, dim3(nblocks), dim3(64), 0, st, d); }
-    else if (s->type == SONDE_LMS6) { SoftinLms6Args d{a, s->d_l6_chan, s->d_l6_out + off, s->l6_vit, s->l6_auto}; hipLaunchKernelGGL(k_softin_lms6, dim3(nblocks), dim3(64), 0, st, d); }
-    else {
-        hipLaunchKernelGGL(k_softin_rs41, dim3(nblocks), dim3(64), 0, st, a);
-        if (s->ecc_level > 0)
-            sonde_launch_rs41_ecc_batch_n(a.frames, a.flen, a.count, a.cap, s->ecc_level, s->d_ecc + off, s->d_codes + 2 * (size_t)off, s->d_synd + 48 * (size_t)off, s->d_gf, s->d_gf + 512, st);
-    }
+    s->kind->launch(s, a, nblocks, st);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(s->h_count + which, a.count, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(s->h_count, a.count, 4, hipMemcpyDeviceToHost, st));
     return 0;
 }
 // records [from, to) of the call to the host
 static int softin_copy(sonde_softin_dev *s, hipStream_t st, const int from, const int to) {
     if (to <= from) return 0;
-    const size_t n = (size_t)(to - from);
-    if (s->type == SONDE_DFM09) HIPCHK(hipMemcpyAsync(s->h_dfm.data() + from, s->d_dfm_out + from, n * sizeof(sonde_dfm_frame_t), hipMemcpyDeviceToHost, st));
-    else if (s->type == SONDE_M10) HIPCHK(hipMemcpyAsync(s->h_m10.data() + from, s->d_m10_out + from, n * sizeof(sonde_m10_frame_t), hipMemcpyDeviceToHost, st));
-    else if (s->type == SONDE_M20) HIPCHK(hipMemcpyAsync(s->h_m20.data() + from, s->d_m20_out + from, n * sizeof(sonde_m20_frame_t), hipMemcpyDeviceToHost, st));
-    else if (s->type == SONDE_RD94RD41) HIPCHK(hipMemcpyAsync(s->h_drop.data() + from, s->d_drop_out + from, n * sizeof(DropFrame), hipMemcpyDeviceToHost, st));
-    else if (s->type == SONDE_RS92) HIPCHK(hipMemcpyAsync(s->h_r92.data() + from, s->d_r92_out + from, n * sizeof(SoftinRs92Rec), hipMemcpyDeviceToHost, st));
-    else if (s->type == SONDE_IMET54) HIPCHK(hipMemcpyAsync(s->h_i54.data() + from, s->d_i54_out + from, n * sizeof(SoftinImet54Rec), hipMemcpyDeviceToHost, st));
-    else if (s->type == SONDE_MEISEI) HIPCHK(hipMemcpyAsync(s->h_mei.data() + from, s->d_mei_out + from, n * sizeof(SoftinMeiseiRec), hipMemcpyDeviceToHost, st));
-    else if (s->type == SONDE_LMS6) HIPCHK(hipMemcpyAsync(s->h_l6.data() + from, s->d_l6_out + from, n * sizeof(Lms6Block), hipMemcpyDeviceToHost, st));
+    const size_t n = (size_t)(to - from), rec = s->kind->rec;
+    if (rec) HIPCHK(hipMemcpyAsync(s->h_rec + from * rec, s->d_rec + from * rec, n * rec, hipMemcpyDeviceToHost, st));
     else {
-        HIPCHK(hipMemcpyAsync(s->h_meta.data() + from, s->d_meta + from, n * sizeof(SoftinMeta), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(s->h_ecc.data() + from, s->d_ecc + from, n * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(s->h_frames.data() + (size_t)from * 518, s->d_frames + (size_t)from * 518, n * 518, hipMemcpyDeviceToHost, st));   // 518 bytes per frame and second: not the soft decisions
+        HIPCHK(hipMemcpyAsync(s->h_meta + from, s->d_meta + from, n * sizeof(SoftinMeta), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(s->h_ecc + from, s->d_ecc + from, n * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(s->h_frames + (size_t)from * 518, s->d_frames + (size_t)from * 518, n * 518, hipMemcpyDeviceToHost, st));   // 518 bytes per frame and second: not the soft decisions
     }
     return 0;
 }
@@ -1187,41 +1163,45 @@ static int softin_finish_lms6(sonde_softin_dev *s, hipStream_t st, long long n) 
     for (;;) {
         int nlist = 0;
         for (long long i = 0; i < n; i++) {
-            const Lms6Block &b = s->h_l6[i];
+            const Lms6Block &b = s->landed<Lms6Block>(i);
             if (b.channel < 0 || b.channel >= s->C) continue;
-            sonde_lms6_dec_t *d = s->l6_dec[(size_t)b.channel];
+            sonde_lms6_dec_t *d = s->decoder<sonde_lms6_dec_t>(b.channel);
             sonde_lms6_softin_t r; memset(&r, 0, sizeof r);
             const float nanv = __builtin_nanf("");             // dsp_t stays zeroed with soft input: frm_rate and the elapsed time are 0 / 0
             const int len = sonde_lms6_dec_block_bytes(d, b.bytes, b.blen, b.pos, b.mv, nanv, (double)nanv, r.text, sizeof r.text);
             if (len < 0) return len;
             r.channel = b.channel; r.type = sonde_lms6_dec_type(d, nullptr); r.mv = b.mv; r.text_len = len; r.hdr_bit = b.hdr_bit; r.blen = b.blen; r.err = b.err;
-            s->ql6.push_back(r);
+            s->queue(r);
             s->frames_total++;
             int64_t ok = 0;
             (void)sonde_lms6_dec_counts(d, nullptr, &ok);                 // the decoder's own tally of CRC-good frames, whatever the output form
             s->ecc_ok_total += ok - s->l6_ok[(size_t)b.channel]; s->l6_ok[(size_t)b.channel] = ok;
             const int want = sonde_lms6_dec_block_bits(d) + LMS6_BLOCKSTART;
             if (want != s->l6_len[(size_t)b.channel]) {
-                s->l6_len[(size_t)b.channel] = want; s->h_l6_len[(size_t)b.channel] = want;
-                HIPCHK(hipMemcpyAsync(&s->d_l6_chan[b.channel].rawblk_len, &s->h_l6_len[(size_t)b.channel], sizeof(int), hipMemcpyHostToDevice, st));
+                s->l6_len[(size_t)b.channel] = want; s->h_l6_len[b.channel] = want;
+                HIPCHK(hipMemcpyAsync(&s->chan<Lms6Chan>()[b.channel].rawblk_len, &s->h_l6_len[b.channel], sizeof(int), hipMemcpyHostToDevice, st));
             }
-            if (b.more && nlist < s->C) s->h_l6_list[(size_t)nlist++] = b.channel;
+            if (b.more && nlist < s->C) s->h_l6_list[nlist++] = b.channel;
         }
         if (!nlist) return 0;
-        HIPCHK(hipMemcpyAsync(s->d_l6_list, s->h_l6_list.data(), (size_t)nlist * sizeof(int), hipMemcpyHostToDevice, st));
-        { const int rc = softin_pass(s, st, 0, nlist, s->d_l6_list, 0); if (rc) return rc; }
+        HIPCHK(hipMemcpyAsync(s->d_l6_list, s->h_l6_list, (size_t)nlist * sizeof(int), hipMemcpyHostToDevice, st));
+        { const int rc = softin_pass(s, st, nlist, s->d_l6_list); if (rc) return rc; }
         { const int rc = softin_copy(s, st, 0, std::min(nlist, s->cap)); if (rc) return rc; }
         HIPCHK(hipStreamSynchronize(st));
         n = std::min<long long>(s->h_count[0], std::min(nlist, s->cap));
     }
 }
 
+static int softin_own_stream(sonde_softin_dev *s) {
+    if (!s->stream) HIPCHK(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
+    return 0;
+}
 // enqueue a call: the framer over what args.sd / nbits describe, the block code, the counter and the records a call normally completes (`head`) on their way to the host
-static int softin_enqueue(sonde_softin_dev *s, hipStream_t st) {
+static int softin_enqueue(sonde_softin_dev *s) {
     if (s->pending) return SONDE_E_ARG;
-    { const int rc = softin_pass(s, st, 0, s->C, nullptr, 0); if (rc) return rc; }
-    { const int rc = softin_copy(s, st, 0, s->head); if (rc) return rc; }
-    s->pending = true; s->pend_stream = st;
+    { const int rc = softin_pass(s, s->stream, s->C, nullptr); if (rc) return rc; }
+    { const int rc = softin_copy(s, s->stream, 0, s->head); if (rc) return rc; }
+    s->pending = true; s->pend_stream = s->stream;
     return 0;
 }
 // the other half: wait, take what the head did not cover, queue the frames and add up the tallies
@@ -1235,125 +1215,45 @@ static int softin_finish(sonde_softin_dev *s) {
     const int have = (int)std::min<long long>(n, s->head);
     if (n > have) { const int rc = softin_copy(s, st, have, (int)n); if (rc) return rc; HIPCHK(hipStreamSynchronize(st)); }
     if (s->type == SONDE_LMS6) return softin_finish_lms6(s, st, n);
-    if (s->type == SONDE_RS92) {
-        // (frames of one channel in order: the slots of a call are handed out in completion order per channel, channels interleave)
-        for (long long i = 0; i < n; i++) {
-            const SoftinRs92Rec &r = s->h_r92[i];
-            if (r.channel < 0 || r.channel >= s->C) continue;
-            s->qr92.push_back(r); s->frames_total++;
-            if (r.ec >= 0) s->ecc_ok_total++;
-            if (r.ec > 0) { s->repaired_total++; s->symbols_total += r.ec; }
-        }
-        return 0;
-    }
-    if (s->type == SONDE_IMET54) {
-        for (long long i = 0; i < n; i++) {
-            const SoftinImet54Rec &r = s->h_i54[i];
-            if (r.channel < 0 || r.channel >= s->C) continue;
-            s->qi54.push_back(r); s->frames_total++;
-            // the JSON rule without the status bits (imet54mod.c:583): frm_ok and a check sum good, or every codeword of the standard frame clean
-            if (r.ecc_frm >= 0 && (r.crc_std || r.crc_cont || r.ecc_std == 0)) s->ecc_ok_total++;
-            if (r.ecc_frm > 0) { s->repaired_total++; s->symbols_total += r.ecc_frm; }
-        }
-        return 0;
-    }
-    if (s->type == SONDE_MEISEI) {
-        for (long long i = 0; i < n; i++) {
-            const SoftinMeiseiRec &r = s->h_mei[i];
-            if (r.channel < 0 || r.channel >= s->C) continue;
-            s->qmei.push_back(r); s->frames_total++;
-            int bad = 0, fixed = 0;
-            for (int k = 0; k < MEISEI_BLOCKS; k++) { if (r.block_err[k] >= 0xE) bad++; else fixed += r.block_err[k]; }
-            if (!bad) s->ecc_ok_total++;
-            if (fixed) { s->repaired_total++; s->symbols_total += fixed; }
-        }
-        return 0;
-    }
-    if (s->type == SONDE_DFM09) {
-        // (frames of one channel in order: the slots of a call are handed out in completion order per channel, channels interleave)
-        for (long long i = 0; i < n; i++) {
-            const sonde_dfm_frame_t &f = s->h_dfm[i];
-            s->qdfm.push_back(f); s->frames_total++;
-            const bool okf = f.ecc[0] >= 0 && f.ecc[1] >= 0 && f.ecc[2] >= 0;
-            if (okf) s->ecc_ok_total++;
-            if (okf && (f.ecc[0] > 0 || f.ecc[1] > 0 || f.ecc[2] > 0)) { s->repaired_total++; s->symbols_total += __builtin_popcount((unsigned)f.ecc[0]) + __builtin_popcount((unsigned)f.ecc[1]) + __builtin_popcount((unsigned)f.ecc[2]); }
-        }
-    } else if (s->type == SONDE_M10) {
-        for (long long i = 0; i < n; i++) { s->qm10.push_back(s->h_m10[i]); s->frames_total++; if (s->h_m10[i].cs_ok) s->ecc_ok_total++; }
-    } else if (s->type == SONDE_M20) {
-        for (long long i = 0; i < n; i++) { s->qm20.push_back(s->h_m20[i]); s->frames_total++; if (s->h_m20[i].cs_ok) s->ecc_ok_total++; }
-    } else if (s->type == SONDE_RD94RD41) {
-        for (long long i = 0; i < n; i++) {
-            const DropFrame &g = s->h_drop[i];
-            sonde_drop_frame_t f; memset(&f, 0, sizeof f);
-            f.channel = g.channel; f.nraw = g.nraw; f.complete = g.complete; f.err94 = g.err94; f.err41 = g.err41; f.sample = g.sample;
-            memcpy(f.bytes, g.bytes, sizeof f.bytes);
-            s->qdrop.push_back(f); s->frames_total++;
-            // print_frame's type choice and frm_ok (rd94rd41drop.c:1028-1038, :1213): more than two failing RD41 blocks = RD94
-            if (__builtin_popcount((unsigned)g.err41) > 2 ? g.err94 == 0 : g.err41 == 0) s->ecc_ok_total++;
-        }
-    } else {
-        for (long long i = 0; i < n; i++) {
-            sonde_frame_t f; memset(&f, 0, sizeof f);
-            const SoftinMeta &m = s->h_meta[i];
-            f.channel = m.channel; f.len = m.len; f.nbytes = m.nbytes; f.mv = m.mv; f.mv_pos = (uint32_t)m.hdr_bit;
-            f.ecc = s->ecc_level > 0 ? s->h_ecc[i] : 0;
-            memcpy(f.frame, s->h_frames.data() + (size_t)i * 518, 518);
-            s->queue.push_back(f);
-            s->frames_total++;
-            if (f.ecc >= 0) s->ecc_ok_total++;
-            if (f.ecc > 0) { s->repaired_total++; s->symbols_total += f.ecc; }
-        }
-    }
+    s->kind->tally(s, n);
     return 0;
 }
 
-// the modem's last launch (waited for first: its channels' frame counts come from the host's copy of the records, and whatever the modem had to repeat is repeated by
-// then) as this call's input: the soft decisions where that launch left them, the bits per channel uploaded
-static int softin_bind_fsk(sonde_softin_dev *s, sonde_fsk_t *modem, hipStream_t st) {
-    const float *d_sd = nullptr; long long cap = 0; const FskChan *d_chan = nullptr; int bpf = 0, nch = 0; hipStream_t ms = nullptr;
-    { const int rc = sonde_fsk_wait(modem); if (rc) return rc; }
-    const int rc = sonde_fsk_dev_view(modem, &d_sd, &cap, &d_chan, &bpf, &nch, &ms);
-    if (rc) return rc;
-    if (nch != s->C) return SONDE_E_ARG;
-    if (!s->h_nbits) {
-        if (hipHostMalloc((void **)&s->h_nbits, (size_t)s->C * sizeof(int)) != hipSuccess || hipMalloc((void **)&s->d_nbits, (size_t)s->C * sizeof(int)) != hipSuccess) return SONDE_E_NOMEM;
-    }
-    { const int rc2 = sonde_fsk_host_frames(modem, s->h_nbits); if (rc2) return rc2; }
+// A launch of the modem as this call's input: its soft decisions where that launch left them (d_sd, `cap` a channel), the bits per channel — h_nbits holds the
+// channels' frame counts, bpf bits each — uploaded; then the call is enqueued.  LMS6 with auto detection launches again per completed block and reads the soft
+// decisions each time: its call is completed here, so that the point of the stream the modem is told about next lies behind every read — whatever the caller
+// does before sonde_softin_dev_collect.
+static int softin_consume_launch(sonde_softin_dev *s, const float *d_sd, const long long cap, const int bpf) {
     for (int c = 0; c < s->C; c++) s->h_nbits[c] = s->h_nbits[c] > 0 ? s->h_nbits[c] * bpf : 0;
-    HIPCHK(hipMemcpyAsync(s->d_nbits, s->h_nbits, (size_t)s->C * sizeof(int), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(s->d_nbits, s->h_nbits, (size_t)s->C * sizeof(int), hipMemcpyHostToDevice, s->stream));
     SoftinArgs &a = s->args;
-    a.sd = d_sd; a.ch_stride = cap; a.fsk_chan = nullptr; a.bits_per_frame = bpf; a.nbits_ch = s->d_nbits; a.nbits = 0;
+    a.sd = d_sd; a.ch_stride = cap; a.nbits_ch = s->d_nbits; a.nbits = 0;
+    { const int rc = softin_enqueue(s); if (rc) return rc; }
+    if (s->type == SONDE_LMS6 && s->l6_auto) return softin_finish(s);
     return 0;
 }
-static int softin_own_stream(sonde_softin_dev *s) {
-    if (!s->stream) { HIPCHK(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking)); s->own_stream = true; }
-    return 0;
-}
-int sonde_softin_dev_push_fsk(sonde_softin_dev_t *s, sonde_fsk_t *modem) {
-    if (!s || !modem) return SONDE_E_ARG;
-    { const int rc = softin_finish(s); if (rc) return rc; }
-    { const int rc = softin_own_stream(s); if (rc) return rc; }
-    { const int rc = softin_bind_fsk(s, modem, s->stream); if (rc) return rc; }
-    { const int rc = softin_enqueue(s, s->stream); if (rc) return rc; }
-    { const int rc = sonde_fsk_dev_reader_done(modem, s->stream); if (rc) return rc; }
-    return softin_finish(s);
-}
-// the same in two halves: submit waits for the modem's launch (sonde_fsk_wait), then enqueues the consumer's kernels and the copies of its frames on the consumer's OWN
-// stream and returns; collect waits for them.  In between the modem can be given its next second (sonde_fsk_submit_device): the modem keeps the soft decisions of two
-// launches (they alternate between two buffers), so the consumer of second k runs beside the modem of second k + 1.  Collect before the modem's launch after that.
+
+// Submit waits for the modem's launch (sonde_fsk_wait: its channels' frame counts come from the host's copy of the records, and whatever the modem had to repeat is
+// repeated by then), then enqueues the consumer's kernels and the copies of its frames on the consumer's OWN stream and returns; collect waits for them.  In between
+// the modem can be given its next second (sonde_fsk_submit_device): the modem keeps the soft decisions of two launches (they alternate between two buffers), so the
+// consumer of second k runs beside the modem of second k + 1.  Collect before the modem's launch after that.
 int sonde_softin_dev_submit_fsk(sonde_softin_dev_t *s, sonde_fsk_t *modem) {
     if (!s || !modem) return SONDE_E_ARG;
     { const int rc = softin_finish(s); if (rc) return rc; }
     { const int rc = softin_own_stream(s); if (rc) return rc; }
-    { const int rc = softin_bind_fsk(s, modem, s->stream); if (rc) return rc; }
-    { const int rc = softin_enqueue(s, s->stream); if (rc) return rc; }
-    // LMS6 with auto detection launches again per completed block and reads the soft decisions each time: the call is completed here, so that the point of the
-    // stream the modem is told about below lies behind every read — whatever the caller does before sonde_softin_dev_collect
-    if (s->type == SONDE_LMS6 && s->l6_auto) { const int rc = softin_finish(s); if (rc) return rc; }
+    const float *d_sd = nullptr; long long cap = 0; const FskChan *d_chan = nullptr; int bpf = 0, nch = 0; hipStream_t ms = nullptr;
+    { const int rc = sonde_fsk_wait(modem); if (rc) return rc; }
+    { const int rc = sonde_fsk_dev_view(modem, &d_sd, &cap, &d_chan, &bpf, &nch, &ms); if (rc) return rc; }
+    if (nch != s->C) return SONDE_E_ARG;
+    { const int rc = sonde_fsk_host_frames(modem, s->h_nbits); if (rc) return rc; }
+    { const int rc = softin_consume_launch(s, d_sd, cap, bpf); if (rc) return rc; }
     // the modem's launch that reuses this buffer of soft decisions (the next but one) waits for the consumer's kernels: submitting the modem twice before
     // sonde_softin_dev_collect is slower, not wrong
     return sonde_fsk_dev_reader_done(modem, s->stream);
+}
+int sonde_softin_dev_push_fsk(sonde_softin_dev_t *s, sonde_fsk_t *modem) {
+    const int rc = sonde_softin_dev_submit_fsk(s, modem);
+    return rc ? rc : softin_finish(s);
 }
 // The consumer over the launch BEFORE the one the modem has in flight: for a caller that hands the modem its next second first (sonde_fsk_wait (k - 1),
 // sonde_fsk_submit_device (k), then this for k - 1) — the modem's stream never waits for the host's decoder bookkeeping.  Nothing waits here; with no launch in
@@ -1362,21 +1262,13 @@ int sonde_softin_dev_submit_fsk_behind(sonde_softin_dev_t *s, sonde_fsk_t *modem
     if (!s || !modem) return SONDE_E_ARG;
     { const int rc = softin_finish(s); if (rc) return rc; }
     { const int rc = softin_own_stream(s); if (rc) return rc; }
-    if (!s->h_nbits) {
-        if (hipHostMalloc((void **)&s->h_nbits, (size_t)s->C * sizeof(int)) != hipSuccess || hipMalloc((void **)&s->d_nbits, (size_t)s->C * sizeof(int)) != hipSuccess) return SONDE_E_NOMEM;
-    }
     const float *d_sd = nullptr; long long cap = 0; int bpf = 0, nch = s->C;
     const int have = sonde_fsk_dev_view_prev(modem, &d_sd, &cap, &bpf, &nch, s->h_nbits);
     if (have < 0) return have;
     if (have == 0) return sonde_softin_dev_submit_fsk(s, modem);
     if (nch != s->C) return SONDE_E_ARG;
-    for (int c = 0; c < s->C; c++) s->h_nbits[c] = s->h_nbits[c] > 0 ? s->h_nbits[c] * bpf : 0;
-    HIPCHK(hipMemcpyAsync(s->d_nbits, s->h_nbits, (size_t)s->C * sizeof(int), hipMemcpyHostToDevice, s->stream));
-    SoftinArgs &a = s->args;
-    a.sd = d_sd; a.ch_stride = cap; a.fsk_chan = nullptr; a.bits_per_frame = bpf; a.nbits_ch = s->d_nbits; a.nbits = 0;
-    { const int rc = softin_enqueue(s, s->stream); if (rc) return rc; }
-    // (LMS6 with auto detection reads the soft decisions again in its later rounds, and the modem's launch in flight is the one that overwrites them next)
-    if (s->type == SONDE_LMS6 && s->l6_auto) { const int rc = softin_finish(s); if (rc) return rc; }
+    // (the modem's launch in flight is the one that overwrites these soft decisions next)
+    { const int rc = softin_consume_launch(s, d_sd, cap, bpf); if (rc) return rc; }
     return sonde_fsk_dev_reader_done_prev(modem, s->stream);
 }
 int sonde_softin_dev_collect(sonde_softin_dev_t *s) {
@@ -1387,136 +1279,90 @@ int sonde_softin_dev_collect(sonde_softin_dev_t *s) {
 int sonde_softin_dev_push_device(sonde_softin_dev_t *s, const float *d_soft, int64_t ch_stride, int32_t n_bits) {
     if (!s || !d_soft || n_bits < 0 || ch_stride < n_bits) return SONDE_E_ARG;
     { const int rc = softin_finish(s); if (rc) return rc; }
-    if (!s->stream) { HIPCHK(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking)); s->own_stream = true; }
+    { const int rc = softin_own_stream(s); if (rc) return rc; }
     SoftinArgs &a = s->args;
-    a.sd = d_soft; a.ch_stride = ch_stride; a.fsk_chan = nullptr; a.nbits_ch = nullptr; a.nbits = n_bits;
-    { const int rc = softin_enqueue(s, s->stream); if (rc) return rc; }
+    a.sd = d_soft; a.ch_stride = ch_stride; a.nbits_ch = nullptr; a.nbits = n_bits;
+    { const int rc = softin_enqueue(s); if (rc) return rc; }
     return softin_finish(s);
 }
 
-int sonde_softin_dev_fetch(sonde_softin_dev_t *s, sonde_frame_t *out, int32_t max) {
-    if (s && (s->type == SONDE_RS92 || s->type == SONDE_IMET54 || s->type == SONDE_MEISEI)) return SONDE_E_ARG;
-    if (s && s->pending) { const int rc_ = softin_finish(s); if (rc_) return rc_; }
-    if (!s || (!out && max > 0)) return SONDE_E_ARG;
-    const int n = (int)std::min<size_t>(s->queue.size(), (size_t)(max < 0 ? 0 : max));
-    for (int i = 0; i < n; i++) out[i] = s->queue[i];
-    s->queue.erase(s->queue.begin(), s->queue.begin() + n);
+}  // extern "C"
+
+// Every fetch call: up to max of the queued records Q of a consumer of `type`, each through conv into out[i].  A consumer of another kind has no such records; the
+// calls of the kinds whose records carry a text made at fetch time (RS92, iMet-54, Meisei) and of M20 say so (SONDE_E_ARG), and so does every call on a consumer
+// of one of the three text kinds; the older calls on the older kinds return an empty queue.
+static bool softin_text_kind(const int t) { return t == SONDE_RS92 || t == SONDE_IMET54 || t == SONDE_MEISEI; }
+// -> how many records of `rec` bytes this call takes from the front of the queue, or the error
+static int softin_fetch_count(sonde_softin_dev *s, const int type, const bool have_out, const int32_t max, const size_t rec) {
+    if (!s) return SONDE_E_ARG;
+    if (s->type != type && (type == SONDE_M20 || softin_text_kind(type) || softin_text_kind(s->type))) return SONDE_E_ARG;
+    if (!have_out && max > 0) return SONDE_E_ARG;
+    { const int rc = softin_finish(s); if (rc) return rc; }
+    if (s->type != type) return 0;
+    return (int)std::min<size_t>(s->q.size() / rec, (size_t)(max < 0 ? 0 : max));
+}
+template <class T> static int softin_fetch_plain(sonde_softin_dev *s, const int type, T *out, const int32_t max) {
+    const int n = softin_fetch_count(s, type, out != nullptr, max, sizeof(T));
+    if (n > 0) { memcpy((void *)out, s->q.data(), (size_t)n * sizeof(T)); s->q.erase(s->q.begin(), s->q.begin() + (size_t)n * sizeof(T)); }
+    return n;
+}
+template <class Q, class O, class F>
+static int softin_fetch(sonde_softin_dev *s, const int type, O *out, const int32_t max, const F &conv) {
+    const int n = softin_fetch_count(s, type, out != nullptr, max, sizeof(Q));
+    for (int i = 0; i < n; i++) { Q r; memcpy((void *)&r, s->q.data() + (size_t)i * sizeof(Q), sizeof(Q)); conv(r, out[i]); }
+    if (n > 0) s->q.erase(s->q.begin(), s->q.begin() + (size_t)n * sizeof(Q));
     return n;
 }
 
-int sonde_softin_dev_fetch_dfm(sonde_softin_dev_t *s, sonde_dfm_frame_t *out, int32_t max) {
-    if (s && (s->type == SONDE_RS92 || s->type == SONDE_IMET54 || s->type == SONDE_MEISEI)) return SONDE_E_ARG;
-    if (s && s->pending) { const int rc_ = softin_finish(s); if (rc_) return rc_; }
-    if (!s || (!out && max > 0)) return SONDE_E_ARG;
-    const int n = (int)std::min<size_t>(s->qdfm.size(), (size_t)(max < 0 ? 0 : max));
-    for (int i = 0; i < n; i++) out[i] = s->qdfm[i];
-    s->qdfm.erase(s->qdfm.begin(), s->qdfm.begin() + n);
-    return n;
-}
+extern "C" {
 
-int sonde_softin_dev_fetch_m10(sonde_softin_dev_t *s, sonde_m10_frame_t *out, int32_t max) {
-    if (s && (s->type == SONDE_RS92 || s->type == SONDE_IMET54 || s->type == SONDE_MEISEI)) return SONDE_E_ARG;
-    if (s && s->pending) { const int rc_ = softin_finish(s); if (rc_) return rc_; }
-    if (!s || (!out && max > 0)) return SONDE_E_ARG;
-    const int n = (int)std::min<size_t>(s->qm10.size(), (size_t)(max < 0 ? 0 : max));
-    for (int i = 0; i < n; i++) out[i] = s->qm10[i];
-    s->qm10.erase(s->qm10.begin(), s->qm10.begin() + n);
-    return n;
-}
+int sonde_softin_dev_fetch(sonde_softin_dev_t *s, sonde_frame_t *out, int32_t max) { return softin_fetch_plain(s, SONDE_RS41, out, max); }
+int sonde_softin_dev_fetch_dfm(sonde_softin_dev_t *s, sonde_dfm_frame_t *out, int32_t max) { return softin_fetch_plain(s, SONDE_DFM09, out, max); }
+int sonde_softin_dev_fetch_m10(sonde_softin_dev_t *s, sonde_m10_frame_t *out, int32_t max) { return softin_fetch_plain(s, SONDE_M10, out, max); }
+int sonde_softin_dev_fetch_m20(sonde_softin_dev_t *s, sonde_m20_frame_t *out, int32_t max) { return softin_fetch_plain(s, SONDE_M20, out, max); }
+int sonde_softin_dev_fetch_drop(sonde_softin_dev_t *s, sonde_drop_frame_t *out, int32_t max) { return softin_fetch_plain(s, SONDE_RD94RD41, out, max); }
+int sonde_softin_dev_fetch_lms6(sonde_softin_dev_t *s, sonde_lms6_softin_t *out, int32_t max) { return softin_fetch_plain(s, SONDE_LMS6, out, max); }
 
 int sonde_softin_dev_set_m20_skip(sonde_softin_dev_t *s, int32_t skip) {
     if (!s || s->type != SONDE_M20) return SONDE_E_ARG;
-    s->m20_skip = skip != 0;                       // (takes effect with the next call; a call in flight has its own copy)
+    s->opt = skip != 0;                            // (takes effect with the next call; a call in flight has its own copy)
     return 0;
 }
 
-int sonde_softin_dev_fetch_m20(sonde_softin_dev_t *s, sonde_m20_frame_t *out, int32_t max) {
-    if (!s || s->type != SONDE_M20 || (!out && max > 0)) return SONDE_E_ARG;
-    if (s->pending) { const int rc_ = softin_finish(s); if (rc_) return rc_; }
-    const int n = (int)std::min<size_t>(s->qm20.size(), (size_t)(max < 0 ? 0 : max));
-    for (int i = 0; i < n; i++) out[i] = s->qm20[i];
-    s->qm20.erase(s->qm20.begin(), s->qm20.begin() + n);
-    return n;
-}
-
-int sonde_softin_dev_fetch_drop(sonde_softin_dev_t *s, sonde_drop_frame_t *out, int32_t max) {
-    if (s && (s->type == SONDE_RS92 || s->type == SONDE_IMET54 || s->type == SONDE_MEISEI)) return SONDE_E_ARG;
-    if (s && s->pending) { const int rc_ = softin_finish(s); if (rc_) return rc_; }
-    if (!s || (!out && max > 0)) return SONDE_E_ARG;
-    const int n = (int)std::min<size_t>(s->qdrop.size(), (size_t)(max < 0 ? 0 : max));
-    for (int i = 0; i < n; i++) out[i] = s->qdrop[i];
-    s->qdrop.erase(s->qdrop.begin(), s->qdrop.begin() + n);
-    return n;
-}
-
-int sonde_softin_dev_fetch_lms6(sonde_softin_dev_t *s, sonde_lms6_softin_t *out, int32_t max) {
-    if (s && (s->type == SONDE_RS92 || s->type == SONDE_IMET54 || s->type == SONDE_MEISEI)) return SONDE_E_ARG;
-    if (s && s->pending) { const int rc_ = softin_finish(s); if (rc_) return rc_; }
-    if (!s || (!out && max > 0)) return SONDE_E_ARG;
-    const int n = (int)std::min<size_t>(s->ql6.size(), (size_t)(max < 0 ? 0 : max));
-    for (int i = 0; i < n; i++) out[i] = s->ql6[i];
-    s->ql6.erase(s->ql6.begin(), s->ql6.begin() + n);
-    return n;
-}
-
+// The text of a record is made here, by the channel's own decoder and from the device's bytes and verdicts, not in the push call: collect stays short.
+// (a negative text_len: the text did not fit; the frame is delivered all the same)
 int sonde_softin_dev_fetch_rs92(sonde_softin_dev_t *s, sonde_rs92_softin_t *out, int32_t max) {
-    if (!s || s->type != SONDE_RS92 || (!out && max > 0)) return SONDE_E_ARG;
-    if (s->pending) { const int rc_ = softin_finish(s); if (rc_) return rc_; }
-    const int n = (int)std::min<size_t>(s->qr92.size(), (size_t)(max < 0 ? 0 : max));
-    for (int i = 0; i < n; i++) {
-        // print_frame behind rs92_ecc, by the channel's own decoder (its calibration rows, its orbit data): here, not in the push call, so that collect stays short
-        const SoftinRs92Rec &r = s->qr92[i];
-        sonde_rs92_softin_t &o = out[i];
+    return softin_fetch<SoftinRs92Rec>(s, SONDE_RS92, out, max, [s](const SoftinRs92Rec &r, sonde_rs92_softin_t &o) {
+        // print_frame behind rs92_ecc (the decoder's calibration rows, its orbit data)
         o.channel = r.channel; o.ec = r.ec; o.mv = r.mv; o.hdr_bit = r.hdr_bit;
         memcpy(o.frame, r.frame, sizeof o.frame);
-        const int len = sonde_rs92_dec_corrected(s->r92_dec[(size_t)r.channel], r.frame, r.ec, o.text, sizeof o.text);
-        o.text_len = len;                                      // (negative: the text did not fit; the frame is delivered all the same)
-        if (len < 0) o.text[0] = 0;
-    }
-    s->qr92.erase(s->qr92.begin(), s->qr92.begin() + n);
-    return n;
+        o.text_len = sonde_rs92_dec_corrected(s->decoder<sonde_rs92_dec_t>(r.channel), r.frame, r.ec, o.text, sizeof o.text);
+        if (o.text_len < 0) o.text[0] = 0;
+    });
 }
-
 int sonde_softin_dev_fetch_imet54(sonde_softin_dev_t *s, sonde_imet54_softin_t *out, int32_t max) {
-    if (!s || s->type != SONDE_IMET54 || (!out && max > 0)) return SONDE_E_ARG;
-    if (s->pending) { const int rc_ = softin_finish(s); if (rc_) return rc_; }
-    const int n = (int)std::min<size_t>(s->qi54.size(), (size_t)(max < 0 ? 0 : max));
-    for (int i = 0; i < n; i++) {
-        // print_frame behind the Hamming step, by the channel's own decoder and from the device's verdicts: here, not in the push call, so that collect stays short
-        const SoftinImet54Rec &r = s->qi54[i];
-        sonde_imet54_softin_t &o = out[i];
+    return softin_fetch<SoftinImet54Rec>(s, SONDE_IMET54, out, max, [s](const SoftinImet54Rec &r, sonde_imet54_softin_t &o) {
+        // print_frame behind the Hamming step
         o.channel = r.channel; o.ecc_frm = r.ecc_frm; o.ecc_tlm = r.ecc_tlm; o.ecc_std = r.ecc_std; o.crc = r.crc_std ? 1 : r.crc_cont ? 2 : 0; o.mv = r.mv; o.hdr_bit = r.hdr_bit;
         memcpy(o.frame, r.frame, sizeof o.frame);
-        const int len = sonde_imet54_dec_decoded(s->i54_dec[(size_t)r.channel], r.frame, r.ecc_frm, r.ecc_tlm, r.ecc_std, r.crc_std, r.crc_cont, o.text, sizeof o.text);
-        o.text_len = len;                                      // (negative: the text did not fit; the frame is delivered all the same)
-        if (len < 0) o.text[0] = 0;
-    }
-    s->qi54.erase(s->qi54.begin(), s->qi54.begin() + n);
-    return n;
+        o.text_len = sonde_imet54_dec_decoded(s->decoder<sonde_imet54_dec_t>(r.channel), r.frame, r.ecc_frm, r.ecc_tlm, r.ecc_std, r.crc_std, r.crc_cont, o.text, sizeof o.text);
+        if (o.text_len < 0) o.text[0] = 0;
+    });
 }
-
 int sonde_softin_dev_fetch_meisei(sonde_softin_dev_t *s, sonde_meisei_softin_t *out, int32_t max) {
-    if (!s || s->type != SONDE_MEISEI || (!out && max > 0)) return SONDE_E_ARG;
-    if (s->pending) { const int rc_ = softin_finish(s); if (rc_) return rc_; }
-    const int n = (int)std::min<size_t>(s->qmei.size(), (size_t)(max < 0 ? 0 : max));
-    for (int i = 0; i < n; i++) {
-        // the printers behind the block loop, by the channel's own decoder and from the device's bits and verdicts: here, not in the push call, so that collect stays short
-        const SoftinMeiseiRec &r = s->qmei[i];
-        sonde_meisei_softin_t &o = out[i];
+    return softin_fetch<SoftinMeiseiRec>(s, SONDE_MEISEI, out, max, [s](const SoftinMeiseiRec &r, sonde_meisei_softin_t &o) {
+        // the printers behind the block loop
         o.channel = r.channel; o.mv = r.mv; o.hdr_bit = r.hdr_bit; o.err_frm = 0; o.err_blks = 0;
         for (int k = 0; k < MEISEI_BLOCKS; k++) { o.block_err[k] = r.block_err[k]; o.err_frm += r.block_err[k] >= 0xE; o.err_blks += r.block_err[k] != 0; }
         memcpy(o.bits, r.bits, sizeof o.bits);
-        const int len = sonde_meisei_dec_decoded(s->mei_dec[(size_t)r.channel], r.bits, r.block_err, o.text, sizeof o.text);
-        o.text_len = len;                                      // (negative: the text did not fit; the frame is delivered all the same)
-        if (len < 0) o.text[0] = 0;
-    }
-    s->qmei.erase(s->qmei.begin(), s->qmei.begin() + n);
-    return n;
+        o.text_len = sonde_meisei_dec_decoded(s->decoder<sonde_meisei_dec_t>(r.channel), r.bits, r.block_err, o.text, sizeof o.text);
+        if (o.text_len < 0) o.text[0] = 0;
+    });
 }
 
 int sonde_softin_dev_counts(sonde_softin_dev_t *s, int64_t *frames, int64_t *ecc_ok, int64_t *repaired, int64_t *symbols, int64_t *dropped) {
-    if (s && s->pending) { const int rc_ = softin_finish(s); if (rc_) return rc_; }
     if (!s) return SONDE_E_ARG;
+    { const int rc = softin_finish(s); if (rc) return rc; }
     if (frames) *frames = s->frames_total;
     if (ecc_ok) *ecc_ok = s->ecc_ok_total;
     if (repaired) *repaired = s->repaired_total;

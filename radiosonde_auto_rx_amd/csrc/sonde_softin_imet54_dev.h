@@ -23,7 +23,7 @@
 // (tests/emu/softin_imet54_emu.cpp).  Control flow around every cross-lane primitive is wave-uniform.
 #ifndef SONDE_SOFTIN_IMET54_DEV_H
 #define SONDE_SOFTIN_IMET54_DEV_H
-#include "sonde_softin_mxx_dev.h"
+#include "sonde_softin_wave_dev.h"                                     // the staged call, softin_wave_score<HL>, the ring refresh, softin_wave_8n1 / _xor
 // (no contraction: the reference is plain C on x86-64 — every product and sum rounded on its own)
 #pragma clang fp contract(off)
 
@@ -113,48 +113,6 @@ static inline void imet54_crc_table(uint32_t *t) {
     for (int k = 0; k < 8; k++) for (int j = 0; j < 4; j++) t[3 * (8 * (52 + j) + k) + 2] = 1u << (8 * (3 - j) + k);
 }
 
-// ---- what a later consumer of the same shape (a +-1 header of HL <= 64 symbols, 8N1 characters) can reuse
-// score of the window W(k0) .. W(k0 + HL - 1) against the header hbits (symbol i in bit i): float first, the reference's double form where that is not safely below ths
-template <int HL, class WF>
-static RSW_DEV float softin_wave_score(const WF &W, const int k0, const unsigned long long hbits, const float ths) {
-    float fs = 0.f, fn = 0.f;
-    for (int i = 0; i < HL; i++) {
-        const float v = W(k0 + i);
-        fs += ((hbits >> i) & 1ull) ? v : -v;
-        fn = fmaf(v, v, fn);
-    }
-    float mv = fs * mxxw_rsq(fn * (float)HL);
-    if (!(fabsf(mv) < ths - 1e-3f)) {                                 // (also NaN: an all-zero window is the reference's 0 / 0)
-        double sum = 0.0, normx = 0.0;
-        for (int i = 0; i < HL; i++) {
-            const float v = W(k0 + i);
-            const float y = ((hbits >> i) & 1ull) ? 1.f : -1.f;
-            sum += (double)(y * v);
-            normx += (double)(v * v);
-        }
-        sum /= sqrt(normx * (double)HL);
-        mv = (float)sum;
-    }
-    return mv;
-}
-// nchars 8N1 characters from the symbols S(0), S(1), .. on a lane per character: bit = (s >= 0) ^ inv, data bit k (symbol 1 + k of the character) in bit k
-template <class SF>
-static RSW_DEV void softin_wave_8n1(const SF &S, const int nchars, const int inv, uint8_t *out, const int lane) {
-    for (int j = lane; j < nchars; j += 64) {
-        unsigned byte = 0;
-        for (int k = 0; k < 8; k++) {
-            const int bit = (S(10 * j + 1 + k) >= 0.0f ? 1 : 0) ^ inv;
-            byte |= (unsigned)bit << k;
-        }
-        out[j] = (uint8_t)byte;
-    }
-}
-// XOR of v over the 64 lanes, on every lane
-static RSW_DEV uint32_t softin_wave_xor(uint32_t v, const int lane) {
-    for (int d = 1; d < 64; d <<= 1) v ^= (uint32_t)rsw_shfl_up((int)v, d, lane);
-    return (uint32_t)rsw_bcast((int)v, 63);
-}
-
 // print_frame's work on the 220 characters in L->chr (imet54mod.c:626-660): L->fr gets the 108 frame bytes, the return value is the same on every lane.
 // tab: imet54_crc_table's words (global memory).
 static RSW_DEV Imet54Verdict imet54_wave_end(SoftinImet54Lds *L, const int ecc, const uint32_t *tab, const int lane) {
@@ -224,10 +182,8 @@ static RSW_DEV void imet54_wave_channel(SoftinImet54Chan *st, const float *x, co
     if (lane < IMET54_HEADLEN) L->hist[lane] = st->hist[lane];
     if (lane < IMET54_CHARSYM) L->carry[lane] = st->carry[lane];
     for (int i = lane; i < IMET54_CHARS; i += 64) L->chr[i] = st->chr[i];
-    const bool staged = nb <= stage_cap;
-    if (staged) for (int i = lane; i < nb; i += 64) s_x[i] = sgn * x[i];
+    const SoftinX X = softin_wave_stage(s_x, x, sgn, nb, stage_cap, lane);                        // symbol p of this call, --softinv applied
     rsw_wave_sync();
-    auto X = [&](const int p) -> float { return staged ? s_x[p] : sgn * x[p]; };                  // symbol p of this call, --softinv applied
     const unsigned long long hbits = imet54_header_mask();
     int cur = 0;
     while (cur < nb) {
@@ -248,21 +204,14 @@ static RSW_DEV void imet54_wave_channel(SoftinImet54Chan *st, const float *x, co
                     // a header of the other polarity (:1018-1022): dropped — the ring stays, so the hits behind it in this round are what the reference sees —
                     // or with --auto the option flips and the hit counts
                     if ((double)mvl * (0.5 - inv) < 0) { if (!aut) continue; inv ^= 1; }
-                    // the ring as the header leaves it: the 40 elements up to the hit
-                    const float v = W(qs - cur0 + 1 + (lane < IMET54_HEADLEN ? lane : 0));
-                    rsw_wave_sync();
-                    if (lane < IMET54_HEADLEN) L->hist[lane] = v;
-                    rsw_wave_sync();
+                    softin_wave_ring<IMET54_HEADLEN>(L->hist, W, qs - cur0 + 1, lane);             // the ring as the header leaves it: the 40 elements up to the hit
                     stop = true;
                     mode = 1; done = 0; carry_n = 0; mv_hdr = mvl; hdr_bit = bits0 + (unsigned long long)qs + 1ull;
                     cur = qs + 1;
                 }
             }
             if (!stop) {
-                const float v = W(nb - cur0 + (lane < IMET54_HEADLEN ? lane : 0));                  // the 40 elements up to the call's last symbol
-                rsw_wave_sync();
-                if (lane < IMET54_HEADLEN) L->hist[lane] = v;
-                rsw_wave_sync();
+                softin_wave_ring<IMET54_HEADLEN>(L->hist, W, nb - cur0, lane);                     // the 40 elements up to the call's last symbol
                 cur = nb;
             }
         } else {
@@ -281,9 +230,7 @@ static RSW_DEV void imet54_wave_channel(SoftinImet54Chan *st, const float *x, co
             carry_n = rest; done += take; cur += take;
             if (done == IMET54_NSYM) {
                 const Imet54Verdict v = imet54_wave_end(L, ecc, tab, lane);
-                unsigned slot = 0;
-                if (lane == 0) slot = mxxw_atomic_inc(count);
-                slot = (unsigned)rsw_bcast((int)slot, 0);
+                const unsigned slot = softin_wave_slot(count, lane);
                 if ((int)slot < cap && (int)slot >= 0) {
                     SoftinImet54Rec *o = out + slot;
                     for (int i = lane; i < IMET54_FRAME; i += 64) o->frame[i] = L->fr[i];

@@ -22,7 +22,7 @@
 // (tests/emu/softin_meisei_emu.cpp).  Control flow around every cross-lane primitive is wave-uniform.
 #ifndef SONDE_SOFTIN_MEISEI_DEV_H
 #define SONDE_SOFTIN_MEISEI_DEV_H
-#include "sonde_softin_imet54_dev.h"                                   // softin_wave_score<HL>, softin_wave_xor
+#include "sonde_softin_wave_dev.h"                                     // the staged call, softin_wave_score<HL>, the ring refresh, softin_wave_xor
 // (no contraction: the reference is plain C on x86-64 — every product and sum rounded on its own)
 #pragma clang fp contract(off)
 
@@ -151,10 +151,8 @@ static RSW_DEV void meisei_wave_channel(SoftinMeiseiChan *st, const float *x, co
     if (lane < MEISEI_HEADLEN) L->hist[lane] = st->hist[lane];
     if (lane < MEISEI_WORDS) L->w[lane] = st->w[lane];
     if (lane == 0) L->carry = st->carry;
-    const bool staged = nb <= stage_cap;
-    if (staged) for (int i = lane; i < nb; i += 64) s_x[i] = sgn * x[i];
+    const SoftinX X = softin_wave_stage(s_x, x, sgn, nb, stage_cap, lane);                        // half symbol p of this call, --softinv applied
     rsw_wave_sync();
-    auto X = [&](const int p) -> float { return staged ? s_x[p] : sgn * x[p]; };                  // half symbol p of this call, --softinv applied
     const unsigned long long hbits = meisei_header_mask();
     int cur = 0;
     while (cur < nb) {
@@ -172,7 +170,7 @@ static RSW_DEV void meisei_wave_channel(SoftinMeiseiChan *st, const float *x, co
                     // every hit counts, in either polarity: the first one starts the frame, the positions behind it are frame symbols
                     const int l = __builtin_ctzll(hits), qs = base + l;
                     const float mvl = mxxw_bcast_f(mv, l);
-                    // the ring as the header leaves it: the 48 elements up to the hit
+                    // the ring as the header leaves it: the 48 elements up to the hit (softin_wave_ring with the frame's first words in the same step)
                     const float v = W(qs - cur0 + 1 + (lane < MEISEI_HEADLEN ? lane : 0));
                     rsw_wave_sync();
                     if (lane < MEISEI_HEADLEN) L->hist[lane] = v;
@@ -184,10 +182,7 @@ static RSW_DEV void meisei_wave_channel(SoftinMeiseiChan *st, const float *x, co
                 }
             }
             if (!stop) {
-                const float v = W(nb - cur0 + (lane < MEISEI_HEADLEN ? lane : 0));                  // the 48 elements up to the call's last symbol
-                rsw_wave_sync();
-                if (lane < MEISEI_HEADLEN) L->hist[lane] = v;
-                rsw_wave_sync();
+                softin_wave_ring<MEISEI_HEADLEN>(L->hist, W, nb - cur0, lane);                     // the 48 elements up to the call's last symbol
                 cur = nb;
             }
         } else {
@@ -218,9 +213,7 @@ static RSW_DEV void meisei_wave_channel(SoftinMeiseiChan *st, const float *x, co
             if (done == MEISEI_NSYM) {
                 const unsigned long long be = ecc ? meisei_wave_end(L, lane) : 0ull;
                 rsw_wave_sync();
-                unsigned slot = 0;
-                if (lane == 0) slot = mxxw_atomic_inc(count);
-                slot = (unsigned)rsw_bcast((int)slot, 0);
+                const unsigned slot = softin_wave_slot(count, lane);
                 if ((int)slot < cap && (int)slot >= 0) {
                     SoftinMeiseiRec *o = out + slot;
                     for (int k = lane; k < MEISEI_NBYTES; k += 64) {

@@ -11,39 +11,25 @@
 //   end of frame: a lane per byte, then the frame checksum on lane 0 and the block checksum on lane 1.
 //
 // Compiled twice, like sonde_vit_dev.h: by hipcc into k_softin_m20 (sonde_softin_dev.hip) and by g++ under tests/emu/wave_emu.h (tests/emu/softin_m20_emu.cpp).
-// Control flow around every cross-lane primitive is wave-uniform.  k_softin_m10 (sonde_softin_dev.hip) is the same scheme with 968 bits and M10's verdicts, written
-// before this file and left as it is.
+// Control flow around every cross-lane primitive is wave-uniform.  k_softin_m10 (sonde_softin_dev.hip) is the same scheme with 968 bits and M10's verdicts, a body of
+// its own.  What both share with the other consumers — the staged call, the header score, the ring refresh, the slot of a record — is sonde_softin_wave_dev.h.
 #ifndef SONDE_SOFTIN_MXX_DEV_H
 #define SONDE_SOFTIN_MXX_DEV_H
-#include <math.h>
-#include <stdint.h>
-#include <string.h>
-#include "sonde_rs_dev.h"
+#include "sonde_softin_wave_dev.h"                                     // the staged call, softin_wave_score<HL>, the ring refresh, the slot of a record
 #include "../../include/sonde_hip.h"
 // (no contraction: the reference is plain C on x86-64 — every product and sum rounded on its own)
 #pragma clang fp contract(off)
 
-// ---- the primitives sonde_rs_dev.h does not have: a float from a wave-uniform lane, the reciprocal square root of the float score, the counter of a launch
-static RSW_DEV float mxxw_bcast_f(float v, int src) { int u; memcpy(&u, &v, 4); u = rsw_bcast(u, src); memcpy(&v, &u, 4); return v; }
-#ifndef SONDE_RS_EMU
-static RSW_DEV float mxxw_rsq(float v) { return __builtin_amdgcn_rsqf(v); }
-static RSW_DEV unsigned mxxw_atomic_inc(unsigned *p) { return atomicAdd(p, 1u); }
-#else
-static inline float mxxw_rsq(float v) { return 1.0f / sqrtf(v); }
-static inline unsigned mxxw_atomic_inc(unsigned *p) { return (*p)++; }
-#endif
-
-#define M10_STAGE_MAX 12288                     // soft decisions of a call k_softin_m10 / k_softin_m20 keep in LDS (48 KB); longer calls read them from global memory
 #define M20_HEADLEN   32
 #define M20_NBYTES    (101 + 64)                // FRAME_LEN + AUX_LEN (m20mod.c:83-87)
 #define M20_NBITS     (M20_NBYTES * 8)          // 1320 bits = 2640 symbols
 #define M20_SKIP_END  (5 * 808)                 // bitpos up to which the rest of the second is dropped (m20mod.c:1362)
 #define M20_AUX_MAX   64
 // the raw header m20mod hands to find_softbinhead (m20mod.c:81), one character per symbol
-static RSW_DEV unsigned m20_header_mask() {
+static RSW_DEV unsigned long long m20_header_mask() {
     const char h[M20_HEADLEN + 1] = "10011001100110010100110010011001";
-    unsigned m = 0;
-    for (int i = 0; i < M20_HEADLEN; i++) m |= (unsigned)(h[i] & 1) << i;
+    unsigned long long m = 0;
+    for (int i = 0; i < M20_HEADLEN; i++) m |= (unsigned long long)(h[i] & 1) << i;
     return m;
 }
 
@@ -110,63 +96,33 @@ static RSW_DEV void m20_wave_channel(SoftinM20Chan *st, const float *x, const in
     if (mpos < 0 || mpos > M20_NBITS || nb < 0) return;                          // (never: the host zeroes the state)
     if (lane < M20_HEADLEN) L->hist[lane] = st->hist[lane];
     if (mode == 1) for (int i = lane; i < mpos; i += 64) L->mb[i] = st->mbits[i];
-    const bool staged = nb <= stage_cap;
-    if (staged) for (int i = lane; i < nb; i += 64) s_x[i] = sgn * x[i];
+    const SoftinX X = softin_wave_stage(s_x, x, sgn, nb, stage_cap, lane);                        // symbol p of this call, --softinv applied
     rsw_wave_sync();
-    const unsigned hbits = m20_header_mask();
+    const unsigned long long hbits = m20_header_mask();
     int cur = 0;
     while (cur < nb) {
         if (mode == 0) {
+            // element k of hist ++ the call's symbols from `cur`
+            const int cur0 = cur;
+            auto W = [&](const int k) -> float { return k < M20_HEADLEN ? L->hist[k] : X(cur0 + (k - M20_HEADLEN)); };
             bool found = false;
-            for (int base = cur; base < nb && !found; base += 64) {
+            for (int base = cur0; base < nb && !found; base += 64) {
                 const int q = base + lane;
                 float mv = 0.f;
-                if (q < nb) {
-                    // the window of position q: elements e-31 .. e of hist ++ the call's symbols from cur
-                    const int e = M20_HEADLEN + (q - cur);
-                    float fs = 0.f, fn = 0.f;
-                    for (int i = 0; i < M20_HEADLEN; i++) {
-                        const int k = e - (M20_HEADLEN - 1) + i;
-                        const float v = k < M20_HEADLEN ? L->hist[k] : staged ? s_x[cur + (k - M20_HEADLEN)] : sgn * x[cur + (k - M20_HEADLEN)];
-                        fs += ((hbits >> i) & 1u) ? v : -v;
-                        fn = fmaf(v, v, fn);
-                    }
-                    mv = fs * mxxw_rsq(fn * 32.0f);
-                    if (!(fabsf(mv) < ths - 1e-3f)) {                     // (also NaN: an all-zero window is the reference's 0 / 0)
-                        double sum = 0.0, normx = 0.0;
-                        for (int i = 0; i < M20_HEADLEN; i++) {
-                            const int k = e - (M20_HEADLEN - 1) + i;
-                            const float v = k < M20_HEADLEN ? L->hist[k] : staged ? s_x[cur + (k - M20_HEADLEN)] : sgn * x[cur + (k - M20_HEADLEN)];
-                            const float y = ((hbits >> i) & 1u) ? 1.f : -1.f;
-                            sum += (double)(y * v);
-                            normx += (double)(v * v);
-                        }
-                        sum /= sqrt(normx * 32.0);
-                        mv = (float)sum;
-                    }
-                }
+                if (q < nb) mv = softin_wave_score<M20_HEADLEN>(W, q - cur0 + 1, hbits, ths);      // the window of position q ends with the symbol at q
                 const unsigned long long hits = rsw_ballot(q < nb && fabsf(mv) > ths);
                 if (hits) {
                     const int l = __builtin_ctzll(hits), qs = base + l;
                     const float mvl = mxxw_bcast_f(mv, l);
                     if ((double)mvl * (0.5 - inv) < 0) inv ^= 1;
-                    // the ring as the header leaves it: the 32 elements up to the hit
-                    const int k = M20_HEADLEN + (qs - cur) - (M20_HEADLEN - 1) + (lane & (M20_HEADLEN - 1));
-                    const float v = k < M20_HEADLEN ? L->hist[k] : staged ? s_x[cur + (k - M20_HEADLEN)] : sgn * x[cur + (k - M20_HEADLEN)];
-                    rsw_wave_sync();
-                    if (lane < M20_HEADLEN) L->hist[lane] = v;
-                    rsw_wave_sync();
+                    softin_wave_ring<M20_HEADLEN>(L->hist, W, qs - cur0 + 1, lane);                // the ring as the header leaves it: the 32 elements up to the hit
                     found = true;
                     mode = 1; mpos = 0; mhalf = 0; mbit0 = '0'; mv_hdr = mvl; hdr_bit = bits0 + (unsigned long long)qs + 1ull;
                     cur = qs + 1;
                 }
             }
             if (!found) {
-                const int k = M20_HEADLEN + (nb - 1 - cur) - (M20_HEADLEN - 1) + (lane & (M20_HEADLEN - 1));
-                const float v = k < M20_HEADLEN ? L->hist[k] : staged ? s_x[cur + (k - M20_HEADLEN)] : sgn * x[cur + (k - M20_HEADLEN)];
-                rsw_wave_sync();
-                if (lane < M20_HEADLEN) L->hist[lane] = v;
-                rsw_wave_sync();
+                softin_wave_ring<M20_HEADLEN>(L->hist, W, nb - cur0, lane);                        // the 32 elements up to the call's last symbol
                 cur = nb;
             }
         } else if (mode == 1) {
@@ -178,7 +134,7 @@ static RSW_DEV void m20_wave_channel(SoftinM20Chan *st, const float *x, const in
                 int bit = 0;
                 if (j < nbits) {
                     const int p1 = cur + 2 * j - mhalf, p2 = p1 + 1;
-                    const float s1 = (j == 0 && mhalf) ? ms1 : staged ? s_x[p1] : sgn * x[p1], s2 = staged ? s_x[p2] : sgn * x[p2];
+                    const float s1 = (j == 0 && mhalf) ? ms1 : X(p1), s2 = X(p2);
                     bit = (s2 - s1) >= 0.0f;
                 }
                 int prev = rsw_shfl_up(bit, 1, lane);
@@ -188,13 +144,11 @@ static RSW_DEV void m20_wave_channel(SoftinM20Chan *st, const float *x, const in
                 last_bit = rsw_bcast(bit, cnt - 1);
             }
             if (nbits > 0) mbit0 = last_bit;
-            if ((mhalf + take) & 1) { const int p = cur + take - 1; ms1 = staged ? s_x[p] : sgn * x[p]; mhalf = 1; } else mhalf = 0;
+            if ((mhalf + take) & 1) { ms1 = X(cur + take - 1); mhalf = 1; } else mhalf = 0;
             mpos += nbits; cur += take;
             if (mpos == M20_NBITS) {
                 rsw_wave_sync();
-                unsigned slot = 0;
-                if (lane == 0) slot = mxxw_atomic_inc(count);
-                slot = (unsigned)rsw_bcast((int)slot, 0);
+                const unsigned slot = softin_wave_slot(count, lane);
                 for (int i = lane; i < 172; i += 64) {                    // bits2bytes (m20mod.c:192-220): big endian, anything but '1' counts as 0
                     unsigned v = 0;
                     if (i < M20_NBYTES) for (int k = 0; k < 8; k++) if (L->mb[8 * i + 7 - k] == '1') v |= 1u << k;

@@ -19,7 +19,7 @@
 // Control flow around every cross-lane primitive is wave-uniform.
 #ifndef SONDE_SOFTIN_RS92_DEV_H
 #define SONDE_SOFTIN_RS92_DEV_H
-#include "sonde_softin_mxx_dev.h"
+#include "sonde_softin_wave_dev.h"                                     // the staged call, softin_wave_score<HL>, the ring refresh, the slot of a record
 // (no contraction: the reference is plain C on x86-64 — every product and sum rounded on its own)
 #pragma clang fp contract(off)
 
@@ -109,42 +109,20 @@ static RSW_DEV void rs92_wave_channel(SoftinRs92Chan *st, const float *x, const 
     for (int i = lane; i < RS92_FRAME_LEN; i += 64) L->frame[i] = st->frame[i];
     for (int i = lane; i < 512; i += 64) L->gexp[i] = gf[i];
     for (int i = lane; i < 256; i += 64) L->glog[i] = gf[512 + i];
-    const bool staged = nb <= stage_cap;
-    if (staged) for (int i = lane; i < nb; i += 64) s_x[i] = sgn * x[i];
+    const SoftinX X = softin_wave_stage(s_x, x, sgn, nb, stage_cap, lane);                        // symbol p of this call, --softinv applied
     rsw_wave_sync();
-    auto X = [&](const int p) -> float { return staged ? s_x[p] : sgn * x[p]; };                  // symbol p of this call, --softinv applied
-    // element k of hist ++ the call's symbols from `cur`
-    auto W = [&](const int k, const int cur) -> float { return k < RS92_HEADLEN ? L->hist[k] : X(cur + (k - RS92_HEADLEN)); };
     const unsigned long long hbits = rs92_header_mask();
     int cur = 0;
     while (cur < nb) {
         if (mode == 0) {
+            // element k of hist ++ the call's symbols from `cur`
+            const int cur0 = cur;
+            auto W = [&](const int k) -> float { return k < RS92_HEADLEN ? L->hist[k] : X(cur0 + (k - RS92_HEADLEN)); };
             bool stop = false;
-            for (int base = cur; base < nb && !stop; base += 64) {
+            for (int base = cur0; base < nb && !stop; base += 64) {
                 const int q = base + lane;
                 float mv = 0.f;
-                if (q < nb) {
-                    // the window of position q: elements k0 .. k0 + 59, the last of them the symbol at q
-                    const int k0 = q - cur + 1;
-                    float fs = 0.f, fn = 0.f;
-                    for (int i = 0; i < RS92_HEADLEN; i++) {
-                        const float v = W(k0 + i, cur);
-                        fs += ((hbits >> i) & 1ull) ? v : -v;
-                        fn = fmaf(v, v, fn);
-                    }
-                    mv = fs * mxxw_rsq(fn * 60.0f);
-                    if (!(fabsf(mv) < ths - 1e-3f)) {                     // (also NaN: an all-zero window is the reference's 0 / 0)
-                        double sum = 0.0, normx = 0.0;
-                        for (int i = 0; i < RS92_HEADLEN; i++) {
-                            const float v = W(k0 + i, cur);
-                            const float y = ((hbits >> i) & 1ull) ? 1.f : -1.f;
-                            sum += (double)(y * v);
-                            normx += (double)(v * v);
-                        }
-                        sum /= sqrt(normx * 60.0);
-                        mv = (float)sum;
-                    }
-                }
+                if (q < nb) mv = softin_wave_score<RS92_HEADLEN>(W, q - cur0 + 1, hbits, ths);     // the window of position q ends with the symbol at q
                 const unsigned long long hits = rsw_ballot(q < nb && fabsf(mv) > ths);
                 if (hits) {
                     // the first hit counts; whatever the lanes behind it saw, they saw over a ring this hit empties: the search goes on from the next symbol
@@ -162,10 +140,7 @@ static RSW_DEV void rs92_wave_channel(SoftinRs92Chan *st, const float *x, const 
                 }
             }
             if (!stop) {
-                const float v = W(nb - cur + (lane < RS92_HEADLEN ? lane : 0), cur);          // the 60 elements up to the call's last symbol
-                rsw_wave_sync();
-                if (lane < RS92_HEADLEN) L->hist[lane] = v;
-                rsw_wave_sync();
+                softin_wave_ring<RS92_HEADLEN>(L->hist, W, nb - cur0, lane);                       // the 60 elements up to the call's last symbol
                 cur = nb;
             }
         } else {
@@ -191,9 +166,7 @@ static RSW_DEV void rs92_wave_channel(SoftinRs92Chan *st, const float *x, const 
             carry_n = rest; done += take; cur += take;
             if (done == RS92_NSYM) {
                 const int ec = rs92_wave_ecc(L, lane);
-                unsigned slot = 0;
-                if (lane == 0) slot = mxxw_atomic_inc(count);
-                slot = (unsigned)rsw_bcast((int)slot, 0);
+                const unsigned slot = softin_wave_slot(count, lane);
                 if ((int)slot < cap && (int)slot >= 0) {
                     SoftinRs92Rec *o = out + slot;
                     for (int i = lane; i < RS92_FRAME_LEN; i += 64) o->frame[i] = L->frame[i];

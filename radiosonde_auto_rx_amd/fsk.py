@@ -81,6 +81,10 @@ class MeiseiSoftinRec(C.Structure):
 # auto_rx's `meisei100mod --softin --json --ptu --ecc` (auto_rx/autorx/decode.py:1343-1379)
 MEISEI_DEFAULTS = dict(ecc=1, json=1, ptu=1)
 
+# the kinds whose consumer is made from the options struct of their host decoder: struct (family.py), auto_rx's defaults, create call
+_OPTS_KINDS = {"rs92": ("Rs92Opts", RS92_DEFAULTS, "sonde_softin_dev_create_rs92"), "imet54": ("Imet54Opts", IMET54_DEFAULTS, "sonde_softin_dev_create_imet54"),
+               "meisei": ("MeiseiOpts", MEISEI_DEFAULTS, "sonde_softin_dev_create_meisei")}
+
 _proto = False
 
 
@@ -252,39 +256,20 @@ class SoftinDev:
         from .engine import SONDE_RS41, SONDE_DFM09, SONDE_M10, SONDE_M20, SONDE_RD94RD41
         h = C.c_void_p()
         self.kind, self.ecc = kind, ecc
-        if kind == "rs92":
-            from .family import Rs92Opts
-            kw = dict(RS92_DEFAULTS)
-            kw.update(rs92_opts or {})
+        if kind in _OPTS_KINDS:
+            from . import family
+            opts_name, defaults, create = _OPTS_KINDS[kind]
+            kw = dict(defaults)
+            kw.update({"rs92": rs92_opts, "imet54": imet54_opts, "meisei": meisei_opts}[kind] or {})
             if isinstance(kw.get("version"), str):
                 kw["version"] = kw["version"].encode()
-            o = Rs92Opts(**kw)
-            _chk(_lib().sonde_softin_dev_create_rs92(n_channels, C.byref(o), int(softinv), C.byref(h)))
+            o = getattr(family, opts_name)(**kw)
+            _chk(getattr(_lib(), create)(n_channels, C.byref(o), int(softinv), C.byref(h)))
             self._h, self.n_channels = h, n_channels
-            if ephemeris:
+            if kind == "rs92" and ephemeris:
                 self.load_rs92_ephemeris(ephemeris)
-            if almanac:
+            if kind == "rs92" and almanac:
                 self.load_rs92_almanac(almanac)
-            return
-        if kind == "imet54":
-            from .family import Imet54Opts
-            kw = dict(IMET54_DEFAULTS)
-            kw.update(imet54_opts or {})
-            if isinstance(kw.get("version"), str):
-                kw["version"] = kw["version"].encode()
-            o = Imet54Opts(**kw)
-            _chk(_lib().sonde_softin_dev_create_imet54(n_channels, C.byref(o), int(softinv), C.byref(h)))
-            self._h, self.n_channels = h, n_channels
-            return
-        if kind == "meisei":
-            from .family import MeiseiOpts
-            kw = dict(MEISEI_DEFAULTS)
-            kw.update(meisei_opts or {})
-            if isinstance(kw.get("version"), str):
-                kw["version"] = kw["version"].encode()
-            o = MeiseiOpts(**kw)
-            _chk(_lib().sonde_softin_dev_create_meisei(n_channels, C.byref(o), int(softinv), C.byref(h)))
-            self._h, self.n_channels = h, n_channels
             return
         if kind == "lms6":
             o = Lms6Opts(raw=int(raw), ecc=1 if ecc else 0, vit=vit, json=int(json), typ=typ, gpsweek=gpsweek, jsn_freq_khz=freq_khz, version=version.encode())
@@ -408,30 +393,34 @@ class SoftinDev:
         """RS92 consumers: an SEM almanac (rs92mod -a) for every channel's decoder"""
         _chk(_lib().sonde_softin_dev_rs92_load_almanac(self._h, os.fsencode(path)))
 
+    def _fetch_text(self, call: str, rec, max_frames: int, fields):
+        """the records whose text is made at fetch time: the named fields (byte arrays as bytes) and text"""
+        buf = (rec * max_frames)()
+        n = _chk(getattr(_lib(), call)(self._h, buf, max_frames))
+        out = []
+        for r in buf[:n]:
+            d = {k: getattr(r, k) for k in fields}
+            d.update({k: bytes(v) for k, v in d.items() if isinstance(v, C.Array)})
+            d["text"] = r.text[:max(r.text_len, 0)].decode()
+            out.append(d)
+        return out
+
     def fetch_rs92(self, max_frames: int = 1024):
         """RS92 consumers: a dict per completed frame — channel, ec (rs_decode's value: 0, repaired bytes, negative = left as received), mv, hdr_bit (symbols read when
         the header matched), frame = the 240 bytes behind rs92_ecc, text = what `rs92mod` prints for it (the channel's own decoder: calibration rows, orbit data)"""
-        buf = (Rs92SoftinRec * max_frames)()
-        n = _chk(_lib().sonde_softin_dev_fetch_rs92(self._h, buf, max_frames))
-        return [dict(channel=r.channel, ec=r.ec, mv=r.mv, hdr_bit=r.hdr_bit, frame=bytes(r.frame), text=r.text[:max(r.text_len, 0)].decode()) for r in buf[:n]]
+        return self._fetch_text("sonde_softin_dev_fetch_rs92", Rs92SoftinRec, max_frames, ("channel", "ec", "mv", "hdr_bit", "frame"))
 
     def fetch_imet54(self, max_frames: int = 1024):
         """iMet-54 consumers: a dict per completed frame — channel, ecc_frm / ecc_tlm / ecc_std (print_frame's sums: repaired codewords, -1 behind an uncorrectable
         one), crc (0 neither check sum, 1 the standard frame's, 2 the continuous frame's), mv, hdr_bit (symbols read when the header matched), frame = the 108 bytes
         behind Hamming(8,4), text = what `imet54mod` prints for it from the device's verdicts"""
-        buf = (Imet54SoftinRec * max_frames)()
-        n = _chk(_lib().sonde_softin_dev_fetch_imet54(self._h, buf, max_frames))
-        return [dict(channel=r.channel, ecc_frm=r.ecc_frm, ecc_tlm=r.ecc_tlm, ecc_std=r.ecc_std, crc=r.crc, mv=r.mv, hdr_bit=r.hdr_bit, frame=bytes(r.frame),
-                     text=r.text[:max(r.text_len, 0)].decode()) for r in buf[:n]]
+        return self._fetch_text("sonde_softin_dev_fetch_imet54", Imet54SoftinRec, max_frames, ("channel", "ecc_frm", "ecc_tlm", "ecc_std", "crc", "mv", "hdr_bit", "frame"))
 
     def fetch_meisei(self, max_frames: int = 1024):
         """Meisei consumers: a dict per completed frame — channel, block_err (12 verdicts, subframe 0 first: 0 / 1 / 2 corrected bits, 0xF padding or word parity,
         0xE uncorrectable), err_frm / err_blks (blocks 0xE / 0xF, blocks not 0), mv (with its sign), hdr_bit (half symbols read when the header matched), bits =
         the 600 frame bits behind BCH in 75 bytes, MSB first, text = what `meisei100mod` prints for it from the device's bits and verdicts"""
-        buf = (MeiseiSoftinRec * max_frames)()
-        n = _chk(_lib().sonde_softin_dev_fetch_meisei(self._h, buf, max_frames))
-        return [dict(channel=r.channel, block_err=bytes(r.block_err), err_frm=r.err_frm, err_blks=r.err_blks, mv=r.mv, hdr_bit=r.hdr_bit, bits=bytes(r.bits),
-                     text=r.text[:max(r.text_len, 0)].decode()) for r in buf[:n]]
+        return self._fetch_text("sonde_softin_dev_fetch_meisei", MeiseiSoftinRec, max_frames, ("channel", "block_err", "err_frm", "err_blks", "mv", "hdr_bit", "bits"))
 
     def counts(self):
         v = [C.c_int64(0) for _ in range(5)]

@@ -23,13 +23,13 @@ CSRC = os.path.join(ROOT, "radiosonde_auto_rx_amd", "csrc")
 EMU_DIR = os.path.join(ROOT, "tests", "emu")
 EMU_SRC = os.path.join(EMU_DIR, "softin_imet54_emu.cpp")
 EMU_SO = os.path.join(EMU_DIR, "libsoftin_imet54_emu.so")
-DEPS = [EMU_SRC, os.path.join(EMU_DIR, "wave_emu.h"), os.path.join(CSRC, "sonde_softin_imet54_dev.h"), os.path.join(CSRC, "sonde_softin_mxx_dev.h"),
+DEPS = [EMU_SRC, os.path.join(EMU_DIR, "wave_emu.h"), os.path.join(CSRC, "sonde_softin_imet54_dev.h"), os.path.join(CSRC, "sonde_softin_wave_dev.h"),
         os.path.join(CSRC, "sonde_rs_dev.h"), os.path.join(ROOT, "include", "sonde_hip.h")]
 REF = os.path.join(ROOT, "oracle", "_ref", "imet54mod")
 HEADER = "0000000001" "0101010101" "0001001001" "0001001001"          # the 40 header symbols `imet54mod` searches for: 00 AA 24 24 as 8N1
 HDR = np.array([int(c) for c in HEADER], np.uint8)
 NSYM = 2200                                                 # symbols of a frame behind the header
-STAGE_MAX = 12288                                           # M10_STAGE_MAX of sonde_softin_mxx_dev.h
+STAGE_MAX = 12288                                           # M10_STAGE_MAX of sonde_softin_wave_dev.h
 CUTS = [4800, 1000, 251, 1, 9, 10, 11, 39, 40, 41, 63, 64, 65]
 PRE, IDLE = 60, 30                                          # preamble and idle symbols of the short on-air frames the cases use
 

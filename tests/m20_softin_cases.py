@@ -18,11 +18,11 @@ CSRC = os.path.join(ROOT, "radiosonde_auto_rx_amd", "csrc")
 EMU_DIR = os.path.join(ROOT, "tests", "emu")
 EMU_SRC = os.path.join(EMU_DIR, "softin_m20_emu.cpp")
 EMU_SO = os.path.join(EMU_DIR, "libsoftin_m20_emu.so")
-DEPS = [EMU_SRC, os.path.join(EMU_DIR, "wave_emu.h"), os.path.join(CSRC, "sonde_softin_mxx_dev.h"), os.path.join(CSRC, "sonde_rs_dev.h"), os.path.join(ROOT, "include", "sonde_hip.h")]
+DEPS = [EMU_SRC, os.path.join(EMU_DIR, "wave_emu.h"), os.path.join(CSRC, "sonde_softin_mxx_dev.h"), os.path.join(CSRC, "sonde_softin_wave_dev.h"), os.path.join(CSRC, "sonde_rs_dev.h"), os.path.join(ROOT, "include", "sonde_hip.h")]
 REF = os.path.join(ROOT, "oracle", "_ref", "m20mod")
 HEADER = "10011001100110010100110010011001"                # the 32 raw header symbols `m20mod` searches for
 NSYM = 2 * (101 + 64) * 8                                   # symbols of a frame behind the header
-STAGE_MAX = 12288                                           # M10_STAGE_MAX of sonde_softin_mxx_dev.h
+STAGE_MAX = 12288                                           # M10_STAGE_MAX of sonde_softin_wave_dev.h
 
 
 class EmuState(C.Structure):

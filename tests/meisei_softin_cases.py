@@ -24,8 +24,8 @@ CSRC = os.path.join(ROOT, "radiosonde_auto_rx_amd", "csrc")
 EMU_DIR = os.path.join(ROOT, "tests", "emu")
 EMU_SRC = os.path.join(EMU_DIR, "softin_meisei_emu.cpp")
 EMU_SO = os.path.join(EMU_DIR, "libsoftin_meisei_emu.so")
-DEPS = [EMU_SRC, os.path.join(EMU_DIR, "wave_emu.h"), os.path.join(CSRC, "sonde_softin_meisei_dev.h"), os.path.join(CSRC, "sonde_softin_imet54_dev.h"),
-        os.path.join(CSRC, "sonde_softin_mxx_dev.h"), os.path.join(CSRC, "sonde_rs_dev.h"), os.path.join(ROOT, "include", "sonde_hip.h")]
+DEPS = [EMU_SRC, os.path.join(EMU_DIR, "wave_emu.h"), os.path.join(CSRC, "sonde_softin_meisei_dev.h"), os.path.join(CSRC, "sonde_softin_wave_dev.h"),
+        os.path.join(CSRC, "sonde_rs_dev.h"), os.path.join(ROOT, "include", "sonde_hip.h")]
 REF = os.path.join(ROOT, "oracle", "_ref", "meisei100mod")
 HEADER = "101010101011010100101011001101001100101011001101"      # the 48 header half symbols `meisei100mod` searches for: 0x049DCE in biphase-S
 HDR = np.array([int(c) for c in HEADER], np.uint8)
@@ -33,7 +33,7 @@ HDR24 = [int(c) for c in "000001001001110111001110"]
 HL = 48
 NSYM = 1152                                                 # half symbols of a frame behind the header
 FRAME = HL + NSYM                                           # 1200: the spacing of back-to-back frames
-STAGE_MAX = 12288                                           # M10_STAGE_MAX of sonde_softin_mxx_dev.h
+STAGE_MAX = 12288                                           # M10_STAGE_MAX of sonde_softin_wave_dev.h
 CUTS = [2400, 1000, 251, 1, 2, 47, 48, 49, 63, 64, 65]
 F08 = np.float32(0.8)
 

@@ -21,13 +21,13 @@ CSRC = os.path.join(ROOT, "radiosonde_auto_rx_amd", "csrc")
 EMU_DIR = os.path.join(ROOT, "tests", "emu")
 EMU_SRC = os.path.join(EMU_DIR, "softin_rs92_emu.cpp")
 EMU_SO = os.path.join(EMU_DIR, "libsoftin_rs92_emu.so")
-DEPS = [EMU_SRC, os.path.join(EMU_DIR, "wave_emu.h"), os.path.join(CSRC, "sonde_softin_rs92_dev.h"), os.path.join(CSRC, "sonde_softin_mxx_dev.h"),
+DEPS = [EMU_SRC, os.path.join(EMU_DIR, "wave_emu.h"), os.path.join(CSRC, "sonde_softin_rs92_dev.h"), os.path.join(CSRC, "sonde_softin_wave_dev.h"),
         os.path.join(CSRC, "sonde_rs_dev.h"), os.path.join(ROOT, "include", "sonde_hip.h")]
 REF = os.path.join(ROOT, "oracle", "_ref", "rs92mod")
 HEADER = "10100110011001101001" "1010011001100110100110101010100110101001"      # the 60 raw header symbols `rs92mod` searches for: 2A 2A 10
 NSYM = 234 * 20                                             # symbols of a frame behind the header
 ONAIR = 240 * 20                                            # symbols of a frame on air: 2A 2A 2A, the header, the body
-STAGE_MAX = 12288                                           # M10_STAGE_MAX of sonde_softin_mxx_dev.h
+STAGE_MAX = 12288                                           # M10_STAGE_MAX of sonde_softin_wave_dev.h
 CUTS = [1, 19, 20, 21, 59, 60, 61, 4679, 4680, 4681, 4800]
 AUTORX = dict(verbose=1, aux=1, ecc=2, gps_vel=4, json=1, ptu=1, gpsepoch=-1)       # rs92mod -vx -v --crc --ecc --vel --json --ptu (inv = -i per case)
 

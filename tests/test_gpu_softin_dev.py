@@ -426,3 +426,96 @@ def test_decoder_submitted_behind_the_modems_next_second_gives_the_same_frames(k
     assert got[0] == plain[0] and got[1] == plain[1]
     for k in range(3):
         assert np.array_equal(got[2][k], plain[2][k])
+
+
+# ---------------------------------------------------------------- every fetch call on every kind of consumer
+KINDS = ("rs41", "dfm", "m10", "m20", "drop", "lms6", "rs92", "imet54", "meisei")
+
+
+def test_every_fetch_call_on_a_consumer_of_every_kind():
+    """nine one-channel consumers, nothing pushed, nine fetch calls each (include/sonde_fsk.h): the call of the consumer's own kind finds an empty queue; the call of
+    another kind is SONDE_E_ARG where the call is one of m20 / rs92 / imet54 / meisei or the consumer one of rs92 / imet54 / meisei, and an empty queue otherwise; a
+    null handle and a null buffer with room asked for are SONDE_E_ARG everywhere; set_m20_skip belongs to M20 consumers alone"""
+    import ctypes as C
+    from radiosonde_auto_rx_amd.engine import SondeFrame, SondeDfmFrame, SondeM10Frame, SondeM20Frame
+    from radiosonde_auto_rx_amd.fsk import SoftinDev, _lib, MeiseiSoftinRec, Imet54SoftinRec, Rs92SoftinRec, Lms6SoftinRec
+    from radiosonde_auto_rx_amd.drop import DropFrame
+    L = _lib()
+    calls = dict(rs41=("fetch", SondeFrame), dfm=("fetch_dfm", SondeDfmFrame), m10=("fetch_m10", SondeM10Frame), m20=("fetch_m20", SondeM20Frame),
+                 drop=("fetch_drop", DropFrame), lms6=("fetch_lms6", Lms6SoftinRec), rs92=("fetch_rs92", Rs92SoftinRec), imet54=("fetch_imet54", Imet54SoftinRec),
+                 meisei=("fetch_meisei", MeiseiSoftinRec))
+    assert tuple(calls) == KINDS
+    got, want = {}, {}
+    for kind in KINDS:
+        sf = SoftinDev(1, kind=kind)
+        for x, (fn, typ) in calls.items():
+            f = getattr(L, "sonde_softin_dev_" + fn)
+            buf = (typ * 2)()
+            got[kind, x] = (f(sf._h, buf, 2), f(sf._h, None, 2), f(None, buf, 2))
+            refused = x != kind and (x in ("m20", "rs92", "imet54", "meisei") or kind in ("rs92", "imet54", "meisei"))
+            want[kind, x] = (-1 if refused else 0, -1, -1)
+        got[kind, "skip"] = L.sonde_softin_dev_set_m20_skip(sf._h, 1)
+        want[kind, "skip"] = 0 if kind == "m20" else -1
+        assert sf.counts() == dict(frames=0, ecc_ok=0, repaired=0, symbols=0, dropped=0)
+        sf.close()
+    assert got == want, {k: (got[k], want[k]) for k in got if got[k] != want[k]}
+
+
+# ---------------------------------------------------------------- the staged consumers on both sides of the staging limit
+STAGE_MAX = 12288                                          # M10_STAGE_MAX of sonde_softin_wave_dev.h
+
+
+def _staged_case(kind):
+    """(one stream of more than 2 STAGE_MAX + 1 symbols, symbols a second, the consumer's keywords, its fetch call)"""
+    import sys
+    sys.path.insert(0, ROOT)
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    if kind == "m10":
+        import make_golden
+        return make_golden.m10_field_symbols(make_golden.M10_FIELD_SCENARIOS["m10f_gtop_8"])[:4 * 9616], 9616, dict(ecc=0, inv=False), "fetch_m10"
+    if kind == "m20":
+        import m20_softin_cases as M
+        return M.dense_stream(12, seed=12), 9600, dict(skip=False), "fetch_m20"
+    if kind == "rs92":
+        import rs92_softin_cases as M
+        return np.concatenate([M.soft(M.fsym(k)) for k in range(6)]), 4800, dict(rs92_opts=dict(M.AUTORX, inv=0)), "fetch_rs92"
+    if kind == "imet54":
+        import imet54_softin_cases as M
+        s = np.concatenate([M.soft(M.onair(M.fbits(M.frame(k, sn=54000100)), pre=0, idle=0)) for k in range(13)])
+        return s, 4800, dict(imet54_opts=dict(raw=1, ecc=1, json=0, ptu=0, inv=0)), "fetch_imet54"
+    import meisei_softin_cases as M
+    return M.soft(M.fsym(0, "ims100", 24)), 2400, dict(meisei_opts=dict(raw=1, ecc=1, verbose=1, json=0, ptu=0)), "fetch_meisei"
+
+
+@pytest.mark.parametrize("kind", ["m10", "m20", "rs92", "imet54", "meisei"])
+def test_staged_consumers_on_both_sides_of_the_staging_limit(kind):
+    """two channels, the same frames behind leads of 0 and 37 symbols, in calls of [STAGE_MAX, STAGE_MAX + 1, the rest] — the longest call that is staged in LDS
+    (the 48 KB the launcher has to ask the device for), the shortest that is read where it lies, and what is left — give the records and the counts of the same
+    streams in calls of a second, which are all staged"""
+    import torch
+    from radiosonde_auto_rx_amd.fsk import SoftinDev
+    s, second, kw, fetch = _staged_case(kind)
+    rng = np.random.default_rng(37)
+    quiet = lambda n: rng.normal(0.0, 0.05, n).astype(np.float32)
+    S = np.ascontiguousarray(np.stack([np.concatenate([s, quiet(37 + 60)]), np.concatenate([quiet(37), s, quiet(60)])]), np.float32)
+    n = S.shape[1]
+    assert n > 2 * STAGE_MAX + 1                              # (there is a rest)
+    d = torch.from_numpy(S).cuda()
+
+    def run(calls):
+        sf = SoftinDev(2, kind=kind, **kw)
+        recs, pos, i = {0: [], 1: []}, 0, 0
+        while pos < n:
+            k = min(calls[min(i, len(calls) - 1)], n - pos)
+            chunk = d[:, pos:pos + k].contiguous()
+            sf.push_device(chunk.data_ptr(), k, k)
+            for f in getattr(sf, fetch)():
+                recs[f["channel"]].append(f)
+            pos += k; i += 1
+        cnt = sf.counts()
+        sf.close()
+        return recs, cnt
+
+    want, got = run([second]), run([STAGE_MAX, STAGE_MAX + 1, n])
+    assert len(want[0][0]) >= 2 and len(want[0][1]) == len(want[0][0]) and want[1]["dropped"] == 0
+    assert got == want

@@ -39,3 +39,9 @@ def test_the_other_consumers_are_in_the_same_report(report):
     """the report this module reads is the softin translation unit's: the kernels DESIGN 4.7a tabulates are all there, without scratch"""
     for name in ("k_softin_m20", "k_softin_rs92", "k_softin_imet54", "k_softin_meisei"):
         assert report[name]["scratch"] == 0 and report[name]["vgpr_spill"] == 0, name
+    # all nine: nothing in scratch memory, and the static LDS of a wave — each kernel's channel state, the shared helpers add none
+    lds = dict(k_softin_rs41=816, k_softin_dfm=1536, k_softin_m10=1228, k_softin_m20=1628, k_softin_rs92=1648, k_softin_imet54=748, k_softin_meisei=272,
+               k_softin_drop=2528, k_softin_lms6=38656)
+    for name, want in lds.items():
+        assert report[name]["scratch"] == 0 and report[name]["vgpr_spill"] == 0, name
+        assert report[name]["lds"] == want, (name, report[name]["lds"])
