@@ -12,11 +12,11 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <vector>
 #include <algorithm>
 #include "../../include/sonde_chan.h"
-
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "libsonde_hip: %s failed: %s\n", #x, hipGetErrorString(e_)); return SONDE_E_NOGPU; } } while (0)
+#include "sonde_devmem.h"
 
 #define CH_F 16               // output samples per workgroup
 #define CH_THREADS 256
@@ -103,12 +103,17 @@ void k_channelize(const ChanArgs a) {
 }
 
 struct sonde_chan {
+    DevMem mem;                         // everything below that lives on the device, the row buffers of sonde_chan_rows_alloc() included
+    ~sonde_chan() {
+        if (stream) { hipStreamSynchronize(stream); hipStreamDestroy(stream); }
+        if (ev_a) hipEventDestroy(ev_a);
+        if (ev_b) hipEventDestroy(ev_b);
+    }
     sonde_chan_cfg_t cfg{};
     sonde_chan_info_t info{};
     hipStream_t stream = nullptr;
-    uint32_t *d_x = nullptr; float *d_h = nullptr; float2 *d_tw = nullptr; void *d_stage = nullptr;
+    uint32_t *d_x = nullptr; float *d_h = nullptr; float2 *d_tw = nullptr; uint32_t *d_stage = nullptr;
     float2 *d_own = nullptr;            // sonde_chan_output(): [M][max_frames] owned by the channelizer (callers without a device allocator of their own)
-    std::vector<void *> rows;           // sonde_chan_rows_alloc()
     int T = 0, log2M = 0, hist = 0;
     size_t lds = 0;                     // dynamic LDS of every launch (chan_lds_bytes)
     long long n_in = 0, m_out = 0;      // stream samples consumed, output samples produced (per channel)
@@ -145,7 +150,8 @@ int sonde_chan_create(const sonde_chan_cfg_t *cfg, sonde_chan_t **out) {
         return SONDE_E_ARG;
     }
     if (lds > 64 * 1024) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_channelize), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-    sonde_chan *c = new sonde_chan();
+    std::unique_ptr<sonde_chan> owner(new sonde_chan());
+    sonde_chan *c = owner.get();
     c->cfg = *cfg; c->lds = lds;
     const int M = cfg->M, T = M * cfg->P;
     c->T = T; c->hist = T - 1;
@@ -168,27 +174,15 @@ int sonde_chan_create(const sonde_chan_cfg_t *cfg, sonde_chan_t **out) {
     for (int j = 0; j < M / 2; j++) tw[j] = make_float2((float)cos(2.0 * M_PI * j / M), (float)sin(2.0 * M_PI * j / M));
     HIPCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     HIPCHK(hipEventCreate(&c->ev_a)); HIPCHK(hipEventCreate(&c->ev_b));
-    HIPCHK(hipMalloc((void **)&c->d_x, ((size_t)c->hist + cfg->max_chunk) * sizeof(uint32_t)));
-    HIPCHK(hipMemset(c->d_x, 0, ((size_t)c->hist + cfg->max_chunk) * sizeof(uint32_t)));      // the filter starts from silence
-    HIPCHK(hipMalloc((void **)&c->d_h, T * sizeof(float)));
-    HIPCHK(hipMalloc((void **)&c->d_tw, (M / 2) * sizeof(float2)));
-    HIPCHK(hipMemcpy(c->d_h, h.data(), T * sizeof(float), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(c->d_tw, tw.data(), (M / 2) * sizeof(float2), hipMemcpyHostToDevice));
+    TRY(c->mem.dalloc(&c->d_x, (size_t)c->hist + cfg->max_chunk));      // zeroed: the filter starts from silence
+    TRY(c->mem.upload(&c->d_h, h)); TRY(c->mem.upload(&c->d_tw, tw));
     c->info.out_rate_num = cfg->sample_rate; c->info.out_rate_den = cfg->D; c->info.taps = T;
     c->info.max_frames = cfg->max_chunk / cfg->D + 2; c->info.spacing_hz = (float)cfg->sample_rate / (float)M;
-    *out = c;
+    *out = owner.release();
     return 0;
 }
 
-void sonde_chan_destroy(sonde_chan_t *c) {
-    if (!c) return;
-    if (c->stream) { hipStreamSynchronize(c->stream); hipStreamDestroy(c->stream); }
-    if (c->ev_a) hipEventDestroy(c->ev_a);
-    if (c->ev_b) hipEventDestroy(c->ev_b);
-    for (void *p : { (void *)c->d_x, (void *)c->d_h, (void *)c->d_tw, c->d_stage, (void *)c->d_own }) if (p) hipFree(p);
-    for (void *p : c->rows) if (p) hipFree(p);
-    delete c;
-}
+void sonde_chan_destroy(sonde_chan_t *c) { delete c; }
 
 int sonde_chan_info(const sonde_chan_t *c, sonde_chan_info_t *info) {
     if (!c || !info) return SONDE_E_ARG;
@@ -220,7 +214,7 @@ int sonde_chan_process_device(sonde_chan_t *c, const void *d_iq, int32_t n_sampl
     if (n_samples >= c->hist) HIPCHK(hipMemcpyAsync(c->d_x, c->d_x + n_samples, (size_t)c->hist * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
     else if (n_samples > 0) {
         // short call: shift the window by n_samples (overlapping ranges: through the staging buffer)
-        if (!c->d_stage) HIPCHK(hipMalloc(&c->d_stage, (size_t)c->hist * sizeof(uint32_t)));
+        if (!c->d_stage) TRY(c->mem.dalloc(&c->d_stage, (size_t)c->hist, false));
         HIPCHK(hipMemcpyAsync(c->d_stage, c->d_x + n_samples, (size_t)c->hist * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
         HIPCHK(hipMemcpyAsync(c->d_x, c->d_stage, (size_t)c->hist * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
     }
@@ -251,19 +245,14 @@ void *sonde_chan_stream(sonde_chan_t *c) { return c ? (void *)c->stream : nullpt
 // the decoder engines, and the copy of chosen channel rows into such a buffer (on the channelizer's stream, behind the call that produced them).
 int sonde_chan_output(sonde_chan_t *c, void **d_out, int64_t *out_stride) {
     if (!c || !d_out || !out_stride) return SONDE_E_ARG;
-    if (!c->d_own) {
-        HIPCHK(hipMalloc((void **)&c->d_own, (size_t)c->cfg.M * c->info.max_frames * sizeof(float2)));
-        HIPCHK(hipMemset(c->d_own, 0, (size_t)c->cfg.M * c->info.max_frames * sizeof(float2)));
-    }
+    if (!c->d_own) TRY(c->mem.dalloc(&c->d_own, (size_t)c->cfg.M * c->info.max_frames));
     *d_out = c->d_own; *out_stride = c->info.max_frames;
     return 0;
 }
 int sonde_chan_rows_alloc(sonde_chan_t *c, int32_t n_rows, void **d_rows) {
     if (!c || !d_rows || n_rows < 1) return SONDE_E_ARG;
-    void *p = nullptr;
-    if (hipMalloc(&p, (size_t)n_rows * c->info.max_frames * sizeof(float2)) != hipSuccess) return SONDE_E_NOMEM;
-    HIPCHK(hipMemset(p, 0, (size_t)n_rows * c->info.max_frames * sizeof(float2)));
-    c->rows.push_back(p);
+    float2 *p = nullptr;
+    TRY(c->mem.dalloc(&p, (size_t)n_rows * c->info.max_frames));
     *d_rows = p;
     return 0;
 }

@@ -13,24 +13,27 @@
 // those through the float32 mixer / FIR kernels, create_impl), and for an IF rate whose filters need more LDS per workgroup of k_if_chain than the device has.
 #include "../../include/sonde_hip.h"
 #include "sonde_dev.h"
+#include "sonde_devmem.h"
 #include "sonde_host.h"
+#include "sonde_pinned.h"
 #include "sonde_scan_dev.h"
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <string>
 #include <vector>
 
 using namespace sonde;
 
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "libsonde_hip: %s failed: %s\n", #x, hipGetErrorString(e_)); return SONDE_E_NOGPU; } } while (0)
-
 struct KernelStat { double ms = 0; int64_t n = 0; };
 struct PendingEvt { hipEvent_t a, b; const char *name; };
 
 struct sonde_engine {
+    DevMem mem;                        // every device buffer below but d_wfprof (and a group's d_y: rows of its owner's)
+    ~sonde_engine();
     sonde_cfg_t cfg{};
     sonde_info_t info{};
     hipStream_t stream = nullptr;      // A: input staging, k_mix_decimate, k_dc_update
@@ -44,9 +47,9 @@ struct sonde_engine {
     std::vector<sonde_dfm_frame_t> h_dfm; std::vector<sonde_m10_frame_t> h_m10; bool soft_lazy = false; unsigned soft_lazy_start = 0;
     uint32_t *d_ecc_list = nullptr; unsigned *d_ecc_cnt = nullptr;     // two work lists of max_frames record slots, alternating per call; {count[2], done[2]}
     hipEvent_t ev_a[4] = {}, ev_b[4] = {}, ev_if[4] = {};      // per call: decimator done (A), records complete (B / E), y ring read (B: IF chain done)
-    unsigned *h_count = nullptr;       // pinned: frame counter snapshot after each call's framesync
+    Pinned<unsigned> h_count;          // mapped: frame counter snapshot after each call's framesync
     unsigned *h_count_dev = nullptr;   // the same words as the device addresses them (k_publish_u32 writes them)
-    FrameRec *h_recs = nullptr;        // pinned staging for record fetches
+    Pinned<FrameRec> h_recs;           // staging for record fetches
     int64_t call = 0;                  // process calls issued
     unsigned read_idx = 0;             // frames already handed to the caller (monotonic)
     bool eof_pending = false;          // an end-of-stream framesync ran after the last counter snapshot
@@ -78,13 +81,13 @@ struct sonde_engine {
     SyncState *d_state = nullptr; FrameRec *d_frames = nullptr; unsigned *d_fcount = nullptr; float *d_soft = nullptr, *d_soft1 = nullptr;
     uint4 *d_bitwin = nullptr; uint32_t *d_bitend = nullptr;
     uint8_t *d_consts = nullptr;   // hdr[64] | hdr_bytes[8] | mask[64] | gf_exp[512] | gf_log[256]
-    int16_t *d_stage = nullptr; size_t stage_bytes = 0;
+    uint8_t *d_stage = nullptr; size_t stage_bytes = 0;
     bool ifiq = false;                             // --iq0/2/3 input
     // --dc: AFC state and the rings a restart needs (rotated pre-filter stream, raw FM, FM-stream correlation)
     int opt_iq = 5; float match_sum = 0.f;
     std::vector<float> w_iq0; float *d_wiq0 = nullptr;
     float2 *d_yrot = nullptr; float *d_fmraw = nullptr, *d_corr2 = nullptr;
-    AfcState *d_afc = nullptr; uint32_t *d_start = nullptr; unsigned *d_pending = nullptr, *h_pending = nullptr;
+    AfcState *d_afc = nullptr; uint32_t *d_start = nullptr; unsigned *d_pending = nullptr; Pinned<unsigned> h_pending;
     // float32 input: IQ-DC sums in double, ring of mixed base-rate samples, taps in time order
     double *d_dcsums_f = nullptr; float2 *d_zring = nullptr; float *d_taps_f = nullptr; uint32_t zmask = 0;
     hipEvent_t ev_copy = nullptr;                  // end of the host -> staging copy of process_host
@@ -124,13 +127,7 @@ struct sonde_engine {
     bool merged = false, borrowed_b = false;     // merged (owner): one launch per IF-rate stage for all groups, on the one stream B they share; borrowed_b (group): stream_b is the owner's
 };
 // how sonde_engine_create_mixed creates its parts
-struct CreateLink { bool is_group, front_only; int min_ring; hipStream_t shared_b; };     // shared_b: the ONE stream B of a mixed engine whose groups' IF-rate stages share launches (nullptr: a stream B per part)
-
-template <class T> static int dalloc(T **p, size_t n, bool zero = true) {
-    HIPCHK(hipMalloc((void **)p, n * sizeof(T)));
-    if (zero) HIPCHK(hipMemset(*p, 0, n * sizeof(T)));
-    return 0;
-}
+struct CreateLink { bool is_group, front_only, design_only; int min_ring; hipStream_t shared_b; };     // design_only: stop behind engine_design (the caller wants ring_len); shared_b: the ONE stream B of a mixed engine whose groups' IF-rate stages share launches (nullptr: a stream B per part)
 
 static void prof_begin(sonde_engine *e, const char *name, hipStream_t s) {
     if (!e->prof || (e->prof_level == 1 && strcmp(name, "mix_decimate") != 0)) { e->prof_skip = true; return; }
@@ -182,13 +179,13 @@ static int collect_records(sonde_engine *e, int lag, std::vector<FrameRec> &recs
     while (done < n) {
         const unsigned idx = (e->read_idx + done) % (unsigned)e->max_frames;
         const unsigned run = std::min<unsigned>(n - done, (unsigned)e->max_frames - idx);
-        if (hipMemcpyAsync(e->h_recs + done, e->d_frames + idx, (size_t)run * sizeof(FrameRec), hipMemcpyDeviceToHost, cs) != hipSuccess) return SONDE_E_NOGPU;
+        if (hipMemcpyAsync(e->h_recs.data() + done, e->d_frames + idx, (size_t)run * sizeof(FrameRec), hipMemcpyDeviceToHost, cs) != hipSuccess) return SONDE_E_NOGPU;
         if (soft && e->d_soft && hipMemcpyAsync(soft->data() + (size_t)done * e->nbits, e->d_soft + (size_t)idx * e->nbits,
                                                 (size_t)run * e->nbits * sizeof(float), hipMemcpyDeviceToHost, cs) != hipSuccess) return SONDE_E_NOGPU;
         done += run;
     }
     if (n && hipStreamSynchronize(cs) != hipSuccess) return SONDE_E_NOGPU;
-    if (n) memcpy(recs.data(), e->h_recs, (size_t)n * sizeof(FrameRec));
+    if (n) memcpy(recs.data(), e->h_recs.data(), (size_t)n * sizeof(FrameRec));
     e->read_idx += n;
     return (int)n;
 }
@@ -276,6 +273,7 @@ int sonde_rs41_ecc_device(uint8_t *frames, const int32_t *flen, int32_t n, int32
     if (!frames || !flen || !ecc || n < 0 || level < 1 || level > 2) return SONDE_E_ARG;
     if (n == 0) return 0;
     for (int i = 0; i < n; i++) if (flen[i] < 0 || flen[i] > 518) return SONDE_E_ARG;
+    // one-shot temporaries of this call, no object behind them: allocated and freed here (every path reaches the frees below)
     uint8_t *d_fr = nullptr, *d_syn = nullptr, *d_gf = nullptr; int32_t *d_len = nullptr, *d_ecc = nullptr, *d_codes = nullptr;
     int rc = 0;
     auto ok = [&](hipError_t e) { if (e != hipSuccess && rc == 0) { fprintf(stderr, "libsonde_hip: sonde_rs41_ecc_device: %s\n", hipGetErrorString(e)); rc = SONDE_E_NOGPU; } return rc == 0; };
@@ -304,44 +302,33 @@ int sonde_engine_create_generic(const sonde_cfg_t *cfg, const double *fq, const 
 }  // extern "C"
 
 static IfArgs fill_if(sonde_engine *e, int n_if, uint32_t m_first);
-static int create_impl(const sonde_cfg_t *cfg, const double *fq, const sonde_generic_t *gen, const CreateLink *lk, sonde_engine_t **out) {
-    if (!cfg || !fq || !out || cfg->abi_version != SONDE_ABI_VERSION) return SONDE_E_ARG;
-    if (cfg->sonde_type == SONDE_GENERIC && !gen) return SONDE_E_ARG;
-    // a description next to a PRESET type (DFM09 / M10 / M20 / RS41): only its baud is read — the decoders' --br option (dfm09mod.c:1436-1443,
-    // 1590-1594; m20mod.c:1082-1089): dsp.br / dsp.sps are replaced before init_buffers(), so filters, template and slicers all follow
-    float baud_override = 0.f;
-    if (gen && cfg->sonde_type != SONDE_GENERIC) { if (!(gen->baud > 0.f)) return SONDE_E_ARG; baud_override = gen->baud; gen = nullptr; }
-    if (gen) {
-        const size_t hl = strnlen(gen->header, sizeof gen->header);
-        if (hl < 8 || hl > 64 || !(gen->baud > 0.f) || !(gen->bt > 0.f) || !(gen->h > 0.f) || gen->symlen < 1 || gen->symlen > 2 || gen->symhd < 1 || gen->symhd > gen->symlen ||
-            hl % gen->symhd || gen->hdmax < 0 || gen->bitofs < -8 || gen->bitofs > 64 || gen->nbits < 1 || gen->nbits > 8192 || gen->skip_bits < 0 || gen->slice_baud < 0.f) return SONDE_E_ARG;
-    }
-    if (cfg->n_channels < 1 || cfg->sample_rate < 1 || (cfg->bits != 16 && cfg->bits != 8 && cfg->bits != 32)) return SONDE_E_ARG;
-    // every decoder of the reference turns the FM low-pass on when it runs `--IQ fq` with `--dc` (rs41mod.c:2747, dfm09mod.c:1475, m10mod.c:1320, ... — all eleven
-    // have the line): an engine that stands for such a decoder does the same, whether its caller remembered or not
-    sonde_cfg_t cfg_own = *cfg;
-    if (cfg->input == SONDE_IN_IQ && cfg->opt_dc && cfg->sonde_type != SONDE_FRONTEND) cfg_own.opt_lp |= SONDE_LP_FM;
-    cfg = &cfg_own;
-    if ((cfg->sonde_type != SONDE_RS41 && cfg->sonde_type != SONDE_DFM09 && cfg->sonde_type != SONDE_M10 && cfg->sonde_type != SONDE_M20 && cfg->sonde_type != SONDE_FRONTEND && cfg->sonde_type != SONDE_GENERIC) ) return SONDE_E_ARG;
-    if (cfg->opt_dc && cfg->sonde_type == SONDE_FRONTEND) return SONDE_E_ARG;
-    if (cfg->opt_nolut && (cfg->opt_dc || cfg->input != SONDE_IN_IQ)) return SONDE_E_ARG;     // --noLUT folds Df into the base-rate mixer: not with --dc here
-    if (cfg->if_tune && (cfg->input < SONDE_IN_IFIQ0 || cfg->bits != 32 || cfg->opt_dc)) return SONDE_E_ARG;   // fine tuning: float32 IF-rate IQ only
-    if (cfg->sonde_type == SONDE_FRONTEND && cfg->input != SONDE_IN_IQ) return SONDE_E_ARG;
-    if (cfg->input < SONDE_IN_IQ || cfg->input > SONDE_IN_IFIQ3) return SONDE_E_ARG;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1 || cfg->device >= ndev) {
-        fprintf(stderr, "libsonde_hip: no usable HIP device (the engine has no CPU fallback)\n");
-        return SONDE_E_NOGPU;
-    }
-    HIPCHK(hipSetDevice(cfg->device));
-    sonde_engine *e = new sonde_engine();
-    e->cfg = *cfg;
+
+// Length of an engine's IF-rate rings: a call's IF samples with a frame and the search windows behind them, two calls when stream A runs ahead (pipeline).
+// min_ring: the length the parts of a mixed engine share (the y ring is the owner's); 0 elsewhere
+static int ring_length(int max_if, int frame_samples, int M, bool pipeline, int min_ring) {
+    int ring = 1; while (ring < max_if + frame_samples + 2 * M + 4096 || ring < 4 * M || (pipeline && ring < 2 * max_if + 4096)) ring <<= 1;
+    return std::max(ring, min_ring);
+}
+
+// what the design part of a create leaves for the device part to upload
+struct HostTables {
+    std::string header;
+    std::vector<float> wtab2, Fm, tws, shapes, symsign;       // wtab2: the decimator's tap rows as the kernels fetch them; Fm, tws: (re, im) pairs
+    std::vector<double> f0s;
+    std::vector<int> symtype;
+    std::vector<uint32_t> bitwin, bitend;
+};
+
+// Create, part 1: everything that follows from the configuration, into e's host members and t.  No HIP call but sonde_if_chain_reserve; every configuration
+// that is refused is refused here, before anything is allocated.  (cfg = &e->cfg.)
+static int engine_design(sonde_engine *e, const double *fq, const sonde_generic_t *gen, const CreateLink *lk, float baud_override, HostTables &t) {
+    const sonde_cfg_t *cfg = &e->cfg;
     const int C = cfg->n_channels;
     const bool is_group = lk && lk->is_group, front_only = lk && lk->front_only;
     e->is_group = is_group; e->front_only = front_only;
 
     // ---- sonde preset (rs41mod.c:2591-2597,2812-2836,2882,2920-2923)
-    std::string header;
+    std::string &header = t.header;
     int lpiq_def, lpfm_bw;
     int skip_last = -1;
     if (gen) {                                   // any other 2-FSK sonde of the reference's demod/mod family: what its main() puts into dsp_t / passes to find_header()
@@ -386,7 +373,7 @@ static int create_impl(const sonde_cfg_t *cfg, const double *fq, const sonde_gen
     // more tap columns than the packed kernels hold (a narrow transition band at a high decimation, e.g. `iq_dec --IFbw 32` at 960 kHz: 321 taps, D = 30): the plain
     // float32 mixer / FIR kernels take any length; 16- / 8-bit samples are converted for them first (x / 32768, what f32read_cblock does)
     const bool wide = e->Q > 8;
-    if (D > 1024 || (wide && (audio || ifiq || lk || cfg->input != SONDE_IN_IQ))) { delete e; return SONDE_E_ARG; }
+    if (D > 1024 || (wide && (audio || ifiq || lk || cfg->input != SONDE_IN_IQ))) return SONDE_E_ARG;
     e->f32_path = cfg->bits == 32 || wide; e->conv32 = wide && cfg->bits != 32;
     if ((cfg->opt_lp & SONDE_LP_IQ) && !audio) {
         float f_lp = (float)(24e3 / (float)sr / 2.0);
@@ -424,12 +411,10 @@ static int create_impl(const sonde_cfg_t *cfg, const double *fq, const sonde_gen
     if (!audio && !front_only) {
         const IfArgs ia = fill_if(e, 0, 0);
         const int rc = sonde_if_chain_reserve(&ia, cfg->device);
-        if (rc) { delete e; return rc == -1 ? SONDE_E_ARG : SONDE_E_NOGPU; }
+        if (rc) return rc == -1 ? SONDE_E_ARG : SONDE_E_NOGPU;
     }
 
-    const int max_if = (cfg->max_chunk + D - 1) / D;
-    int ring = 1; while (ring < max_if + (int)e->frame_samples + 2 * M + 4096 || ring < 4 * M || (cfg->pipeline && ring < 2 * max_if + 4096)) ring <<= 1;
-    if (lk && ring < lk->min_ring) ring = lk->min_ring;        // the parts of a mixed engine share one ring length (the y ring is the owner's)
+    const int ring = ring_length((cfg->max_chunk + D - 1) / D, (int)e->frame_samples, M, cfg->pipeline != 0, lk ? lk->min_ring : 0);
     e->ring_len = ring;
     e->max_frames = cfg->max_frames > 0 ? cfg->max_frames : 4 * C;
 
@@ -438,90 +423,47 @@ static int create_impl(const sonde_cfg_t *cfg, const double *fq, const sonde_gen
     I.L = L; I.M = M; I.K = K; I.N = M; I.delay = delay; I.sps = e->sps_design; I.ring_len = ring;
 
     // ---- decimator taps, front-padded to Q*D and laid out [r][q] so that step r loads its Q taps with one scalar load
-    if (wide) e->wtab.assign((size_t)std::max(64, D) * 8, 0.f);      // (not used: the float32 kernels read the taps as they are, d_taps_f)
-    else {
+    e->wtab.assign((size_t)std::max(64, D) * 8, 0.f);         // (wide: not used, the float32 kernels read the taps as they are, d_taps_f)
+    if (!wide) {
         const int pad = e->Q * D - T;
         std::vector<float> wpad((size_t)e->Q * D, 0.f);
         for (int k = 0; k < T; k++) wpad[pad + k] = e->dec.taps[k];
-        e->wtab.assign((size_t)std::max(64, D) * 8, 0.f);
         for (int r = 0; r < D; r++) for (int q = 0; q < e->Q; q++) e->wtab[(size_t)r * 8 + q] = wpad[(size_t)D * q + r];
         if (D > 64) {                                         // wide decimation (k_mix_decimate_wide): taps in global memory
             for (int k = 64; k >= 4; k--) if (D % k == 0) { e->DS = k; break; }
-            if (!e->DS || e->Q < 5) { delete e; return SONDE_E_ARG; }
+            if (!e->DS || e->Q < 5) return SONDE_E_ARG;
         }
         // the tap rows in global memory too: the wide variant and the hand-scheduled D = 50 stream fetch them with scalar loads
         // (for D <= 64 a second copy follows, scaled by 2^-15 — exact — which takes over the 1/32768 of the int16 samples)
-        {
-            std::vector<float> both(e->wtab);
-            if (D <= 64) for (size_t i = 0; i < e->wtab.size(); i++) both.push_back(e->wtab[i] * 3.0517578125e-05f);
-            if (dalloc(&e->d_wtab, both.size(), false)) { delete e; return SONDE_E_NOMEM; }
-            HIPCHK(hipMemcpy(e->d_wtab, both.data(), both.size() * sizeof(float), hipMemcpyHostToDevice));
-        }
+        t.wtab2 = e->wtab;
+        if (D <= 64) for (size_t i = 0; i < e->wtab.size(); i++) t.wtab2.push_back(e->wtab[i] * 3.0517578125e-05f);
     }
     // ---- mixer: snapped frequency per channel (xlt_fq = -fq, rs41mod.c:2685); the table period is common
-    {
-        std::vector<double> f0s(C);
-        for (int c = 0; c < C; c++) {
-            const Mixer m = design_mixer(-std::max(-0.5, std::min(0.5, fq[c])), cfg->sample_rate);
-            f0s[c] = m.f0; e->lut_len = m.lut_len;
-            if (cfg->opt_nolut || cfg->if_tune) f0s[c] = -std::max(-0.5, std::min(0.5, fq[c]));   // xlt_fq itself, not the table's snapped value
-        }
-        I.lut_len = e->lut_len;
-        if (dalloc(&e->d_chanf0, (size_t)C, false)) { delete e; return SONDE_E_NOMEM; }
-        HIPCHK(hipMemcpy(e->d_chanf0, f0s.data(), f0s.size() * sizeof(double), hipMemcpyHostToDevice));
+    t.f0s.resize((size_t)C);
+    for (int c = 0; c < C; c++) {
+        const Mixer m = design_mixer(-std::max(-0.5, std::min(0.5, fq[c])), cfg->sample_rate);
+        t.f0s[c] = m.f0; e->lut_len = m.lut_len;
+        if (cfg->opt_nolut || cfg->if_tune) t.f0s[c] = -std::max(-0.5, std::min(0.5, fq[c]));   // xlt_fq itself, not the table's snapped value
     }
+    I.lut_len = e->lut_len;
     // ---- 2.4 Msps -> 48 kHz class (D = 50, Q = 7, float table phase, rows aligned with the mixer table): the hand-scheduled
-    // decimator, which subtracts the IQ-DC mean per output as avg * E — E tabulated here, once (k_md_etable)
+    // decimator, which subtracts the IQ-DC mean per output as avg * E — E tabulated once on the device (k_md_etable, engine_device)
     if (D == 50 && e->Q == 7 && !audio && cfg->bits != 32 && cfg->sonde_type != SONDE_FRONTEND && !cfg->opt_nolut && e->lut_len % D == 0
-        && cfg->input == SONDE_IN_IQ && !is_group) {
-        e->etab_len = e->lut_len / D;
-        if (dalloc(&e->d_etab, (size_t)C * e->etab_len, false) || dalloc(&e->d_dcavg_prev, C)) { sonde_engine_destroy(e); return SONDE_E_NOMEM; }
-        sonde_launch_md_etable(e->d_chanf0, e->d_wtab, D, e->Q, e->etab_len, C, e->d_etab, nullptr);
-        HIPCHK(hipDeviceSynchronize());
-    }
-    int bad = 0;
-    bad |= dalloc(&e->d_dcavg, C); bad |= dalloc(&e->d_dcsums, 2 * (size_t)C);
-    bad |= dalloc(&e->d_ptail[0], (size_t)C * 64); bad |= dalloc(&e->d_ptail[1], (size_t)C * 64);
-    if (audio) bad |= dalloc(&e->d_raw, (size_t)C * ring);
-    else { if (!is_group) bad |= dalloc(&e->d_y, (size_t)C * ring); if (!front_only) bad |= dalloc(&e->d_ifiq, (size_t)C * ring); }
-    if (!front_only) { bad |= dalloc(&e->d_fm, (size_t)C * ring); bad |= dalloc(&e->d_bufs, (size_t)C * ring); bad |= dalloc(&e->d_corr, (size_t)C * ring); }
-    bad |= dalloc(&e->d_state, C); bad |= dalloc(&e->d_frames, e->max_frames); bad |= dalloc(&e->d_fcount, 1 + 4);      // the counter, and its value behind each of the last four calls (what a call publishes)
-    if (cfg->keep_soft || cfg->sonde_type != SONDE_RS41) bad |= dalloc(&e->d_soft, (size_t)e->max_frames * e->nbits);
-    if (cfg->keep_soft == 2) bad |= dalloc(&e->d_soft1, (size_t)e->max_frames * e->nbits);
-    if (cfg->sonde_type == SONDE_DFM09) { bad |= dalloc(&e->d_dfm_out, (size_t)e->max_frames * 8); bad |= dalloc(&e->d_blk_done, 2); }
-    if (cfg->sonde_type == SONDE_M10) { bad |= dalloc(&e->d_m10_out, (size_t)e->max_frames); bad |= dalloc(&e->d_blk_done, 2); bad |= dalloc(&e->d_m10_bits, (size_t)C * ((101 + 20) * 8 + 8)); }
-    bad |= dalloc(&e->d_match, L, false);
-    if (!e->w_iq.empty()) bad |= dalloc(&e->d_wiq, e->w_iq.size(), false);
-    if (!e->w_fm.empty()) bad |= dalloc(&e->d_wfm, e->w_fm.size(), false);
-    bad |= dalloc(&e->d_consts, 1024, true);
-    if (bad) { sonde_engine_destroy(e); return SONDE_E_NOMEM; }
-    HIPCHK(hipMemcpy(e->d_match, e->match.data(), L * sizeof(float), hipMemcpyHostToDevice));
+        && cfg->input == SONDE_IN_IQ && !is_group) e->etab_len = e->lut_len / D;
     e->dev_ecc = getenv("SONDE_HOST_ECC") == nullptr;
-    {   // Fm = rdft(time-reversed match) with the reference's transform (init_buffers, demod_mod.c:1446-1449); N = 8192 only
-        if (!cfg->opt_dc && M == 8192 && K + L <= M) {
-            std::vector<float> m(2 * (size_t)M, 0.f);
-            for (int i = 0; i < L; i++) m[2 * (size_t)(L - 1 - i)] = e->match[i];
-            ref_dft_8192(m);
-            const std::vector<float> tw = ref_twiddle_table();
-            e->win_W = 8;
-            m.resize(4 * (size_t)M);                          // behind the table its bit-reversed copy (the conjugate-and-swap pass reads both coalesced)
-            for (int i = 0; i < M; i++) {
-                int r = 0; for (int b = 0; b < 13; b++) if (i >> b & 1) r |= 1 << (12 - b);
-                m[2 * (size_t)(M + i)] = m[2 * (size_t)r]; m[2 * (size_t)(M + i) + 1] = m[2 * (size_t)r + 1];
-            }
-            if (dalloc(&e->d_Fm, 2 * (size_t)M, false) || dalloc(&e->d_tws, tw.size() / 2, false) || dalloc(&e->d_win, (size_t)C * e->win_W) ||
-                dalloc(&e->d_work, (size_t)C * e->win_W) || dalloc(&e->d_work_count, 2)) { sonde_engine_destroy(e); return SONDE_E_NOMEM; }
-            HIPCHK(hipMemcpy(e->d_Fm, m.data(), m.size() * sizeof(float), hipMemcpyHostToDevice));
-            HIPCHK(hipMemcpy(e->d_tws, tw.data(), tw.size() * sizeof(float), hipMemcpyHostToDevice));
+    // Fm = rdft(time-reversed match) with the reference's transform (init_buffers, demod_mod.c:1446-1449); N = 8192 only
+    if (!cfg->opt_dc && M == 8192 && K + L <= M) {
+        std::vector<float> &m = t.Fm;
+        m.assign(2 * (size_t)M, 0.f);
+        for (int i = 0; i < L; i++) m[2 * (size_t)(L - 1 - i)] = e->match[i];
+        ref_dft_8192(m);
+        t.tws = ref_twiddle_table();
+        e->win_W = 8;
+        m.resize(4 * (size_t)M);                              // behind the table its bit-reversed copy (the conjugate-and-swap pass reads both coalesced)
+        for (int i = 0; i < M; i++) {
+            int r = 0; for (int b = 0; b < 13; b++) if (i >> b & 1) r |= 1 << (12 - b);
+            m[2 * (size_t)(M + i)] = m[2 * (size_t)r]; m[2 * (size_t)(M + i) + 1] = m[2 * (size_t)r + 1];
         }
-    }
-    if (e->d_wiq) HIPCHK(hipMemcpy(e->d_wiq, e->w_iq.data(), e->w_iq.size() * sizeof(float), hipMemcpyHostToDevice));
-    if (e->d_wfm) HIPCHK(hipMemcpy(e->d_wfm, e->w_fm.data(), e->w_fm.size() * sizeof(float), hipMemcpyHostToDevice));
-    {
-        uint8_t cb[1024]; memset(cb, 0, sizeof cb);
-        memcpy(cb, header.data(), header.size()); memcpy(cb + 64, kRs41HeaderBytes, 8); memcpy(cb + 72, kRs41Mask, 64);
-        memcpy(cb + 136, gf_exp_table(), 512); memcpy(cb + 648, gf_log_table(), 256);
-        HIPCHK(hipMemcpy(e->d_consts, cb, sizeof cb, hipMemcpyHostToDevice));
     }
     // ---- factorised header correlation tables (integer samples/symbol only; else the direct L-tap kernel runs)
     {
@@ -535,85 +477,117 @@ static int create_impl(const sonde_cfg_t *cfg, const double *fq, const sonde_gen
                 const int l = (k > 0) ? ((header[k - 1] & 1) ? 1 : -1) * b : 0;
                 const int r = (k < nsym - 1) ? ((header[k + 1] & 1) ? 1 : -1) * b : 0;
                 const int ky = (l + 1) * 3 + (r + 1);
-                int t = -1;
-                for (size_t q = 0; q < key.size(); q++) if (key[q] == ky) t = (int)q;
-                if (t < 0) {
-                    t = (int)key.size(); key.push_back(ky);
+                int ty = -1;
+                for (size_t q = 0; q < key.size(); q++) if (key[q] == ky) ty = (int)q;
+                if (ty < 0) {
+                    ty = (int)key.size(); key.push_back(ky);
                     for (int d = 0; d < isps; d++) shapes.push_back((float)b * e->match[(size_t)isps * k + d]);
                 } else {
-                    for (int d = 0; d < isps; d++) ok &= (shapes[(size_t)t * isps + d] == (float)b * e->match[(size_t)isps * k + d]);
+                    for (int d = 0; d < isps; d++) ok &= (shapes[(size_t)ty * isps + d] == (float)b * e->match[(size_t)isps * k + d]);
                 }
-                type[k] = t; sign[k] = (float)b;
+                type[k] = ty; sign[k] = (float)b;
             }
-            if (ok && key.size() <= 9) {
-                e->corr_types = (int)key.size(); e->corr_isps = isps;
-                bad = 0;
-                bad |= dalloc(&e->d_shapes, shapes.size(), false); bad |= dalloc(&e->d_symtype, nsym, false); bad |= dalloc(&e->d_symsign, nsym, false);
-                if (bad) { sonde_engine_destroy(e); return SONDE_E_NOMEM; }
-                HIPCHK(hipMemcpy(e->d_shapes, shapes.data(), shapes.size() * sizeof(float), hipMemcpyHostToDevice));
-                HIPCHK(hipMemcpy(e->d_symtype, type.data(), nsym * sizeof(int), hipMemcpyHostToDevice));
-                HIPCHK(hipMemcpy(e->d_symsign, sign.data(), nsym * sizeof(float), hipMemcpyHostToDevice));
-            }
+            if (ok && key.size() <= 9) { e->corr_types = (int)key.size(); e->corr_isps = isps; t.shapes = shapes; t.symtype = type; t.symsign = sign; }
         }
     }
     // ---- per-bit slicing ranges (position independent): read_softbit2p's double-edge / integer-counter walk, tabulated
-    {
-        std::vector<uint32_t> win((size_t)e->nbits * 4), end(e->nbits);
-        for (int bp = 0; bp < e->nbits; bp++) {
-            uint32_t q0, q1, qa, qb; double mid;
-            if (e->symlen == 2) { bit_window(bp, 0, 2, e->sps, q0, q1, mid); slice_range(q0, q1, mid, e->l_win, qa, qb); }
-            else { qa = qb = 0; }
-            win[4 * bp] = qa; win[4 * bp + 1] = qb;
-            bit_window(bp, e->symlen - 1, e->symlen, e->sps, q0, q1, mid);
-            slice_range(q0, q1, mid, e->l_win, qa, qb);
-            win[4 * bp + 2] = qa; win[4 * bp + 3] = qb; end[bp] = q1;
-        }
-        bad = 0;
-        bad |= dalloc(&e->d_bitwin, (size_t)e->nbits, false); bad |= dalloc(&e->d_bitend, (size_t)e->nbits, false);
-        if (bad) { sonde_engine_destroy(e); return SONDE_E_NOMEM; }
-        HIPCHK(hipMemcpy(e->d_bitwin, win.data(), win.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(e->d_bitend, end.data(), end.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    t.bitwin.resize((size_t)e->nbits * 4); t.bitend.resize((size_t)e->nbits);
+    for (int bp = 0; bp < e->nbits; bp++) {
+        uint32_t q0, q1, qa, qb; double mid;
+        if (e->symlen == 2) { bit_window(bp, 0, 2, e->sps, q0, q1, mid); slice_range(q0, q1, mid, e->l_win, qa, qb); }
+        else { qa = qb = 0; }
+        t.bitwin[4 * bp] = qa; t.bitwin[4 * bp + 1] = qb;
+        bit_window(bp, e->symlen - 1, e->symlen, e->sps, q0, q1, mid);
+        slice_range(q0, q1, mid, e->l_win, qa, qb);
+        t.bitwin[4 * bp + 2] = qa; t.bitwin[4 * bp + 3] = qb; t.bitend[bp] = q1;
     }
     // IQ-DC segment schedule (demod_mod.c:1351-1357)
     e->dc_lim = (uint32_t)sr; e->dc_max = e->dc_lim / 32;
     if (D > 1) { e->dc_lim *= D; e->dc_max *= D; }
-    if (e->dc_max == 0 || e->dc_max % D) { sonde_engine_destroy(e); return SONDE_E_ARG; }
+    if (e->dc_max == 0 || e->dc_max % D) return SONDE_E_ARG;
     e->dc_max0 = e->dc_max;
     e->ifiq = ifiq;
+    if (e->f32_path && !audio && !ifiq) { uint32_t zl = 1; while (zl < (uint32_t)cfg->max_chunk + (uint32_t)T + (uint32_t)D + 64u) zl <<= 1; e->zmask = zl - 1; }
+    e->opt_iq = audio ? 0 : ifiq ? (cfg->input == SONDE_IN_IFIQ0 ? 1 : cfg->input == SONDE_IN_IFIQ2 ? 2 : 3) : 5;
+    { double sm = 0.0; for (float v : e->match) sm += (double)v; e->match_sum = (float)sm; }
+    e->last_frame.assign((size_t)C * 518, 0);
+    for (int c = 0; c < C; c++) memcpy(e->last_frame.data() + (size_t)c * 518, kRs41HeaderBytes, 8);
+    // pipeline: stream A (staging, decimator) may run ONE call ahead of stream B (IF-rate kernels); the rings hold that (see
+    // process_device).  The FM-audio path writes the rings B reads from on stream A, so it does not pipeline.
+    if (cfg->pipeline && audio) return SONDE_E_ARG;
+    return 0;
+}
+
+// two words of a table per device element (float2 from (re, im) pairs, uint4 from four words)
+template <class D, class T> static int upload_as(DevMem &mem, D **p, const std::vector<T> &v) {
+    T *q = nullptr;
+    TRY(mem.upload(&q, v));
+    *p = (D *)q;
+    return 0;
+}
+
+// Create, part 2: device memory, uploads, streams and events of the engine engine_design() has laid out.  Every return leaves what exists so far to ~sonde_engine.
+static int engine_device(sonde_engine *e, const CreateLink *lk, const HostTables &t) {
+    const sonde_cfg_t *cfg = &e->cfg;
+    DevMem &mem = e->mem;
+    const int C = cfg->n_channels, D = e->info.decM;
+    const size_t ring = (size_t)e->ring_len;
+    const bool audio = cfg->input == SONDE_IN_AUDIO;
+    if (!t.wtab2.empty()) TRY(mem.upload(&e->d_wtab, t.wtab2));
+    TRY(mem.upload(&e->d_chanf0, t.f0s));
+    if (e->etab_len) {
+        TRY(mem.dalloc(&e->d_etab, (size_t)C * e->etab_len, false)); TRY(mem.dalloc(&e->d_dcavg_prev, C));
+        sonde_launch_md_etable(e->d_chanf0, e->d_wtab, D, e->Q, e->etab_len, C, e->d_etab, nullptr);
+        HIPCHK(hipDeviceSynchronize());
+    }
+    TRY(mem.dalloc(&e->d_dcavg, C)); TRY(mem.dalloc(&e->d_dcsums, 2 * (size_t)C));
+    TRY(mem.dalloc(&e->d_ptail[0], (size_t)C * 64)); TRY(mem.dalloc(&e->d_ptail[1], (size_t)C * 64));
+    if (audio) TRY(mem.dalloc(&e->d_raw, (size_t)C * ring));
+    else {
+        if (!e->is_group) TRY(mem.dalloc(&e->d_y, (size_t)C * ring));      // (a group reads its rows of the owner's: sonde_engine_create_mixed points d_y there, unregistered)
+        if (!e->front_only) TRY(mem.dalloc(&e->d_ifiq, (size_t)C * ring));
+    }
+    if (!e->front_only) { TRY(mem.dalloc(&e->d_fm, (size_t)C * ring)); TRY(mem.dalloc(&e->d_bufs, (size_t)C * ring)); TRY(mem.dalloc(&e->d_corr, (size_t)C * ring)); }
+    TRY(mem.dalloc(&e->d_state, C)); TRY(mem.dalloc(&e->d_frames, e->max_frames));
+    TRY(mem.dalloc(&e->d_fcount, 1 + 4));       // the counter, and its value behind each of the last four calls (what a call publishes)
+    if (cfg->keep_soft || cfg->sonde_type != SONDE_RS41) TRY(mem.dalloc(&e->d_soft, (size_t)e->max_frames * e->nbits));
+    if (cfg->keep_soft == 2) TRY(mem.dalloc(&e->d_soft1, (size_t)e->max_frames * e->nbits));
+    if (cfg->sonde_type == SONDE_DFM09) { TRY(mem.dalloc(&e->d_dfm_out, (size_t)e->max_frames * 8)); TRY(mem.dalloc(&e->d_blk_done, 2)); }
+    if (cfg->sonde_type == SONDE_M10) { TRY(mem.dalloc(&e->d_m10_out, (size_t)e->max_frames)); TRY(mem.dalloc(&e->d_blk_done, 2)); TRY(mem.dalloc(&e->d_m10_bits, (size_t)C * ((101 + 20) * 8 + 8))); }
+    TRY(mem.upload(&e->d_match, e->match));
+    if (!e->w_iq.empty()) TRY(mem.upload(&e->d_wiq, e->w_iq));
+    if (!e->w_fm.empty()) TRY(mem.upload(&e->d_wfm, e->w_fm));
+    {
+        std::vector<uint8_t> cb(1024, 0);
+        memcpy(cb.data(), t.header.data(), t.header.size()); memcpy(cb.data() + 64, kRs41HeaderBytes, 8); memcpy(cb.data() + 72, kRs41Mask, 64);
+        memcpy(cb.data() + 136, gf_exp_table(), 512); memcpy(cb.data() + 648, gf_log_table(), 256);
+        TRY(mem.upload(&e->d_consts, cb));
+    }
+    if (e->win_W) {
+        TRY(upload_as(mem, &e->d_Fm, t.Fm)); TRY(upload_as(mem, &e->d_tws, t.tws));
+        TRY(mem.dalloc(&e->d_win, (size_t)C * e->win_W)); TRY(mem.dalloc(&e->d_work, (size_t)C * e->win_W)); TRY(mem.dalloc(&e->d_work_count, 2));
+    }
+    if (e->corr_types) { TRY(mem.upload(&e->d_shapes, t.shapes)); TRY(mem.upload(&e->d_symtype, t.symtype)); TRY(mem.upload(&e->d_symsign, t.symsign)); }
+    TRY(upload_as(mem, &e->d_bitwin, t.bitwin)); TRY(mem.upload(&e->d_bitend, t.bitend));
     if (e->f32_path) {
-        bad = dalloc(&e->d_dcsums_f, 2 * (size_t)C);
-        if (e->conv32) bad |= dalloc(&e->d_conv32, (size_t)C * (size_t)cfg->max_chunk, false);
-        if (!audio && !ifiq) {
-            uint32_t zl = 1; while (zl < (uint32_t)cfg->max_chunk + (uint32_t)T + (uint32_t)D + 64u) zl <<= 1;
-            e->zmask = zl - 1;
-            bad |= dalloc(&e->d_zring, (size_t)C * zl); bad |= dalloc(&e->d_taps_f, (size_t)T, false);
-            if (!bad) HIPCHK(hipMemcpy(e->d_taps_f, e->dec.taps.data(), (size_t)T * sizeof(float), hipMemcpyHostToDevice));
-        }
-        if (bad) { sonde_engine_destroy(e); return SONDE_E_NOMEM; }
+        TRY(mem.dalloc(&e->d_dcsums_f, 2 * (size_t)C));
+        if (e->conv32) TRY(mem.dalloc(&e->d_conv32, (size_t)C * (size_t)cfg->max_chunk, false));
+        if (e->zmask) { TRY(mem.dalloc(&e->d_zring, (size_t)C * ((size_t)e->zmask + 1))); TRY(mem.upload(&e->d_taps_f, e->dec.taps)); }
     }
     if (cfg->opt_inv) {                                       // -i: every channel starts with inverted polarity
         std::vector<SyncState> st0(C); for (auto &q : st0) { memset(&q, 0, sizeof q); q.inv = 1; }
         HIPCHK(hipMemcpy(e->d_state, st0.data(), st0.size() * sizeof(SyncState), hipMemcpyHostToDevice));
     }
-    e->opt_iq = audio ? 0 : ifiq ? (cfg->input == SONDE_IN_IFIQ0 ? 1 : cfg->input == SONDE_IN_IFIQ2 ? 2 : 3) : 5;
-    { double sm = 0.0; for (float v : e->match) sm += (double)v; e->match_sum = (float)sm; }
     if (cfg->opt_dc) {
-        bad = 0;
-        bad |= dalloc(&e->d_afc, C); bad |= dalloc(&e->d_start, C); bad |= dalloc(&e->d_pending, 1);
-        if (!audio) { bad |= dalloc(&e->d_yrot, (size_t)C * ring); bad |= dalloc(&e->d_fmraw, (size_t)C * ring); }
-        if (e->opt_iq >= 2) bad |= dalloc(&e->d_corr2, (size_t)C * ring);
-        if (!e->w_iq0.empty()) bad |= dalloc(&e->d_wiq0, e->w_iq0.size(), false);
-        if (bad) { sonde_engine_destroy(e); return SONDE_E_NOMEM; }
-        if (e->d_wiq0) HIPCHK(hipMemcpy(e->d_wiq0, e->w_iq0.data(), e->w_iq0.size() * sizeof(float), hipMemcpyHostToDevice));
-        HIPCHK(hipHostMalloc((void **)&e->h_pending, sizeof(unsigned), hipHostMallocDefault));
+        TRY(mem.dalloc(&e->d_afc, C)); TRY(mem.dalloc(&e->d_start, C)); TRY(mem.dalloc(&e->d_pending, 1));
+        if (!audio) { TRY(mem.dalloc(&e->d_yrot, (size_t)C * ring)); TRY(mem.dalloc(&e->d_fmraw, (size_t)C * ring)); }
+        if (e->opt_iq >= 2) TRY(mem.dalloc(&e->d_corr2, (size_t)C * ring));
+        if (!e->w_iq0.empty()) TRY(mem.upload(&e->d_wiq0, e->w_iq0));
+        if (!e->h_pending.alloc(1)) return SONDE_E_NOGPU;
     }
-    e->last_frame.assign((size_t)C * 518, 0);
-    for (int c = 0; c < C; c++) memcpy(e->last_frame.data() + (size_t)c * 518, kRs41HeaderBytes, 8);
+    if (cfg->sonde_type == SONDE_RS41) { TRY(mem.dalloc(&e->d_ecc_list, 2 * (size_t)e->max_frames, false)); TRY(mem.dalloc(&e->d_ecc_cnt, 4)); }
     HIPCHK(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
-    // pipeline: stream A (staging, decimator) may run ONE call ahead of stream B (IF-rate kernels); the rings hold that (see
-    // process_device).  The FM-audio path writes the rings B reads from on stream A, so it does not pipeline.
-    if (cfg->pipeline && audio) { sonde_engine_destroy(e); return SONDE_E_ARG; }
-    if (lk && lk->shared_b) { e->stream_b = lk->shared_b; e->borrowed_b = is_group; }
+    if (lk && lk->shared_b) { e->stream_b = lk->shared_b; e->borrowed_b = true; }      // sonde_engine_create_mixed owns it until the whole engine stands
     else if (cfg->pipeline) {
         // the IF-rate tail of call k runs beside the decimator of call k+1: few, latency-bound workgroups against thousands of bandwidth-bound
         // ones — B gets the higher dispatch priority so that its workgroups take the next free CU slot instead of queueing behind the decimator's
@@ -632,33 +606,61 @@ static int create_impl(const sonde_cfg_t *cfg, const double *fq, const sonde_gen
         else HIPCHK(hipStreamCreateWithFlags(&e->stream_e, hipStreamNonBlocking));
     }
     HIPCHK(hipEventCreateWithFlags(&e->ev_s, hipEventDisableTiming));
-    if (cfg->sonde_type == SONDE_RS41) {
-        HIPCHK(hipMalloc((void **)&e->d_ecc_list, 2 * (size_t)e->max_frames * sizeof(uint32_t)));
-        HIPCHK(hipMalloc((void **)&e->d_ecc_cnt, 4 * sizeof(unsigned)));
-        HIPCHK(hipMemset(e->d_ecc_cnt, 0, 4 * sizeof(unsigned)));
-    }
     for (int i = 0; i < 4; i++) { HIPCHK(hipEventCreateWithFlags(&e->ev_a[i], hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&e->ev_b[i], hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&e->ev_if[i], hipEventDisableTiming)); }
     HIPCHK(hipEventCreateWithFlags(&e->ev_copy, hipEventDisableTiming));
-    HIPCHK(hipHostMalloc((void **)&e->h_count, 4 * sizeof(unsigned), hipHostMallocMapped));
-    memset(e->h_count, 0, 4 * sizeof(unsigned));
-    HIPCHK(hipHostGetDevicePointer((void **)&e->h_count_dev, e->h_count, 0));
-    HIPCHK(hipHostMalloc((void **)&e->h_recs, (size_t)e->max_frames * sizeof(FrameRec), hipHostMallocDefault));
-    *out = e;
+    if (!e->h_count.alloc(4, hipHostMallocMapped) || !e->h_recs.alloc((size_t)e->max_frames)) return SONDE_E_NOGPU;
+    HIPCHK(hipHostGetDevicePointer((void **)&e->h_count_dev, e->h_count.data(), 0));
     return 0;
 }
 
-extern "C" {
+static int create_impl(const sonde_cfg_t *cfg, const double *fq, const sonde_generic_t *gen, const CreateLink *lk, sonde_engine_t **out) {
+    if (!cfg || !fq || !out || cfg->abi_version != SONDE_ABI_VERSION) return SONDE_E_ARG;
+    if (cfg->sonde_type == SONDE_GENERIC && !gen) return SONDE_E_ARG;
+    // a description next to a PRESET type (DFM09 / M10 / M20 / RS41): only its baud is read — the decoders' --br option (dfm09mod.c:1436-1443,
+    // 1590-1594; m20mod.c:1082-1089): dsp.br / dsp.sps are replaced before init_buffers(), so filters, template and slicers all follow
+    float baud_override = 0.f;
+    if (gen && cfg->sonde_type != SONDE_GENERIC) { if (!(gen->baud > 0.f)) return SONDE_E_ARG; baud_override = gen->baud; gen = nullptr; }
+    if (gen) {
+        const size_t hl = strnlen(gen->header, sizeof gen->header);
+        if (hl < 8 || hl > 64 || !(gen->baud > 0.f) || !(gen->bt > 0.f) || !(gen->h > 0.f) || gen->symlen < 1 || gen->symlen > 2 || gen->symhd < 1 || gen->symhd > gen->symlen ||
+            hl % gen->symhd || gen->hdmax < 0 || gen->bitofs < -8 || gen->bitofs > 64 || gen->nbits < 1 || gen->nbits > 8192 || gen->skip_bits < 0 || gen->slice_baud < 0.f) return SONDE_E_ARG;
+    }
+    if (cfg->n_channels < 1 || cfg->sample_rate < 1 || (cfg->bits != 16 && cfg->bits != 8 && cfg->bits != 32)) return SONDE_E_ARG;
+    // every decoder of the reference turns the FM low-pass on when it runs `--IQ fq` with `--dc` (rs41mod.c:2747, dfm09mod.c:1475, m10mod.c:1320, ... — all eleven
+    // have the line): an engine that stands for such a decoder does the same, whether its caller remembered or not
+    sonde_cfg_t cfg_own = *cfg;
+    if (cfg->input == SONDE_IN_IQ && cfg->opt_dc && cfg->sonde_type != SONDE_FRONTEND) cfg_own.opt_lp |= SONDE_LP_FM;
+    cfg = &cfg_own;
+    if ((cfg->sonde_type != SONDE_RS41 && cfg->sonde_type != SONDE_DFM09 && cfg->sonde_type != SONDE_M10 && cfg->sonde_type != SONDE_M20 && cfg->sonde_type != SONDE_FRONTEND && cfg->sonde_type != SONDE_GENERIC) ) return SONDE_E_ARG;
+    if (cfg->opt_dc && cfg->sonde_type == SONDE_FRONTEND) return SONDE_E_ARG;
+    if (cfg->opt_nolut && (cfg->opt_dc || cfg->input != SONDE_IN_IQ)) return SONDE_E_ARG;     // --noLUT folds Df into the base-rate mixer: not with --dc here
+    if (cfg->if_tune && (cfg->input < SONDE_IN_IFIQ0 || cfg->bits != 32 || cfg->opt_dc)) return SONDE_E_ARG;   // fine tuning: float32 IF-rate IQ only
+    if (cfg->sonde_type == SONDE_FRONTEND && cfg->input != SONDE_IN_IQ) return SONDE_E_ARG;
+    if (cfg->input < SONDE_IN_IQ || cfg->input > SONDE_IN_IFIQ3) return SONDE_E_ARG;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1 || cfg->device >= ndev) {
+        fprintf(stderr, "libsonde_hip: no usable HIP device (the engine has no CPU fallback)\n");
+        return SONDE_E_NOGPU;
+    }
+    HIPCHK(hipSetDevice(cfg->device));
+    std::unique_ptr<sonde_engine> e(new sonde_engine());
+    e->cfg = *cfg;
+    HostTables t;
+    TRY(engine_design(e.get(), fq, gen, lk, baud_override, t));
+    if (!lk || !lk->design_only) TRY(engine_device(e.get(), lk, t));
+    *out = e.release();
+    return 0;
+}
 
-void sonde_engine_destroy(sonde_engine_t *e) {
-    if (!e) return;
-    for (sonde_engine *g : e->groups) sonde_engine_destroy(g);      // (they borrow rows of this object's y ring)
-    e->groups.clear();
-    if (e->is_group) e->d_y = nullptr;
+// synchronise, print what a profile left on the device, destroy streams and events; the members then free the memory
+sonde_engine::~sonde_engine() {
+    sonde_engine *e = this;
+    for (sonde_engine *g : e->groups) delete g;                     // first: they borrow this object's stream B and rows of its y ring
     if (e->stream) hipStreamSynchronize(e->stream);
     if (e->stream_b) hipStreamSynchronize(e->stream_b);
     if (e->stream_e) hipStreamSynchronize(e->stream_e);
     prof_collect(e);
-    if (e->d_wfprof) {
+    if (e->d_wfprof) {                                              // (not in mem: allocated inside a launch path that cannot fail, read here, freed here)
         unsigned long long h[32] = {0};
         if (hipMemcpy(h, e->d_wfprof, sizeof h, hipMemcpyDeviceToHost) == hipSuccess && h[31]) {
             static const char *nm[7] = {"setup", "search", "headcmp", "slot", "slice", "syndromes+record", "exit"};
@@ -676,26 +678,18 @@ void sonde_engine_destroy(sonde_engine_t *e) {
         }
         hipFree(e->d_wfprof);
     }
-    { hipStream_t sa = e->stream; if (sa) hipStreamDestroy(sa); }
     if (e->stream_b && e->stream_b != e->stream && !e->borrowed_b) hipStreamDestroy(e->stream_b);
+    if (e->stream) hipStreamDestroy(e->stream);
     if (e->stream_c) hipStreamDestroy(e->stream_c);
     if (e->stream_e) hipStreamDestroy(e->stream_e);
     if (e->ev_s) hipEventDestroy(e->ev_s);
-    hipFree(e->d_dfm_out); hipFree(e->d_m10_out); hipFree(e->d_blk_done); hipFree(e->d_m10_bits);
-    hipFree(e->d_ecc_list); hipFree(e->d_ecc_cnt);
     for (int i = 0; i < 4; i++) { if (e->ev_a[i]) hipEventDestroy(e->ev_a[i]); if (e->ev_b[i]) hipEventDestroy(e->ev_b[i]); if (e->ev_if[i]) hipEventDestroy(e->ev_if[i]); }
     if (e->ev_copy) hipEventDestroy(e->ev_copy);
-    if (e->h_pending) hipHostFree(e->h_pending);
-    if (e->h_count) hipHostFree(e->h_count);
-    if (e->h_recs) hipHostFree(e->h_recs);
-    void *ptrs[] = { e->d_Bop, e->d_chanf0, e->d_dcavg, e->d_dcsums, e->d_ptail[0], e->d_ptail[1], e->d_y, e->d_ifiq, e->d_fm,
-                     e->d_bufs, e->d_corr, e->d_wiq, e->d_wfm, e->d_match, e->d_state, e->d_frames, e->d_fcount, e->d_soft, e->d_soft1,
-                     e->d_epoch, e->d_work, e->d_work_count, e->d_consts, e->d_stage, e->d_shapes, e->d_symtype, e->d_symsign, e->d_bitwin, e->d_bitend, e->d_raw, e->d_wtab, e->d_conv, e->d_conv32,
-                     e->d_dcsums_f, e->d_zring, e->d_taps_f, e->d_wiq0, e->d_yrot, e->d_fmraw, e->d_corr2, e->d_afc, e->d_start, e->d_pending,
-                     e->d_etab, e->d_dcavg_prev, e->d_win, e->d_Fm, e->d_tws, e->d_epoch_phase, e->d_pcs_cnt, e->d_pcs_max, e->d_pcs_since, e->d_in_row, e->d_sum_map, e->d_wcount };
-    for (void *p : ptrs) if (p) hipFree(p);
-    delete e;
 }
+
+extern "C" void sonde_engine_destroy(sonde_engine_t *e) { delete e; }
+
+extern "C" {
 
 int sonde_engine_info(const sonde_engine_t *e, sonde_info_t *info) {
     if (!e || !info) return SONDE_E_ARG;
@@ -745,7 +739,7 @@ int sonde_engine_process_device(sonde_engine_t *e, const void *d_iq, int64_t ch_
     if (n_samples <= 0 || n_samples > e->cfg.max_chunk || n_samples % D || (ch_stride != 0 && ch_stride < n_samples)) return SONDE_E_RANGE;
     if (e->cfg.bits == 8) {                        // cu8: (u-128)/128 == ((u-128)*256)/32768 -> feed the 16-bit path
         const int epf = e->cfg.input == SONDE_IN_AUDIO ? std::max(1, e->cfg.audio_channels) : 2;    // bytes per sample / audio frame
-        if (!e->d_conv) HIPCHK(hipMalloc((void **)&e->d_conv, (size_t)C * e->cfg.max_chunk * epf * 2));
+        if (!e->d_conv) TRY(e->mem.dalloc(&e->d_conv, (size_t)C * e->cfg.max_chunk * epf, false));
         sonde_launch_u8_to_s16((const uint8_t *)d_iq, ch_stride * epf, e->d_conv, (long long)n_samples * epf, ch_stride == 0 ? 1 : C, n_samples * epf, e->stream);
         d_iq = e->d_conv; if (ch_stride != 0) ch_stride = n_samples;
     }
@@ -934,9 +928,9 @@ static int tail_enqueue(sonde_engine *e, int32_t n_samples, uint32_t m_first, hi
             prof_begin(e, "header_corr", sb); sonde_launch_header_corr(&c, sb); prof_end(e, sb);
             if (e->opt_iq >= 2) { CorrArgs c2 = c; c2.bufs = e->d_fm; c2.corr = e->d_corr2; sonde_launch_header_corr(&c2, sb); }
             launch_framesync(e, 0);
-            hipMemcpyAsync(e->h_pending, e->d_pending, sizeof(unsigned), hipMemcpyDeviceToHost, sb);
+            hipMemcpyAsync(e->h_pending.data(), e->d_pending, sizeof(unsigned), hipMemcpyDeviceToHost, sb);
             HIPCHK(hipStreamSynchronize(sb));
-            if (*e->h_pending == 0) break;
+            if (e->h_pending[0] == 0) break;
         }
         if (e->stream_b != fs) hipEventRecord(e->ev_if[slot], e->stream_b);
     } else {
@@ -990,19 +984,25 @@ static int tail_enqueue_merged(sonde_engine *e, int32_t n_samples, uint32_t m_fi
     const int slot = (int)(e->call & 3);
     hipStreamWaitEvent(sb, e->ev_a[slot], 0);
     IfArgs ia[SONDE_MAX_GROUPS]; WinPlanArgs pa[SONDE_MAX_GROUPS]; WinFftArgs fa[SONDE_MAX_GROUPS]; SyncArgs sa[SONDE_MAX_GROUPS];
+    // a launcher that refuses its arguments (-1) or whose launch fails (-2) ends the call: no group stays inside it
+    auto refused = [&](int lrc) { for (sonde_engine *g : e->groups) { g->in_call = false; g->ecc_listed = false; } return lrc == -2 ? SONDE_E_NOGPU : SONDE_E_ARG; };
+    int lrc;
     for (int g = 0; g < G; g++) ia[g] = fill_if(e->groups[(size_t)g], n_if, m_first);
-    prof_begin(e, "if_chain", sb); sonde_launch_if_chain_multi(ia, G, sb); prof_end(e, sb);
+    prof_begin(e, "if_chain", sb); lrc = sonde_launch_if_chain_multi(ia, G, sb); prof_end(e, sb);
+    if (lrc < 0) return refused(lrc);
     for (sonde_engine *g : e->groups) hipEventRecord(g->ev_if[slot], sb);         // (what tail_begin makes the next-but-one decimator wait for)
     int rounds = 0;
     for (sonde_engine *g : e->groups) rounds = std::max(rounds, sync_rounds_of(g, n_if));
     for (int round = 0; round < rounds; round++) {
         for (int g = 0; g < G; g++) fill_round(e->groups[(size_t)g], round == 0 ? 2 : e->groups[(size_t)g]->win_W, pa[g], fa[g]);
         prof_begin(e, "header_corr", sb);
-        sonde_launch_sync_plan_multi(pa, G, sb);
-        sonde_launch_sync_window_fft_multi(fa, G, sb);
+        lrc = sonde_launch_sync_plan_multi(pa, G, sb);
+        if (lrc >= 0) lrc = sonde_launch_sync_window_fft_multi(fa, G, sb);
         prof_end(e, sb);
+        if (lrc < 0) return refused(lrc);
         for (int g = 0; g < G; g++) sa[g] = fill_sync(e->groups[(size_t)g], 0);
-        prof_begin(e, "framesync", sb); sonde_launch_framesync_multi(sa, G, sb); prof_end(e, sb);
+        prof_begin(e, "framesync", sb); lrc = sonde_launch_framesync_multi(sa, G, sb); prof_end(e, sb);
+        if (lrc < 0) return refused(lrc);
         for (sonde_engine *g : e->groups) launch_blockcodes(g);
     }
     int rc = 0;
@@ -1120,8 +1120,8 @@ int sonde_engine_process_host(sonde_engine_t *e, const void *h_iq, int64_t ch_st
     const int rows = ch_stride == 0 ? 1 : C;                   // shared wideband stream: staged once
     const size_t need = (size_t)rows * n_samples * unit;
     if (need > e->stage_bytes) {
-        if (e->d_stage) { hipStreamSynchronize(e->stream); hipFree(e->d_stage); e->d_stage = nullptr; }
-        HIPCHK(hipMalloc((void **)&e->d_stage, need)); e->stage_bytes = need;
+        if (e->d_stage) { hipStreamSynchronize(e->stream); e->mem.release(e->d_stage); e->stage_bytes = 0; }
+        TRY(e->mem.dalloc(&e->d_stage, need, false)); e->stage_bytes = need;
     }
     HIPCHK(hipMemcpy2DAsync(e->d_stage, (size_t)n_samples * unit, h_iq, (size_t)std::max<int64_t>(ch_stride, n_samples) * unit, (size_t)n_samples * unit, rows,
                             hipMemcpyHostToDevice, e->stream));
@@ -1205,7 +1205,7 @@ int sonde_engine_set_search_rounds(sonde_engine_t *e, int32_t on) {
 }
 int sonde_engine_count_windows(sonde_engine_t *e, int32_t on, int64_t *out) {
     if (!e || !e->groups.empty()) return SONDE_E_ARG;
-    if (on && !e->d_wcount && e->d_win && dalloc(&e->d_wcount, 1)) return SONDE_E_NOMEM;
+    if (on && !e->d_wcount && e->d_win) TRY(e->mem.dalloc(&e->d_wcount, 1));
     if (hipStreamSynchronize(e->stream_b) != hipSuccess) return SONDE_E_NOGPU;
     e->count_windows = on != 0;
     if (out) {
@@ -1498,7 +1498,11 @@ int sonde_engine_restart_channel(sonde_engine_t *e, int32_t channel) {
         if (!e->pcs) {
             e->pcs_cnt.assign((size_t)C, e->dc_cnt); e->pcs_max.assign((size_t)C, e->dc_max);
             std::vector<uint32_t> zero((size_t)C, 0u); std::vector<int32_t> since((size_t)C, e->dc_since);
-            if (dalloc(&e->d_epoch_phase, (size_t)C) || dalloc(&e->d_pcs_cnt, (size_t)C) || dalloc(&e->d_pcs_max, (size_t)C) || dalloc(&e->d_pcs_since, (size_t)C)) return SONDE_E_NOMEM;
+            // (pcs turns true below, once all four stand: a call that failed half way is repeated without allocating what it already has)
+            if (!e->d_epoch_phase) TRY(e->mem.dalloc(&e->d_epoch_phase, (size_t)C));
+            if (!e->d_pcs_cnt) TRY(e->mem.dalloc(&e->d_pcs_cnt, (size_t)C));
+            if (!e->d_pcs_max) TRY(e->mem.dalloc(&e->d_pcs_max, (size_t)C));
+            if (!e->d_pcs_since) TRY(e->mem.dalloc(&e->d_pcs_since, (size_t)C));
             HIPCHK(hipMemcpy(e->d_pcs_cnt, e->pcs_cnt.data(), (size_t)C * sizeof(uint32_t), hipMemcpyHostToDevice));
             HIPCHK(hipMemcpy(e->d_pcs_max, e->pcs_max.data(), (size_t)C * sizeof(uint32_t), hipMemcpyHostToDevice));
             HIPCHK(hipMemcpy(e->d_pcs_since, since.data(), (size_t)C * sizeof(int32_t), hipMemcpyHostToDevice));
@@ -1524,10 +1528,8 @@ int sonde_engine_restart_channel(sonde_engine_t *e, int32_t channel) {
     if (e->d_bufs) HIPCHK(hipMemset(e->d_bufs + row, 0, ring * sizeof(float)));
     if (e->d_corr) HIPCHK(hipMemset(e->d_corr + row, 0, ring * sizeof(float)));
     if (e->d_raw)  HIPCHK(hipMemset(e->d_raw + row, 0, ring * sizeof(float)));
-    if (e->epoch.empty()) {
-        e->epoch.assign((size_t)C, 0u);
-        if (dalloc(&e->d_epoch, (size_t)C)) return SONDE_E_NOMEM;
-    }
+    if (!e->d_epoch) TRY(e->mem.dalloc(&e->d_epoch, (size_t)C));
+    if (e->epoch.empty()) e->epoch.assign((size_t)C, 0u);
     e->epoch[channel] = e->m_out;
     HIPCHK(hipMemcpy(e->d_epoch, e->epoch.data(), (size_t)C * sizeof(uint32_t), hipMemcpyHostToDevice));
     SyncState st; memset(&st, 0, sizeof st);
@@ -1663,19 +1665,21 @@ int sonde_engine_create_mixed(const sonde_cfg_t *cfg, const double *fq, const so
     int n_used = 0;
     for (int g = 0; g < n_groups; g++) n_used += ch_of[(size_t)g].empty() ? 0 : 1;
     const bool merged = n_used <= SONDE_MAX_GROUPS;
-    hipStream_t shared_b = nullptr;
+    // That stream has ONE owner at any time: this function until the whole engine stands (every part, the front end's owner included, borrows it), then the
+    // front end's owner.  Declared before the parts: their destructors still synchronise it.
+    struct StreamGuard { hipStream_t s = nullptr; ~StreamGuard() { if (s) (void)hipStreamDestroy(s); } } shared_b;
     if (merged) {
         int lo = 0, hi = 0;
         HIPCHK(hipSetDevice(cfg->device));
-        if (hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && hi != lo) HIPCHK(hipStreamCreateWithPriority(&shared_b, hipStreamNonBlocking, hi));
-        else HIPCHK(hipStreamCreateWithFlags(&shared_b, hipStreamNonBlocking));
+        if (hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && hi != lo) HIPCHK(hipStreamCreateWithPriority(&shared_b.s, hipStreamNonBlocking, hi));
+        else HIPCHK(hipStreamCreateWithFlags(&shared_b.s, hipStreamNonBlocking));
     }
-    // groups first (their rings tell how long the shared y ring must be), then the owner of the front end
-    std::vector<sonde_engine *> parts; std::vector<int> part_grp;
-    auto drop = [&]() { for (sonde_engine *g : parts) sonde_engine_destroy(g); parts.clear(); part_grp.clear(); };
+    // groups first — pass 0 their designs alone: the longest of their rings (ring_length) is the length of the shared y ring; pass 1 the groups themselves, every
+    // one at that length — then the owner of the front end
+    std::vector<std::unique_ptr<sonde_engine>> parts; std::vector<int> part_grp;
     int min_ring = 0;
     for (int pass = 0; pass < 2; pass++) {
-        int ring = 0; bool same = true;
+        int ring = 0;
         for (int g = 0; g < n_groups; g++) {
             const std::vector<int32_t> &chs = ch_of[(size_t)g];
             if (chs.empty()) continue;
@@ -1686,47 +1690,46 @@ int sonde_engine_create_mixed(const sonde_cfg_t *cfg, const double *fq, const so
             c2.max_frames = cfg->max_frames > 0 ? std::max(16, (int)(((long long)cfg->max_frames * (long long)chs.size() + C - 1) / C)) : 0;
             std::vector<double> f2(chs.size());
             for (size_t i = 0; i < chs.size(); i++) f2[i] = fq[chs[i]];
-            const CreateLink lk{ true, false, min_ring, shared_b };
+            const CreateLink lk{ true, false, pass == 0, min_ring, shared_b.s };
             sonde_engine *ge = nullptr;
-            const int rc = create_impl(&c2, f2.data(), nullptr, &lk, &ge);
-            if (rc) { drop(); if (shared_b) hipStreamDestroy(shared_b); return rc; }
-            parts.push_back(ge); part_grp.push_back(g);
-            if (ring && ge->ring_len != ring) same = false;
-            ring = std::max(ring, ge->ring_len);
+            TRY(create_impl(&c2, f2.data(), nullptr, &lk, &ge));
+            std::unique_ptr<sonde_engine> part(ge);
+            ring = std::max(ring, part->ring_len);
+            if (pass == 1) { parts.push_back(std::move(part)); part_grp.push_back(g); }
         }
-        if (parts.empty()) { if (shared_b) hipStreamDestroy(shared_b); return SONDE_E_ARG; }
+        if (!ring) return SONDE_E_ARG;
         min_ring = ring;
-        if (same) break;
-        if (pass == 0) drop();                                        // once more, every part at the longest ring
     }
     // the owner: channels in row order = group after group
     std::vector<int32_t> in_row; std::vector<double> f_rows;
     for (size_t k = 0; k < parts.size(); k++) for (int32_t c : ch_of[(size_t)part_grp[k]]) { in_row.push_back(c); f_rows.push_back(fq[c]); }
     sonde_cfg_t cf = *cfg;
     cf.sonde_type = SONDE_RS41; cf.ecc_level = 0; cf.pipeline = 1; cf.max_frames = 16; cf.thres = 0.f; cf.lpiq_bw = 0; cf.opt_inv = 0; cf.opt_auto = 0;      // (the preset is never used: front_only)
-    const CreateLink lf{ false, true, min_ring, shared_b };
-    sonde_engine *e = nullptr;
-    const int rc = create_impl(&cf, f_rows.data(), nullptr, &lf, &e);
-    if (rc) { drop(); if (shared_b) hipStreamDestroy(shared_b); return rc; }
+    const CreateLink lf{ false, true, false, min_ring, shared_b.s };
+    sonde_engine *owner = nullptr;
+    TRY(create_impl(&cf, f_rows.data(), nullptr, &lf, &owner));
+    std::unique_ptr<sonde_engine> e(owner);
+    if (e->ring_len != min_ring) return SONDE_E_NOMEM;
     e->cfg.sonde_type = SONDE_MIXED; e->merged = merged;
-    for (sonde_engine *g : parts) if (merged && !g->d_win) e->merged = false;      // (every group must be on the window-transform search)
-    e->groups = parts; e->ch_of_grp.resize(parts.size());
+    for (const auto &g : parts) if (merged && !g->d_win) e->merged = false;      // (every group must be on the window-transform search)
+    e->ch_of_grp.resize(parts.size());
     e->grp_of_ch.assign((size_t)C, 0); e->row_of_ch.assign((size_t)C, 0);
     int row = 0;
     for (size_t k = 0; k < parts.size(); k++) {
-        sonde_engine *g = parts[k];
-        g->front = e; g->front_row = row; g->d_y = e->d_y + (size_t)row * e->ring_len;
+        sonde_engine *g = parts[k].get();
+        g->front = e.get(); g->front_row = row; g->d_y = e->d_y + (size_t)row * e->ring_len;      // rows of the owner's ring: not registered with the group's mem
         e->ch_of_grp[k] = ch_of[(size_t)part_grp[k]];
         for (size_t i = 0; i < e->ch_of_grp[k].size(); i++) { e->grp_of_ch[(size_t)e->ch_of_grp[k][i]] = (int32_t)k; e->row_of_ch[(size_t)e->ch_of_grp[k][i]] = row + (int32_t)i; }
-        if (dalloc(&g->d_sum_map, e->ch_of_grp[k].size(), false) ||
-            hipMemcpy(g->d_sum_map, e->ch_of_grp[k].data(), e->ch_of_grp[k].size() * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) { sonde_engine_destroy(e); return SONDE_E_NOMEM; }
+        if (g->mem.upload(&g->d_sum_map, e->ch_of_grp[k])) return SONDE_E_NOMEM;
         row += g->cfg.n_channels;
     }
-    if (e->ring_len != min_ring || dalloc(&e->d_in_row, in_row.size(), false) ||
-        hipMemcpy(e->d_in_row, in_row.data(), in_row.size() * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) { sonde_engine_destroy(e); return SONDE_E_NOMEM; }
-    *out = e;
+    if (e->mem.upload(&e->d_in_row, in_row)) return SONDE_E_NOMEM;
+    for (auto &g : parts) e->groups.push_back(g.release());
+    if (shared_b.s) { e->borrowed_b = false; shared_b.s = nullptr; }      // the hand-over: ~sonde_engine destroys the stream from here on
+    *out = e.release();
     return 0;
 }
+
 
 int sonde_engine_group_info(const sonde_engine_t *e, int32_t channel, int32_t *sonde_type, sonde_info_t *info) {
     if (!e || channel < 0 || channel >= e->cfg.n_channels) return SONDE_E_ARG;

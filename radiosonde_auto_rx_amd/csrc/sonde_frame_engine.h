@@ -4,6 +4,7 @@
 #ifndef SONDE_FRAME_ENGINE_H
 #define SONDE_FRAME_ENGINE_H
 #include "../../include/sonde_hip.h"
+#include "sonde_devmem.h"
 #include "sonde_host.h"
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -14,38 +15,21 @@
 #include <type_traits>
 #include <vector>
 
-// HIPCHK and TRY are for the engine .cpp files that include this header; the other host files of the library define a HIPCHK of their own
-// and must not include it.
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "libsonde_hip: %s failed: %s\n", #x, hipGetErrorString(e_)); return SONDE_E_NOGPU; } } while (0)
-#define TRY(x) do { const int rc_ = (x); if (rc_) return rc_; } while (0)
-
 namespace sonde {
 
 // Frame: the frame record of the engine's public header
 template <class Frame> struct FrameEngine {
+    DevMem mem;
     hipStream_t stream = nullptr;
     int n_ch = 0, max_chunk = 0, dec_m = 1, in_bytes = 0, finished = 0;   // in_bytes: of one input sample of one channel
     void *d_in = nullptr;                                                 // process_host's copy of the caller's samples
-    std::vector<void *> allocs;
     std::vector<Frame> pending;                                           // fetched from the device, not yet handed out
     size_t pending_pos = 0;
     int overflowed = 0;
 
-    template <class T> int dalloc(T **p, size_t n) {
-        HIPCHK(hipMalloc((void **)p, (n ? n : 1) * sizeof(T)));
-        allocs.push_back(*p);
-        HIPCHK(hipMemsetAsync(*p, 0, (n ? n : 1) * sizeof(T), stream));
-        return 0;
-    }
-    // P: T or const T
-    template <class P, class T> int upload(P **p, const std::vector<T> &v) {
-        T *q = nullptr;
-        TRY(dalloc(&q, v.size()));
-        if (!v.empty()) HIPCHK(hipMemcpyAsync(q, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, stream));
-        HIPCHK(hipStreamSynchronize(stream));                             // v may be a temporary
-        *p = q;
-        return 0;
-    }
+    // zeroed on the stream, in order with what run() enqueues there
+    template <class T> int dalloc(T **p, size_t n) { TRY(mem.dalloc(p, n, false)); HIPCHK(hipMemsetAsync(*p, 0, (n ? n : 1) * sizeof(T), stream)); return 0; }
+    template <class P, class T> int upload(P **p, const std::vector<T> &v) { return mem.upload(p, v); }       // P: T or const T
     int alloc_input() {
         uint8_t *din;
         TRY(dalloc(&din, (size_t)n_ch * max_chunk * in_bytes));
@@ -55,10 +39,7 @@ template <class Frame> struct FrameEngine {
     void close_stream() {
         if (stream) { (void)hipStreamSynchronize(stream); (void)hipStreamDestroy(stream); stream = nullptr; }
     }
-    ~FrameEngine() {
-        close_stream();
-        for (void *p : allocs) (void)hipFree(p);
-    }
+    ~FrameEngine() { close_stream(); }
 
     // one launch over a's input, then the frames it completed into the host queue in channel / time order.  a: the kernel's argument
     // record with its queue (q, q_count, q_cap); convert: device record -> Frame

@@ -11,17 +11,19 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <vector>
+#include "sonde_devmem.h"
 #include "sonde_pinned.h"
 
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "libsonde_hip: %s failed: %s\n", #x, hipGetErrorString(e_)); return SONDE_E_NOGPU; } } while (0)
-
 struct sonde_fsk {
+    DevMem mem;                                    // every device buffer below but d_prof
+    ~sonde_fsk();
     sonde_fsk_cfg_t cfg{};
     sonde_fsk_info_t info{};
     FskArgs args{};
     hipStream_t stream = nullptr;
-    void *d_in = nullptr; float *d_hann = nullptr, *d_fmask = nullptr, *d_Sf = nullptr, *d_sd = nullptr, *d_eye = nullptr;
+    uint8_t *d_in = nullptr; float *d_hann = nullptr, *d_fmask = nullptr, *d_Sf = nullptr, *d_sd = nullptr, *d_eye = nullptr;
     float *d_sd_alt = nullptr;                     // the soft decisions of the launch before the last: d_sd and d_sd_alt swap at every launch, so a consumer on the device
                                                    // (sonde_softin_dev_submit_fsk) can still read launch k's while launch k + 1 runs
     unsigned long long *d_prof = nullptr;          // SONDE_FSK_PROF
@@ -46,17 +48,6 @@ struct sonde_fsk {
     hipEvent_t ev_rd[2] = { nullptr, nullptr }; bool rd_set[2] = { false, false }; int sd_idx = 0;
 };
 
-template <class T> static int dalloc(T **p, size_t n, bool zero = true) {
-    HIPCHK(hipMalloc((void **)p, (n ? n : 1) * sizeof(T)));
-    if (zero) HIPCHK(hipMemset(*p, 0, (n ? n : 1) * sizeof(T)));
-    return 0;
-}
-template <class T> static int dupload(T **p, const std::vector<T> &v) {
-    if (dalloc(p, v.size(), false)) return SONDE_E_NOMEM;
-    if (!v.empty()) HIPCHK(hipMemcpy(*p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    return 0;
-}
-
 static float2 exp_j(float phi) { return fsk_exp_j(phi); }
 
 extern "C" {
@@ -74,13 +65,14 @@ int sonde_fsk_create(const sonde_fsk_cfg_t *cfg, sonde_fsk_t **out) {
         return SONDE_E_NOGPU;
     }
     HIPCHK(hipSetDevice(cfg->device));
-    sonde_fsk *f = new sonde_fsk();
+    std::unique_ptr<sonde_fsk> owner(new sonde_fsk());
+    sonde_fsk *f = owner.get();
     f->cfg = *cfg;
     const int C = cfg->n_channels, nsym = cfg->nsym, M = cfg->M;
 
     // ---- fsk_create_core's constants and every data-independent table (sonde_fsk_tables.h)
     FskTables T;
-    if (fsk_build_tables(*cfg, T)) { delete f; return SONDE_E_ARG; }
+    if (fsk_build_tables(*cfg, T)) return SONDE_E_ARG;
     const int Ndft = T.Ndft, Ts = T.Ts, N = T.N;
     FskArgs &a = f->args;
     fsk_tables_to_args(*cfg, T, a);
@@ -94,33 +86,38 @@ int sonde_fsk_create(const sonde_fsk_cfg_t *cfg, sonde_fsk_t **out) {
     uint32_t ring = 1; while (ring < (uint32_t)(cfg->max_chunk + N + Ts + 16)) ring <<= 1;
     a.ring = ring;
     f->unit = cfg->format == SONDE_FSK_CF32 ? 8 : cfg->format == SONDE_FSK_CS16 ? 4 : 2;
-    int bad = 0;
-    bad |= dalloc((char **)&f->d_in, (size_t)C * ring * f->unit);
-    bad |= dupload(&f->d_hann, hann); bad |= dupload(&f->d_tw, tw); bad |= dupload(&f->d_perm, perm); bad |= dupload(&f->d_iperm, iperm); bad |= dupload(&f->d_dpeak, dpeak); bad |= dupload(&f->d_dmask, dmask);
-    bad |= dupload(&f->d_fmask, fmask); bad |= dupload(&f->d_phift, phift);
-    bad |= dalloc(&f->d_eye, (size_t)C * 8 * 160); bad |= dalloc(&f->d_Sf, (size_t)C * Ndft); bad |= dalloc(&f->d_tail, (size_t)C * M * a.NT);
-    bad |= dalloc(&f->d_sd, (size_t)C * a.sd_cap); bad |= dalloc(&f->d_sd_alt, (size_t)C * a.sd_cap); bad |= dalloc(&f->d_hb, (size_t)C * a.sd_cap); bad |= dalloc(&f->d_recs, (size_t)C * a.rec_cap); bad |= dalloc(&f->d_chan, (size_t)C, false);
-    if (bad) { sonde_fsk_destroy(f); return SONDE_E_NOMEM; }
-    if (!f->h_chan.alloc(C)) { sonde_fsk_destroy(f); return SONDE_E_NOMEM; }
+    DevMem &mem = f->mem;
+    TRY(mem.dalloc(&f->d_in, (size_t)C * ring * f->unit));
+    TRY(mem.upload(&f->d_hann, hann)); TRY(mem.upload(&f->d_tw, tw)); TRY(mem.upload(&f->d_perm, perm)); TRY(mem.upload(&f->d_iperm, iperm));
+    TRY(mem.upload(&f->d_dpeak, dpeak)); TRY(mem.upload(&f->d_dmask, dmask)); TRY(mem.upload(&f->d_fmask, fmask)); TRY(mem.upload(&f->d_phift, phift));
+    TRY(mem.dalloc(&f->d_eye, (size_t)C * 8 * 160)); TRY(mem.dalloc(&f->d_Sf, (size_t)C * Ndft)); TRY(mem.dalloc(&f->d_tail, (size_t)C * M * a.NT));
+    TRY(mem.dalloc(&f->d_sd, (size_t)C * a.sd_cap)); TRY(mem.dalloc(&f->d_sd_alt, (size_t)C * a.sd_cap)); TRY(mem.dalloc(&f->d_hb, (size_t)C * a.sd_cap));
+    TRY(mem.dalloc(&f->d_recs, (size_t)C * a.rec_cap)); TRY(mem.dalloc(&f->d_chan, (size_t)C, false));
+    if (!f->h_chan.alloc(C)) return SONDE_E_NOMEM;
     for (auto &c : f->h_chan) { memset(&c, 0, sizeof c); for (int m = 0; m < 4; m++) c.phi_c[m] = exp_j(0); c.nin = N; }
     HIPCHK(hipMemcpy(f->d_chan, f->h_chan.data(), (size_t)C * sizeof(FskChan), hipMemcpyHostToDevice));
     a.in = f->d_in; a.hann = f->d_hann; a.tw = f->d_tw; a.perm = f->d_perm; a.iperm = f->d_iperm; a.dphi_peak = f->d_dpeak; a.dphi_mask = f->d_dmask; a.f_mask = f->d_fmask;
     a.phi_ft = f->d_phift; a.chan = f->d_chan; a.Sf = f->d_Sf; a.eye = f->d_eye; a.tail = f->d_tail; a.sd = f->d_sd; a.hb = f->d_hb; a.recs = f->d_recs;
-    if (!f->h_sd.alloc((size_t)C * a.sd_cap) || !f->h_hb.alloc((size_t)C * a.sd_cap) || !f->h_recs.alloc((size_t)C * a.rec_cap)) { sonde_fsk_destroy(f); return SONDE_E_NOMEM; }
+    if (!f->h_sd.alloc((size_t)C * a.sd_cap) || !f->h_hb.alloc((size_t)C * a.sd_cap) || !f->h_recs.alloc((size_t)C * a.rec_cap)) return SONDE_E_NOMEM;
     // the per-launch results come back into these (never resized again): page-locked, so that the copies are real asynchronous DMA and not staged through
     // a bounce buffer — with the pipelined kernel the copies of a thousand channels were a fifth of a step
     f->pinned = true;
     HIPCHK(hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking));
-    *out = f;
+    *out = owner.release();
     return 0;
 }
 
-void sonde_fsk_destroy(sonde_fsk_t *f) {
-    if (!f) return;
+void sonde_fsk_destroy(sonde_fsk_t *f) { delete f; }
+
+}  // extern "C"
+
+sonde_fsk::~sonde_fsk() {
+    sonde_fsk *f = this;
     if (f->stream) { hipStreamSynchronize(f->stream); hipStreamDestroy(f->stream); }
-    if (f->ev0) { hipEventDestroy(f->ev0); hipEventDestroy(f->ev1); }
+    if (f->ev0) hipEventDestroy(f->ev0);
+    if (f->ev1) hipEventDestroy(f->ev1);
     for (hipEvent_t ev : f->ev_rd) if (ev) hipEventDestroy(ev);
-    if (f->d_prof) {
+    if (f->d_prof) {                               // (not in mem: allocated inside the profiled launch, read here, freed here)
         unsigned long long h[32];
         if (hipMemcpy(h, f->d_prof, sizeof h, hipMemcpyDeviceToHost) == hipSuccess) {
             static const char *nm[9] = { "input", "fft", "Sf+estimators", "oscillator", "downconv+tail", "integrate", "timing", "soft", "ebno+record" };
@@ -151,10 +148,9 @@ void sonde_fsk_destroy(sonde_fsk_t *f) {
         }
         hipFree(f->d_prof);
     }
-    void *ptrs[] = { f->d_in, f->d_hann, f->d_fmask, f->d_Sf, f->d_sd, f->d_tw, f->d_dpeak, f->d_dmask, f->d_phift, f->d_tail, f->d_chan, f->d_recs, f->d_eye, f->d_hb, f->d_perm, f->d_iperm, f->d_wr, f->d_Sf_bak, f->d_tail_bak, f->d_chlist, f->d_sd_alt, f->d_scratch };
-    for (void *p : ptrs) if (p) hipFree(p);
-    delete f;
 }
+
+extern "C" {
 
 int sonde_fsk_info(const sonde_fsk_t *f, sonde_fsk_info_t *info) {
     if (!f || !info) return SONDE_E_ARG;
@@ -178,12 +174,12 @@ static int launch_enqueue(sonde_fsk_t *f) {
     // channels are repeated with the frame-at-a-time kernel (same arithmetic, no waits between waves) from the state they had before the launch: the channel
     // records are still on the host, Sf and the tone tails are copied aside first (two small device copies).
     const int Ndft = f->info.Ndft;
-    if (!f->d_Sf_bak) {
-        if (dalloc(&f->d_Sf_bak, (size_t)C * Ndft, false) || dalloc(&f->d_tail_bak, (size_t)C * a.M * a.NT, false) || dalloc(&f->d_chlist, (size_t)C, false)) return SONDE_E_NOMEM;
-    }
+    if (!f->d_Sf_bak) TRY(f->mem.dalloc(&f->d_Sf_bak, (size_t)C * Ndft, false));
+    if (!f->d_tail_bak) TRY(f->mem.dalloc(&f->d_tail_bak, (size_t)C * a.M * a.NT, false));
+    if (!f->d_chlist) TRY(f->mem.dalloc(&f->d_chlist, (size_t)C, false));
     if (!f->d_scratch) {                                       // frames longer than a CU's LDS holds: k_fsk_demod's regions in global memory (sonde_fsk.hip)
         const long long nf = sonde_fsk_scratch_floats(&a);
-        if (nf > 0) { if (dalloc(&f->d_scratch, (size_t)C * (size_t)nf, false)) return SONDE_E_NOMEM; a.scratch = f->d_scratch; a.scratch_stride = nf; }
+        if (nf > 0) { TRY(f->mem.dalloc(&f->d_scratch, (size_t)C * (size_t)nf, false)); a.scratch = f->d_scratch; a.scratch_stride = nf; }
     }
     if (!f->ev0) { HIPCHK(hipEventCreate(&f->ev0)); HIPCHK(hipEventCreate(&f->ev1)); }
     f->h_chan_prev.assign(f->h_chan.begin(), f->h_chan.end());
@@ -308,8 +304,8 @@ int sonde_fsk_process_host_var(sonde_fsk_t *f, const void *const *h_in, const in
     const int C = f->cfg.n_channels;
     if (f->wr_ch.empty()) {
         if (f->wr != 0) return SONDE_E_ARG;                     // one feeding mode per engine
+        if (!f->d_wr) TRY(f->mem.dalloc(&f->d_wr, (size_t)C));
         f->wr_ch.assign(C, 0);
-        if (dalloc(&f->d_wr, (size_t)C)) return SONDE_E_NOMEM;
         f->args.wr_ch = f->d_wr;
     }
     for (int c = 0; c < C; c++) if (n_samples[c] < 0 || n_samples[c] > f->cfg.max_chunk || (n_samples[c] > 0 && !h_in[c])) return SONDE_E_RANGE;

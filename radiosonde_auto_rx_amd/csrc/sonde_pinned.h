@@ -3,7 +3,7 @@
 //  unregistered unpins it under the other.  The engines' host-side landing buffers are therefore allocated, not registered.)
 #ifndef SONDE_PINNED_H
 #define SONDE_PINNED_H
-#include <hip/hip_runtime.h>
+#include <hip/hip_runtime_api.h>
 #include <stddef.h>
 #include <string.h>
 
@@ -13,10 +13,10 @@ template <class T> struct Pinned {
     Pinned(const Pinned &) = delete;
     Pinned &operator=(const Pinned &) = delete;
     ~Pinned() { release(); }
-    // -> false when the allocation fails (nothing is held then)
-    bool alloc(size_t count) {
+    // -> false when the allocation fails (nothing is held then); flags: hipHostMallocMapped for memory the device addresses as well
+    bool alloc(size_t count, unsigned flags = hipHostMallocDefault) {
         release();
-        if (hipHostMalloc((void **)&p, (count ? count : 1) * sizeof(T), hipHostMallocDefault) != hipSuccess) { p = nullptr; (void)hipGetLastError(); return false; }
+        if (hipHostMalloc((void **)&p, (count ? count : 1) * sizeof(T), flags) != hipSuccess) { p = nullptr; (void)hipGetLastError(); return false; }
         memset((void *)p, 0, (count ? count : 1) * sizeof(T));
         n = count;
         return true;

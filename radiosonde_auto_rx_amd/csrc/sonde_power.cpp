@@ -2,6 +2,7 @@
 // carried tail, the launch shape, fetch (un-permute, shift, crop, dB), and auto_rx's peak pick and log line as pure host functions.
 #include "../../include/sonde_power.h"
 #include "sonde_power_dev.h"
+#include "sonde_devmem.h"
 #include "sonde_pinned.h"
 #include <algorithm>
 #include <cmath>
@@ -9,16 +10,21 @@
 #include <cstring>
 #include <ctime>
 #include <map>
+#include <memory>
 #include <string>
 #include <vector>
-
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "libsonde_hip: %s failed: %s\n", #x, hipGetErrorString(e_)); return SONDE_E_NOGPU; } } while (0)
 
 namespace {
 struct KStat { double ms = 0; int64_t n = 0; };
 }
 
 struct sonde_power {
+    DevMem mem;
+    ~sonde_power() {
+        if (stream) { hipStreamSynchronize(stream); hipStreamDestroy(stream); }
+        if (ev0) hipEventDestroy(ev0);
+        if (ev1) hipEventDestroy(ev1);
+    }
     sonde_power_cfg_t cfg{};
     sonde_power_info_t info{};
     int log2n = 0, drop = 0;
@@ -28,7 +34,7 @@ struct sonde_power {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool ev_pending = false;
     float2 *d_tw = nullptr; float *d_win = nullptr, *d_partial = nullptr; double *d_acc = nullptr;
-    void *d_tail = nullptr, *d_stage = nullptr;
+    uint8_t *d_tail = nullptr, *d_stage = nullptr;
     size_t stage_bytes = 0;
     Pinned<uint8_t> h_stage;
     Pinned<double> h_acc;
@@ -60,7 +66,8 @@ int sonde_power_create(const sonde_power_cfg_t *cfg, sonde_power_t **out) {
         return SONDE_E_NOGPU;
     }
     HIPCHK(hipSetDevice(cfg->device));
-    sonde_power *s = new sonde_power();
+    std::unique_ptr<sonde_power> owner(new sonde_power());
+    sonde_power *s = owner.get();
     s->cfg = *cfg;
     const int N = cfg->nfft, C = cfg->n_streams;
     while ((1 << s->log2n) < N) s->log2n++;
@@ -81,36 +88,25 @@ int sonde_power_create(const sonde_power_cfg_t *cfg, sonde_power_t **out) {
 
     PowerKernelInfo ki{};
     hipDeviceProp_t prop;
-    auto fail = [&](int rc) { sonde_power_destroy(s); return rc; };
-    if (hipGetDeviceProperties(&prop, cfg->device) != hipSuccess) return fail(SONDE_E_NOGPU);
-    if (sonde_power_kernel_info(s->log2n, &ki) != 0) return fail(SONDE_E_NOGPU);
+    if (hipGetDeviceProperties(&prop, cfg->device) != hipSuccess) return SONDE_E_NOGPU;
+    if (sonde_power_kernel_info(s->log2n, &ki) != 0) return SONDE_E_NOGPU;
     s->info.nfft = N; s->info.bins = N - 2 * s->drop;
     s->info.threads = ki.threads; s->info.lds_bytes = ki.lds_bytes; s->info.workgroups_per_cu = ki.max_per_cu;
     s->info.max_workgroups = std::max(1, prop.multiProcessorCount) * ki.max_per_cu;
     s->info.step_hz = (double)cfg->sample_rate / N; s->info.window_sum = wsum;
 
-    if (hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess) return fail(SONDE_E_NOGPU);
-    if (hipEventCreate(&s->ev0) != hipSuccess || hipEventCreate(&s->ev1) != hipSuccess) return fail(SONDE_E_NOGPU);
+    HIPCHK(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
+    HIPCHK(hipEventCreate(&s->ev0)); HIPCHK(hipEventCreate(&s->ev1));
     const size_t rows = (size_t)std::max(C, s->info.max_workgroups);        // every stream gets at least one workgroup
-    if (hipMalloc((void **)&s->d_tw, (size_t)N * sizeof(float)) != hipSuccess || hipMalloc((void **)&s->d_partial, rows * N * sizeof(float)) != hipSuccess ||
-        hipMalloc((void **)&s->d_acc, (size_t)C * N * sizeof(double)) != hipSuccess || hipMalloc(&s->d_tail, (size_t)C * N * s->unit) != hipSuccess ||
-        (!win.empty() && hipMalloc((void **)&s->d_win, (size_t)N * sizeof(float)) != hipSuccess) || !s->h_acc.alloc(N)) { (void)hipGetLastError(); return fail(SONDE_E_NOMEM); }
-    if (hipMemcpy(s->d_tw, tw.data(), (size_t)N * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return fail(SONDE_E_NOGPU);
-    if (!win.empty() && hipMemcpy(s->d_win, win.data(), (size_t)N * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return fail(SONDE_E_NOGPU);
-    if (hipMemset(s->d_acc, 0, (size_t)C * N * sizeof(double)) != hipSuccess || hipMemset(s->d_tail, 0, (size_t)C * N * s->unit) != hipSuccess) return fail(SONDE_E_NOGPU);
-    *out = s;
+    { float *q = nullptr; TRY(s->mem.upload(&q, tw)); s->d_tw = (float2 *)q; }      // (re, im) pairs
+    if (!win.empty()) TRY(s->mem.upload(&s->d_win, win));
+    TRY(s->mem.dalloc(&s->d_partial, rows * N, false)); TRY(s->mem.dalloc(&s->d_acc, (size_t)C * N)); TRY(s->mem.dalloc(&s->d_tail, (size_t)C * N * s->unit));
+    if (!s->h_acc.alloc(N)) return SONDE_E_NOMEM;
+    *out = owner.release();
     return 0;
 }
 
-void sonde_power_destroy(sonde_power_t *s) {
-    if (!s) return;
-    if (s->stream) { hipStreamSynchronize(s->stream); hipStreamDestroy(s->stream); }
-    if (s->ev0) hipEventDestroy(s->ev0);
-    if (s->ev1) hipEventDestroy(s->ev1);
-    void *ptrs[] = { s->d_tw, s->d_win, s->d_partial, s->d_acc, s->d_tail, s->d_stage };
-    for (void *p : ptrs) if (p) hipFree(p);
-    delete s;
-}
+void sonde_power_destroy(sonde_power_t *s) { delete s; }
 
 int sonde_power_info(const sonde_power_t *s, sonde_power_info_t *info) {
     if (!s || !info) return SONDE_E_ARG;
@@ -157,8 +153,9 @@ int sonde_power_process_host(sonde_power_t *s, const void *h_in, int64_t stream_
     const int C = s->cfg.n_streams;
     const size_t row = (size_t)n_samples * s->unit, need = row * C;
     if (need > s->stage_bytes) {
-        if (s->d_stage) { hipStreamSynchronize(s->stream); hipFree(s->d_stage); s->d_stage = nullptr; s->stage_bytes = 0; }
-        if (hipMalloc(&s->d_stage, need) != hipSuccess || !s->h_stage.alloc(need)) { (void)hipGetLastError(); return SONDE_E_NOMEM; }
+        if (s->d_stage) { hipStreamSynchronize(s->stream); s->mem.release(s->d_stage); s->stage_bytes = 0; }
+        TRY(s->mem.dalloc(&s->d_stage, need, false));
+        if (!s->h_stage.alloc(need)) return SONDE_E_NOMEM;
         s->stage_bytes = need;
     }
     HIPCHK(hipStreamSynchronize(s->stream));                   // the staging buffer's last transfer and its readers are done

@@ -12,7 +12,9 @@
 // prefilter and every pair runs the reference's transform network on an array in global memory (k_scan_corr_t<true>) — rare, exactness over speed.
 #include "../../include/sonde_scan.h"
 #include "sonde_dev.h"
+#include "sonde_devmem.h"
 #include "sonde_host.h"
+#include "sonde_pinned.h"
 #include "sonde_scan_dev.h"
 #include <algorithm>
 #include <cmath>
@@ -20,12 +22,12 @@
 #include <cstdio>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <string>
 #include <vector>
 
 using namespace sonde;
 
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "libsonde_hip: %s failed: %s\n", #x, hipGetErrorString(e_)); return SONDE_E_NOGPU; } } while (0)
 
 namespace {
 
@@ -164,6 +166,8 @@ void ref_dft_8192(std::vector<float> &re_im) {
 }  // namespace sonde
 
 struct sonde_scan {
+    DevMem mem;                                    // every device buffer below but d_spprof
+    ~sonde_scan();
     sonde_scan_cfg_t cfg{};
     sonde_scan_info_t info{};
     hipStream_t stream = nullptr;
@@ -184,12 +188,12 @@ struct sonde_scan {
     double *d_chanf0 = nullptr; float2 *d_dcavg = nullptr; long long *d_dcsums = nullptr; float2 *d_ptail[2] = {nullptr, nullptr}; int ptail_cur = 0;
     float2 *d_y = nullptr; float *d_fm = nullptr; float *d_wiq = nullptr; float2 *d_G = nullptr, *d_tw = nullptr, *d_WS = nullptr;
     uint8_t *d_hdr = nullptr; int *d_bnd = nullptr; ScanItem *d_items = nullptr; ScanRes *d_res = nullptr;
-    ScanItem *h_items = nullptr; ScanRes *h_res = nullptr; int item_cap = 0;
+    Pinned<ScanItem> h_items; Pinned<ScanRes> h_res; int item_cap = 0;
     // prefilter (k_scan_pre): A fragments of the templates / FM low-passes, per-pair results, work list of the exact kernel
     uint16_t *d_amatch = nullptr, *d_aws = nullptr; float *d_wstail = nullptr; int a_off[SC_NTPL] = {0}, nc2[SC_NTPL] = {0}, nc1 = 0, ws_pad = 0;
     float kap[SC_NTPL] = {0};
-    ScanPre *d_pre = nullptr, *h_pre = nullptr; ScanWork *d_work = nullptr, *h_work = nullptr; bool use_pre = false;
-    void *d_stage = nullptr; size_t stage_bytes = 0;
+    ScanPre *d_pre = nullptr; Pinned<ScanPre> h_pre; ScanWork *d_work = nullptr; Pinned<ScanWork> h_work; bool use_pre = false;
+    uint8_t *d_stage = nullptr; size_t stage_bytes = 0;
     int16_t *d_conv = nullptr;                     // cu8 input: converted int16 copy
     double *d_dcsums_f = nullptr; float2 *d_zring = nullptr; float *d_taps_f = nullptr; uint32_t zmask = 0;   // float32 input (MixF32Args)
     int ring_len = 0;
@@ -203,6 +207,28 @@ struct sonde_scan {
     std::map<std::string, KStat> stats;
 };
 
+sonde_scan::~sonde_scan() {
+    if (stream) { hipStreamSynchronize(stream); hipStreamDestroy(stream); }
+    for (auto &e : ev_fe) if (e) hipEventDestroy(e);
+    for (auto &e : ev_rw) if (e) hipEventDestroy(e);
+    if (ev_wait) hipEventDestroy(ev_wait);
+    if (d_spprof) {                                // (not in mem: allocated inside the profiled call, read here, freed here)
+        unsigned long long h[8] = {0};
+        if (hipMemcpy(h, d_spprof, sizeof h, hipMemcpyDeviceToHost) == hipSuccess && h[7])
+            fprintf(stderr, "scan_pre prof (template 1, %llu workgroups, mean shader cycles): load+dc %llu  convert+stage %llu  fm-lowpass %llu  prefix %llu  correlation %llu  reduce %llu\n",
+                    h[7], h[0] / h[7], h[1] / h[7], h[2] / h[7], h[3] / h[7], h[4] / h[7], h[5] / h[7]);
+        hipFree(d_spprof);
+    }
+}
+
+// IQ-DC windows of a call (sums of 8 bytes per component, table of means): allocated by the first call that needs them
+static int alloc_dc_windows(sonde_scan *s) {
+    const size_t C = (size_t)s->cfg.n_channels, nseg_cap = (size_t)(s->cfg.max_chunk / (int)s->dc_max + 2);
+    if (!s->d_segsums) TRY(s->mem.dalloc(&s->d_segsums, C * nseg_cap * 2, false));
+    if (!s->d_dcseg) TRY(s->mem.dalloc(&s->d_dcseg, C * (nseg_cap + 1), false));
+    return 0;
+}
+
 static void timed(sonde_scan *s, const char *name, hipEvent_t a, hipEvent_t b) {
     float ms = 0; if (hipEventElapsedTime(&ms, a, b) == hipSuccess) { auto &k = s->stats[name]; k.ms += ms; k.n += 1; }
 }
@@ -212,17 +238,6 @@ static void flush_front_timing(sonde_scan *s) {
     if (!s->fe_pending) return;
     s->fe_pending = false;
     if (s->fe_timed) { timed(s, "front_end", s->ev_fe[0], s->ev_fe[1]); timed(s, "scan_if", s->ev_fe[1], s->ev_fe[2]); }
-}
-
-template <class T> static int dalloc(T **p, size_t n, bool zero = true) {
-    HIPCHK(hipMalloc((void **)p, n * sizeof(T)));
-    if (zero) HIPCHK(hipMemset(*p, 0, n * sizeof(T)));
-    return 0;
-}
-template <class T> static int dupload(T **p, const std::vector<T> &v) {
-    if (dalloc(p, v.size() ? v.size() : 1, false)) return SONDE_E_NOMEM;
-    if (!v.empty()) HIPCHK(hipMemcpy(*p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    return 0;
 }
 
 // ---- prefilter tables (k_scan_pre, sonde_scan_pre.hip)
@@ -260,7 +275,8 @@ int sonde_scan_create(const sonde_scan_cfg_t *cfg, const double *fq, sonde_scan_
         return SONDE_E_NOGPU;
     }
     HIPCHK(hipSetDevice(cfg->device));
-    sonde_scan *s = new sonde_scan();
+    std::unique_ptr<sonde_scan> owner(new sonde_scan());
+    sonde_scan *s = owner.get();
     s->cfg = *cfg;
     const int C = cfg->n_channels;
     const bool iq = cfg->iq_mode != SONDE_SCAN_AUDIO;
@@ -275,7 +291,7 @@ int sonde_scan_create(const sonde_scan_cfg_t *cfg, const double *fq, sonde_scan_
         if (D == 1) s->dec.taps.assign(1, 1.0f);
         const int T = (int)s->dec.taps.size();
         s->Q = (T + D - 1) / D;
-        if (D > 1024) { delete s; return SONDE_E_ARG; }
+        if (D > 1024) return SONDE_E_ARG;
         if (s->Q > 8) { s->wide_fe = true; s->Q = 8; }         // (wide IF: 267 taps over D = 25) -> the plain float32 mixer / FIR kernels, any tap count
         s->wtab.assign((size_t)std::max(64, D) * 8, 0.f);
         if (!s->wide_fe) {
@@ -286,19 +302,19 @@ int sonde_scan_create(const sonde_scan_cfg_t *cfg, const double *fq, sonde_scan_
         }
         if (D > 64 && !s->wide_fe) {                                         // wide decimation: taps in global memory, D walked in pieces of DS
             for (int k = 64; k >= 4; k--) if (D % k == 0) { s->DS = k; break; }
-            if (!s->DS || s->Q < 5) { delete s; return SONDE_E_ARG; }
-            if (dupload(&s->d_wtab, s->wtab)) { sonde_scan_destroy(s); return SONDE_E_NOMEM; }
+            if (!s->DS || s->Q < 5) return SONDE_E_ARG;
+            TRY(s->mem.upload(&s->d_wtab, s->wtab));
         } else if (!s->wide_fe) {                                            // the generated D = 50 kernel reads the tap rows * 2^-15 behind the table
             std::vector<float> both(s->wtab);
             for (size_t i = 0; i < s->wtab.size(); i++) both.push_back(s->wtab[i] * 3.0517578125e-05f);
-            if (dupload(&s->d_wtab, both)) { sonde_scan_destroy(s); return SONDE_E_NOMEM; }
+            TRY(s->mem.upload(&s->d_wtab, both));
         }
         std::vector<double> f0s(C);
         for (int c = 0; c < C; c++) {
             const Mixer m = design_mixer(-std::max(-0.5, std::min(0.5, fq[c])), cfg->sample_rate);
             f0s[c] = m.f0; s->lut_len = m.lut_len;
         }
-        if (dupload(&s->d_chanf0, f0s)) { sonde_scan_destroy(s); return SONDE_E_NOMEM; }
+        TRY(s->mem.upload(&s->d_chanf0, f0s));
     }
     std::vector<float> w_iq, w_lp;
     if (iq) {
@@ -331,7 +347,7 @@ int sonde_scan_create(const sonde_scan_cfg_t *cfg, const double *fq, sonde_scan_
     }
     const int L2 = 2 * Lmax;
     int p2 = 1; while (p2 < 3 * L2) p2 <<= 1; while (p2 < 0x2000) p2 <<= 1;
-    if (p2 != 8192 && p2 != 16384 && p2 != 32768) { delete s; return SONDE_E_ARG; }
+    if (p2 != 8192 && p2 != 16384 && p2 != 32768) return SONDE_E_ARG;
     s->N = p2; s->log2n = 13 + (p2 > 8192) + (p2 > 16384);
     const int N = s->N;
     s->K = N - L2; s->delay = L2 / 16;
@@ -398,23 +414,19 @@ int sonde_scan_create(const sonde_scan_cfg_t *cfg, const double *fq, sonde_scan_
     I.if_sr = sr; I.decM = D; I.dectaps = (D == 1) ? 0 : (int)s->dec.taps.size(); I.lpiq_taps = s->lpiq_taps; I.lpfm_taps = s->lpfm_taps;
     I.K = s->K; I.N = N; I.delay = s->delay; I.L2 = L2; I.ring_len = ring;
 
-    int bad = 0;
-    bad |= dalloc(&s->d_dcavg, C); bad |= dalloc(&s->d_dcsums, 2 * (size_t)C);
-    if (cfg->iq_mode == SONDE_SCAN_BBIQ) { bad |= dalloc(&s->d_ptail[0], (size_t)C * 64); bad |= dalloc(&s->d_ptail[1], (size_t)C * 64); }
-    if (iq) bad |= dalloc(&s->d_y, (size_t)C * ring);
-    bad |= dalloc(&s->d_fm, (size_t)s->nstreams * C * ring);
-    bad |= dupload(&s->d_G, G); bad |= dupload(&s->d_tw, tws); bad |= dupload(&s->d_hdr, hdrbits); bad |= dupload(&s->d_bnd, bnd);
-    if (iq) { bad |= dupload(&s->d_wiq, w_iq); std::vector<float2> ws2(WS[0]); ws2.insert(ws2.end(), WS[1].begin(), WS[1].end()); bad |= dupload(&s->d_WS, ws2); }
+    DevMem &mem = s->mem;
+    TRY(mem.dalloc(&s->d_dcavg, C)); TRY(mem.dalloc(&s->d_dcsums, 2 * (size_t)C));
+    if (cfg->iq_mode == SONDE_SCAN_BBIQ) { TRY(mem.dalloc(&s->d_ptail[0], (size_t)C * 64)); TRY(mem.dalloc(&s->d_ptail[1], (size_t)C * 64)); }
+    if (iq) TRY(mem.dalloc(&s->d_y, (size_t)C * ring));
+    TRY(mem.dalloc(&s->d_fm, (size_t)s->nstreams * C * ring));
+    TRY(mem.upload(&s->d_G, G)); TRY(mem.upload(&s->d_tw, tws)); TRY(mem.upload(&s->d_hdr, hdrbits)); TRY(mem.upload(&s->d_bnd, bnd));
+    if (iq) { TRY(mem.upload(&s->d_wiq, w_iq)); std::vector<float2> ws2(WS[0]); ws2.insert(ws2.end(), WS[1].begin(), WS[1].end()); TRY(mem.upload(&s->d_WS, ws2)); }
     s->item_cap = C * (max_if / (s->K - 4) + 2);
     const size_t icap = (size_t)s->item_cap + C;           // + one re-evaluated window of the previous call per channel (prefilter)
-    bad |= dalloc(&s->d_items, icap, false); bad |= dalloc(&s->d_res, icap * SC_NTPL, false);
-    bad |= dupload(&s->d_amatch, a_match); bad |= dupload(&s->d_aws, a_ws); bad |= dupload(&s->d_wstail, ws_tail);
-    bad |= dalloc(&s->d_pre, icap * SC_NTPL, false); bad |= dalloc(&s->d_work, icap * SC_NTPL, false);
-    if (bad) { sonde_scan_destroy(s); return SONDE_E_NOMEM; }
-    HIPCHK(hipHostMalloc((void **)&s->h_items, icap * sizeof(ScanItem), hipHostMallocDefault));
-    HIPCHK(hipHostMalloc((void **)&s->h_res, icap * SC_NTPL * sizeof(ScanRes), hipHostMallocDefault));
-    HIPCHK(hipHostMalloc((void **)&s->h_pre, icap * SC_NTPL * sizeof(ScanPre), hipHostMallocDefault));
-    HIPCHK(hipHostMalloc((void **)&s->h_work, icap * SC_NTPL * sizeof(ScanWork), hipHostMallocDefault));
+    TRY(mem.dalloc(&s->d_items, icap, false)); TRY(mem.dalloc(&s->d_res, icap * SC_NTPL, false));
+    TRY(mem.upload(&s->d_amatch, a_match)); TRY(mem.upload(&s->d_aws, a_ws)); TRY(mem.upload(&s->d_wstail, ws_tail));
+    TRY(mem.dalloc(&s->d_pre, icap * SC_NTPL, false)); TRY(mem.dalloc(&s->d_work, icap * SC_NTPL, false));
+    if (!s->h_items.alloc(icap) || !s->h_res.alloc(icap * SC_NTPL) || !s->h_pre.alloc(icap * SC_NTPL) || !s->h_work.alloc(icap * SC_NTPL)) return SONDE_E_NOGPU;
     {   // the scanner's kernels are short and its call waits for them between stages: on a device that also runs a demodulator engine they must not
         // queue behind a millisecond of decimator workgroups — highest stream priority (the engine's streams have the default one)
         int lo = 0, hi = 0;
@@ -424,7 +436,7 @@ int sonde_scan_create(const sonde_scan_cfg_t *cfg, const double *fq, sonde_scan_
 
     // IQ-DC: always on, fixed window (dft_detect.c:1152-1156)
     s->dc_max = (uint32_t)(sr / 32); if (D > 1) s->dc_max *= (uint32_t)D;
-    if (iq && (s->dc_max == 0 || s->dc_max % D)) { sonde_scan_destroy(s); return SONDE_E_ARG; }
+    if (iq && (s->dc_max == 0 || s->dc_max % D)) return SONDE_E_ARG;
     {   // int16 / 8-bit base-rate input at the generated decimator's geometry (D = 50, Q = 7, a mixer table whose period is whole blocks): the front end reads its
         // input ONCE (k_mix_decimate50r + the fold at the IF rate) instead of a summing pass and a mixing pass.  SONDE_SCAN_TWO_PASS=1: the two-pass form (A/B)
         const bool two_pass = getenv("SONDE_SCAN_TWO_PASS") != nullptr;
@@ -432,9 +444,9 @@ int sonde_scan_create(const sonde_scan_cfg_t *cfg, const double *fq, sonde_scan_
             s->etab_len = s->lut_len / D;
             s->bsum_stride = (cfg->max_chunk + D - 1) / D;
             const int nseg_cap = cfg->max_chunk / (int)s->dc_max + 2;
-            if (dalloc(&s->d_etab64, (size_t)C * s->etab_len, false) || dalloc(&s->d_bsum, (size_t)C * s->bsum_stride, false)
-                || dalloc(&s->d_corr, (size_t)C * (nseg_cap + 1) * 8) || dalloc(&s->d_dcprev[0], (size_t)C) || dalloc(&s->d_dcprev[1], (size_t)C)
-                || dalloc(&s->d_hist[0], (size_t)C * s->lpiq_taps) || dalloc(&s->d_hist[1], (size_t)C * s->lpiq_taps)) { sonde_scan_destroy(s); return SONDE_E_NOMEM; }
+            TRY(mem.dalloc(&s->d_etab64, (size_t)C * s->etab_len, false)); TRY(mem.dalloc(&s->d_bsum, (size_t)C * s->bsum_stride, false));
+            TRY(mem.dalloc(&s->d_corr, (size_t)C * (nseg_cap + 1) * 8)); TRY(mem.dalloc(&s->d_dcprev[0], (size_t)C)); TRY(mem.dalloc(&s->d_dcprev[1], (size_t)C));
+            TRY(mem.dalloc(&s->d_hist[0], (size_t)C * s->lpiq_taps)); TRY(mem.dalloc(&s->d_hist[1], (size_t)C * s->lpiq_taps));
             sonde_launch_md_etable64(s->d_chanf0, s->d_wtab, D, s->Q, s->etab_len, C, s->d_etab64, nullptr);      // E of the double-phase mixer table, once
             HIPCHK(hipDeviceSynchronize());
             s->front_raw = true;
@@ -445,32 +457,11 @@ int sonde_scan_create(const sonde_scan_cfg_t *cfg, const double *fq, sonde_scan_
         for (int j = 0; j < kNrs; j++) { c.mv[j] = 0; c.mv_pos[j] = 0; c.mv0_pos[j] = 0; c.mp[j] = 0; c.dc[j] = 0; c.df[j] = 0; c.type[j] = kTpl[j].type; c.tn[j] = kTpl[j].tn; c.detect2[j] = 0; }
         c.next_sin = (uint32_t)(s->K - 4);
     }
-    *out = s;
+    *out = owner.release();
     return 0;
 }
 
-void sonde_scan_destroy(sonde_scan_t *s) {
-    if (!s) return;
-    if (s->stream) { hipStreamSynchronize(s->stream); hipStreamDestroy(s->stream); }
-    for (auto &e : s->ev_fe) if (e) hipEventDestroy(e);
-    for (auto &e : s->ev_rw) if (e) hipEventDestroy(e);
-    if (s->ev_wait) hipEventDestroy(s->ev_wait);
-    if (s->d_spprof) {
-        unsigned long long h[8] = {0};
-        if (hipMemcpy(h, s->d_spprof, sizeof h, hipMemcpyDeviceToHost) == hipSuccess && h[7])
-            fprintf(stderr, "scan_pre prof (template 1, %llu workgroups, mean shader cycles): load+dc %llu  convert+stage %llu  fm-lowpass %llu  prefix %llu  correlation %llu  reduce %llu\n",
-                    h[7], h[0] / h[7], h[1] / h[7], h[2] / h[7], h[3] / h[7], h[4] / h[7], h[5] / h[7]);
-        hipFree(s->d_spprof);
-    }
-    if (s->h_items) hipHostFree(s->h_items);
-    if (s->h_res) hipHostFree(s->h_res);
-    if (s->h_pre) hipHostFree(s->h_pre);
-    if (s->h_work) hipHostFree(s->h_work);
-    void *ptrs[] = { s->d_amatch, s->d_aws, s->d_wstail, s->d_pre, s->d_work, s->d_scratch, s->d_f32in, s->d_chanf0, s->d_dcavg, s->d_dcsums, s->d_ptail[0], s->d_ptail[1], s->d_y, s->d_fm, s->d_wiq, s->d_WS, s->d_G, s->d_tw,
-                     s->d_hdr, s->d_bnd, s->d_items, s->d_res, s->d_stage, s->d_wtab, s->d_conv, s->d_dcsums_f, s->d_zring, s->d_taps_f, s->d_segsums, s->d_dcseg, s->d_etab64, s->d_bsum, s->d_corr, s->d_dcprev[0], s->d_dcprev[1], s->d_hist[0], s->d_hist[1] };
-    for (void *p : ptrs) if (p) hipFree(p);
-    delete s;
-}
+void sonde_scan_destroy(sonde_scan_t *s) { delete s; }
 
 int sonde_scan_info(const sonde_scan_t *s, sonde_scan_info_t *info) {
     if (!s || !info) return SONDE_E_ARG;
@@ -659,7 +650,7 @@ static int run_windows(sonde_scan *s) {
         if (!s->use_pre && s->N > SC_N) {
             // N_DFT 16384 / 32768: every pair through the global-memory form of the exact kernel, in batches that share the scratch arrays
             hipEventRecord(e0, s->stream);
-            HIPCHK(hipMemcpyAsync(s->d_items, s->h_items, (size_t)n_items * sizeof(ScanItem), hipMemcpyHostToDevice, s->stream));
+            HIPCHK(hipMemcpyAsync(s->d_items, s->h_items.data(), (size_t)n_items * sizeof(ScanItem), hipMemcpyHostToDevice, s->stream));
             hipEventRecord(e1, s->stream);
             int n_work = 0;
             for (int i = 0; i < n_items; i++) for (int j = 0; j < SC_NTPL; j++) {
@@ -667,16 +658,16 @@ static int run_windows(sonde_scan *s) {
                 else s->h_res[(size_t)i * SC_NTPL + j] = ScanRes{ 0, 0.f, 0u, 0.f, -1, 0u };
             }
             const int batch = 256;
-            if (!s->d_scratch) { HIPCHK(hipMalloc((void **)&s->d_scratch, (size_t)batch * s->N * sizeof(float2))); s->scratch_pairs = batch; }
-            HIPCHK(hipMemcpyAsync(s->d_work, s->h_work, (size_t)n_work * sizeof(ScanWork), hipMemcpyHostToDevice, s->stream));
+            if (!s->d_scratch) { TRY(s->mem.dalloc(&s->d_scratch, (size_t)batch * s->N, false)); s->scratch_pairs = batch; }
+            HIPCHK(hipMemcpyAsync(s->d_work, s->h_work.data(), (size_t)n_work * sizeof(ScanWork), hipMemcpyHostToDevice, s->stream));
             HIPCHK(hipMemsetAsync(s->d_res, 0, (size_t)n_items * SC_NTPL * sizeof(ScanRes), s->stream));
             a.N = s->N; a.log2n = s->log2n; a.scratch = s->d_scratch;
             for (int w0 = 0; w0 < n_work; w0 += batch) {
                 a.work = s->d_work + w0; a.n_work = std::min(batch, n_work - w0);
                 if (sonde_launch_scan_corr(&a, s->stream) < 0) return SONDE_E_NOGPU;
             }
-            std::vector<ScanRes> keep(s->h_res, s->h_res + (size_t)n_items * SC_NTPL);
-            HIPCHK(hipMemcpyAsync(s->h_res, s->d_res, (size_t)n_items * SC_NTPL * sizeof(ScanRes), hipMemcpyDeviceToHost, s->stream));
+            std::vector<ScanRes> keep(s->h_res.data(), s->h_res.data() + (size_t)n_items * SC_NTPL);
+            HIPCHK(hipMemcpyAsync(s->h_res.data(), s->d_res, (size_t)n_items * SC_NTPL * sizeof(ScanRes), hipMemcpyDeviceToHost, s->stream));
             hipEventRecord(e2, s->stream);
             HIPCHK(hipStreamSynchronize(s->stream)); flush_front_timing(s);
             for (int i = 0; i < n_items; i++) for (int j = 0; j < SC_NTPL; j++) if (!s->tpl[j].active) s->h_res[(size_t)i * SC_NTPL + j] = keep[(size_t)i * SC_NTPL + j];
@@ -684,10 +675,10 @@ static int run_windows(sonde_scan *s) {
             for (int i = 0; i < n_items; i++) exact[i] = 0xffffu;
         } else if (!s->use_pre) {
             hipEventRecord(e0, s->stream);
-            HIPCHK(hipMemcpyAsync(s->d_items, s->h_items, (size_t)n_items * sizeof(ScanItem), hipMemcpyHostToDevice, s->stream));
+            HIPCHK(hipMemcpyAsync(s->d_items, s->h_items.data(), (size_t)n_items * sizeof(ScanItem), hipMemcpyHostToDevice, s->stream));
             hipEventRecord(e1, s->stream);
             if (sonde_launch_scan_corr(&a, s->stream) < 0) return SONDE_E_NOGPU;
-            HIPCHK(hipMemcpyAsync(s->h_res, s->d_res, (size_t)n_items * SC_NTPL * sizeof(ScanRes), hipMemcpyDeviceToHost, s->stream));
+            HIPCHK(hipMemcpyAsync(s->h_res.data(), s->d_res, (size_t)n_items * SC_NTPL * sizeof(ScanRes), hipMemcpyDeviceToHost, s->stream));
             hipEventRecord(e2, s->stream);
             HIPCHK(hipStreamSynchronize(s->stream)); flush_front_timing(s);
             timed(s, "scan_corr", e1, e2);
@@ -702,14 +693,14 @@ static int run_windows(sonde_scan *s) {
             pa.K = s->K; pa.opt_dc = s->cfg.opt_dc; pa.opt_iq = a.opt_iq; pa.lpfm_taps = s->lpfm_taps; pa.out = s->d_pre;
             memcpy(pa.kap, s->kap, sizeof pa.kap);
             hipEventRecord(e0, s->stream);
-            HIPCHK(hipMemcpyAsync(s->d_items, s->h_items, (size_t)n_items * sizeof(ScanItem), hipMemcpyHostToDevice, s->stream));
+            HIPCHK(hipMemcpyAsync(s->d_items, s->h_items.data(), (size_t)n_items * sizeof(ScanItem), hipMemcpyHostToDevice, s->stream));
             {   // profiling aid: cycles per phase of k_scan_pre, printed when the scanner is destroyed
                 static const bool want = getenv("SONDE_SP_PROF") != nullptr;
                 if (want && !s->d_spprof) { if (hipMalloc((void **)&s->d_spprof, 8 * sizeof(unsigned long long)) == hipSuccess) hipMemset(s->d_spprof, 0, 8 * sizeof(unsigned long long)); }
                 pa.prof = s->d_spprof;
             }
             if (sonde_launch_scan_pre(&pa, s->stream) < 0) return SONDE_E_NOGPU;
-            HIPCHK(hipMemcpyAsync(s->h_pre, s->d_pre, (size_t)n_items * SC_NTPL * sizeof(ScanPre), hipMemcpyDeviceToHost, s->stream));
+            HIPCHK(hipMemcpyAsync(s->h_pre.data(), s->d_pre, (size_t)n_items * SC_NTPL * sizeof(ScanPre), hipMemcpyDeviceToHost, s->stream));
             hipEventRecord(e1, s->stream);
             HIPCHK(hipStreamSynchronize(s->stream)); flush_front_timing(s);
             timed(s, "scan_pre", e0, e1);
@@ -735,10 +726,10 @@ static int run_windows(sonde_scan *s) {
             if (n_work > 0) {
                 hipEventRecord(e1, s->stream);
                 a.n_items = n_all; a.work = s->d_work; a.n_work = n_work;
-                if (n_all > n_items) HIPCHK(hipMemcpyAsync(s->d_items + n_items, s->h_items + n_items, (size_t)(n_all - n_items) * sizeof(ScanItem), hipMemcpyHostToDevice, s->stream));
-                HIPCHK(hipMemcpyAsync(s->d_work, s->h_work, (size_t)n_work * sizeof(ScanWork), hipMemcpyHostToDevice, s->stream));
+                if (n_all > n_items) HIPCHK(hipMemcpyAsync(s->d_items + n_items, s->h_items.data() + n_items, (size_t)(n_all - n_items) * sizeof(ScanItem), hipMemcpyHostToDevice, s->stream));
+                HIPCHK(hipMemcpyAsync(s->d_work, s->h_work.data(), (size_t)n_work * sizeof(ScanWork), hipMemcpyHostToDevice, s->stream));
                 if (sonde_launch_scan_corr(&a, s->stream) < 0) return SONDE_E_NOGPU;
-                HIPCHK(hipMemcpyAsync(s->h_res, s->d_res, (size_t)n_all * SC_NTPL * sizeof(ScanRes), hipMemcpyDeviceToHost, s->stream));
+                HIPCHK(hipMemcpyAsync(s->h_res.data(), s->d_res, (size_t)n_all * SC_NTPL * sizeof(ScanRes), hipMemcpyDeviceToHost, s->stream));
                 hipEventRecord(e2, s->stream);
                 HIPCHK(hipStreamSynchronize(s->stream)); flush_front_timing(s);
                 timed(s, "scan_corr", e1, e2);
@@ -766,7 +757,7 @@ static int run_windows(sonde_scan *s) {
             Chan &cs = s->chan[c];
             for (int i = first_item[c]; i < first_item[c + 1]; i++) {
                 if (cs.done || cs.imet_hold) break;
-                const ScanRes *r = s->h_res + (size_t)i * SC_NTPL;
+                const ScanRes *r = s->h_res.data() + (size_t)i * SC_NTPL;
                 sonde_scan_window_t w; memset(&w, 0, sizeof w);
                 w.channel = c; w.pos = s->h_items[i].pos;
                 for (int j = 0; j < SC_NTPL; j++) { w.mp[j] = r[j].mp; w.mv[j] = r[j].mv; w.mpos[j] = r[j].mpos; w.dc[j] = r[j].dc; w.herrs[j] = r[j].herrs; w.m10[j] = (s->tpl[j].is_m10 && r[j].herrs >= 0) ? m10_bytes(kTpl[j].hdr, r[j].m10, r[j].mv < 0) : 0u; }
@@ -788,14 +779,14 @@ int sonde_scan_process_device(sonde_scan_t *s, const void *d_in, int64_t ch_stri
     if (s->cfg.bits == 8) {                        // cu8: (u-128)/128 == ((u-128)*256)/32768 -> feed the 16-bit path
         const int nc = ch_stride == 0 ? 1 : C;
         const int epf = mode == SONDE_SCAN_AUDIO ? std::max(1, s->cfg.audio_channels) : 2;          // bytes per sample / audio frame
-        if (!s->d_conv) HIPCHK(hipMalloc((void **)&s->d_conv, (size_t)C * s->cfg.max_chunk * epf * 2));
+        if (!s->d_conv) TRY(s->mem.dalloc(&s->d_conv, (size_t)C * s->cfg.max_chunk * epf, false));
         sonde_launch_u8_to_s16((const uint8_t *)d_in, ch_stride * epf, s->d_conv, (long long)n_samples * epf, nc, n_samples * epf, s->stream);
         d_in = s->d_conv; if (ch_stride != 0) ch_stride = n_samples;
     }
     bool f32in = s->cfg.bits == 32;
     if (s->wide_fe && !f32in) {                    // wide IF: the decimator has more than 8 blocks of taps -> float32 copy (x / 32768, exact) for the plain kernels
         const int nc = ch_stride == 0 ? 1 : C;
-        if (!s->d_f32in) HIPCHK(hipMalloc((void **)&s->d_f32in, (size_t)C * s->cfg.max_chunk * sizeof(float2)));
+        if (!s->d_f32in) TRY(s->mem.dalloc(&s->d_f32in, (size_t)C * s->cfg.max_chunk, false));
         sonde_launch_s16_to_f32((const int16_t *)d_in, ch_stride, s->d_f32in, n_samples, nc, n_samples, s->stream);
         d_in = s->d_f32in; if (ch_stride != 0) ch_stride = n_samples;
         f32in = true;
@@ -819,10 +810,7 @@ int sonde_scan_process_device(sonde_scan_t *s, const void *d_in, int64_t ch_stri
             // one pass over the input: raw mix + block sums, then window sums -> means -> y -= mean * E at the IF rate
             if (mode != SONDE_SCAN_BBIQ || f32in || n_samples % D || s->dc_cnt % (uint32_t)D) return SONDE_E_ARG;      // (cannot happen: whole blocks per call)
             const int nseg_cap = s->cfg.max_chunk / (int)s->dc_max + 2;
-            if (!s->d_segsums) {
-                HIPCHK(hipMalloc((void **)&s->d_segsums, (size_t)C * nseg_cap * 2 * sizeof(long long)));
-                HIPCHK(hipMalloc((void **)&s->d_dcseg, (size_t)C * (nseg_cap + 1) * sizeof(float2)));
-            }
+            TRY(alloc_dc_windows(s));
             const int nb = n_samples / D, seg_off = (int)(s->dc_cnt / (uint32_t)D), seg_blocks = (int)(s->dc_max / (uint32_t)D);
             MixDecArgs a{};
             a.iq = (const int16_t *)d_in; a.ch_stride = ch_stride; a.n_ch = C; a.nblocks = nb;
@@ -854,10 +842,7 @@ int sonde_scan_process_device(sonde_scan_t *s, const void *d_in, int64_t ch_stri
         }
         if (done < n_samples && mode == SONDE_SCAN_BBIQ && !f32in && D <= 64 && n_samples % D == 0 && s->dc_cnt % (uint32_t)D == 0) {
             const int nseg_cap = s->cfg.max_chunk / (int)s->dc_max + 2;
-            if (!s->d_segsums) {
-                HIPCHK(hipMalloc((void **)&s->d_segsums, (size_t)C * nseg_cap * 2 * sizeof(long long)));
-                HIPCHK(hipMalloc((void **)&s->d_dcseg, (size_t)C * (nseg_cap + 1) * sizeof(float2)));
-            }
+            TRY(alloc_dc_windows(s));
             sonde_launch_dc_segments((const int16_t *)d_in, ch_stride, C, n_samples, s->dc_cnt, s->dc_max, s->d_segsums, s->d_dcsums, s->d_dcavg,
                                      s->d_dcseg, nseg_cap + 1, s->stream);
             MixDecArgs a{};
@@ -879,11 +864,8 @@ int sonde_scan_process_device(sonde_scan_t *s, const void *d_in, int64_t ch_stri
         // instead of a mixer launch and a mean update per 1/32 s window (63 launches of 4-9 us per second of signal: 0.4 of scan_wide's 2.5 ms)
         if (mode != SONDE_SCAN_BBIQ && f32in && n_samples > 0) {
             const int nseg_cap = s->cfg.max_chunk / (int)s->dc_max + 2;
-            if (!s->d_dcsums_f) { HIPCHK(hipMalloc((void **)&s->d_dcsums_f, 2 * (size_t)C * sizeof(double))); HIPCHK(hipMemset(s->d_dcsums_f, 0, 2 * (size_t)C * sizeof(double))); }
-            if (!s->d_segsums) {
-                HIPCHK(hipMalloc((void **)&s->d_segsums, (size_t)C * nseg_cap * 2 * sizeof(double)));
-                HIPCHK(hipMalloc((void **)&s->d_dcseg, (size_t)C * (nseg_cap + 1) * sizeof(float2)));
-            }
+            if (!s->d_dcsums_f) TRY(s->mem.dalloc(&s->d_dcsums_f, 2 * (size_t)C));
+            TRY(alloc_dc_windows(s));
             sonde_launch_dc_segments_f32((const float2 *)d_in, ch_stride, C, n_samples, s->dc_cnt, s->dc_max, (double *)s->d_segsums, s->d_dcsums_f, s->d_dcavg,
                                          s->d_dcseg, nseg_cap + 1, s->stream);
             MixF32Args a{}; a.x = (const float2 *)d_in; a.ch_stride = ch_stride; a.n_ch = C; a.n = n_samples;
@@ -898,15 +880,12 @@ int sonde_scan_process_device(sonde_scan_t *s, const void *d_in, int64_t ch_stri
         while (done < n_samples) {
             const int take = (int)std::min<uint32_t>((uint32_t)(n_samples - done), s->dc_max - s->dc_cnt);
             if (f32in) {                                     // float32 IQ (or the wide-IF copy): plain mixer / FIR kernels, IQ-DC sums in double
-                if (!s->d_dcsums_f) {
-                    HIPCHK(hipMalloc((void **)&s->d_dcsums_f, 2 * (size_t)C * sizeof(double))); HIPCHK(hipMemset(s->d_dcsums_f, 0, 2 * (size_t)C * sizeof(double)));
-                    if (mode == SONDE_SCAN_BBIQ) {
-                        uint32_t zl = 1; while (zl < (uint32_t)s->cfg.max_chunk + (uint32_t)s->dec.taps.size() + (uint32_t)D + 64u) zl <<= 1;
-                        s->zmask = zl - 1;
-                        HIPCHK(hipMalloc((void **)&s->d_zring, (size_t)C * zl * sizeof(float2))); HIPCHK(hipMemset(s->d_zring, 0, (size_t)C * zl * sizeof(float2)));
-                        HIPCHK(hipMalloc((void **)&s->d_taps_f, s->dec.taps.size() * sizeof(float)));
-                        HIPCHK(hipMemcpy(s->d_taps_f, s->dec.taps.data(), s->dec.taps.size() * sizeof(float), hipMemcpyHostToDevice));
-                    }
+                if (!s->d_dcsums_f) TRY(s->mem.dalloc(&s->d_dcsums_f, 2 * (size_t)C));
+                if (mode == SONDE_SCAN_BBIQ && !s->d_taps_f) {
+                    uint32_t zl = 1; while (zl < (uint32_t)s->cfg.max_chunk + (uint32_t)s->dec.taps.size() + (uint32_t)D + 64u) zl <<= 1;
+                    s->zmask = zl - 1;
+                    if (!s->d_zring) TRY(s->mem.dalloc(&s->d_zring, (size_t)C * zl));
+                    TRY(s->mem.upload(&s->d_taps_f, s->dec.taps));
                 }
                 MixF32Args a{}; a.x = (const float2 *)d_in + (size_t)done; a.ch_stride = ch_stride; a.n_ch = C; a.n = take;
                 a.chan_f0 = s->d_chanf0; a.lut_len = s->lut_len; a.lut_phase = (uint32_t)(s->samples_in % (uint64_t)std::max(1, s->lut_len));
@@ -983,8 +962,8 @@ int sonde_scan_process_host(sonde_scan_t *s, const void *h_in, int64_t ch_stride
     if (ch_stride == 0) {                                  // one wideband stream: staged once, every channel mixes its own fq out of it
         const size_t need1 = (size_t)n_samples * unit;
         if (need1 > s->stage_bytes) {
-            if (s->d_stage) { hipStreamSynchronize(s->stream); hipFree(s->d_stage); s->d_stage = nullptr; }
-            HIPCHK(hipMalloc(&s->d_stage, need1)); s->stage_bytes = need1;
+            if (s->d_stage) { hipStreamSynchronize(s->stream); s->mem.release(s->d_stage); s->stage_bytes = 0; }
+            TRY(s->mem.dalloc(&s->d_stage, need1, false)); s->stage_bytes = need1;
         }
         HIPCHK(hipMemcpyAsync(s->d_stage, h_in, need1, hipMemcpyHostToDevice, s->stream));
         HIPCHK(hipStreamSynchronize(s->stream));     // h_in belongs to the caller again when this returns
@@ -992,8 +971,8 @@ int sonde_scan_process_host(sonde_scan_t *s, const void *h_in, int64_t ch_stride
     }
     const size_t need = (size_t)C * n_samples * unit;
     if (need > s->stage_bytes) {
-        if (s->d_stage) { hipStreamSynchronize(s->stream); hipFree(s->d_stage); s->d_stage = nullptr; }
-        HIPCHK(hipMalloc(&s->d_stage, need)); s->stage_bytes = need;
+        if (s->d_stage) { hipStreamSynchronize(s->stream); s->mem.release(s->d_stage); s->stage_bytes = 0; }
+        TRY(s->mem.dalloc(&s->d_stage, need, false)); s->stage_bytes = need;
     }
     HIPCHK(hipMemcpy2DAsync(s->d_stage, (size_t)n_samples * unit, h_in, (size_t)ch_stride * unit, (size_t)n_samples * unit, C,
                             hipMemcpyHostToDevice, s->stream));

@@ -27,11 +27,11 @@
 #include "../../include/sonde_rs92.h"
 #include "../../include/sonde_imet54.h"
 #include "../../include/sonde_meisei.h"
+#include "sonde_devmem.h"
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <vector>
-
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "libsonde_hip: %s failed: %s\n", #x, hipGetErrorString(e_)); return SONDE_E_NOGPU; } } while (0)
 
 struct SoftinChan {
     int   mode;                    // 0 searching, 1 inside a frame
@@ -779,6 +779,7 @@ extern "C" int sonde_fsk_dev_reader_done_prev(sonde_fsk_t *f, hipStream_t consum
 // ------------------------------------------------------------------------------------------------
 // The host side.  One handle for every kind; what differs from kind to kind is a SoftinKind: the record the kernel leaves, the launch, and what a record counts for.
 // ------------------------------------------------------------------------------------------------
+#include "sonde_pinned.h"
 struct SoftinKind {
     size_t rec;                                    // bytes of a record in d_rec / h_rec; 0 = RS41's three arrays (frames / flen / meta + ecc: what k_rs41_ecc_batch reads)
     void (*launch)(sonde_softin_dev *s, const SoftinArgs &a, int nblocks, hipStream_t st);
@@ -786,6 +787,8 @@ struct SoftinKind {
 };
 
 struct sonde_softin_dev {
+    DevMem mem;                                    // every d_ buffer below; the h_ ones are page-locked landing buffers of their own (sonde_pinned.h)
+    ~sonde_softin_dev();
     int C = 0, type = SONDE_RS41, cap = 0;
     int head = 0;                                  // records copied to the host without asking how many there are (what a call of a second normally completes)
     const SoftinKind *kind = nullptr;
@@ -793,40 +796,35 @@ struct sonde_softin_dev {
     int opt = 0;                                   // the kind's own switch: M20 skip, dropsonde / RS92 inv, iMet-54 / Meisei ecc, LMS6 vit
     SoftinArgs args{};
     hipStream_t stream = nullptr;                  // the consumer's own, made by its first call (softin_enqueue): behind the modem's streams, in the order of use
-    std::vector<std::pair<void *, bool>> allocs;   // every buffer below (true: page-locked host memory), freed by destroy
     void *d_state = nullptr;                       // the channels between calls
-    unsigned char *d_rec = nullptr, *h_rec = nullptr;      // a call's records, and their page-locked landing buffer
-    unsigned *d_count = nullptr, *h_count = nullptr;
-    int *d_nbits = nullptr, *h_nbits = nullptr;    // bits per channel of the modem launch a call consumes
+    unsigned char *d_rec = nullptr; Pinned<unsigned char> h_rec;      // a call's records, and their landing buffer
+    unsigned *d_count = nullptr; Pinned<unsigned> h_count;
+    int *d_nbits = nullptr; Pinned<int> h_nbits;   // bits per channel of the modem launch a call consumes
     unsigned char *d_hdr = nullptr, *d_gf = nullptr; uint32_t *d_tab = nullptr;
     // SONDE_RS41: the frames as sonde_launch_rs41_ecc_batch_n takes them
-    unsigned char *d_frames = nullptr, *d_synd = nullptr, *h_frames = nullptr; int *d_flen = nullptr, *d_ecc = nullptr, *d_codes = nullptr, *h_ecc = nullptr;
-    SoftinMeta *d_meta = nullptr, *h_meta = nullptr;
+    unsigned char *d_frames = nullptr, *d_synd = nullptr; Pinned<unsigned char> h_frames; int *d_flen = nullptr, *d_ecc = nullptr, *d_codes = nullptr; Pinned<int> h_ecc;
+    SoftinMeta *d_meta = nullptr; Pinned<SoftinMeta> h_meta;
     // SONDE_LMS6: the channels of a relaunch, the block length each channel has on the device, the decoders' tallies so far
-    int l6_auto = 0; int *d_l6_list = nullptr, *h_l6_list = nullptr, *h_l6_len = nullptr; std::vector<int> l6_len; std::vector<int64_t> l6_ok;
+    int l6_auto = 0; int *d_l6_list = nullptr; Pinned<int> h_l6_list, h_l6_len; std::vector<int> l6_len; std::vector<int64_t> l6_ok;
     // LMS6 / RS92 / iMet-54 / Meisei: a host decoder per channel (what a sonde collects — calibration rows, configuration words, counters — is per channel)
     std::vector<void *> dec; void (*dec_free)(void *) = nullptr;
     std::vector<unsigned char> q;                  // the records not yet fetched, in the form the kind's tally queues
     long long frames_total = 0, ecc_ok_total = 0, repaired_total = 0, symbols_total = 0, dropped = 0;
     bool pending = false; hipStream_t pend_stream = nullptr;
 
-    template <class T> bool dalloc(T **p, size_t n) {
-        if (hipMalloc((void **)p, (n ? n : 1) * sizeof(T)) != hipSuccess) { *p = nullptr; return false; }
-        allocs.push_back({*p, false});
-        return true;
-    }
-    template <class T> bool halloc(T **p, size_t n) {
-        if (hipHostMalloc((void **)p, (n ? n : 1) * sizeof(T), hipHostMallocDefault) != hipSuccess) { *p = nullptr; return false; }
-        allocs.push_back({*p, true});
-        memset((void *)*p, 0, (n ? n : 1) * sizeof(T));
-        return true;
-    }
+    template <class T> bool dalloc(T **p, size_t n) { return mem.dalloc(p, n, false) == 0; }
     template <class T> T *chan() { return (T *)d_state; }
     template <class T> T *recs() { return (T *)d_rec; }
-    template <class T> const T &landed(long long i) const { return ((const T *)h_rec)[i]; }
+    template <class T> const T &landed(long long i) const { return ((const T *)h_rec.data())[i]; }
     template <class T> void queue(const T &r) { const unsigned char *b = (const unsigned char *)&r; q.insert(q.end(), b, b + sizeof(T)); }
     template <class T> T *decoder(int ch) { return (T *)dec[(size_t)ch]; }
 };
+
+sonde_softin_dev::~sonde_softin_dev() {
+    if (pending && pend_stream) (void)hipStreamSynchronize(pend_stream);
+    if (stream) { hipStreamSynchronize(stream); hipStreamDestroy(stream); }
+    for (void *d : dec) dec_free(d);
+}
 
 // ---- the launches.  The staged kinds keep the call's soft decisions in LDS: what a call can hold (a modem launch: its capacity; a pushed stream: its length), up to
 // M10_STAGE_MAX; beyond that, or where the device refuses the dynamic LDS, the kernel reads them where they lie.  The attribute is a property of (function, device):
@@ -885,7 +883,7 @@ static void tally_rs41(sonde_softin_dev *s, long long n) {
         const SoftinMeta &m = s->h_meta[i];
         f.channel = m.channel; f.len = m.len; f.nbytes = m.nbytes; f.mv = m.mv; f.mv_pos = (uint32_t)m.hdr_bit;
         f.ecc = s->ecc_level > 0 ? s->h_ecc[i] : 0;
-        memcpy(f.frame, s->h_frames + (size_t)i * 518, 518);
+        memcpy(f.frame, s->h_frames.data() + (size_t)i * 518, 518);
         s->queue(f); s->frames_total++;
         if (f.ecc >= 0) s->ecc_ok_total++;
         if (f.ecc > 0) { s->repaired_total++; s->symbols_total += f.ecc; }
@@ -948,21 +946,22 @@ static int softin_new(const int32_t n_channels, const int type, const int per_ca
                       const void *init, const size_t chan_bytes, sonde_softin_dev **out) {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { fprintf(stderr, "libsonde_hip: no usable HIP device (the batched soft-bit framer has no CPU fallback)\n"); return SONDE_E_NOGPU; }
-    sonde_softin_dev *s = new sonde_softin_dev();
+    std::unique_ptr<sonde_softin_dev> owner(new sonde_softin_dev());
+    sonde_softin_dev *s = owner.get();
     s->C = n_channels; s->type = type; s->kind = softin_kind(type);
     s->cap = per_cap * n_channels + 16; s->head = std::min(s->cap, per_head * n_channels + 16);
     const size_t C = (size_t)n_channels, cap = (size_t)s->cap;
     std::vector<unsigned char> img(C * chan_bytes);
     for (size_t c = 0; c < C; c++) memcpy(img.data() + c * chan_bytes, init, chan_bytes);
     unsigned char *state = nullptr;
-    bool ok = s->dalloc(&state, img.size()) && s->dalloc(&s->d_count, 2) && s->halloc(&s->h_count, 2) && s->dalloc(&s->d_nbits, C) && s->halloc(&s->h_nbits, C)
+    bool ok = s->dalloc(&state, img.size()) && s->dalloc(&s->d_count, 2) && s->h_count.alloc(2) && s->dalloc(&s->d_nbits, C) && s->h_nbits.alloc(C)
            && hipMemcpy(state, img.data(), img.size(), hipMemcpyHostToDevice) == hipSuccess;
-    if (ok && s->kind->rec) ok = s->dalloc(&s->d_rec, cap * s->kind->rec) && s->halloc(&s->h_rec, cap * s->kind->rec);
-    if (!ok) { sonde_softin_dev_destroy(s); return SONDE_E_NOMEM; }
+    if (ok && s->kind->rec) ok = s->dalloc(&s->d_rec, cap * s->kind->rec) && s->h_rec.alloc(cap * s->kind->rec);
+    if (!ok) return SONDE_E_NOMEM;
     s->d_state = state;
     SoftinArgs &a = s->args;
     a.n_ch = n_channels; a.inv_in = invert_stream ? 1 : 0; a.ths = ths; a.count = s->d_count; a.cap = s->cap;
-    *out = s;
+    *out = owner.release();
     return 0;
 }
 // the option checks of a kind's host decoder, before the device is touched; and a decoder per channel
@@ -983,9 +982,10 @@ template <class D, class O, void (*Destroy)(D *)> static int softin_decoders(son
 }
 // the end of every create: what the kind added is in place (ok) and the handle is the caller's, or it goes
 static int softin_created(sonde_softin_dev *s, const bool ok, sonde_softin_dev **out) {
+    std::unique_ptr<sonde_softin_dev> owner(s);
     (void)hipGetLastError();
-    if (!ok) { sonde_softin_dev_destroy(s); return SONDE_E_NOMEM; }
-    *out = s;
+    if (!ok) return SONDE_E_NOMEM;
+    *out = owner.release();
     return 0;
 }
 
@@ -1035,7 +1035,7 @@ int sonde_softin_dev_create(int32_t n_channels, int32_t sonde_type, int32_t ecc_
     if (ok && sonde_type == SONDE_RS41) {
         const size_t cap = (size_t)s->cap;
         ok = s->dalloc(&s->d_frames, cap * 518) && s->dalloc(&s->d_gf, 768) && s->dalloc(&s->d_synd, cap * 48) && s->dalloc(&s->d_flen, cap) && s->dalloc(&s->d_ecc, cap)
-          && s->dalloc(&s->d_codes, cap * 2) && s->dalloc(&s->d_meta, cap) && s->halloc(&s->h_ecc, cap) && s->halloc(&s->h_meta, cap) && s->halloc(&s->h_frames, cap * 518)
+          && s->dalloc(&s->d_codes, cap * 2) && s->dalloc(&s->d_meta, cap) && s->h_ecc.alloc(cap) && s->h_meta.alloc(cap) && s->h_frames.alloc(cap * 518)
           && hipMemcpy(s->d_gf, sonde::gf_exp_table(), 512, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(s->d_gf + 512, sonde::gf_log_table(), 256, hipMemcpyHostToDevice) == hipSuccess
           && hipMemset(s->d_ecc, 0, cap * 4) == hipSuccess;
         SoftinArgs &a = s->args;
@@ -1064,7 +1064,7 @@ int sonde_softin_dev_create_lms6(int32_t n_channels, const sonde_lms6_opts_t *op
     s->opt = o.vit; s->l6_auto = o.typ == 0;
     s->l6_len.assign(C, len0); s->l6_ok.assign(C, 0);
     const bool ok = softin_decoders<sonde_lms6_dec_t, sonde_lms6_opts_t, sonde_lms6_dec_destroy>(s, &o, sonde_lms6_dec_create) == 0
-                 && s->dalloc(&s->d_l6_list, C) && s->halloc(&s->h_l6_list, C) && s->halloc(&s->h_l6_len, C) && s->dalloc(&s->d_hdr, 64)
+                 && s->dalloc(&s->d_l6_list, C) && s->h_l6_list.alloc(C) && s->h_l6_len.alloc(C) && s->dalloc(&s->d_hdr, 64)
                  && hipMemcpy(s->d_hdr, sonde_lms6_raw_header(), 64, hipMemcpyHostToDevice) == hipSuccess;
     s->args.hdr = s->d_hdr;
     return softin_created(s, ok, out);
@@ -1124,15 +1124,7 @@ int sonde_softin_dev_rs92_load_almanac(sonde_softin_dev_t *s, const char *path) 
     return 0;
 }
 
-void sonde_softin_dev_destroy(sonde_softin_dev_t *s) {
-    if (!s) return;
-    if (s->pending && s->pend_stream) (void)hipStreamSynchronize(s->pend_stream);
-    if (s->stream) { hipStreamSynchronize(s->stream); hipStreamDestroy(s->stream); }
-    for (const auto &p : s->allocs) { if (p.second) (void)hipHostFree(p.first); else (void)hipFree(p.first); }
-    (void)hipGetLastError();
-    for (void *d : s->dec) s->dec_free(d);
-    delete s;
-}
+void sonde_softin_dev_destroy(sonde_softin_dev_t *s) { delete s; }
 
 // one pass of the framer (and rs41_ecc() over the frames it completes) over the channels of ch_list (null: all)
 static int softin_pass(sonde_softin_dev *s, hipStream_t st, const int nblocks, const int *ch_list) {
@@ -1141,18 +1133,18 @@ static int softin_pass(sonde_softin_dev *s, hipStream_t st, const int nblocks, c
     HIPCHK(hipMemsetAsync(a.count, 0, 4, st));
     s->kind->launch(s, a, nblocks, st);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(s->h_count, a.count, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(s->h_count.data(), a.count, 4, hipMemcpyDeviceToHost, st));
     return 0;
 }
 // records [from, to) of the call to the host
 static int softin_copy(sonde_softin_dev *s, hipStream_t st, const int from, const int to) {
     if (to <= from) return 0;
     const size_t n = (size_t)(to - from), rec = s->kind->rec;
-    if (rec) HIPCHK(hipMemcpyAsync(s->h_rec + from * rec, s->d_rec + from * rec, n * rec, hipMemcpyDeviceToHost, st));
+    if (rec) HIPCHK(hipMemcpyAsync(s->h_rec.data() + from * rec, s->d_rec + from * rec, n * rec, hipMemcpyDeviceToHost, st));
     else {
-        HIPCHK(hipMemcpyAsync(s->h_meta + from, s->d_meta + from, n * sizeof(SoftinMeta), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(s->h_ecc + from, s->d_ecc + from, n * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(s->h_frames + (size_t)from * 518, s->d_frames + (size_t)from * 518, n * 518, hipMemcpyDeviceToHost, st));   // 518 bytes per frame and second: not the soft decisions
+        HIPCHK(hipMemcpyAsync(s->h_meta.data() + from, s->d_meta + from, n * sizeof(SoftinMeta), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(s->h_ecc.data() + from, s->d_ecc + from, n * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(s->h_frames.data() + (size_t)from * 518, s->d_frames + (size_t)from * 518, n * 518, hipMemcpyDeviceToHost, st));   // 518 bytes per frame and second: not the soft decisions
     }
     return 0;
 }
@@ -1184,7 +1176,7 @@ static int softin_finish_lms6(sonde_softin_dev *s, hipStream_t st, long long n) 
             if (b.more && nlist < s->C) s->h_l6_list[nlist++] = b.channel;
         }
         if (!nlist) return 0;
-        HIPCHK(hipMemcpyAsync(s->d_l6_list, s->h_l6_list, (size_t)nlist * sizeof(int), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(s->d_l6_list, s->h_l6_list.data(), (size_t)nlist * sizeof(int), hipMemcpyHostToDevice, st));
         { const int rc = softin_pass(s, st, nlist, s->d_l6_list); if (rc) return rc; }
         { const int rc = softin_copy(s, st, 0, std::min(nlist, s->cap)); if (rc) return rc; }
         HIPCHK(hipStreamSynchronize(st));
@@ -1225,7 +1217,7 @@ static int softin_finish(sonde_softin_dev *s) {
 // does before sonde_softin_dev_collect.
 static int softin_consume_launch(sonde_softin_dev *s, const float *d_sd, const long long cap, const int bpf) {
     for (int c = 0; c < s->C; c++) s->h_nbits[c] = s->h_nbits[c] > 0 ? s->h_nbits[c] * bpf : 0;
-    HIPCHK(hipMemcpyAsync(s->d_nbits, s->h_nbits, (size_t)s->C * sizeof(int), hipMemcpyHostToDevice, s->stream));
+    HIPCHK(hipMemcpyAsync(s->d_nbits, s->h_nbits.data(), (size_t)s->C * sizeof(int), hipMemcpyHostToDevice, s->stream));
     SoftinArgs &a = s->args;
     a.sd = d_sd; a.ch_stride = cap; a.nbits_ch = s->d_nbits; a.nbits = 0;
     { const int rc = softin_enqueue(s); if (rc) return rc; }
@@ -1245,7 +1237,7 @@ int sonde_softin_dev_submit_fsk(sonde_softin_dev_t *s, sonde_fsk_t *modem) {
     { const int rc = sonde_fsk_wait(modem); if (rc) return rc; }
     { const int rc = sonde_fsk_dev_view(modem, &d_sd, &cap, &d_chan, &bpf, &nch, &ms); if (rc) return rc; }
     if (nch != s->C) return SONDE_E_ARG;
-    { const int rc = sonde_fsk_host_frames(modem, s->h_nbits); if (rc) return rc; }
+    { const int rc = sonde_fsk_host_frames(modem, s->h_nbits.data()); if (rc) return rc; }
     { const int rc = softin_consume_launch(s, d_sd, cap, bpf); if (rc) return rc; }
     // the modem's launch that reuses this buffer of soft decisions (the next but one) waits for the consumer's kernels: submitting the modem twice before
     // sonde_softin_dev_collect is slower, not wrong
@@ -1263,7 +1255,7 @@ int sonde_softin_dev_submit_fsk_behind(sonde_softin_dev_t *s, sonde_fsk_t *modem
     { const int rc = softin_finish(s); if (rc) return rc; }
     { const int rc = softin_own_stream(s); if (rc) return rc; }
     const float *d_sd = nullptr; long long cap = 0; int bpf = 0, nch = s->C;
-    const int have = sonde_fsk_dev_view_prev(modem, &d_sd, &cap, &bpf, &nch, s->h_nbits);
+    const int have = sonde_fsk_dev_view_prev(modem, &d_sd, &cap, &bpf, &nch, s->h_nbits.data());
     if (have < 0) return have;
     if (have == 0) return sonde_softin_dev_submit_fsk(s, modem);
     if (nch != s->C) return SONDE_E_ARG;
