@@ -17,6 +17,8 @@
 #include "sonde_rs92.h"
 #include "sonde_imet54.h"
 #include "sonde_meisei.h"
+#include "sonde_mrz.h"
+#include "sonde_mts01.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -277,7 +279,75 @@ typedef struct {
 /* frames completed by the push calls since the last fetch (per channel in stream order); returns the count (<= max) */
 int  sonde_softin_dev_fetch_meisei(sonde_softin_dev_t *s, sonde_meisei_softin_t *out, int32_t max);
 
-/* tallies since creation: frames completed (SONDE_LMS6: blocks; accepted = the frames with a good CRC-16 that ended in them, the decoders' own count), frames accepted (RS41: rs41_ecc() >= 0; DFM: no block uncorrectable; M10 / M20: checksum good; RD94RD41: every block of the type print_frame chooses good; RS92: rs_decode >= 0; iMet-54: ecc_frm >= 0 and a check sum good, or ecc_std == 0 — the JSON rule without the status bits; Meisei: no block 0xE / 0xF), frames repaired (RS92: rs_decode > 0; iMet-54: ecc_frm > 0; Meisei: any block 1 or 2), symbols / codewords repaired (RS92: the sum of the positive rs_decode values; iMet-54: of the positive ecc_frm; Meisei: the sum of the corrected bits), frames lost to a full buffer */
+/* ---- SONDE_MRZ consumers: `mp3h1mod --softin [-i] [--auto] [--ofs n] ...` for every channel (auto_rx's pipe `fsk_demod --cs16 -s -b -10000 -u 10000 --stats=N 2 48000
+ * 2400 - - | mp3h1mod --auto --json --softin --ptu`, auto_rx/autorx/decode.py:1256-1293).  On the device, one wavefront per channel (mp3h1mod.c:1151-1242, :157-183,
+ * :280-310, :805-815): the 44 header half symbols at 0.82 (a score of exactly 0.82f and the NaN of an all-zero window are no hits; the ring is left as it is on a
+ * hit and frame symbols never enter it; a hit of the other polarity is dropped, or with --auto flips the polarity for good), Manchester bits from two half symbols
+ * each (s2 - s1 >= 0, inverted unless the polarity is) behind the 22 known header bits, up to the frame length in effect: 408 bits (ECEF) or 384 (lat / lon).  At
+ * the end of a frame (not with -R) the bytes from bit --ofs on, the frame type (FF FF at bytes 30 / 31: CRC over 42 bytes, else 45) and the CRC-16 (0xA001
+ * reflected, start value 0xFFFF, from byte 3) are the device's; a good CRC sets the length of the channel's next frame, in the same call or a later one.
+ * Per completed frame 80 bytes come to the host, where the consumer's own sonde_mrz_dec_t of that channel (configuration words, serial numbers, --uniq and the
+ * JSON time-out state) prints from the device's bits and the device's verdict (sonde_mrz_dec_decoded) when the record is fetched.  Only complete frames are
+ * delivered: a consumer behind a live modem has no end of input.
+ * opts as for sonde_mrz_dec_create (SONDE_E_ARG as it returns it); opts->inv = -i, opts->aut = --auto; invert_stream = --softinv.  sonde_softin_dev_create with
+ * SONDE_MRZ is SONDE_E_ARG (the kind needs its options); the other kinds' fetch calls refuse an MRZ consumer and fetch_mrz refuses the other kinds.  One launch
+ * per push call: submit_fsk / collect keep the overlap with the modem's next second.
+ * A push call holds at most 8 * n_channels + 16 frames over all channels (a channel completes at most one per 44 + 2 (384 - 22) = 768 half symbols, seven in two
+ * seconds at 2400); frames beyond that are decoded — the length switch included — not delivered, and counted as dropped. */
+int  sonde_softin_dev_create_mrz(int32_t n_channels, const sonde_mrz_opts_t *opts, int32_t invert_stream, sonde_softin_dev_t **out);
+/* The text of a frame under any options.  The -r line: 51 x "XX " 153, the tag 6: below 160.  The -R line: 408 bits and the newline.  The position line: counter 6,
+ * time 12, lat / lon / alt 75 (32-bit integers over 1e6 / 1e2, or angles and a height from 32-bit ECEF centimetres), speeds 40, sats 12, d_alt 25, four PTU fields
+ * of 16-bit and range-checked values 60, the tag 6 (-c: 24), the -vv configuration word 60 (%.5f of any float: 46), --dbg 40: below 400.  The JSON object: 330 of
+ * fixed text and bounded fields, freq 11, version 31: below 450.  1024 leaves room for line and object. */
+#define SONDE_MRZ_TEXT_MAX 1024
+#define SONDE_MRZ_BITS_BYTES 52
+typedef struct {
+    int32_t  channel;
+    int32_t  nbits;          /* 408 / 384: the frame length in effect for this frame, counted from the header's first bit          */
+    int32_t  inv;            /* polarity in effect for the frame's bits (-i, or what --auto made of it)                           */
+    int32_t  crc_ok;         /* the device's CRC verdict (0 with -R: never looked at)                                             */
+    int32_t  crclen;         /* 42 (lat / lon) / 45 (ECEF) bytes under the CRC (0 with -R)                                        */
+    float    mv;             /* score of the header in front of the frame, with its sign                                          */
+    uint64_t hdr_bit;        /* half symbols read when the header matched                                                         */
+    int32_t  text_len;       /* SONDE_E_ARG (negative) if the text did not fit: text is "" then                                   */
+    uint8_t  bits[SONDE_MRZ_BITS_BYTES];      /* the frame bits from the header's first, MSB first; 0 behind nbits                 */
+    char     text[SONDE_MRZ_TEXT_MAX];        /* what the reference prints for this frame, NUL-terminated                          */
+} sonde_mrz_softin_t;
+/* frames completed by the push calls since the last fetch (per channel in stream order); returns the count (<= max) */
+int  sonde_softin_dev_fetch_mrz(sonde_softin_dev_t *s, sonde_mrz_softin_t *out, int32_t max);
+
+/* ---- SONDE_MTS01 consumers: `mts01mod --softin ...` for every channel.  On the device, one wavefront per channel (mts01mod.c:543-618, :76-127, :151-162): the 32
+ * header symbols AA AA B4 2B at 0.8 in either polarity (a score of exactly 0.8f and the NaN of an all-zero window are no hits; every hit counts; the ring is left as
+ * it is on a hit and frame symbols never enter it), 1048 bits read raw, one symbol each (s >= 0) — an inverted stream gives inverted bits and a failing CRC, as the
+ * reference does; --softinv puts it right — then the 131 bytes MSB first and the CRC-16 (0x8005, MSB first, start value 0xFFFF, over bytes 1 .. 128, bit-reversed,
+ * against bytes[130] << 8 | bytes[129]).  Per completed frame 152 bytes come to the host, where the consumer's own sonde_mts01_dec_t of that channel prints from
+ * the device's bytes, CRC value and verdict (sonde_mts01_dec_decoded) when the record is fetched.  Only complete frames are delivered.
+ * opts as for sonde_mts01_dec_create (SONDE_E_ARG as it returns it); invert_stream = --softinv.  sonde_softin_dev_create with SONDE_MTS01 is SONDE_E_ARG (the kind
+ * needs its options); the other kinds' fetch calls refuse an MTS01 consumer and fetch_mts01 refuses the other kinds.  One launch per push call.
+ * A push call holds at most 4 * n_channels + 16 frames over all channels (a channel completes at most one per 32 + 1048 = 1080 symbols of the 1200 a second);
+ * frames beyond that are decoded, not delivered, and counted as dropped. */
+int  sonde_softin_dev_create_mts01(int32_t n_channels, const sonde_mts01_opts_t *opts, int32_t invert_stream, sonde_softin_dev_t **out);
+/* The text of a frame under any options.  The -R line alone: 1048 bits, a blank per byte 131, the newline: 1180.  The -r line: 131 x "XX " 393, " # [XXXX:XXXX]"
+ * 14, " # [OK]" 7, the newline: 415.  The text line: the frame's string 130 at the most, the tag 7.  The -v line and the JSON object print numbers read from the
+ * frame's own text with %f: a field like 1e308 takes 316 characters, and the printer cuts each of its formatted pieces at 639 — two such pieces in the -v line
+ * (below 1500 with the rest of it) and one in the JSON object (below 900).  4096 leaves room for all three at their worst. */
+#define SONDE_MTS01_TEXT_MAX 4096
+#define SONDE_MTS01_FRAME_BYTES 131
+typedef struct {
+    int32_t  channel;
+    int32_t  crcval;         /* crc16_re over bytes 1 .. 128, as the device computed it                                           */
+    int32_t  crcdat;         /* bytes[130] << 8 | bytes[129]                                                                      */
+    int32_t  crc_ok;         /* the device's verdict                                                                              */
+    float    mv;             /* score of the header in front of the frame, with its sign                                          */
+    int32_t  text_len;       /* SONDE_E_ARG (negative) if the text did not fit: text is "" then                                   */
+    uint64_t hdr_bit;        /* symbols read when the header matched                                                              */
+    uint8_t  bytes[SONDE_MTS01_FRAME_BYTES];  /* the 1048 frame bits, MSB first                                                    */
+    char     text[SONDE_MTS01_TEXT_MAX];      /* what the reference prints for this frame, NUL-terminated                          */
+} sonde_mts01_softin_t;
+/* frames completed by the push calls since the last fetch (per channel in stream order); returns the count (<= max) */
+int  sonde_softin_dev_fetch_mts01(sonde_softin_dev_t *s, sonde_mts01_softin_t *out, int32_t max);
+
+/* tallies since creation: frames completed (SONDE_LMS6: blocks; accepted = the frames with a good CRC-16 that ended in them, the decoders' own count), frames accepted (RS41: rs41_ecc() >= 0; DFM: no block uncorrectable; M10 / M20: checksum good; RD94RD41: every block of the type print_frame chooses good; RS92: rs_decode >= 0; iMet-54: ecc_frm >= 0 and a check sum good, or ecc_std == 0 — the JSON rule without the status bits; Meisei: no block 0xE / 0xF; MRZ / MTS01: CRC-16 good, and their repaired and symbol tallies stay 0), frames repaired (RS92: rs_decode > 0; iMet-54: ecc_frm > 0; Meisei: any block 1 or 2), symbols / codewords repaired (RS92: the sum of the positive rs_decode values; iMet-54: of the positive ecc_frm; Meisei: the sum of the corrected bits), frames lost to a full buffer */
 int  sonde_softin_dev_counts(sonde_softin_dev_t *s, int64_t *frames, int64_t *ecc_ok, int64_t *repaired, int64_t *symbols, int64_t *dropped);
 
 #ifdef __cplusplus

@@ -48,7 +48,9 @@ extern "C" {
 #define SONDE_RS92   92         /* rs92mod.c: Vaisala RS92-SGP / -NGP; only as the type of a soft-bit consumer (sonde_softin_dev_create_rs92, include/sonde_fsk.h) */
 #define SONDE_IMET54 54         /* imet54mod.c: InterMet iMet-54 / iMet-50; only as the type of a soft-bit consumer (sonde_softin_dev_create_imet54, include/sonde_fsk.h) */
 #define SONDE_MEISEI 11         /* meisei100mod.c: Meisei iMS-100 / RS-11G; only as the type of a soft-bit consumer (sonde_softin_dev_create_meisei, include/sonde_fsk.h) */
-#define SONDE_MIXED  100        /* cfg.sonde_type of sonde_engine_create_mixed: the type is a property of the channel (its group), not of the engine */
+#define SONDE_MRZ    31         /* mp3h1mod.c: Meteo-Radiy MRZ / MP3-H1; only as the type of a soft-bit consumer (sonde_softin_dev_create_mrz, include/sonde_fsk.h) */
+#define SONDE_MTS01  71         /* mts01mod.c: Meteosis MTS01; only as the type of a soft-bit consumer (sonde_softin_dev_create_mts01, include/sonde_fsk.h) */
+#define SONDE_MIXED  100       /* cfg.sonde_type of sonde_engine_create_mixed: the type is a property of the channel (its group), not of the engine */
 #define SONDE_GENERIC 99        /* any other 2-FSK sonde of the reference's demod/mod family, described by a sonde_generic_t given to sonde_engine_create_generic;
                                  * header hits + soft bits only (sonde_engine_fetch_hits), framing stays with the caller */
 

@@ -59,6 +59,11 @@ int  sonde_mrz_dec_rawhex(sonde_mrz_dec_t *d, const char *line, char *out, size_
 /* Soft-symbol input (`mp3h1mod --softin`, decode.py:1293: two float32 half symbols per bit): header search, polarity and frame assembly
  * inside; finish != 0 at end of input. */
 int  sonde_mrz_dec_push_soft(sonde_mrz_dec_t *d, const float *soft, int32_t n, int32_t invert, int32_t finish, char *out, size_t outlen);
+/* A frame a soft-bit consumer completed on the device (sonde_softin_dev_fetch_mrz, include/sonde_fsk.h): nbits (408 or 384) frame bits from the header's first,
+ * MSB first, in the polarity the device read them with — the decoder's own inv plays no part — and the DEVICE's CRC verdict.  Prints what print_frame prints for
+ * that frame without computing the CRC again; the frame type is read from the bytes, and a good verdict moves the decoder's frame length and crclen as the
+ * reference's own check does, so sonde_mrz_dec_frame_bits stays in step with the device. */
+int  sonde_mrz_dec_decoded(sonde_mrz_dec_t *d, const uint8_t *bits, int32_t nbits, int32_t crc_ok, char *out, size_t outlen);
 
 #ifdef __cplusplus
 }

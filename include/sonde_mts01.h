@@ -45,6 +45,9 @@ int  sonde_mts01_dec_frame(sonde_mts01_dec_t *d, const float *soft, int32_t n, c
 /* Soft-bit input (`mts01mod --softin`): header search and frame assembly inside; finish != 0 at end of input (a frame in progress is
  * printed with the bits that exist, :613-615). */
 int  sonde_mts01_dec_push_soft(sonde_mts01_dec_t *d, const float *soft, int32_t n, int32_t invert, int32_t finish, char *out, size_t outlen);
+/* A frame a soft-bit consumer completed on the device (sonde_softin_dev_fetch_mts01, include/sonde_fsk.h): the 131 bytes (the 1048 frame bits, MSB first), the
+ * DEVICE's CRC value (crc16_re over bytes 1 .. 128) and verdict.  Prints what print_frame prints for that frame without computing the CRC again. */
+int  sonde_mts01_dec_decoded(sonde_mts01_dec_t *d, const uint8_t *bytes131, int32_t crcval, int32_t crc_ok, char *out, size_t outlen);
 
 #ifdef __cplusplus
 }

@@ -258,24 +258,25 @@ struct sonde_mrz_dec {
         }
     }
 
-    void classify(int &ok) {
+    // verdict: -1 = the CRC is checked here; 0 / 1 = the caller's (the device's, sonde_mrz_dec_decoded), and no CRC is computed
+    void classify(int &ok, int verdict) {
         crclen = (u2(frame + 30) == 0xFFFF) ? CRCLEN_LATLON : CRCLEN_ECEF;
-        ok = check_CRC((uint32_t)crclen) == 0;
+        ok = verdict < 0 ? check_CRC((uint32_t)crclen) == 0 : verdict != 0;
         if (ok) bitfrm_len = (crclen + 6) * 8;
     }
-    void print_frame(Out &w, int npos, int b2B) {
+    void print_frame(Out &w, int npos, int b2B, int verdict = -1) {
         int ok = 0;
         if (b2B) {
             if (o.raw == 2) { for (int j = 0; j < npos; j++) w.s += frame_bits[j]; w.f("\n"); return; }
             const int frmlen = (npos - bits_ofs) / 8;
             bits2bytes(frame_bits + bits_ofs, frmlen);
-            classify(ok);
+            classify(ok, verdict);
             if (o.raw == 1) {
                 for (int j = 0; j < frmlen; j++) w.f("%02X ", frame[j]);
                 w.f(" %s", ok ? "[OK]" : "[NO]"); w.f("\n");
             } else if (npos / 8 > P_ECEFV + 6) print_gpx(w, ok);
         } else {
-            classify(ok);
+            classify(ok, verdict);
             if (o.raw) {
                 for (int j = 0; j < npos; j++) w.f("%02X ", frame[j]);
                 w.f(" %s", ok ? "[OK]" : "[NO]"); w.f("\n");
@@ -317,6 +318,16 @@ int sonde_mrz_dec_frame(sonde_mrz_dec_t *d, const float *soft, int32_t n, char *
     for (int j = 0; j < n; j++) d->frame_bits[d->pos++] = (char)(0x30 + !(soft[j] >= 0.0f));        // the engine's bits carry the polarity; Manchester1 = the other sense
     d->frame_bits[d->pos] = '\0';
     d->print_frame(w, d->pos, 1);
+    return finish_out(w, out, outlen);
+}
+
+int sonde_mrz_dec_decoded(sonde_mrz_dec_t *d, const uint8_t *bits, int32_t nbits, int32_t crc_ok, char *out, size_t outlen) {
+    if (!d || !bits || !out || (nbits != BITFRAME_LEN && nbits != (CRCLEN_LATLON + 6) * 8)) return SONDE_E_ARG;
+    Out w;
+    for (int j = 0; j < nbits; j++) d->frame_bits[j] = (char)(0x30 + ((bits[j >> 3] >> (7 - (j & 7))) & 1));
+    d->frame_bits[nbits] = '\0';
+    d->pos = nbits;
+    d->print_frame(w, nbits, 1, crc_ok ? 1 : 0);
     return finish_out(w, out, outlen);
 }
 

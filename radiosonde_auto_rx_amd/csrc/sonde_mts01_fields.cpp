@@ -67,9 +67,12 @@ struct sonde_mts01_dec {
             for (int i = 0; i < 8; i++) if (frame_bits[8 * b + 7 - i] == '1') v += 1 << i;
             frame_bytes[b] = (uint8_t)v;
         }
-        const int crcdat = (frame_bytes[OFS + DATLEN + 1] << 8) | frame_bytes[OFS + DATLEN];
         const int crcval = (int)crc16_re(frame_bytes + OFS, DATLEN);
-        const bool crc_ok = crcdat == crcval;
+        print_bytes(w, crcval, ((frame_bytes[OFS + DATLEN + 1] << 8) | frame_bytes[OFS + DATLEN]) == crcval);
+    }
+    // frame_bits / frame_bytes printed under a CRC value and verdict: print_frame's own, or a soft-bit consumer's from the device (sonde_mts01_dec_decoded)
+    void print_bytes(Out &w, const int crcval, const bool crc_ok) {
+        const int crcdat = (frame_bytes[OFS + DATLEN + 1] << 8) | frame_bytes[OFS + DATLEN];
         if (o.raw) {
             if (o.raw == 1) {
                 for (int j = 0; j < FRAMELEN; j++) w.f("%02X ", frame_bytes[j]);
@@ -158,6 +161,16 @@ int sonde_mts01_dec_frame(sonde_mts01_dec_t *d, const float *soft, int32_t n, ch
     for (int j = 0; j < n; j++) d->frame_bits[j] = (char)(0x30 + (soft[j] >= 0.0f));
     d->frame_bits[n] = '\0';
     d->print_frame(w, n);
+    return finish_out(w, out, outlen);
+}
+
+int sonde_mts01_dec_decoded(sonde_mts01_dec_t *d, const uint8_t *bytes131, int32_t crcval, int32_t crc_ok, char *out, size_t outlen) {
+    if (!d || !bytes131 || !out) return SONDE_E_ARG;
+    Out w;
+    for (int j = 0; j < BITFRAMELEN; j++) d->frame_bits[j] = (char)(0x30 + ((bytes131[j >> 3] >> (7 - (j & 7))) & 1));
+    d->frame_bits[BITFRAMELEN] = '\0';
+    memcpy(d->frame_bytes, bytes131, FRAMELEN);
+    d->print_bytes(w, crcval & 0xFFFF, crc_ok != 0);
     return finish_out(w, out, outlen);
 }
 

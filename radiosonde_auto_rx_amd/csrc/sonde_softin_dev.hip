@@ -23,10 +23,14 @@
 #include "sonde_softin_rs92_dev.h"
 #include "sonde_softin_imet54_dev.h"
 #include "sonde_softin_meisei_dev.h"
+#include "sonde_softin_mrz_dev.h"
+#include "sonde_softin_mts01_dev.h"
 #include "../../include/sonde_drop.h"
 #include "../../include/sonde_rs92.h"
 #include "../../include/sonde_imet54.h"
 #include "../../include/sonde_meisei.h"
+#include "../../include/sonde_mrz.h"
+#include "../../include/sonde_mts01.h"
 #include "sonde_devmem.h"
 #include <cstdio>
 #include <cstring>
@@ -558,6 +562,43 @@ void k_softin_meisei(const SoftinMeiseiArgs A) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// MRZ / MP3-H1: mp3h1mod --softin [-i] [--auto] [--ofs n] (mp3h1mod.c:1151-1242, :157-183, :280-310, :805-815) — the 44 header half symbols at 0.82 with the polarity
+// rule and the ring left as it is, Manchester bits (s2 - s1) on a lane per bit packed by ballot, then bytes, frame type and the CRC-16 on the same wave (a lane per
+// byte carried through the shifts behind it, the XOR over the wave): the verdict sets the length of the channel's NEXT frame, 408 or 384 bits, inside the same
+// call: sonde_softin_mrz_dev.h, which the CPU wave emulator compiles as well.  The call's soft decisions are staged in LDS as for the other staged kinds (a second
+// at 2400 half symbols: 9.6 KB + 0.28 KB of state).  A record per completed frame; the fields and the text are the host's (sonde_mrz_dec_decoded).
+// ------------------------------------------------------------------------------------------------
+struct SoftinMrzArgs { SoftinArgs base; SoftinMrzChan *chan; SoftinMrzRec *out; int stage_cap, classify, bits_ofs; };
+
+__global__ __launch_bounds__(64)
+void k_softin_mrz(const SoftinMrzArgs A) {
+    const SoftinArgs &a = A.base;
+    extern __shared__ float s_x[];                     // [stage_cap] sgn * x of this call (staged: nb <= stage_cap)
+    __shared__ SoftinMrzLds s_l;
+    SoftinIn in;
+    if (!softin_input(a, in)) return;
+    mrz_wave_channel(A.chan + in.ch, in.x, in.nb, in.sgn, a.opt_auto, A.classify, A.bits_ofs, a.ths, &s_l, s_x, A.stage_cap, A.out, a.count, a.cap, in.ch, threadIdx.x);
+}
+
+// ------------------------------------------------------------------------------------------------
+// MTS01: mts01mod --softin (mts01mod.c:543-618, :76-127, :151-162) — the 32 header symbols at 0.8 in either polarity with the ring left as it is, 1048 bits read raw
+// on a lane per bit packed by ballot, then the 131 bytes and the CRC-16 on the same wave (two bytes per lane, the XOR over the wave, bit-reversed):
+// sonde_softin_mts01_dev.h, which the CPU wave emulator compiles as well.  Staged as the others (a second at 1200 symbols: 4.8 KB + 0.39 KB of state).  A record
+// per completed frame; the fields and the text are the host's (sonde_mts01_dec_decoded).
+// ------------------------------------------------------------------------------------------------
+struct SoftinMts01Args { SoftinArgs base; SoftinMts01Chan *chan; SoftinMts01Rec *out; int stage_cap; };
+
+__global__ __launch_bounds__(64)
+void k_softin_mts01(const SoftinMts01Args A) {
+    const SoftinArgs &a = A.base;
+    extern __shared__ float s_x[];                     // [stage_cap] sgn * x of this call (staged: nb <= stage_cap)
+    __shared__ SoftinMts01Lds s_l;
+    SoftinIn in;
+    if (!softin_input(a, in)) return;
+    mts01_wave_channel(A.chan + in.ch, in.x, in.nb, in.sgn, a.ths, &s_l, s_x, A.stage_cap, A.out, a.count, a.cap, in.ch, threadIdx.x);
+}
+
+// ------------------------------------------------------------------------------------------------
 // RD94 / RD41 dropsondes: rd94rd41drop --softin / --softinv [-i] (rd94rd41drop.c:1357-1386) — no correlation: the sign of every soft bit (s >= 0 after the two
 // inversions, which cancel each other) goes into the 40-bit ring, a frame is the 2360 raw bits behind a ring that equals FC 1D as Manchester-coded 8N1, and the
 // bits of a frame enter the ring too.  64 soft bits a pass: signs by ballot, every lane tests the ring as it stands behind its bit (values and "holds a bit"
@@ -793,7 +834,8 @@ struct sonde_softin_dev {
     int head = 0;                                  // records copied to the host without asking how many there are (what a call of a second normally completes)
     const SoftinKind *kind = nullptr;
     int ecc_level = 0;                             // RS41, DFM09
-    int opt = 0;                                   // the kind's own switch: M20 skip, dropsonde / RS92 inv, iMet-54 / Meisei ecc, LMS6 vit
+    int opt = 0;                                   // the kind's own switch: M20 skip, dropsonde / RS92 inv, iMet-54 / Meisei ecc, LMS6 vit, MRZ classify (not -R)
+    int opt2 = 0;                                  // MRZ: --ofs
     SoftinArgs args{};
     hipStream_t stream = nullptr;                  // the consumer's own, made by its first call (softin_enqueue): behind the modem's streams, in the order of use
     void *d_state = nullptr;                       // the channels between calls
@@ -806,7 +848,7 @@ struct sonde_softin_dev {
     SoftinMeta *d_meta = nullptr; Pinned<SoftinMeta> h_meta;
     // SONDE_LMS6: the channels of a relaunch, the block length each channel has on the device, the decoders' tallies so far
     int l6_auto = 0; int *d_l6_list = nullptr; Pinned<int> h_l6_list, h_l6_len; std::vector<int> l6_len; std::vector<int64_t> l6_ok;
-    // LMS6 / RS92 / iMet-54 / Meisei: a host decoder per channel (what a sonde collects — calibration rows, configuration words, counters — is per channel)
+    // LMS6 / RS92 / iMet-54 / Meisei / MRZ / MTS01: a host decoder per channel (what a sonde collects — calibration rows, configuration words, counters — is per channel)
     std::vector<void *> dec; void (*dec_free)(void *) = nullptr;
     std::vector<unsigned char> q;                  // the records not yet fetched, in the form the kind's tally queues
     long long frames_total = 0, ecc_ok_total = 0, repaired_total = 0, symbols_total = 0, dropped = 0;
@@ -863,6 +905,12 @@ static void launch_imet54(sonde_softin_dev *s, const SoftinArgs &a, int nblocks,
 }
 static void launch_meisei(sonde_softin_dev *s, const SoftinArgs &a, int nblocks, hipStream_t st) {
     softin_launch_staged(k_softin_meisei, SoftinMeiseiArgs{a, s->chan<SoftinMeiseiChan>(), s->recs<SoftinMeiseiRec>(), 0, s->opt}, nblocks, st);
+}
+static void launch_mrz(sonde_softin_dev *s, const SoftinArgs &a, int nblocks, hipStream_t st) {
+    softin_launch_staged(k_softin_mrz, SoftinMrzArgs{a, s->chan<SoftinMrzChan>(), s->recs<SoftinMrzRec>(), 0, s->opt, s->opt2}, nblocks, st);
+}
+static void launch_mts01(sonde_softin_dev *s, const SoftinArgs &a, int nblocks, hipStream_t st) {
+    softin_launch_staged(k_softin_mts01, SoftinMts01Args{a, s->chan<SoftinMts01Chan>(), s->recs<SoftinMts01Rec>(), 0}, nblocks, st);
 }
 static void launch_drop(sonde_softin_dev *s, const SoftinArgs &a, int nblocks, hipStream_t st) {
     const SoftinDropArgs d{a, s->chan<SoftinDropChan>(), s->recs<DropFrame>(), s->opt};
@@ -926,16 +974,28 @@ static void tally_meisei(sonde_softin_dev *s, const SoftinMeiseiRec &r) {
     if (!bad) s->ecc_ok_total++;
     if (fixed) { s->repaired_total++; s->symbols_total += fixed; }
 }
+static void tally_mrz(sonde_softin_dev *s, const SoftinMrzRec &r) {
+    if (r.channel < 0 || r.channel >= s->C) return;
+    s->queue(r); s->frames_total++;
+    if (r.crc_ok) s->ecc_ok_total++;
+}
+static void tally_mts01(sonde_softin_dev *s, const SoftinMts01Rec &r) {
+    if (r.channel < 0 || r.channel >= s->C) return;
+    s->queue(r); s->frames_total++;
+    if (r.crc_ok) s->ecc_ok_total++;
+}
 
 static const SoftinKind *softin_kind(const int type) {
     static const SoftinKind rs41{0, launch_rs41, tally_rs41}, dfm{sizeof(sonde_dfm_frame_t), launch_dfm, tally_all<sonde_dfm_frame_t, tally_dfm>},
         m10{sizeof(sonde_m10_frame_t), launch_m10, tally_all<sonde_m10_frame_t, tally_m10>}, m20{sizeof(sonde_m20_frame_t), launch_m20, tally_all<sonde_m20_frame_t, tally_m20>},
         drop{sizeof(DropFrame), launch_drop, tally_all<DropFrame, tally_drop>}, lms6{sizeof(Lms6Block), launch_lms6, nullptr},
         rs92{sizeof(SoftinRs92Rec), launch_rs92, tally_all<SoftinRs92Rec, tally_rs92>}, imet54{sizeof(SoftinImet54Rec), launch_imet54, tally_all<SoftinImet54Rec, tally_imet54>},
-        meisei{sizeof(SoftinMeiseiRec), launch_meisei, tally_all<SoftinMeiseiRec, tally_meisei>};
+        meisei{sizeof(SoftinMeiseiRec), launch_meisei, tally_all<SoftinMeiseiRec, tally_meisei>},
+        mrz{sizeof(SoftinMrzRec), launch_mrz, tally_all<SoftinMrzRec, tally_mrz>}, mts01{sizeof(SoftinMts01Rec), launch_mts01, tally_all<SoftinMts01Rec, tally_mts01>};
     switch (type) {
         case SONDE_RS41: return &rs41;     case SONDE_DFM09: return &dfm;   case SONDE_M10: return &m10;       case SONDE_M20: return &m20;       case SONDE_RD94RD41: return &drop;
         case SONDE_LMS6: return &lms6;     case SONDE_RS92: return &rs92;   case SONDE_IMET54: return &imet54; case SONDE_MEISEI: return &meisei;
+        case SONDE_MRZ: return &mrz;       case SONDE_MTS01: return &mts01;
     }
     return nullptr;
 }
@@ -1113,6 +1173,33 @@ int sonde_softin_dev_create_meisei(int32_t n_channels, const sonde_meisei_opts_t
     return softin_created(s, ok, out);
 }
 
+int sonde_softin_dev_create_mrz(int32_t n_channels, const sonde_mrz_opts_t *opts, int32_t invert_stream, sonde_softin_dev_t **out) {
+    if (!out || n_channels < 1 || !opts) return SONDE_E_ARG;
+    if (const int rc = softin_probe(opts, sonde_mrz_dec_create, sonde_mrz_dec_destroy)) return rc;
+    sonde_softin_dev *s = nullptr;
+    SoftinMrzChan c; memset((void *)&c, 0, sizeof c);
+    c.inv = opts->inv ? 1 : 0; c.bitfrm_len = MRZ_MAXBITS;
+    // frames a call can hold over all channels (sonde_fsk.h): a channel completes one per 44 + 2 (384 - 22) = 768 half symbols at the most, so seven in two seconds
+    // at 2400; a second normally completes three at the most
+    if (const int rc = softin_new(n_channels, SONDE_MRZ, 8, 3, 0.82f, invert_stream, &c, sizeof c, &s)) return rc;
+    s->opt = opts->raw == 2 ? 0 : 1;                                                           // -R: the reference never looks at the bytes (mp3h1mod.c:793-797)
+    s->opt2 = opts->bits_ofs_given ? opts->bits_ofs : 8;
+    s->args.opt_auto = opts->aut ? 1 : 0;
+    const bool ok = softin_decoders<sonde_mrz_dec_t, sonde_mrz_opts_t, sonde_mrz_dec_destroy>(s, opts, sonde_mrz_dec_create) == 0;
+    return softin_created(s, ok, out);
+}
+
+int sonde_softin_dev_create_mts01(int32_t n_channels, const sonde_mts01_opts_t *opts, int32_t invert_stream, sonde_softin_dev_t **out) {
+    if (!out || n_channels < 1 || !opts) return SONDE_E_ARG;
+    if (const int rc = softin_probe(opts, sonde_mts01_dec_create, sonde_mts01_dec_destroy)) return rc;
+    sonde_softin_dev *s = nullptr;
+    SoftinMts01Chan c; memset((void *)&c, 0, sizeof c);
+    // frames a call can hold over all channels (sonde_fsk.h): a channel completes one per 32 + 1048 = 1080 symbols at the most; a frame a second and channel
+    if (const int rc = softin_new(n_channels, SONDE_MTS01, 4, 1, 0.8f, invert_stream, &c, sizeof c, &s)) return rc;
+    const bool ok = softin_decoders<sonde_mts01_dec_t, sonde_mts01_opts_t, sonde_mts01_dec_destroy>(s, opts, sonde_mts01_dec_create) == 0;
+    return softin_created(s, ok, out);
+}
+
 int sonde_softin_dev_rs92_load_ephemeris(sonde_softin_dev_t *s, const char *path) {
     if (!s || s->type != SONDE_RS92 || !path) return SONDE_E_ARG;
     for (int c = 0; c < s->C; c++) { const int rc = sonde_rs92_dec_load_ephemeris(s->decoder<sonde_rs92_dec_t>(c), path); if (rc) return rc; }
@@ -1281,9 +1368,9 @@ int sonde_softin_dev_push_device(sonde_softin_dev_t *s, const float *d_soft, int
 }  // extern "C"
 
 // Every fetch call: up to max of the queued records Q of a consumer of `type`, each through conv into out[i].  A consumer of another kind has no such records; the
-// calls of the kinds whose records carry a text made at fetch time (RS92, iMet-54, Meisei) and of M20 say so (SONDE_E_ARG), and so does every call on a consumer
-// of one of the three text kinds; the older calls on the older kinds return an empty queue.
-static bool softin_text_kind(const int t) { return t == SONDE_RS92 || t == SONDE_IMET54 || t == SONDE_MEISEI; }
+// calls of the kinds whose records carry a text made at fetch time (RS92, iMet-54, Meisei, MRZ, MTS01) and of M20 say so (SONDE_E_ARG), and so does every call on a
+// consumer of one of the five text kinds; the older calls on the older kinds return an empty queue.
+static bool softin_text_kind(const int t) { return t == SONDE_RS92 || t == SONDE_IMET54 || t == SONDE_MEISEI || t == SONDE_MRZ || t == SONDE_MTS01; }
 // -> how many records of `rec` bytes this call takes from the front of the queue, or the error
 static int softin_fetch_count(sonde_softin_dev *s, const int type, const bool have_out, const int32_t max, const size_t rec) {
     if (!s) return SONDE_E_ARG;
@@ -1348,6 +1435,24 @@ int sonde_softin_dev_fetch_meisei(sonde_softin_dev_t *s, sonde_meisei_softin_t *
         for (int k = 0; k < MEISEI_BLOCKS; k++) { o.block_err[k] = r.block_err[k]; o.err_frm += r.block_err[k] >= 0xE; o.err_blks += r.block_err[k] != 0; }
         memcpy(o.bits, r.bits, sizeof o.bits);
         o.text_len = sonde_meisei_dec_decoded(s->decoder<sonde_meisei_dec_t>(r.channel), r.bits, r.block_err, o.text, sizeof o.text);
+        if (o.text_len < 0) o.text[0] = 0;
+    });
+}
+int sonde_softin_dev_fetch_mrz(sonde_softin_dev_t *s, sonde_mrz_softin_t *out, int32_t max) {
+    return softin_fetch<SoftinMrzRec>(s, SONDE_MRZ, out, max, [s](const SoftinMrzRec &r, sonde_mrz_softin_t &o) {
+        // print_frame from the device's bits and the device's CRC verdict
+        o.channel = r.channel; o.nbits = r.nbits; o.inv = r.inv; o.crc_ok = r.crc_ok; o.crclen = r.crclen; o.mv = r.mv; o.hdr_bit = r.hdr_bit;
+        memcpy(o.bits, r.bits, sizeof o.bits);
+        o.text_len = sonde_mrz_dec_decoded(s->decoder<sonde_mrz_dec_t>(r.channel), r.bits, r.nbits, r.crc_ok, o.text, sizeof o.text);
+        if (o.text_len < 0) o.text[0] = 0;
+    });
+}
+int sonde_softin_dev_fetch_mts01(sonde_softin_dev_t *s, sonde_mts01_softin_t *out, int32_t max) {
+    return softin_fetch<SoftinMts01Rec>(s, SONDE_MTS01, out, max, [s](const SoftinMts01Rec &r, sonde_mts01_softin_t &o) {
+        // print_frame from the device's bytes, CRC value and verdict
+        o.channel = r.channel; o.crcval = r.crcval; o.crcdat = r.crcdat; o.crc_ok = r.crc_ok; o.mv = r.mv; o.hdr_bit = r.hdr_bit;
+        memcpy(o.bytes, r.bytes, sizeof o.bytes);
+        o.text_len = sonde_mts01_dec_decoded(s->decoder<sonde_mts01_dec_t>(r.channel), r.bytes, r.crcval, r.crc_ok, o.text, sizeof o.text);
         if (o.text_len < 0) o.text[0] = 0;
     });
 }

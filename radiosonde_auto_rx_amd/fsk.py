@@ -81,9 +81,34 @@ class MeiseiSoftinRec(C.Structure):
 # auto_rx's `meisei100mod --softin --json --ptu --ecc` (auto_rx/autorx/decode.py:1343-1379)
 MEISEI_DEFAULTS = dict(ecc=1, json=1, ptu=1)
 
+MRZ_TEXT_MAX = 1024
+
+
+class MrzSoftinRec(C.Structure):
+    """sonde_mrz_softin_t (include/sonde_fsk.h)"""
+    _fields_ = [("channel", C.c_int32), ("nbits", C.c_int32), ("inv", C.c_int32), ("crc_ok", C.c_int32), ("crclen", C.c_int32), ("mv", C.c_float),
+                ("hdr_bit", C.c_uint64), ("text_len", C.c_int32), ("bits", C.c_uint8 * 52), ("text", C.c_char * MRZ_TEXT_MAX)]
+
+
+# auto_rx's `mp3h1mod --auto --json --softin --ptu` (auto_rx/autorx/decode.py:1256-1293)
+MRZ_DEFAULTS = dict(aut=1, json=1, ptu=1)
+
+MTS01_TEXT_MAX = 4096
+
+
+class Mts01SoftinRec(C.Structure):
+    """sonde_mts01_softin_t (include/sonde_fsk.h)"""
+    _fields_ = [("channel", C.c_int32), ("crcval", C.c_int32), ("crcdat", C.c_int32), ("crc_ok", C.c_int32), ("mv", C.c_float), ("text_len", C.c_int32),
+                ("hdr_bit", C.c_uint64), ("bytes", C.c_uint8 * 131), ("text", C.c_char * MTS01_TEXT_MAX)]
+
+
+# `mts01mod --softin --json` (auto_rx starts this decoder on IQ; the pipe is the decoder's own)
+MTS01_DEFAULTS = dict(json=1)
+
 # the kinds whose consumer is made from the options struct of their host decoder: struct (family.py), auto_rx's defaults, create call
 _OPTS_KINDS = {"rs92": ("Rs92Opts", RS92_DEFAULTS, "sonde_softin_dev_create_rs92"), "imet54": ("Imet54Opts", IMET54_DEFAULTS, "sonde_softin_dev_create_imet54"),
-               "meisei": ("MeiseiOpts", MEISEI_DEFAULTS, "sonde_softin_dev_create_meisei")}
+               "meisei": ("MeiseiOpts", MEISEI_DEFAULTS, "sonde_softin_dev_create_meisei"), "mrz": ("MrzOpts", MRZ_DEFAULTS, "sonde_softin_dev_create_mrz"),
+               "mts01": ("Mts01Opts", MTS01_DEFAULTS, "sonde_softin_dev_create_mts01")}
 
 _proto = False
 
@@ -133,6 +158,11 @@ def _lib():
         from .family import MeiseiOpts
         L.sonde_softin_dev_create_meisei.argtypes = [C.c_int32, C.POINTER(MeiseiOpts), C.c_int32, C.POINTER(C.c_void_p)]
         L.sonde_softin_dev_fetch_meisei.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+        from .family import MrzOpts, Mts01Opts
+        L.sonde_softin_dev_create_mrz.argtypes = [C.c_int32, C.POINTER(MrzOpts), C.c_int32, C.POINTER(C.c_void_p)]
+        L.sonde_softin_dev_fetch_mrz.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+        L.sonde_softin_dev_create_mts01.argtypes = [C.c_int32, C.POINTER(Mts01Opts), C.c_int32, C.POINTER(C.c_void_p)]
+        L.sonde_softin_dev_fetch_mts01.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
         _proto = True
     return L
 
@@ -242,7 +272,7 @@ class SoftinDev:
     def __init__(self, n_channels: int, *, ecc: int = 2, softinv: bool = False, inv: bool = True, auto: bool = False, kind: str = "rs41",
                  vit: int = 2, typ: int = 0, json: bool = False, raw: bool = False, gpsweek: int = 0, freq_khz: int = 0, version: str = "", skip: bool = True,
                  rs92_opts: dict | None = None, ephemeris: str | None = None, almanac: str | None = None, imet54_opts: dict | None = None,
-                 meisei_opts: dict | None = None):
+                 meisei_opts: dict | None = None, mrz_opts: dict | None = None, mts01_opts: dict | None = None):
         """kind: "rs41" (rs41mod --softin), "dfm" (dfm09mod --softin: ecc 0 / 1 = --ecc / 2 = --ecc2), "m10" (m10mod --softin), "m20" (m20mod --softin: skip = the rest of
         the second behind a frame is dropped, as m20mod does below -vvv; auto_rx runs `m20mod --json --ptu -vvv --softin -i`: skip=False; ecc, inv and auto mean nothing to it), "drop" (rd94rd41drop --softin /
         --softinv [-i]: auto_rx runs it as softinv=True, inv=False; ecc and auto are ignored) or "lms6" (lms6Xmod --softin: vit 1 = --vit / 2 = --vit2, typ 0 = auto
@@ -252,7 +282,10 @@ class SoftinDev:
         "imet54" (imet54mod --softin: imet54_opts = fields of family.Imet54Opts over auto_rx's defaults ecc 1, json 1, ptu 1, inv 1 — inv there is -i, aut is --auto, json
         implies ecc; ecc, inv and auto of this call mean nothing to it) or "meisei" (meisei100mod --softin: meisei_opts = fields of family.MeiseiOpts over auto_rx's
         defaults ecc 1, json 1, ptu 1 — json implies ecc; there is no -i: biphase-S compares neighbours, and a header counts in either polarity; ecc, inv and auto of
-        this call mean nothing to it)"""
+        this call mean nothing to it) or "mrz" (mp3h1mod --softin: mrz_opts = fields of family.MrzOpts over auto_rx's defaults aut 1, json 1, ptu 1 — inv there is
+        -i, aut is --auto, bits_ofs with bits_ofs_given is --ofs; the frame length follows the device's CRC verdict) or "mts01" (mts01mod --softin: mts01_opts =
+        fields of family.Mts01Opts over the default json 1; a header counts in either polarity and the bits are read raw, so an inverted stream needs softinv);
+        ecc, inv and auto of this call mean nothing to either"""
         from .engine import SONDE_RS41, SONDE_DFM09, SONDE_M10, SONDE_M20, SONDE_RD94RD41
         h = C.c_void_p()
         self.kind, self.ecc = kind, ecc
@@ -260,7 +293,7 @@ class SoftinDev:
             from . import family
             opts_name, defaults, create = _OPTS_KINDS[kind]
             kw = dict(defaults)
-            kw.update({"rs92": rs92_opts, "imet54": imet54_opts, "meisei": meisei_opts}[kind] or {})
+            kw.update({"rs92": rs92_opts, "imet54": imet54_opts, "meisei": meisei_opts, "mrz": mrz_opts, "mts01": mts01_opts}[kind] or {})
             if isinstance(kw.get("version"), str):
                 kw["version"] = kw["version"].encode()
             o = getattr(family, opts_name)(**kw)
@@ -393,7 +426,7 @@ class SoftinDev:
         """RS92 consumers: an SEM almanac (rs92mod -a) for every channel's decoder"""
         _chk(_lib().sonde_softin_dev_rs92_load_almanac(self._h, os.fsencode(path)))
 
-    def _fetch_text(self, call: str, rec, max_frames: int, fields):
+    def _fetch_text(self, call: str, rec, max_frames: int, fields, encoding: str = "utf-8"):
         """the records whose text is made at fetch time: the named fields (byte arrays as bytes) and text"""
         buf = (rec * max_frames)()
         n = _chk(getattr(_lib(), call)(self._h, buf, max_frames))
@@ -401,7 +434,7 @@ class SoftinDev:
         for r in buf[:n]:
             d = {k: getattr(r, k) for k in fields}
             d.update({k: bytes(v) for k, v in d.items() if isinstance(v, C.Array)})
-            d["text"] = r.text[:max(r.text_len, 0)].decode()
+            d["text"] = r.text[:max(r.text_len, 0)].decode(encoding)
             out.append(d)
         return out
 
@@ -421,6 +454,19 @@ class SoftinDev:
         0xE uncorrectable), err_frm / err_blks (blocks 0xE / 0xF, blocks not 0), mv (with its sign), hdr_bit (half symbols read when the header matched), bits =
         the 600 frame bits behind BCH in 75 bytes, MSB first, text = what `meisei100mod` prints for it from the device's bits and verdicts"""
         return self._fetch_text("sonde_softin_dev_fetch_meisei", MeiseiSoftinRec, max_frames, ("channel", "block_err", "err_frm", "err_blks", "mv", "hdr_bit", "bits"))
+
+    def fetch_mrz(self, max_frames: int = 1024):
+        """MRZ consumers: a dict per completed frame — channel, nbits (408 ECEF / 384 lat / lon: the length in effect for the frame), inv (polarity in effect),
+        crc_ok / crclen (the device's verdict and the 42 / 45 bytes it covers; 0 with -R), mv (with its sign), hdr_bit (half symbols read when the header matched),
+        bits = the frame bits from the header's first in 52 bytes, MSB first, text = what `mp3h1mod` prints for it from the device's bits and verdict"""
+        return self._fetch_text("sonde_softin_dev_fetch_mrz", MrzSoftinRec, max_frames, ("channel", "nbits", "inv", "crc_ok", "crclen", "mv", "hdr_bit", "bits"))
+
+    def fetch_mts01(self, max_frames: int = 256):
+        """MTS01 consumers: a dict per completed frame — channel, crcval / crcdat / crc_ok (the device's CRC-16, the stored one, the verdict), mv (with its sign),
+        hdr_bit (symbols read when the header matched), bytes = the 131 frame bytes, text = what `mts01mod` prints for it from the device's bytes and verdict (the
+        frame's own characters are part of it, whatever a damaged frame holds: a character per byte, latin-1)"""
+        return self._fetch_text("sonde_softin_dev_fetch_mts01", Mts01SoftinRec, max_frames, ("channel", "crcval", "crcdat", "crc_ok", "mv", "hdr_bit", "bytes"),
+                                encoding="latin-1")
 
     def counts(self):
         v = [C.c_int64(0) for _ in range(5)]

@@ -31,7 +31,14 @@ meisei_symbols) at sigma 0.3, repeated.  A push is the kernel and the copies of 
 (text_ms).  Beside it the host tier (sonde_meisei_dec_push_soft, one thread) on the same stream in the same run.  No speed threshold: the rows are the measured pair and
 the 9.6 KB of soft decisions per channel and second that stay on the device.
 
-    python tools/bench_softin.py [--kind lms6|m20|rs92|imet54|meisei|all] [--channels 1,64,341,1024] [--pushes 39] [--vit 2] [--typ 0] [--out profiles/softin_bench.json]"""
+--kind mrz, --kind mts01 (or all): the two CRC-only consumers (SoftinDev(kind="mrz"): k_softin_mrz, auto_rx's form `mp3h1mod --auto --json --softin --ptu`;
+SoftinDev(kind="mts01"): k_softin_mts01, `mts01mod --softin --json`), each with its CRC-16 on the wave — N channels x one second per push in device memory (MRZ: 2399 half
+symbols of tools/synth.py mrz_symbols, two copies of the frame a second; MTS01: 1200 symbols of mts01_onair_bits, a frame a second), a 13 s stream at sigma 0.3, repeated.
+A push is the kernel and the copies of its records (push_ms); the text is made when the records are fetched and is timed apart (text_ms).  Beside each the host tier
+(sonde_mrz_dec_push_soft / sonde_mts01_dec_push_soft, one thread) on the same stream in the same run.  No speed threshold: the rows are the measured pair and the 9.6 / 4.8
+KB of soft decisions per channel and second that stay on the device.
+
+    python tools/bench_softin.py [--kind lms6|m20|rs92|imet54|meisei|mrz|mts01|all] [--channels 1,64,341,1024] [--pushes 39] [--vit 2] [--typ 0] [--out profiles/softin_bench.json]"""
 import argparse
 import ctypes as C
 import json
@@ -392,6 +399,103 @@ def meisei_rows(a):
     return rows
 
 
+def mrz_stream(sigma=0.3, seed=6):
+    """13 s at 2399 half symbols: two copies of a frame a second, AA AA and idle (tools/synth.py mrz_symbols), noise on everything"""
+    from tools import synth
+    rng = np.random.default_rng(seed)
+    s = 2.0 * synth.mrz_symbols(13).astype(np.float64) - 1.0
+    assert len(s) == 13 * 2399
+    return (s + rng.normal(0.0, sigma, len(s))).astype(np.float32)
+
+
+def mts01_stream(sigma=0.3, seed=7):
+    """13 s at 1200 symbols: idle, header and a frame a second (tools/synth.py mts01_onair_bits), noise on everything"""
+    from tools import synth
+    rng = np.random.default_rng(seed)
+    s = 2.0 * synth.mts01_onair_bits(13).astype(np.float64) - 1.0
+    assert len(s) == 13 * 1200
+    return (s + rng.normal(0.0, sigma, len(s))).astype(np.float32)
+
+
+# kind -> (stream, symbols a push, options, options struct (family.py), the host tier's calls, what a good frame prints, records a push can hold per channel)
+CRC_KINDS = {"mrz": (mrz_stream, 2399, dict(aut=1, json=1, ptu=1), "MrzOpts", "sonde_mrz_dec", b"[OK]", 8),
+             "mts01": (mts01_stream, 1200, dict(json=1), "Mts01Opts", "sonde_mts01_dec", b"[OK]", 4)}
+
+
+def crc_host_tier(kind, s, pushes, nch):
+    """ms per push of one channel through the kind's host tier (sonde_*_dec_push_soft), [OK] frames of one channel"""
+    from radiosonde_auto_rx_amd.engine import lib
+    from radiosonde_auto_rx_amd import family
+    _, per, opts, struct, calls, mark, _ = CRC_KINDS[kind]
+    L = lib()
+    create, destroy, push = (getattr(L, calls + sfx) for sfx in ("_create", "_destroy", "_push_soft"))
+    O = getattr(family, struct)
+    create.argtypes = [C.POINTER(O), C.POINTER(C.c_void_p)]
+    destroy.argtypes = [C.c_void_p]
+    push.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_char_p, C.c_size_t]
+    o = O(**opts)
+    decs = []
+    for _ in range(nch):
+        d = C.c_void_p()
+        assert create(C.byref(o), C.byref(d)) == 0
+        decs.append(d)
+    out = C.create_string_buffer(1 << 16)
+    walls, ok = [], 0
+    for k in range(13 + pushes):
+        p = s.ctypes.data + (k % 13) * per * 4
+        t0 = time.perf_counter()
+        for d in decs:
+            n = push(d, p, per, 0, 0, out, len(out))
+            assert n >= 0
+        dt = (time.perf_counter() - t0) * 1e3
+        if k >= 13:
+            walls.append(dt / nch)
+            ok += out.raw[:n].count(mark)
+    for d in decs:
+        destroy(d)
+    return walls, ok
+
+
+def crc_rows(a, kind):
+    import torch
+    from radiosonde_auto_rx_amd.fsk import SoftinDev
+    stream, per, opts, _, _, mark, per_cap = CRC_KINDS[kind]
+    s = stream()
+    hw, hok = crc_host_tier(kind, s, a.pushes, a.host_channels)
+    host_ms = statistics.median(hw)
+    rows = []
+    for nch in [int(c) for c in a.channels.split(",")]:
+        d = torch.from_numpy(s).to("cuda").repeat(nch, 1).contiguous()
+        torch.cuda.synchronize()
+        sf = SoftinDev(nch, kind=kind, **{kind + "_opts": dict(opts)})
+        fetch = getattr(sf, "fetch_" + kind)
+        walls, texts, ok, frames, good = [], [], 0, 0, 0
+        for k in range(13 + a.pushes):
+            p = d.data_ptr() + (k % 13) * per * 4
+            t0 = time.perf_counter()
+            sf.push_device(p, d.shape[1], per)
+            t1 = time.perf_counter()
+            recs = fetch(per_cap * nch + 16)
+            t2 = time.perf_counter()
+            if k >= 13:
+                walls.append((t1 - t0) * 1e3); texts.append((t2 - t1) * 1e3)
+                frames += len(recs)
+                ok += sum(r["text"].count(mark.decode()) for r in recs if r["channel"] == 0)
+                good += sum(r["crc_ok"] for r in recs)
+        cnt = sf.counts()
+        sf.close()
+        wall, text = statistics.median(walls), statistics.median(texts)
+        row = {"kind": kind, "channels": nch, "pushes": a.pushes, "push_ms": round(wall, 3), "min_ms": round(min(walls), 3), "max_ms": round(max(walls), 3),
+               "text_ms": round(text, 3), "text_min_ms": round(min(texts), 3), "text_max_ms": round(max(texts), 3), "push_plus_text_ms": round(wall + text, 3),
+               "channel_seconds_per_second": round(nch * 1e3 / (wall + text), 1), "frames": frames, "crc_ok": good, "ok_channel0": ok, "dropped": cnt["dropped"],
+               "soft_bytes_per_channel_second_left_on_device": per * 4,
+               "host_tier_ms_per_channel_second": round(host_ms, 4), "host_tier_min_ms": round(min(hw), 4), "host_tier_max_ms": round(max(hw), 4),
+               "host_tier_ms_for_these_channels": round(host_ms * nch, 2), "host_tier_ok_one_channel": hok}
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    return rows
+
+
 def m20_rows(a):
     import torch
     from radiosonde_auto_rx_amd.fsk import SoftinDev
@@ -429,7 +533,7 @@ def m20_rows(a):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--kind", default="lms6", choices=["lms6", "m20", "rs92", "imet54", "meisei", "all"])
+    ap.add_argument("--kind", default="lms6", choices=["lms6", "m20", "rs92", "imet54", "meisei", "mrz", "mts01", "all"])
     ap.add_argument("--channels", default="1,64,341,1024")
     ap.add_argument("--pushes", type=int, default=39)
     ap.add_argument("--vit", type=int, default=2)
@@ -439,7 +543,8 @@ def main():
     a = ap.parse_args()
     assert a.pushes >= 30
     rows = (lms6_rows(a) if a.kind in ("lms6", "all") else []) + (m20_rows(a) if a.kind in ("m20", "all") else []) + (rs92_rows(a) if a.kind in ("rs92", "all") else []) \
-        + (imet54_rows(a) if a.kind in ("imet54", "all") else []) + (meisei_rows(a) if a.kind in ("meisei", "all") else [])
+        + (imet54_rows(a) if a.kind in ("imet54", "all") else []) + (meisei_rows(a) if a.kind in ("meisei", "all") else []) \
+        + (crc_rows(a, "mrz") if a.kind in ("mrz", "all") else []) + (crc_rows(a, "mts01") if a.kind in ("mts01", "all") else [])
     if a.out:
         kinds = {r["kind"] for r in rows}
         if os.path.exists(a.out):
