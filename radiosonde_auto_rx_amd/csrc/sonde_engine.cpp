@@ -45,6 +45,10 @@ struct sonde_engine {
     // DFM / M10 block codes of the hits on the device (k_dfm_hits / k_m10_hits, sonde_softin_dev.hip): decoded frames per ring slot, {done, ticket}, M10's bit characters per channel
     sonde_dfm_frame_t *d_dfm_out = nullptr; sonde_m10_frame_t *d_m10_out = nullptr; unsigned *d_blk_done = nullptr; char *d_m10_bits = nullptr;
     std::vector<sonde_dfm_frame_t> h_dfm; std::vector<sonde_m10_frame_t> h_m10; bool soft_lazy = false; unsigned soft_lazy_start = 0;
+    // generic engines whose hits are decoded on the device (sonde_engine_set_family; k_family_hits, sonde_family_hits.hip): the kind, its --ecc, a record per ring
+    // slot, what the kind's kernel reads besides the hits; d_blk_done is its {done, ticket}
+    int fam_kind = 0, fam_ecc = 0; sonde_family_hit_t *d_fam_out = nullptr; const uint32_t *d_fam_tab = nullptr; const uint8_t *d_fam_gf = nullptr;
+    std::vector<sonde_family_hit_t> h_fam;
     uint32_t *d_ecc_list = nullptr; unsigned *d_ecc_cnt = nullptr;     // two work lists of max_frames record slots, alternating per call; {count[2], done[2]}
     hipEvent_t ev_a[4] = {}, ev_b[4] = {}, ev_if[4] = {};      // per call: decimator done (A), records complete (B / E), y ring read (B: IF chain done)
     Pinned<unsigned> h_count;          // mapped: frame counter snapshot after each call's framesync
@@ -199,11 +203,21 @@ extern "C" void sonde_launch_dfm_hits(const FrameRec *frames, const float *soft,
                                       int ecc_level, int grid, hipStream_t s);
 extern "C" void sonde_launch_m10_hits(const FrameRec *frames, const float *soft, const float *soft1, int chk3, int nbits, int max_frames, const unsigned *fcount, unsigned *done,
                                       char *chan_bits, sonde_m10_frame_t *out, int grid, hipStream_t s);
+extern "C" void sonde_launch_family_hits(int kind, int ecc, const FrameRec *frames, const int *nbits_direct, const float *soft, long long stride, int max_frames,
+                                         const unsigned *fcount, unsigned *done, const uint32_t *tab, const uint8_t *gf, sonde_family_hit_t *out, int grid, hipStream_t s);
+int sonde_family_tables(DevMem &mem, int kind, const uint32_t **tab, const uint8_t **gf);
 static bool blockcodes_on_device(const sonde_engine *e);
-// behind every frame-sync launch: the block codes of the hits it has queued (DFM Hamming(8,4), M10 checksum), on the same stream
+// a generic engine whose hits are decoded behind the frame sync (sonde_engine_set_family), with the switch of sonde_engine_set_device_ecc as it stands
+static bool family_on_device(const sonde_engine *e) { return e->dev_ecc && e->fam_kind && e->d_soft && e->d_blk_done && e->d_fam_out; }
+// behind every frame-sync launch: the block codes of the hits it has queued (DFM Hamming(8,4), M10 checksum, the generic family's per-hit decoders), on the same stream
 static void launch_blockcodes(sonde_engine *e) {
-    if (!blockcodes_on_device(e)) return;
     const int grid = std::max(1, std::min(e->cfg.n_channels, 1024));
+    if (family_on_device(e)) {
+        sonde_launch_family_hits(e->fam_kind, e->fam_ecc, e->d_frames, nullptr, e->d_soft, (long long)e->nbits, e->max_frames, e->d_fcount, e->d_blk_done, e->d_fam_tab,
+                                 e->d_fam_gf, e->d_fam_out, grid, e->stream_b);
+        return;
+    }
+    if (!blockcodes_on_device(e)) return;
     if (e->cfg.sonde_type == SONDE_DFM09)
         sonde_launch_dfm_hits(e->d_frames, e->d_soft, e->nbits, e->max_frames, e->d_fcount, e->d_blk_done, e->d_dfm_out, e->cfg.ecc_level, grid, e->stream_b);
     else
@@ -1445,6 +1459,40 @@ int sonde_engine_fetch_hits(sonde_engine_t *e, sonde_hit_t *out, int32_t max, in
         out[i].nbits = e->cfg.sonde_type == SONDE_RS41 ? 8 * (r.nbytes - 8) : r.nbytes;      // RS41 records count bytes incl. the 8 header bytes
     }
     return n;                                  // frames dropped by a full queue: sonde_engine_overflowed()
+}
+
+int sonde_engine_set_family(sonde_engine_t *e, int32_t kind, int32_t ecc) {
+    // the descriptions of family.FAMILY: soft bits of a hit, symbol length
+    const int nb = kind == SONDE_MEISEI ? 1152 : kind == SONDE_IMET54 ? 2200 : kind == SONDE_MTS01 ? 1048 : kind == SONDE_RS92 ? 2340 : 0, sl = kind == SONDE_RS92 ? 2 : 1;
+    if (!e || !e->groups.empty() || e->is_group || e->front_only || e->cfg.sonde_type != SONDE_GENERIC || !e->cfg.keep_soft || !e->d_soft || e->call > 0 || e->fam_kind) return SONDE_E_ARG;
+    if (!nb || e->nbits != nb || e->symlen != sl || (kind == SONDE_RS92 && !ecc)) return SONDE_E_ARG;      // (RS92's consumer always corrects)
+    if (!e->d_fam_out) TRY(e->mem.dalloc(&e->d_fam_out, (size_t)e->max_frames));
+    if (!e->d_blk_done) TRY(e->mem.dalloc(&e->d_blk_done, 2));
+    TRY(sonde_family_tables(e->mem, kind, &e->d_fam_tab, &e->d_fam_gf));
+    e->fam_kind = kind; e->fam_ecc = ecc ? 1 : 0;
+    return 0;
+}
+
+int sonde_engine_fetch_family(sonde_engine_t *e, sonde_family_hit_t *out, int32_t max, int32_t finish) {
+    if (!e || !e->groups.empty() || !out || max < 0 || !e->fam_kind) return SONDE_E_ARG;
+    if (finish) launch_framesync(e, 1);
+    std::vector<FrameRec> recs;
+    const bool on_dev = family_on_device(e);
+    const int n = collect_records(e, 0, recs, nullptr, max);
+    if (n < 0) return n;
+    // the hits were decoded on the device behind the frame sync (k_family_hits): only the records come over — the soft bits stay where they are until
+    // sonde_engine_fetch_soft asks for them (a hit that was not decoded gets its host decode that way)
+    const unsigned start = e->read_idx - (unsigned)n;
+    e->last_n = n; e->soft_lazy = true; e->soft_lazy_start = start;
+    if (on_dev && copy_decoded(e, e->d_fam_out, e->h_fam, start, n, 1)) return SONDE_E_NOGPU;
+    for (int h = 0; h < n; h++) {
+        const FrameRec &r = recs[h];
+        sonde_family_hit_t &o = out[h];
+        if (on_dev) o = e->h_fam[h];
+        else { memset(&o, 0, sizeof o); o.channel = r.channel; o.kind = e->fam_kind; o.nbits = r.nbytes; o.mv = r.mv; }      // device decoding is switched off: the host's
+        o.mv_pos = rel_pos(e, r);
+    }
+    return n;                                  // hits dropped by a full queue: sonde_engine_overflowed()
 }
 
 int sonde_engine_set_m10_chk3(sonde_engine_t *e, int32_t on) {

@@ -363,6 +363,34 @@ class Engine:
             _chk(lib().sonde_engine_fetch_soft(self._h, soft.ctypes.data_as(C.c_void_p), k))
         return [dict(channel=buf[i].channel, nbits=buf[i].nbits, mv=buf[i].mv, mv_pos=buf[i].mv_pos, soft=soft[i, :buf[i].nbits].copy()) for i in range(k)]
 
+    def set_family(self, kind: str, ecc: int = 1):
+        """Generic engines carrying Meisei, iMet-54, MTS01 or RS92 (kind = a key of family.DEVICE_KINDS, the engine created with that FAMILY description): decode
+        every hit on the device behind the frame sync; results through fetch_family().  Before the first process call."""
+        from .family import DEVICE_KINDS
+        if kind not in DEVICE_KINDS:
+            raise SondeError(f"set_family: hits of type {kind} are not decoded on the device")
+        f = lib().sonde_engine_set_family
+        f.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
+        _chk(f(self._h, DEVICE_KINDS[kind], int(ecc)))
+
+    def fetch_family(self, finish: bool = False, max_hits: int | None = None):
+        """After set_family(): the hits completed so far as decoded records (dicts of sonde_family_hit_t: channel, kind, nbits, decoded, mv_pos, mv, v, aux, data),
+        for FamilyDecoder.decoded().  A record with decoded = 0 carries its soft bits ("soft") for the host decode; max_hits: the rest stays queued."""
+        from .family import FamilyHit, family_hit_dict
+        n = self._max_frames if max_hits is None else int(max_hits)
+        buf = (FamilyHit * max(n, 1))()
+        f = lib().sonde_engine_fetch_family
+        f.argtypes = [C.c_void_p, C.POINTER(FamilyHit), C.c_int32, C.c_int32]
+        k = _chk(f(self._h, buf, n, int(finish)))
+        recs = [family_hit_dict(buf[i]) for i in range(k)]
+        if any(not r["decoded"] for r in recs):
+            soft = np.zeros((k, self.nbits), np.float32)
+            _chk(lib().sonde_engine_fetch_soft(self._h, soft.ctypes.data_as(C.c_void_p), k))
+            for i, r in enumerate(recs):
+                if not r["decoded"]:
+                    r["soft"] = soft[i, :r["nbits"]].copy()
+        return recs
+
     def fetch_mxx(self, finish: bool = False, verbose: int = 1):
         """M10 / M20 engines: frames as dicts (bytes, checksum verdicts, the `m10mod -r [-v]` / `m20mod -r [-v]` text line)."""
         m20 = self.sonde == "m20"

@@ -85,6 +85,40 @@ FAMILY["LMSX"] = dict(FAMILY["LMS6"], generic=dict(FAMILY["LMS6"]["generic"], sl
 LMS_BASE = {"LMSX": "LMS6"}                      # receiver bookkeeping: the scanner's name of a sonde's type
 
 
+# The kinds whose hits a generic engine decodes on the device (sonde_engine_set_family, include/sonde_hip.h): FAMILY key -> SONDE_* kind.  LMS6 / LMS-X and MRZ
+# keep the host path.
+DEVICE_KINDS = {"MEISEI": 11, "IMET5": 54, "MTS01": 71, "RS92": 92}
+
+
+class FamilyHit(C.Structure):
+    """sonde_family_hit_t (include/sonde_hip.h)"""
+    _fields_ = [("channel", _I), ("kind", _I), ("nbits", _I), ("decoded", _I), ("mv_pos", C.c_uint32), ("mv", C.c_float), ("v", _I * 6), ("aux", C.c_uint8 * 12),
+                ("data", C.c_uint8 * 240)]
+
+
+def family_hit_dict(r: FamilyHit) -> dict:
+    return dict(channel=r.channel, kind=r.kind, nbits=r.nbits, decoded=r.decoded, mv_pos=r.mv_pos, mv=r.mv, v=list(r.v), aux=bytes(r.aux), data=bytes(r.data))
+
+
+def decode_hits_device(kind: str, hits, ecc: int = 1):
+    """The engines' per-hit device decoder (k_family_hits) on hits in host memory (sonde_family_decode_device): kind = a key of DEVICE_KINDS, hits = float32 soft-bit
+    arrays as the engine stores them, each up to the kind's frame length (a shorter one comes back with decoded = 0).  -> dicts; channel = the hit's index."""
+    nb = FAMILY[kind]["generic"]["nbits"]
+    soft = np.zeros((max(len(hits), 1), nb), np.float32)
+    n = np.zeros(max(len(hits), 1), np.int32)
+    for i, h in enumerate(hits):
+        h = np.asarray(h, np.float32)
+        soft[i, :len(h)] = h
+        n[i] = len(h)
+    out = (FamilyHit * max(len(hits), 1))()
+    fn = lib().sonde_family_decode_device
+    fn.argtypes = [_I, _I, C.c_void_p, C.c_int64, C.c_void_p, _I, C.POINTER(FamilyHit)]
+    rc = fn(DEVICE_KINDS[kind], int(ecc), soft.ctypes.data, nb, n.ctypes.data, len(hits), out)
+    if rc < 0:
+        raise SondeError(f"sonde_family_decode_device: {lib().sonde_strerror(rc).decode()} ({rc})")
+    return [family_hit_dict(out[i]) for i in range(len(hits))]
+
+
 class FamilyDecoder:
     """one decoder object of type `typ` (a key of FAMILY): state lives across hits like the reference's gpx_t"""
 
@@ -145,6 +179,31 @@ class FamilyDecoder:
             k = self._fn(self._h, soft.ctypes.data, n, self._buf, len(self._buf))
         if k < 0:
             raise SondeError(f"{self.typ}: decoder call failed ({k})")
+        return self._buf.raw[:k].decode(errors="replace")
+
+    def decoded(self, rec: dict, if_sr: int = 48000) -> str:
+        """one dict of Engine.fetch_family(): the characters the reference decoder prints for that hit, from the device's bytes and verdicts (no block code runs
+        here).  A record the device did not decode (decoded = 0: a hit cut short by the end of input, or device decoding switched off) goes through hit() on its
+        soft bits."""
+        if not rec["decoded"]:
+            return self.hit(rec, if_sr)
+        L, p, d, v = lib(), self.f["prefix"], rec["data"], rec["v"]
+        if self.typ == "MEISEI":
+            L.sonde_meisei_dec_decoded.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_size_t]
+            k = L.sonde_meisei_dec_decoded(self._h, d[:75], rec["aux"], self._buf, len(self._buf))
+        elif self.typ == "IMET5":
+            L.sonde_imet54_dec_decoded.argtypes = [C.c_void_p, C.c_char_p] + [_I] * 5 + [C.c_char_p, C.c_size_t]
+            k = L.sonde_imet54_dec_decoded(self._h, d[:108], v[0], v[1], v[2], v[3], v[4], self._buf, len(self._buf))
+        elif self.typ == "MTS01":
+            L.sonde_mts01_dec_decoded.argtypes = [C.c_void_p, C.c_char_p, _I, _I, C.c_char_p, C.c_size_t]
+            k = L.sonde_mts01_dec_decoded(self._h, d[:131], v[0], v[2], self._buf, len(self._buf))
+        elif self.typ == "RS92":
+            L.sonde_rs92_dec_corrected.argtypes = [C.c_void_p, C.c_char_p, _I, C.c_char_p, C.c_size_t]
+            k = L.sonde_rs92_dec_corrected(self._h, d[:240], v[0], self._buf, len(self._buf))
+        else:
+            raise SondeError(f"{self.typ}: hits of this type are not decoded on the device")
+        if k < 0:
+            raise SondeError(f"{self.typ}: sonde_{p}_dec_decoded failed ({k})")
         return self._buf.raw[:k].decode(errors="replace")
 
     def lms_type(self):

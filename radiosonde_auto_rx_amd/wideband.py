@@ -22,7 +22,7 @@ import numpy as np
 
 from .engine import Engine, snap_fq
 from .scan import Scanner
-from .family import FAMILY, LMS_BASE, FamilyDecoder
+from .family import DEVICE_KINDS, FAMILY, LMS_BASE, FamilyDecoder
 from .imet4 import Imet4Engine, Imet4Printer
 from .mk2a import Mk2aEngine, Mk2aPrinter
 from .wxr import WxrEngine, WxrPrinter
@@ -41,13 +41,16 @@ class WidebandReceiver:
     def __init__(self, sample_rate: int, *, cfreq_hz: int = 0, raster_hz: int = 10_000, span: float = 0.45, chunk: int | None = None,
                  merge_hz: float = 6_000.0, version: str = "sonde_hip", idle_s: float = 30.0, survey_s: float | None = None,
                  survey_nfft: int = 4096, dwell_s: float = 2.0, max_peaks: int = 10, snr_threshold: float = 10.0, min_distance: float = 1000.0,
-                 quantization: float = 10000.0):
+                 quantization: float = 10000.0, device_family: bool = False):
         """idle_s: a decoder that has produced no frame for that long (a false detection, a sonde that has landed) is closed and its engine
         freed; the scanner starts a new one if the signal comes back.
         survey_s: None = a scanner channel on every raster point, all the time.  A number = auto_rx's cycle instead of the raster: the spectrum
         of survey_s seconds of stream (Hann, survey_nfft points, 25 % of the band edge cropped), auto_rx's peak pick on it (snr_threshold dB over
         the median, min_distance, quantization, at most max_peaks — its defaults), then a Scanner(fq=peaks, dc=True) over the next dwell_s
-        seconds (what `dft_detect` per peak is to auto_rx), then the next survey.  Peaks that already have a decoder are not scanned again."""
+        seconds (what `dft_detect` per peak is to auto_rx), then the next survey.  Peaks that already have a decoder are not scanned again.
+        device_family: the block codes of Meisei, iMet-54, MTS01 and RS92 hits run on the device behind the frame sync (Engine.set_family) and decoded records come
+        to the host instead of soft bits; LMS6 and MRZ keep the host path either way."""
+        self.device_family = device_family
         self.sr, self.cfreq, self.merge_hz, self.version, self.idle_s = sample_rate, cfreq_hz, merge_hz, version, idle_s
         self.t = 0.0                           # stream time in seconds
         self.chunk = chunk or sample_rate // 4
@@ -142,8 +145,12 @@ class WidebandReceiver:
 
     def _family_engine(self, typ: str, fq: float):
         f = FAMILY[typ]
-        return Engine([fq], self.sr, sonde="generic", generic=f["generic"], thres=f["thres"], auto=f["auto"], keep_soft=True, lp_iq=True,
-                      max_chunk=self.chunk, max_frames=8)
+        eng = Engine([fq], self.sr, sonde="generic", generic=f["generic"], thres=f["thres"], auto=f["auto"], keep_soft=True, lp_iq=True,
+                     max_chunk=self.chunk, max_frames=8)
+        eng.device_family = self.device_family and typ in DEVICE_KINDS
+        if eng.device_family:
+            eng.set_family(typ, ecc=FAMILY[typ]["kw"].get("ecc", 1))
+        return eng
 
     def _follow_lms(self, s):
         """an LMS6 whose decoder found LMS-X blocks (or the reverse): from the next chunk on its samples go through an engine of the other description
@@ -264,9 +271,10 @@ class WidebandReceiver:
             return out
         if s["type"] in FAMILY:
             out = []
-            for h in e.fetch_hits(finish=finish):
+            on_dev = getattr(e, "device_family", False)      # the hit's block codes ran on the device: a decoded record, not soft bits
+            for h in (e.fetch_family(finish=finish) if on_dev else e.fetch_hits(finish=finish)):
                 s["frames"] += 1
-                js = FamilyDecoder.json_objects(s["telemetry"].hit(h, e.info["if_sr"]))
+                js = FamilyDecoder.json_objects(s["telemetry"].decoded(h, e.info["if_sr"]) if on_dev else s["telemetry"].hit(h, e.info["if_sr"]))
                 s["good"] = s.get("good", 0) + (1 if js else 0)
                 out += js
             return out
@@ -488,6 +496,7 @@ def main(argv=None):
     ap.add_argument("--raster", type=int, default=10_000, help="scanner raster in Hz")
     ap.add_argument("--survey", type=float, default=None, metavar="SECONDS", help="auto_rx's cycle instead of the raster: a spectrum survey of that many seconds, peak pick, a scanner channel per peak")
     ap.add_argument("--channelize", action="store_true", help="polyphase channelizer front end (256 channels at sr / 200): for streams of several Msps")
+    ap.add_argument("--device-family", action="store_true", help="decode Meisei, iMet-54, MTS01 and RS92 hits on the device (not with --channelize)")
     ap.add_argument("--rs92-ephem", help="RINEX navigation file for RS92 positions (rs92mod -e)")
     ap.add_argument("--rs92-alm", help="SEM almanac for RS92 positions (rs92mod -a)")
     ap.add_argument("dash"); ap.add_argument("sr", type=int); ap.add_argument("bits", type=int)
@@ -499,7 +508,7 @@ def main(argv=None):
         ap.error("input is `- <sr> 16` (cs16 on stdin)")
     if a.channelize and a.survey is not None:
         ap.error("--survey belongs to the raster receiver (the channelized one scans all its channels)")
-    rx = ChannelizedReceiver(a.sr, cfreq_hz=a.cfreq) if a.channelize else WidebandReceiver(a.sr, cfreq_hz=a.cfreq, raster_hz=a.raster, survey_s=a.survey)
+    rx = ChannelizedReceiver(a.sr, cfreq_hz=a.cfreq) if a.channelize else WidebandReceiver(a.sr, cfreq_hz=a.cfreq, raster_hz=a.raster, survey_s=a.survey, device_family=a.device_family)
     inp = sys.stdin.buffer
     while True:
         buf = inp.read(rx.chunk * 4)
