@@ -15,6 +15,7 @@
 #include "sonde_drop.h"
 #include "sonde_lms6.h"
 #include "sonde_rs92.h"
+#include "sonde_gps.h"
 #include "sonde_imet54.h"
 #include "sonde_meisei.h"
 #include "sonde_mrz.h"
@@ -213,6 +214,12 @@ typedef struct {
 } sonde_rs92_softin_t;
 /* frames completed by the push calls since the last fetch (per channel in stream order); returns the count (<= max) */
 int  sonde_softin_dev_fetch_rs92(sonde_softin_dev_t *s, sonde_rs92_softin_t *out, int32_t max);
+/* on != 0: fetch_rs92 makes the texts of a fetch through sonde_gps_rs92_text_batch (include/sonde_gps.h): the 4-satellite subset search of every fetched frame in
+ * one launch on the device, the winning subset alone solved by the channel's decoder.  The texts are the same; off (the state of a new consumer) nothing changes.
+ * The first call with on != 0 makes the consumer's solver (SONDE_E_NOMEM / _NOGPU as sonde_gps_dev_create); SONDE_E_ARG for another kind of consumer. */
+int  sonde_softin_dev_set_rs92_gps(sonde_softin_dev_t *s, int32_t on);
+/* the solver's counts so far (sonde_gps_stats_t, include/sonde_gps.h; all zero for a consumer that never had the switch on) */
+int  sonde_softin_dev_rs92_gps_stats(sonde_softin_dev_t *s, sonde_gps_stats_t *out);
 
 /* ---- SONDE_IMET54 consumers: `imet54mod --softin [-i] [--auto] [--ecc] ...` for every channel (auto_rx's pipe `fsk_demod --cs16 -b -10000 -u 10000 -s --stats=N 2 48000
  * 4800 - - | imet54mod --ecc --json --softin -i --ptu`, auto_rx/autorx/decode.py:1215-1250).  On the device, one wavefront per channel (imet54mod.c:1007-1063,

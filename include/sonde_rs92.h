@@ -84,6 +84,59 @@ int  sonde_rs92_dec_corrected(sonde_rs92_dec_t *d, const uint8_t frame[SONDE_RS9
  * inside; finish != 0 at end of input (a frame in progress is printed with the bytes that exist). */
 int  sonde_rs92_dec_push_soft(sonde_rs92_dec_t *d, const float *soft, int32_t n, int32_t invert, int32_t finish, char *out, size_t outlen);
 
+/* ---- the 4-satellite subset search as a job.  The default solver takes the closed-form solution of EVERY 4-satellite subset of the frame's
+ * satellites and keeps the one with the best GDOP; which subset wins is decided by + - x / sqrt on doubles alone, so another processor (the device solver,
+ * include/sonde_gps.h) can decide it bit for bit, and this decoder then computes what it prints from the ONE winning subset with the functions it always used.
+ * A job is what that decision needs: per satellite the position as sent, the position turned by the earth's rotation during the signal's run time (the host's
+ * cos / sin: transcendentals stay out of the decision) and p = pseudorange + clock correction. */
+#define SONDE_GPS_MAX_SATS 12
+typedef struct {
+    double X, Y, Z;          /* ECEF position as sent [m]                                          */
+    double x, y, z;          /* the same turned about z by kOmegaE * 0.072 s (sonde_gps_job_fill)  */
+    double p;                /* pseudorange + satellite clock correction [m]                       */
+} sonde_gps_sat_t;
+typedef struct {
+    sonde_gps_sat_t sat[SONDE_GPS_MAX_SATS];
+    int32_t n;               /* satellites: 4 .. 12 */
+    int32_t reserved;
+} sonde_gps_job_t;
+typedef struct {
+    int32_t num;             /* subsets with a closed-form solution inside the height gate (what solve() returns)                                         */
+    int32_t best;            /* the winner's index in the order ix[0] < ix[1] < ix[2] < ix[3] of the nested loops; -1: no subset with 0 < GDOP < 1000      */
+    int32_t doubt;           /* != 0: a subset came within the guard bands of a decision that goes through atan2 / sin / cos: solve this frame on the host */
+    int32_t n;               /* the job's n                                                                                                               */
+    double  gdop;            /* the winner's GDOP (0.0 when best is -1); compared as bits                                                                 */
+} sonde_gps_pick_t;
+
+/* A job from positions as sent and ranges: the rotation is the decoder's own.  SONDE_E_ARG for n outside 4 .. 12 or NULL. */
+int  sonde_gps_job_fill(sonde_gps_job_t *job, int32_t n, const double *X, const double *Y, const double *Z, const double *p);
+/* The selection by the decoder's own functions (closed form, DOP), subset after subset: the oracle of the device solver and the body of every fallback.  doubt is
+ * always 0.  SONDE_E_ARG for NULL or n outside 4 .. 12. */
+int  sonde_gps_host_solve(const sonde_gps_job_t *job, sonde_gps_pick_t *pick);
+
+/* sonde_rs92_dec_corrected in two halves around the subset search.  begin does everything up to and including the pseudoranges; it returns 1 with *job filled when
+ * the search is wanted (orbit data loaded, GPS block intact, >= 4 satellites, gps_verbose neither 2 nor 8), 0 when it is not, and holds the frame pending either
+ * way.  end finishes it: with pick == NULL, or after a 0 from begin, exactly as sonde_rs92_dec_corrected; with a pick, the winning subset alone is solved by the
+ * functions the full search uses (lat / lon / alt, DOP, velocity, satellite list and count as the full search leaves them).  A pick in doubt, or whose GDOP is not
+ * bit for bit what this decoder computes for that subset (a mismatch), is dropped and the full search runs.  SONDE_E_ARG: NULL, a second begin before end, an end
+ * without begin, an out too small for the text (the frame is finished all the same, as sonde_rs92_dec_corrected leaves it). */
+int  sonde_rs92_dec_begin(sonde_rs92_dec_t *d, const uint8_t frame[SONDE_RS92_FRAME_LEN], int32_t ec, sonde_gps_job_t *job);
+int  sonde_rs92_dec_end(sonde_rs92_dec_t *d, const sonde_gps_pick_t *pick, char *out, size_t outlen);
+/* how the last end got its position: 0 = no pick (today's path), 1 = from the pick, 2 = pick in doubt -> full search, 3 = mismatch -> full search */
+#define SONDE_GPS_VIA_HOST 0
+#define SONDE_GPS_VIA_PICK 1
+#define SONDE_GPS_VIA_DOUBT 2
+#define SONDE_GPS_VIA_MISMATCH 3
+int  sonde_rs92_dec_gps_via(const sonde_rs92_dec_t *d);
+
+/* n records in order through begin / solve / end with any solver: several records may name one decoder, and are taken in rounds (round r begins the r-th pending
+ * record of every decoder, calls solve once on the jobs of the round, ends them), so a decoder sees its frames in order.  out + i * stride receives record i's text
+ * (at most stride bytes with the NUL), len[i] its length or SONDE_E_ARG.  solve == NULL: a loop over sonde_rs92_dec_corrected.  via4 (may be NULL): four counts
+ * added to, indexed by SONDE_GPS_VIA_*.  Returns 0, SONDE_E_ARG, or the solver's error (every record is still finished, by the host search). */
+typedef int (*sonde_gps_solve_fn)(void *ctx, const sonde_gps_job_t *jobs, int32_t n, sonde_gps_pick_t *picks);
+int  sonde_gps_rs92_text_batch_with(sonde_gps_solve_fn solve, void *ctx, sonde_rs92_dec_t *const *decs, const uint8_t (*frames)[SONDE_RS92_FRAME_LEN],
+                                    const int32_t *ec, int32_t n, char *out, size_t stride, int32_t *len, int64_t via4[4]);
+
 #ifdef __cplusplus
 }
 #endif

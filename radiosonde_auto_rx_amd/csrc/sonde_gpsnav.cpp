@@ -114,6 +114,8 @@ double dist3(double X1, double Y1, double Z1, double X2, double Y2, double Z2) {
     return sqrt((X2 - X1) * (X2 - X1) + (Y2 - Y1) * (Y2 - Y1) + (Z2 - Z1) * (Z2 - Z1));
 }
 
+void rot_range_est(double X, double Y, double Z, double *x, double *y, double *z) { rot_z(X, Y, Z, kOmegaE * kRangeEst, x, y, z); }
+
 int read_sem_almanac(FILE *fp, Eph alm[33]) {      // :132-179
     char name[64];
     unsigned n, week, toa, u;

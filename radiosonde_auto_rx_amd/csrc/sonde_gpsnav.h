@@ -32,6 +32,8 @@ bool read_rinex_nav(FILE *fp, std::vector<Eph> &out);               // entries i
 
 void ecef2elli(double X, double Y, double Z, double *lat, double *lon, double *alt);
 double dist3(double X1, double Y1, double Z1, double X2, double Y2, double Z2);
+// the rotation closed_form4 / bancroft / lin_vel apply to a satellite position: about z by the earth's turn during the typical signal run time (0.072 s)
+void rot_range_est(double X, double Y, double Z, double *x, double *y, double *z);
 
 // satellite clock correction [m] (+ drift [m/s]) and ECEF position (+ velocity) at gps week / time of week
 void sat_state(unsigned short week, double tow, const Eph &e, bool with_velocity, Sat &s);

@@ -86,6 +86,9 @@ struct sonde_rs92_dec {
     // --- soft input
     float sbuf[HDRLEN]; int bufpos = -1, in_frame = 0, nsym = 0, byte_count = FRAMESTART, b8pos = 0; float s1 = 0; char bitbuf[BITS];
 
+    // --- a frame between sonde_rs92_dec_begin and _end: its text so far, its blocks' verdicts, whether a job went out
+    bool pend = false, pend_job = false; Out pend_w; int pend_ec = 0, pend_k = 0, pend_err[3] = {0, 0, 0}, gps_via = 0;
+
     sonde_rs92_dec() {
         memset(frame, 0, sizeof frame); memcpy(frame, kHeaderBytes, 6);
         memset(calibytes, 0, sizeof calibytes); memset(calfrchk, 0, sizeof calfrchk); memset(cal_f32, 0, sizeof cal_f32);
@@ -582,17 +585,64 @@ struct sonde_rs92_dec {
         return errors;
     }
 
-    void print_position(Out &w, int ec) {
-        int n = 0;
-        frnr = frame[POS_FRAMENB] + (frame[POS_FRAMENB + 1] << 8);
-        const int err1 = config_block(w);
-        const int err2 = ptu_block();
-        const int err3 = gps_time();
-        aux_block();
-        if (!err3 && (almanac || ephem)) {
-            const int k = pseudoranges();
-            if (k >= 4) n = solve(w, k);
+    // the one winning subset of a pick (include/sonde_rs92.h), solved as the loop of solve() solves it.  false: this decoder does not find the pick's GDOP
+    // for that subset bit for bit (nothing of the solution is touched then: the caller runs solve())
+    bool solve_picked(int N, const sonde_gps_pick_t &pk, int *num) {
+        using namespace sonde::gpsnav;
+        if (pk.n != N || pk.best >= N * (N - 1) * (N - 2) * (N - 3) / 24) return false;
+        if (pk.best < 0) {
+            lat = lon = alt = 0;
+            *num = pk.num;
+            return true;
         }
+        int ix[4] = {0, 1, 2, 3}, at = 0;
+        bool found = false;
+        for (int a = 0; a < N && !found; a++) for (int b = a + 1; b < N && !found; b++) for (int c = b + 1; c < N && !found; c++) for (int e = c + 1; e < N; e++)
+            if (at++ == pk.best) { ix[0] = a; ix[1] = b; ix[2] = c; ix[3] = e; found = true; break; }
+        double la = 0, lo = 0, al = 0, bias = 0, h = 0, dd = 0, u = 0, pos[3], dpos[3], velo[3] = {0, 0, 0}, dvel[3], DOP[4];
+        Sat A[4];
+        for (int q = 0; q < 4; q++) A[q] = sat[prn[ix[q]]];
+        if (closed_form4(A, &la, &lo, &al, &bias, pos) != 0) return false;
+        if (sonde::gpsnav::dop(4, A, pos, DOP) != 0) return false;
+        const double gdop = sqrt(DOP[0] + DOP[1] + DOP[2] + DOP[3]);
+        if (memcmp(&gdop, &pk.gdop, sizeof gdop) != 0 || !(gdop > 0 && gdop < 1000.0)) return false;
+        lin_pos(4, A, pos, bias, dpos, &bias);
+        const double dit = dist3(0, 0, 0, dpos[0], dpos[1], dpos[2]);
+        for (int j = 0; j < 3; j++) pos[j] += dpos[j];
+        ecef2elli(pos[0], pos[1], pos[2], &la, &lo, &al);
+        if (vel == 4) {
+            lin_vel(4, A, pos, velo, 0.0, dvel, &bias);
+            for (int j = 0; j < 3; j++) velo[j] += dvel[j];
+            lin_vel(4, A, pos, velo, bias, dvel, &bias);
+            for (int j = 0; j < 3; j++) velo[j] += dvel[j];
+            ecef_velocity(la, lo, velo, &h, &dd, &u);
+        }
+        lat = la; lon = lo; alt = al;
+        dop = gdop; diter = dit;
+        for (int q = 0; q < 4; q++) sats[q] = prn[ix[q]];
+        if (vel == 4) { vH = h; vD = dd; vU = u; }
+        *num = pk.num;
+        return true;
+    }
+
+    // print_position in two halves around the position solve: a frame may wait between them for a pick from elsewhere (sonde_rs92_dec_begin / _end)
+    struct Blocks { int err1 = 0, err2 = 0, err3 = 0, k = 0; };
+    Blocks position_blocks(Out &w) {
+        Blocks b;
+        frnr = frame[POS_FRAMENB] + (frame[POS_FRAMENB + 1] << 8);
+        b.err1 = config_block(w);
+        b.err2 = ptu_block();
+        b.err3 = gps_time();
+        aux_block();
+        if (!b.err3 && (almanac || ephem)) b.k = pseudoranges();
+        return b;
+    }
+    void print_position(Out &w, int ec) {
+        const Blocks b = position_blocks(w);
+        print_solved(w, ec, b, b.k >= 4 ? solve(w, b.k) : 0);
+    }
+    void print_solved(Out &w, int ec, const Blocks &b, int n) {
+        const int err1 = b.err1, err2 = b.err2, err3 = b.err3;
         if (err1) return;
 
         w.f("[%5d] ", frnr);
@@ -768,6 +818,124 @@ int sonde_rs92_dec_corrected(sonde_rs92_dec_t *d, const uint8_t frame[SONDE_RS92
     memcpy(d->frame, frame, FRAME_LEN);
     d->print_corrected(w, FRAME_LEN, ec);
     return finish_out(w, out, outlen);
+}
+
+// ---- the subset search as a job (include/sonde_rs92.h) ----------------------------------------------------------------------------------------------------
+int sonde_gps_job_fill(sonde_gps_job_t *job, int32_t n, const double *X, const double *Y, const double *Z, const double *p) {
+    if (!job || !X || !Y || !Z || !p || n < 4 || n > SONDE_GPS_MAX_SATS) return SONDE_E_ARG;
+    memset(job, 0, sizeof *job);
+    job->n = n;
+    for (int i = 0; i < n; i++) {
+        sonde_gps_sat_t &s = job->sat[i];
+        s.X = X[i]; s.Y = Y[i]; s.Z = Z[i]; s.p = p[i];
+        sonde::gpsnav::rot_range_est(s.X, s.Y, s.Z, &s.x, &s.y, &s.z);
+    }
+    return 0;
+}
+
+int sonde_gps_host_solve(const sonde_gps_job_t *job, sonde_gps_pick_t *pick) {
+    using namespace sonde::gpsnav;
+    if (!job || !pick || job->n < 4 || job->n > SONDE_GPS_MAX_SATS) return SONDE_E_ARG;
+    const int N = job->n;
+    Sat all[SONDE_GPS_MAX_SATS];
+    for (int i = 0; i < N; i++) { all[i].X = job->sat[i].X; all[i].Y = job->sat[i].Y; all[i].Z = job->sat[i].Z; all[i].pseudorange = job->sat[i].p; }      // (clock_corr 0: p + 0 is p)
+    double la, lo, al, bias, pos[3], DOP[4], gdop, gdop0 = 1000.0;
+    int ix[4], at = 0;
+    *pick = sonde_gps_pick_t{0, -1, 0, N, 0.0};
+    for (ix[0] = 0; ix[0] < N; ix[0]++) for (ix[1] = ix[0] + 1; ix[1] < N; ix[1]++) for (ix[2] = ix[1] + 1; ix[2] < N; ix[2]++) for (ix[3] = ix[2] + 1; ix[3] < N; ix[3]++, at++) {
+        Sat A[4];
+        for (int q = 0; q < 4; q++) A[q] = all[ix[q]];
+        if (closed_form4(A, &la, &lo, &al, &bias, pos) != 0) continue;
+        pick->num += 1;
+        gdop = sonde::gpsnav::dop(4, A, pos, DOP) == 0 ? sqrt(DOP[0] + DOP[1] + DOP[2] + DOP[3]) : -1;
+        if (gdop > 0 && gdop < gdop0) { gdop0 = gdop; pick->best = at; pick->gdop = gdop; }
+    }
+    return 0;
+}
+
+int sonde_rs92_dec_begin(sonde_rs92_dec_t *d, const uint8_t frame[SONDE_RS92_FRAME_LEN], int32_t ec, sonde_gps_job_t *job) {
+    if (!d || !frame || !job || d->pend) return SONDE_E_ARG;
+    d->pend = true; d->pend_job = false; d->pend_w.s.clear(); d->pend_ec = ec; d->pend_k = 0;
+    memcpy(d->frame, frame, FRAME_LEN);
+    if (d->o.raw) return 0;                                     // (printed by end: print_corrected)
+    d->crc = 0;
+    const sonde_rs92_dec::Blocks b = d->position_blocks(d->pend_w);
+    d->pend_err[0] = b.err1; d->pend_err[1] = b.err2; d->pend_err[2] = b.err3; d->pend_k = b.k;
+    if (b.k < 4 || d->vergps == 2 || d->vergps == 8) return 0;
+    double X[12], Y[12], Z[12], p[12];
+    for (int j = 0; j < b.k; j++) {
+        const Sat &s = d->sat[d->prn[j]];
+        X[j] = s.X; Y[j] = s.Y; Z[j] = s.Z; p[j] = s.pseudorange + s.clock_corr;
+    }
+    if (sonde_gps_job_fill(job, b.k, X, Y, Z, p) != 0) return 0;
+    d->pend_job = true;
+    return 1;
+}
+
+int sonde_rs92_dec_end(sonde_rs92_dec_t *d, const sonde_gps_pick_t *pick, char *out, size_t outlen) {
+    if (!d || !out || !d->pend) return SONDE_E_ARG;
+    d->pend = false;
+    d->gps_via = SONDE_GPS_VIA_HOST;
+    Out &w = d->pend_w;
+    if (d->o.raw) d->print_corrected(w, FRAME_LEN, d->pend_ec);
+    else {
+        sonde_rs92_dec::Blocks b;
+        b.err1 = d->pend_err[0]; b.err2 = d->pend_err[1]; b.err3 = d->pend_err[2]; b.k = d->pend_k;
+        int n = 0;
+        bool solved = false;
+        if (pick && d->pend_job) {
+            if (pick->doubt) d->gps_via = SONDE_GPS_VIA_DOUBT;
+            else if (d->solve_picked(b.k, *pick, &n)) { solved = true; d->gps_via = SONDE_GPS_VIA_PICK; }
+            else d->gps_via = SONDE_GPS_VIA_MISMATCH;
+        }
+        if (!solved && b.k >= 4) n = d->solve(w, b.k);
+        d->print_solved(w, d->pend_ec, b, n);
+    }
+    const int rc = finish_out(w, out, outlen);
+    w.s.clear();
+    return rc;
+}
+
+int sonde_rs92_dec_gps_via(const sonde_rs92_dec_t *d) { return d ? d->gps_via : SONDE_E_ARG; }
+
+int sonde_gps_rs92_text_batch_with(sonde_gps_solve_fn solve, void *ctx, sonde_rs92_dec_t *const *decs, const uint8_t (*frames)[SONDE_RS92_FRAME_LEN], const int32_t *ec,
+                                   int32_t n, char *out, size_t stride, int32_t *len, int64_t via4[4]) {
+    if (n < 0 || (n > 0 && (!decs || !frames || !ec || !out || !len))) return SONDE_E_ARG;
+    for (int i = 0; i < n; i++) if (!decs[i] || decs[i]->pend) return SONDE_E_ARG;      // (a frame of the caller's own pending there)
+    if (!solve) {
+        for (int i = 0; i < n; i++) len[i] = sonde_rs92_dec_corrected(decs[i], frames[i], ec[i], out + (size_t)i * stride, stride);
+        return 0;
+    }
+    // rounds: the first record not yet done of every decoder
+    std::vector<int> todo((size_t)n), round, rest, job_of;
+    for (int i = 0; i < n; i++) todo[(size_t)i] = i;
+    std::vector<sonde_gps_job_t> jobs;
+    std::vector<sonde_gps_pick_t> picks;
+    int rc_all = 0;
+    while (!todo.empty()) {
+        round.clear(); rest.clear(); jobs.clear(); job_of.clear();
+        for (int i : todo) {
+            sonde_rs92_dec_t *d = decs[i];
+            if (d->pend) { rest.push_back(i); continue; }                  // begun earlier in this round (none was pending when the call came): next round
+            sonde_gps_job_t job;
+            const int rc = sonde_rs92_dec_begin(d, frames[i], ec[i], &job);
+            if (rc < 0) { len[i] = rc; continue; }
+            round.push_back(i);
+            job_of.push_back(rc == 1 ? (int)jobs.size() : -1);
+            if (rc == 1) jobs.push_back(job);
+        }
+        picks.assign(jobs.size(), sonde_gps_pick_t{0, -1, 0, 0, 0.0});
+        int rc = jobs.empty() ? 0 : solve(ctx, jobs.data(), (int32_t)jobs.size(), picks.data());
+        if (rc < 0) rc_all = rc;
+        for (size_t r = 0; r < round.size(); r++) {
+            const int i = round[r];
+            const sonde_gps_pick_t *pk = (rc == 0 && job_of[r] >= 0) ? &picks[(size_t)job_of[r]] : nullptr;
+            len[i] = sonde_rs92_dec_end(decs[i], pk, out + (size_t)i * stride, stride);
+            if (via4) via4[sonde_rs92_dec_gps_via(decs[i])] += 1;
+        }
+        todo.swap(rest);
+    }
+    return rc_all;
 }
 
 int sonde_rs92_dec_push_soft(sonde_rs92_dec_t *d, const float *soft, int32_t n, int32_t invert, int32_t finish, char *out, size_t outlen) {

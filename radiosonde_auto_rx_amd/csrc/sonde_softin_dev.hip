@@ -850,6 +850,7 @@ struct sonde_softin_dev {
     int l6_auto = 0; int *d_l6_list = nullptr; Pinned<int> h_l6_list, h_l6_len; std::vector<int> l6_len; std::vector<int64_t> l6_ok;
     // LMS6 / RS92 / iMet-54 / Meisei / MRZ / MTS01: a host decoder per channel (what a sonde collects — calibration rows, configuration words, counters — is per channel)
     std::vector<void *> dec; void (*dec_free)(void *) = nullptr;
+    sonde_gps_dev_t *gps = nullptr; bool gps_on = false;   // RS92: the device subset search of fetch_rs92 (sonde_softin_dev_set_rs92_gps), made on first use
     std::vector<unsigned char> q;                  // the records not yet fetched, in the form the kind's tally queues
     long long frames_total = 0, ecc_ok_total = 0, repaired_total = 0, symbols_total = 0, dropped = 0;
     bool pending = false; hipStream_t pend_stream = nullptr;
@@ -866,6 +867,7 @@ sonde_softin_dev::~sonde_softin_dev() {
     if (pending && pend_stream) (void)hipStreamSynchronize(pend_stream);
     if (stream) { hipStreamSynchronize(stream); hipStreamDestroy(stream); }
     for (void *d : dec) dec_free(d);
+    sonde_gps_dev_destroy(gps);
 }
 
 // ---- the launches.  The staged kinds keep the call's soft decisions in LDS: what a call can hold (a modem launch: its capacity; a pushed stream: its length), up to
@@ -1410,7 +1412,42 @@ int sonde_softin_dev_set_m20_skip(sonde_softin_dev_t *s, int32_t skip) {
 
 // The text of a record is made here, by the channel's own decoder and from the device's bytes and verdicts, not in the push call: collect stays short.
 // (a negative text_len: the text did not fit; the frame is delivered all the same)
+int sonde_softin_dev_set_rs92_gps(sonde_softin_dev_t *s, int32_t on) {
+    if (!s || s->type != SONDE_RS92) return SONDE_E_ARG;
+    if (on && !s->gps) TRY(sonde_gps_dev_create(std::max(s->cap, 64), &s->gps));      // (a fetch holds what the push calls since the last one left: larger ones go in chunks)
+    s->gps_on = on != 0;
+    return 0;
+}
+int sonde_softin_dev_rs92_gps_stats(sonde_softin_dev_t *s, sonde_gps_stats_t *out) {
+    if (!s || !out || s->type != SONDE_RS92) return SONDE_E_ARG;
+    if (!s->gps) { memset(out, 0, sizeof *out); return 0; }
+    return sonde_gps_dev_stats(s->gps, out);
+}
+
+// with the switch on: the records of the fetch through begin / one device solve / end, in rounds where a channel has several (sonde_gps_rs92_text_batch)
+static int softin_fetch_rs92_gps(sonde_softin_dev *s, sonde_rs92_softin_t *out, const int32_t max) {
+    const int n = softin_fetch_count(s, SONDE_RS92, out != nullptr, max, sizeof(SoftinRs92Rec));
+    if (n <= 0) return n;
+    std::vector<sonde_rs92_dec_t *> decs((size_t)n);
+    std::vector<int32_t> ec((size_t)n), len((size_t)n);
+    std::vector<uint8_t> frames((size_t)n * SONDE_RS92_FRAME_LEN);
+    for (int i = 0; i < n; i++) {
+        SoftinRs92Rec r; memcpy((void *)&r, s->q.data() + (size_t)i * sizeof r, sizeof r);
+        sonde_rs92_softin_t &o = out[i];
+        o.channel = r.channel; o.ec = r.ec; o.mv = r.mv; o.hdr_bit = r.hdr_bit;
+        memcpy(o.frame, r.frame, sizeof o.frame);
+        memcpy(frames.data() + (size_t)i * SONDE_RS92_FRAME_LEN, r.frame, SONDE_RS92_FRAME_LEN);
+        decs[(size_t)i] = s->decoder<sonde_rs92_dec_t>(r.channel); ec[(size_t)i] = r.ec;
+    }
+    const int rc = sonde_gps_rs92_text_batch(s->gps, decs.data(), (const uint8_t (*)[SONDE_RS92_FRAME_LEN])frames.data(), ec.data(), n, out[0].text, sizeof(sonde_rs92_softin_t),
+                                             len.data());
+    for (int i = 0; i < n; i++) { out[i].text_len = len[(size_t)i]; if (len[(size_t)i] < 0) out[i].text[0] = 0; }
+    s->q.erase(s->q.begin(), s->q.begin() + (size_t)n * sizeof(SoftinRs92Rec));
+    return rc < 0 ? rc : n;
+}
+
 int sonde_softin_dev_fetch_rs92(sonde_softin_dev_t *s, sonde_rs92_softin_t *out, int32_t max) {
+    if (s && s->gps_on && s->gps) return softin_fetch_rs92_gps(s, out, max);
     return softin_fetch<SoftinRs92Rec>(s, SONDE_RS92, out, max, [s](const SoftinRs92Rec &r, sonde_rs92_softin_t &o) {
         // print_frame behind rs92_ecc (the decoder's calibration rows, its orbit data)
         o.channel = r.channel; o.ec = r.ec; o.mv = r.mv; o.hdr_bit = r.hdr_bit;

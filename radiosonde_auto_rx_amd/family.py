@@ -217,3 +217,30 @@ class FamilyDecoder:
     @staticmethod
     def json_objects(text: str):
         return [json.loads(l) for l in text.splitlines() if l.startswith("{")]
+
+
+def rs92_text_batch(decoders, records, solver, if_sr: int = 48000):
+    """FamilyDecoder.decoded for the records of Engine.fetch_family() on an RS92 engine, with the position solve's 4-satellite subset search of all of them on the
+    device (gps.GpsSolver; None = the host's search): decoders[channel] = that channel's RS92 FamilyDecoder (a dict or a sequence), records in fetch order.  A
+    channel's records pass through its decoder in order, several of one channel in rounds.  -> the text of each record, the same characters as
+    decoders[rec["channel"]].decoded(rec) gives one record at a time.  A record the device did not decode (decoded = 0) goes through hit() in its place."""
+    from . import gps
+    texts, run = [None] * len(records), []
+
+    def flush():
+        if run:
+            got = gps.text_batch(solver, [decoders[records[i]["channel"]]._h for i in run], [records[i]["data"][:240] for i in run], [records[i]["v"][0] for i in run])
+            for i, t in zip(run, got):
+                texts[i] = t
+            run.clear()
+    for i, rec in enumerate(records):
+        d = decoders[rec["channel"]]
+        if d.typ != "RS92":
+            raise SondeError("rs92_text_batch: an RS92 decoder per channel")
+        if rec["decoded"]:
+            run.append(i)
+        else:
+            flush()
+            texts[i] = d.hit(rec, if_sr)
+    flush()
+    return texts

@@ -152,6 +152,9 @@ def _lib():
         L.sonde_softin_dev_rs92_load_ephemeris.argtypes = [C.c_void_p, C.c_char_p]
         L.sonde_softin_dev_rs92_load_almanac.argtypes = [C.c_void_p, C.c_char_p]
         L.sonde_softin_dev_fetch_rs92.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+        from .gps import GpsStats
+        L.sonde_softin_dev_set_rs92_gps.argtypes = [C.c_void_p, C.c_int32]
+        L.sonde_softin_dev_rs92_gps_stats.argtypes = [C.c_void_p, C.POINTER(GpsStats)]
         from .family import Imet54Opts
         L.sonde_softin_dev_create_imet54.argtypes = [C.c_int32, C.POINTER(Imet54Opts), C.c_int32, C.POINTER(C.c_void_p)]
         L.sonde_softin_dev_fetch_imet54.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
@@ -272,13 +275,14 @@ class SoftinDev:
     def __init__(self, n_channels: int, *, ecc: int = 2, softinv: bool = False, inv: bool = True, auto: bool = False, kind: str = "rs41",
                  vit: int = 2, typ: int = 0, json: bool = False, raw: bool = False, gpsweek: int = 0, freq_khz: int = 0, version: str = "", skip: bool = True,
                  rs92_opts: dict | None = None, ephemeris: str | None = None, almanac: str | None = None, imet54_opts: dict | None = None,
-                 meisei_opts: dict | None = None, mrz_opts: dict | None = None, mts01_opts: dict | None = None):
+                 meisei_opts: dict | None = None, mrz_opts: dict | None = None, mts01_opts: dict | None = None, gps_device: bool = False):
         """kind: "rs41" (rs41mod --softin), "dfm" (dfm09mod --softin: ecc 0 / 1 = --ecc / 2 = --ecc2), "m10" (m10mod --softin), "m20" (m20mod --softin: skip = the rest of
         the second behind a frame is dropped, as m20mod does below -vvv; auto_rx runs `m20mod --json --ptu -vvv --softin -i`: skip=False; ecc, inv and auto mean nothing to it), "drop" (rd94rd41drop --softin /
         --softinv [-i]: auto_rx runs it as softinv=True, inv=False; ecc and auto are ignored) or "lms6" (lms6Xmod --softin: vit 1 = --vit / 2 = --vit2, typ 0 = auto
         detection / 6 = --lms6 / 10 = --lmsX, ecc != 0 = --ecc, json, raw = -r, gpsweek, freq_khz and version as sonde_lms6_opts_t; inv (-i) means nothing to it) or
         "rs92" (rs92mod --softin: rs92_opts = fields of family.Rs92Opts over auto_rx's defaults verbose 1, aux 1, ecc 2, gps_vel 4, json 1, inv 1 — inv there is -i;
-        ephemeris = a RINEX navigation file (-e), almanac = an SEM almanac (-a) for every channel's decoder; ecc, inv and auto of this call mean nothing to it) or
+        ephemeris = a RINEX navigation file (-e), almanac = an SEM almanac (-a) for every channel's decoder; gps_device = the 4-satellite subset search of the
+        position solve runs on the device, one launch per fetch (gps.py; off by default, the texts are the same); ecc, inv and auto of this call mean nothing to it) or
         "imet54" (imet54mod --softin: imet54_opts = fields of family.Imet54Opts over auto_rx's defaults ecc 1, json 1, ptu 1, inv 1 — inv there is -i, aut is --auto, json
         implies ecc; ecc, inv and auto of this call mean nothing to it) or "meisei" (meisei100mod --softin: meisei_opts = fields of family.MeiseiOpts over auto_rx's
         defaults ecc 1, json 1, ptu 1 — json implies ecc; there is no -i: biphase-S compares neighbours, and a header counts in either polarity; ecc, inv and auto of
@@ -289,6 +293,8 @@ class SoftinDev:
         from .engine import SONDE_RS41, SONDE_DFM09, SONDE_M10, SONDE_M20, SONDE_RD94RD41
         h = C.c_void_p()
         self.kind, self.ecc = kind, ecc
+        if gps_device and kind != "rs92":
+            raise ValueError("gps_device is an RS92 consumer's switch")
         if kind in _OPTS_KINDS:
             from . import family
             opts_name, defaults, create = _OPTS_KINDS[kind]
@@ -303,6 +309,8 @@ class SoftinDev:
                 self.load_rs92_ephemeris(ephemeris)
             if kind == "rs92" and almanac:
                 self.load_rs92_almanac(almanac)
+            if gps_device:
+                self.set_rs92_gps(True)
             return
         if kind == "lms6":
             o = Lms6Opts(raw=int(raw), ecc=1 if ecc else 0, vit=vit, json=int(json), typ=typ, gpsweek=gpsweek, jsn_freq_khz=freq_khz, version=version.encode())
@@ -425,6 +433,18 @@ class SoftinDev:
     def load_rs92_almanac(self, path: str):
         """RS92 consumers: an SEM almanac (rs92mod -a) for every channel's decoder"""
         _chk(_lib().sonde_softin_dev_rs92_load_almanac(self._h, os.fsencode(path)))
+
+    def set_rs92_gps(self, on: bool):
+        """RS92 consumers: True = fetch_rs92 sends the 4-satellite subset search of every fetched frame to the device in one launch (gps.py) and
+        solves only the winning subset on the host; the texts do not change.  From the next fetch on"""
+        _chk(_lib().sonde_softin_dev_set_rs92_gps(self._h, int(bool(on))))
+
+    def rs92_gps_stats(self):
+        """RS92 consumers: jobs / launches / doubts / mismatches / picked of the device subset search so far (all 0 while the switch is off)"""
+        from .gps import GpsStats
+        st = GpsStats()
+        _chk(_lib().sonde_softin_dev_rs92_gps_stats(self._h, C.byref(st)))
+        return st.as_dict()
 
     def _fetch_text(self, call: str, rec, max_frames: int, fields, encoding: str = "utf-8"):
         """the records whose text is made at fetch time: the named fields (byte arrays as bytes) and text"""

@@ -10,7 +10,10 @@ device path's k_family_hits among them), fetch and decode — under one clock.  
 --seconds of timed fetch + decode (and no fewer than --calls).  One decoder object per channel, the receivers' JSON options.  One JSON line per kind with medians,
 minima and maxima per call, the hits and good frames of both paths (they must agree), the bytes copied per hit both ways and the device's clocks.
 
-    python tools/bench_family_hits.py [--kinds MEISEI,IMET5,MTS01,RS92] [--channels 256] [--seconds 1.0] [--calls 12] [--out profiles/family_hits_bench.json]"""
+--gps-device (RS92 only): a third engine on the device path whose records go through family.rs92_text_batch with a gps.GpsSolver — the position solve's
+4-satellite subset search of a call's hits in one launch; one row of kind "RS92_GPS" with all three paths, appended to --out (the stored rows stay).
+
+    python tools/bench_family_hits.py [--gps-device] [--kinds MEISEI,IMET5,MTS01,RS92] [--channels 256] [--seconds 1.0] [--calls 12] [--out profiles/family_hits_bench.json]"""
 import argparse
 import json
 import os
@@ -43,11 +46,11 @@ def capture(kind, tmp):
     return x[:2 * SR * (len(x) // 2 // SR)], dict(ephemeris=p)
 
 
-def run_kind(kind, a, tmp):
+def run_kind(kind, a, tmp, gps_path=False):
     import torch                                                                 # noqa: F401  (PyTorch's HIP runtime first)
     from bench import _device_clocks
     from radiosonde_auto_rx_amd.engine import Engine
-    from radiosonde_auto_rx_amd.family import FAMILY, FamilyDecoder
+    from radiosonde_auto_rx_amd.family import FAMILY, FamilyDecoder, rs92_text_batch
     f = FAMILY[kind]
     x, dkw = capture(kind, tmp)
     secs = len(x) // 2 // SR
@@ -60,6 +63,11 @@ def run_kind(kind, a, tmp):
             e.set_family(kind, ecc=f["kw"].get("ecc", 1))
         return e
     eng = {"device": engine(True), "host": engine(False)}
+    solver = None
+    if gps_path:
+        from radiosonde_auto_rx_amd.gps import GpsSolver
+        eng["device_gps"] = engine(True)
+        solver = GpsSolver(max_jobs=max(nch, 64))
     dec = {p: [FamilyDecoder(kind, version="bench", **dkw) for _ in range(nch)] for p in eng}
     stat = {p: dict(fd=[], call=[], hits=0, json=0, undecoded=0) for p in eng}
 
@@ -69,10 +77,10 @@ def run_kind(kind, a, tmp):
         e.process_host(blocks[k % secs])
         e.sync()
         t1 = time.perf_counter()
-        recs = e.fetch_family() if p == "device" else e.fetch_hits()
+        recs = e.fetch_hits() if p == "host" else e.fetch_family()
         nj = 0
-        for r in recs:
-            text = d[r["channel"]].decoded(r) if p == "device" else d[r["channel"]].hit(r)
+        texts = rs92_text_batch(d, recs, solver) if p == "device_gps" else [d[r["channel"]].decoded(r) if p == "device" else d[r["channel"]].hit(r) for r in recs]
+        for text in texts:
             nj += text.count("\n{")  + text.startswith("{")
         t2 = time.perf_counter()
         if timed:
@@ -81,12 +89,12 @@ def run_kind(kind, a, tmp):
 
     k = 0
     for _ in range(2 * secs):                                                    # warm-up: code objects, the first frames, the decoders' configuration cycles
-        for p in ("device", "host"):
+        for p in eng:
             one_call(p, k, False)
         k += 1
     clocks0 = _device_clocks()
     while k < 2 * secs + 2000 and (k < 2 * secs + a.calls or min(sum(stat[p]["fd"]) for p in eng) < 1e3 * a.seconds):
-        for p in (("device", "host") if k & 1 else ("host", "device")):         # alternating: other people's work shares the box
+        for p in (list(eng) if k & 1 else list(eng)[::-1]):                     # alternating: other people's work shares the box
             one_call(p, k, True)
         k += 1
     clocks1 = _device_clocks()
@@ -96,8 +104,11 @@ def run_kind(kind, a, tmp):
         for d in dec[p]:
             d.close()
     nb = f["generic"]["nbits"]
-    row = {"kind": kind, "channels": nch, "calls": len(stat["device"]["fd"]), "signal_s_per_call": 1.0}
-    for p in ("device", "host"):
+    row = {"kind": kind + "_GPS" if gps_path else kind, "channels": nch, "calls": len(stat["device"]["fd"]), "signal_s_per_call": 1.0}
+    if solver is not None:
+        row["gps"] = solver.stats()
+        solver.close()
+    for p in eng:
         s = stat[p]
         row[p] = {"fetch_decode_ms": round(statistics.median(s["fd"]), 3), "fetch_decode_min_ms": round(min(s["fd"]), 3), "fetch_decode_max_ms": round(max(s["fd"]), 3),
                   "fetch_decode_timed_s": round(sum(s["fd"]) / 1e3, 3), "call_ms": round(statistics.median(s["call"]), 3), "call_min_ms": round(min(s["call"]), 3),
@@ -116,14 +127,18 @@ def main():
     ap.add_argument("--seconds", type=float, default=1.0, help="least timed fetch + decode time per path")
     ap.add_argument("--calls", type=int, default=12, help="least timed calls")
     ap.add_argument("--out", default="")
+    ap.add_argument("--gps-device", action="store_true", help="RS92 alone, with a third path: rs92_text_batch and the device subset search")
     a = ap.parse_args()
     rows = []
     with tempfile.TemporaryDirectory() as tmp:
-        for kind in a.kinds.split(","):
-            row = run_kind(kind, a, tmp)
+        for kind in (["RS92"] if a.gps_device else a.kinds.split(",")):
+            row = run_kind(kind, a, tmp, a.gps_device)
             rows.append(row)
             print(json.dumps(row), flush=True)
     if a.out:
+        if a.gps_device and os.path.exists(a.out):
+            with open(a.out) as f:
+                rows = [r for r in json.load(f) if r.get("kind") != "RS92_GPS"] + rows
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
             json.dump(rows, f, indent=1)

@@ -38,7 +38,10 @@ A push is the kernel and the copies of its records (push_ms); the text is made w
 (sonde_mrz_dec_push_soft / sonde_mts01_dec_push_soft, one thread) on the same stream in the same run.  No speed threshold: the rows are the measured pair and the 9.6 / 4.8
 KB of soft decisions per channel and second that stay on the device.
 
-    python tools/bench_softin.py [--kind lms6|m20|rs92|imet54|meisei|mrz|mts01|all] [--channels 1,64,341,1024] [--pushes 39] [--vit 2] [--typ 0] [--out profiles/softin_bench.json]"""
+--kind rs92 --gps-device: the text of the RS92 fetch alone, with the position solve's 4-satellite subset search on the host and on the device (SoftinDev(gps_device=True),
+DESIGN.md 4.11c), two consumers on the same pushes timed alternately in one run; rows of kind "rs92_gps" (the rs92 rows stay).
+
+    python tools/bench_softin.py [--kind lms6|m20|rs92|imet54|meisei|mrz|mts01|all] [--gps-device] [--channels 1,64,341,1024] [--pushes 39] [--vit 2] [--typ 0] [--out profiles/softin_bench.json]"""
 import argparse
 import ctypes as C
 import json
@@ -227,6 +230,59 @@ def rs92_rows(a):
                    "host_tier_ms_per_channel_second": round(host_ms, 4), "host_tier_min_ms": round(min(hw), 4), "host_tier_max_ms": round(max(hw), 4),
                    "host_tier_no_gps_ms_per_channel_second": round(host0_ms, 4), "host_tier_ms_for_these_channels": round(host_ms * nch, 2),
                    "host_tier_positions_one_channel": hok}
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+    return rows
+
+
+def rs92_gps_rows(a):
+    """--gps-device: the text of an RS92 fetch with the position solve's subset search on the host (today's path) and on the device (SoftinDev(gps_device=True)),
+    timed alternately in ONE run on the same records: two consumers get the same push, their fetches are timed one after the other, the order swapped every push.
+    host_text_in_stored_range says whether the host figure of this run lies within min .. max of the stored rs92 row of the same channel count (a.out), or the
+    stored text_ms within this run's: otherwise the pair is not comparable with the stored rows."""
+    import tempfile
+    import torch
+    from radiosonde_auto_rx_amd.fsk import SoftinDev
+    s, nav = rs92_stream()
+    stored = {}
+    if a.out and os.path.exists(a.out):
+        with open(a.out) as f:
+            stored = {r["channels"]: r for r in json.load(f) if r.get("kind") == "rs92"}
+    rows = []
+    with tempfile.TemporaryDirectory() as tmp:
+        rinex = os.path.join(tmp, "brdc.nav")
+        with open(rinex, "wb") as f:
+            f.write(nav)
+        for nch in [int(c) for c in a.channels.split(",")]:
+            d = torch.from_numpy(s).to("cuda").repeat(nch, 1).contiguous()
+            torch.cuda.synchronize()
+            sf = {dev: SoftinDev(nch, kind="rs92", rs92_opts=dict(ptu=1), ephemeris=rinex, gps_device=dev) for dev in (False, True)}
+            texts, pos, same = {False: [], True: []}, {False: 0, True: 0}, True
+            for k in range(13 + a.pushes):
+                p = d.data_ptr() + (k % 13) * 4800 * 4
+                got = {}
+                for dev in ((False, True) if k % 2 == 0 else (True, False)):
+                    sf[dev].push_device(p, d.shape[1], 4800)
+                    t1 = time.perf_counter()
+                    got[dev] = sf[dev].fetch_rs92(nch + 16)
+                    t2 = time.perf_counter()
+                    if k >= 13:
+                        texts[dev].append((t2 - t1) * 1e3)
+                        pos[dev] += sum(r["text"].count('"lat"') for r in got[dev])
+                key = lambda recs: sorted((r["channel"], r["hdr_bit"], r["text"]) for r in recs)      # noqa: E731
+                same = same and key(got[False]) == key(got[True])
+            st = sf[True].rs92_gps_stats()
+            for v in sf.values():
+                v.close()
+            th, td = statistics.median(texts[False]), statistics.median(texts[True])
+            row = {"kind": "rs92_gps", "channels": nch, "pushes": a.pushes, "text_host_ms": round(th, 3), "text_host_min_ms": round(min(texts[False]), 3),
+                   "text_host_max_ms": round(max(texts[False]), 3), "text_device_ms": round(td, 3), "text_device_min_ms": round(min(texts[True]), 3),
+                   "text_device_max_ms": round(max(texts[True]), 3), "host_over_device": round(th / td, 2), "positions_host": pos[False], "positions_device": pos[True],
+                   "texts_identical": bool(same), "gps_jobs": st["jobs"], "gps_launches": st["launches"], "gps_doubts": st["doubts"], "gps_mismatches": st["mismatches"]}
+            if nch in stored:
+                r0 = stored[nch]
+                row["stored_text_ms"] = r0["text_ms"]
+                row["host_text_in_stored_range"] = bool(min(texts[False]) <= r0["text_ms"] <= max(texts[False]) or r0["text_min_ms"] <= th <= r0["text_max_ms"])
             rows.append(row)
             print(json.dumps(row), flush=True)
     return rows
@@ -540,11 +596,24 @@ def main():
     ap.add_argument("--typ", type=int, default=0)
     ap.add_argument("--host-channels", type=int, default=4)
     ap.add_argument("--out", default="")
+    ap.add_argument("--gps-device", action="store_true", help="--kind rs92: the fetch's text with the subset search on the host and on the device, alternately in one run")
     a = ap.parse_args()
     assert a.pushes >= 30
-    rows = (lms6_rows(a) if a.kind in ("lms6", "all") else []) + (m20_rows(a) if a.kind in ("m20", "all") else []) + (rs92_rows(a) if a.kind in ("rs92", "all") else []) \
+    if a.gps_device:
+        assert a.kind == "rs92", "--gps-device goes with --kind rs92"
+        rows = rs92_gps_rows(a)
+    else:
+        rows = main_rows(a)
+    write_rows(a, rows)
+
+
+def main_rows(a):
+    return (lms6_rows(a) if a.kind in ("lms6", "all") else []) + (m20_rows(a) if a.kind in ("m20", "all") else []) + (rs92_rows(a) if a.kind in ("rs92", "all") else []) \
         + (imet54_rows(a) if a.kind in ("imet54", "all") else []) + (meisei_rows(a) if a.kind in ("meisei", "all") else []) \
         + (crc_rows(a, "mrz") if a.kind in ("mrz", "all") else []) + (crc_rows(a, "mts01") if a.kind in ("mts01", "all") else [])
+
+
+def write_rows(a, rows):
     if a.out:
         kinds = {r["kind"] for r in rows}
         if os.path.exists(a.out):
