@@ -369,7 +369,20 @@ typedef struct {
     float    mv;
     uint8_t  frame[172];
 } sonde_m20_frame_t;
+/* SONDE_M20 engines and the M20 channels of a mixed one: frames completed so far; finish != 0 = end of input (a frame in progress is emitted with the bits that
+ * exist, m20mod.c:1346,1353-1354).  Differential decoding (m20mod.c:1321,1348: the first bit against '0' = 0x30), bits2bytes (:192-220) and what print_frame() derives
+ * (:875-907; checkM10 :562-596, blk_checkM10 :548-560) run on the device behind the frame sync (k_m20_hits, csrc/sonde_m20_hits.hip: one wavefront per hit record,
+ * the bit characters per channel in device memory); 208 bytes a hit come to the host, the soft bits on request (sonde_engine_fetch_soft).  The host decode remains
+ * as the A/B path: sonde_engine_set_device_ecc(e, 0) or SONDE_HOST_ECC=1 — between records only, everything queued fetched first (SONDE_E_ARG otherwise).
+ * _lagged: only the frames of calls up to `lag` calls before the latest one; it does not wait for the call that is still running. */
 int  sonde_engine_fetch_m20(sonde_engine_t *e, sonde_m20_frame_t *out, int32_t max, int32_t finish);
+int  sonde_engine_fetch_m20_lagged(sonde_engine_t *e, sonde_m20_frame_t *out, int32_t max, int32_t lag);
+/* The same kernel on n hits in host memory (tests, tools), processed in the given order: hit i = nbits[i] (0 .. 1320) hard bits, 8 a byte, LSB first, in the 165
+ * bytes at bits + 165 * i, of channel[i] (0 .. n_channels - 1) with header score mv[i] (mv NULL: 0).  The channels' bit characters start at zero, as at an
+ * engine's create, and persist from hit to hit of a channel (gpx.frame_bits, m20mod.c:1348,1353).  out[i].mv_pos = 0.  chars_out (optional): the characters
+ * afterwards, n_channels x (165 * 8 + 8). */
+int  sonde_m20_decode_device(const uint8_t *bits, const int32_t *nbits, const int32_t *channel, const float *mv, int32_t n, int32_t n_channels,
+                             sonde_m20_frame_t *out, char *chars_out);
 /* Fill len / cs_ok / cs_calc (/ blk_ok / fw) from f->frame: what print_frame() derives before printing (m10mod.c:1049-1070, m20mod.c:875-907).
  * For frames that do not come from an engine or soft-symbol framer, e.g. --rawhex input. */
 int  sonde_m10_frame_finish(sonde_m10_frame_t *f);

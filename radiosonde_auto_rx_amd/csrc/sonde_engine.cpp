@@ -42,9 +42,10 @@ struct sonde_engine {
     hipStream_t stream_c = nullptr;    // C: record copies of a lagged fetch (on B they would queue behind the call that is still running)
     hipStream_t stream_e = nullptr;    // E: k_rs41_ecc_frames + the frame-counter publish of a call, beside the next call's decimator (RS41 engines with ECC)
     hipEvent_t ev_s = nullptr;         // B -> E hand-over
-    // DFM / M10 block codes of the hits on the device (k_dfm_hits / k_m10_hits, sonde_softin_dev.hip): decoded frames per ring slot, {done, ticket}, M10's bit characters per channel
-    sonde_dfm_frame_t *d_dfm_out = nullptr; sonde_m10_frame_t *d_m10_out = nullptr; unsigned *d_blk_done = nullptr; char *d_m10_bits = nullptr;
-    std::vector<sonde_dfm_frame_t> h_dfm; std::vector<sonde_m10_frame_t> h_m10; bool soft_lazy = false; unsigned soft_lazy_start = 0;
+    // DFM / M10 / M20 block codes of the hits on the device (k_dfm_hits / k_m10_hits, sonde_softin_dev.hip; k_m20_hits, sonde_m20_hits.hip): decoded frames per ring
+    // slot, {done, ticket}, the bit characters per channel of M10 or M20 (d_m10_bits: mxx_chars() of them a channel)
+    sonde_dfm_frame_t *d_dfm_out = nullptr; sonde_m10_frame_t *d_m10_out = nullptr; sonde_m20_frame_t *d_m20_out = nullptr; unsigned *d_blk_done = nullptr; char *d_m10_bits = nullptr;
+    std::vector<sonde_dfm_frame_t> h_dfm; std::vector<sonde_m10_frame_t> h_m10; std::vector<sonde_m20_frame_t> h_m20; bool soft_lazy = false; unsigned soft_lazy_start = 0;
     // generic engines whose hits are decoded on the device (sonde_engine_set_family; k_family_hits, sonde_family_hits.hip): the kind, its --ecc, a record per ring
     // slot, what the kind's kernel reads besides the hits; d_blk_done is its {done, ticket}
     int fam_kind = 0, fam_ecc = 0; sonde_family_hit_t *d_fam_out = nullptr; const uint32_t *d_fam_tab = nullptr; const uint8_t *d_fam_gf = nullptr;
@@ -203,13 +204,17 @@ extern "C" void sonde_launch_dfm_hits(const FrameRec *frames, const float *soft,
                                       int ecc_level, int grid, hipStream_t s);
 extern "C" void sonde_launch_m10_hits(const FrameRec *frames, const float *soft, const float *soft1, int chk3, int nbits, int max_frames, const unsigned *fcount, unsigned *done,
                                       char *chan_bits, sonde_m10_frame_t *out, int grid, hipStream_t s);
+extern "C" void sonde_launch_m20_hits(const FrameRec *frames, int n_channels, int max_frames, const unsigned *fcount, unsigned *done, char *chan_bits,
+                                      sonde_m20_frame_t *out, int grid, hipStream_t s);
 extern "C" void sonde_launch_family_hits(int kind, int ecc, const FrameRec *frames, const int *nbits_direct, const float *soft, long long stride, int max_frames,
                                          const unsigned *fcount, unsigned *done, const uint32_t *tab, const uint8_t *gf, sonde_family_hit_t *out, int grid, hipStream_t s);
 int sonde_family_tables(DevMem &mem, int kind, const uint32_t **tab, const uint8_t **gf);
 static bool blockcodes_on_device(const sonde_engine *e);
+// bit characters a channel of an M10 / M20 engine keeps from frame to frame: 8 per frame byte and the terminator (m10mod.c:90-94, m20mod.c:83-87)
+static inline size_t mxx_chars(const sonde_engine *e) { return (size_t)(e->cfg.sonde_type == SONDE_M20 ? 101 + 64 : 101 + 20) * 8 + 8; }
 // a generic engine whose hits are decoded behind the frame sync (sonde_engine_set_family), with the switch of sonde_engine_set_device_ecc as it stands
 static bool family_on_device(const sonde_engine *e) { return e->dev_ecc && e->fam_kind && e->d_soft && e->d_blk_done && e->d_fam_out; }
-// behind every frame-sync launch: the block codes of the hits it has queued (DFM Hamming(8,4), M10 checksum, the generic family's per-hit decoders), on the same stream
+// behind every frame-sync launch: the block codes of the hits it has queued (DFM Hamming(8,4), M10 / M20 checksums, the generic family's per-hit decoders), on the same stream
 static void launch_blockcodes(sonde_engine *e) {
     const int grid = std::max(1, std::min(e->cfg.n_channels, 1024));
     if (family_on_device(e)) {
@@ -220,6 +225,8 @@ static void launch_blockcodes(sonde_engine *e) {
     if (!blockcodes_on_device(e)) return;
     if (e->cfg.sonde_type == SONDE_DFM09)
         sonde_launch_dfm_hits(e->d_frames, e->d_soft, e->nbits, e->max_frames, e->d_fcount, e->d_blk_done, e->d_dfm_out, e->cfg.ecc_level, grid, e->stream_b);
+    else if (e->cfg.sonde_type == SONDE_M20)
+        sonde_launch_m20_hits(e->d_frames, e->cfg.n_channels, e->max_frames, e->d_fcount, e->d_blk_done, e->d_m10_bits, e->d_m20_out, grid, e->stream_b);
     else
         sonde_launch_m10_hits(e->d_frames, e->d_soft, e->d_soft1, e->m10_chk3 ? 1 : 0, e->nbits, e->max_frames, e->d_fcount, e->d_blk_done, e->d_m10_bits, e->d_m10_out, grid, e->stream_b);
 }
@@ -228,7 +235,8 @@ static void sync_round(sonde_engine *e, int W);
 static void launch_search_sync(sonde_engine *e);
 
 static bool blockcodes_on_device(const sonde_engine *e) {
-    return e->dev_ecc && e->d_soft && e->d_blk_done && ((e->cfg.sonde_type == SONDE_DFM09 && e->d_dfm_out) || (e->cfg.sonde_type == SONDE_M10 && e->d_m10_out));
+    return e->dev_ecc && e->d_soft && e->d_blk_done && ((e->cfg.sonde_type == SONDE_DFM09 && e->d_dfm_out) || (e->cfg.sonde_type == SONDE_M10 && e->d_m10_out && e->d_m10_bits) ||
+                                                        (e->cfg.sonde_type == SONDE_M20 && e->d_m20_out && e->d_m10_bits));
 }
 // the decoded frames of the n records a fetch has just taken (ring slots from `start` on) -> host
 template <class T> static int copy_decoded(sonde_engine *e, const T *d_out, std::vector<T> &h, unsigned start, int n, int per, int lag = 0) {
@@ -311,6 +319,7 @@ int sonde_engine_create(const sonde_cfg_t *cfg, const double *fq, sonde_engine_t
 static int create_impl(const sonde_cfg_t *cfg, const double *fq, const sonde_generic_t *gen, const CreateLink *lk, sonde_engine_t **out);
 static int fetch_dfm_impl(sonde_engine_t *e, sonde_dfm_frame_t *out, int32_t max, int32_t finish, int lag);
 static int fetch_m10_impl(sonde_engine_t *e, sonde_m10_frame_t *out, int32_t max, int32_t finish, int lag);
+static int fetch_m20_impl(sonde_engine_t *e, sonde_m20_frame_t *out, int32_t max, int32_t finish, int lag);
 int sonde_engine_create_generic(const sonde_cfg_t *cfg, const double *fq, const sonde_generic_t *gen, sonde_engine_t **out) { return create_impl(cfg, fq, gen, nullptr, out); }
 
 }  // extern "C"
@@ -567,7 +576,8 @@ static int engine_device(sonde_engine *e, const CreateLink *lk, const HostTables
     if (cfg->keep_soft || cfg->sonde_type != SONDE_RS41) TRY(mem.dalloc(&e->d_soft, (size_t)e->max_frames * e->nbits));
     if (cfg->keep_soft == 2) TRY(mem.dalloc(&e->d_soft1, (size_t)e->max_frames * e->nbits));
     if (cfg->sonde_type == SONDE_DFM09) { TRY(mem.dalloc(&e->d_dfm_out, (size_t)e->max_frames * 8)); TRY(mem.dalloc(&e->d_blk_done, 2)); }
-    if (cfg->sonde_type == SONDE_M10) { TRY(mem.dalloc(&e->d_m10_out, (size_t)e->max_frames)); TRY(mem.dalloc(&e->d_blk_done, 2)); TRY(mem.dalloc(&e->d_m10_bits, (size_t)C * ((101 + 20) * 8 + 8))); }
+    if (cfg->sonde_type == SONDE_M10) { TRY(mem.dalloc(&e->d_m10_out, (size_t)e->max_frames)); TRY(mem.dalloc(&e->d_blk_done, 2)); TRY(mem.dalloc(&e->d_m10_bits, (size_t)C * mxx_chars(e))); }
+    if (cfg->sonde_type == SONDE_M20) { TRY(mem.dalloc(&e->d_m20_out, (size_t)e->max_frames)); TRY(mem.dalloc(&e->d_blk_done, 2)); TRY(mem.dalloc(&e->d_m10_bits, (size_t)C * mxx_chars(e))); }
     TRY(mem.upload(&e->d_match, e->match));
     if (!e->w_iq.empty()) TRY(mem.upload(&e->d_wiq, e->w_iq));
     if (!e->w_fm.empty()) TRY(mem.upload(&e->d_wfm, e->w_fm));
@@ -1249,7 +1259,7 @@ int sonde_engine_set_device_ecc(sonde_engine_t *e, int32_t on) {
     for (sonde_engine *g : e->groups) { const int rc = sonde_engine_set_device_ecc(g, on); if (rc) return rc; }
     if ((on != 0) == e->dev_ecc) return 0;
     if (e->d_blk_done) {
-        // DFM / M10 engines decide per record range where its block codes run: k_dfm_hits / k_m10_hits behind the frame sync that queued it, or the host inside
+        // DFM / M10 / M20 engines decide per record range where its block codes run: k_dfm_hits / k_m10_hits / k_m20_hits behind the frame sync that queued it, or the host inside
         // the fetch.  A switch therefore takes effect between records only: everything queued so far must have been fetched (SONDE_E_ARG otherwise — fetch first),
         // and the device decoder then starts at the record the next frame sync queues (a toggle between a call and its fetch read slots never decoded).
         if (hipStreamSynchronize(e->stream_b) != hipSuccess) return SONDE_E_NOGPU;
@@ -1374,14 +1384,34 @@ static int mxx_bytes(sonde_engine *e, const FrameRec &r, int nbytes_max, uint8_t
 }
 
 int sonde_engine_fetch_m20(sonde_engine_t *e, sonde_m20_frame_t *out, int32_t max, int32_t finish) {
-    if (e && !e->groups.empty()) return mixed_fetch(e, SONDE_M20, out, max, 0, [finish](sonde_engine *g, sonde_m20_frame_t *o, int32_t m) { return sonde_engine_fetch_m20(g, o, m, finish); });
+    if (e && !e->groups.empty()) return mixed_fetch(e, SONDE_M20, out, max, 0, [finish](sonde_engine *g, sonde_m20_frame_t *o, int32_t m) { return fetch_m20_impl(g, o, m, finish, 0); });
+    return fetch_m20_impl(e, out, max, finish, 0);
+}
+int sonde_engine_fetch_m20_lagged(sonde_engine_t *e, sonde_m20_frame_t *out, int32_t max, int32_t lag) {
+    if (lag < 0) lag = 0;
+    if (e && !e->groups.empty()) return mixed_fetch(e, SONDE_M20, out, max, lag, [lag](sonde_engine *g, sonde_m20_frame_t *o, int32_t m) { return fetch_m20_impl(g, o, m, 0, lag); });
+    return fetch_m20_impl(e, out, max, 0, lag);
+}
+
+static int fetch_m20_impl(sonde_engine_t *e, sonde_m20_frame_t *out, int32_t max, int32_t finish, int lag) {
     if (!e || !out || max < 0 || e->cfg.sonde_type != SONDE_M20) return SONDE_E_ARG;
-    if (finish) launch_framesync(e, 1);
+    if (finish) { launch_framesync(e, 1); lag = 0; }
     std::vector<FrameRec> recs;
     std::vector<float> soft;
-    const int n = collect_records(e, 0, recs, &soft, max);
+    const bool on_dev = blockcodes_on_device(e);
+    const int n = collect_records(e, lag, recs, on_dev ? nullptr : &soft, max);
     if (n < 0) return n;
-    e->last_soft = soft; e->last_n = n; e->soft_lazy = false;
+    e->last_n = n;
+    if (on_dev) {
+        // differential decoding, bytes and both checksums were done on the device behind the frame sync (k_m20_hits): only the records come over — the soft bits
+        // stay where they are until sonde_engine_fetch_soft asks for them
+        const unsigned start = e->read_idx - (unsigned)n;
+        e->soft_lazy = true; e->soft_lazy_start = start;
+        if (copy_decoded(e, e->d_m20_out, e->h_m20, start, n, 1, lag)) return SONDE_E_NOGPU;
+        for (int h = 0; h < n; h++) { out[h] = e->h_m20[h]; out[h].mv_pos = rel_pos(e, recs[h]); }
+        return n;
+    }
+    e->last_soft = soft; e->soft_lazy = false;
     for (int h = 0; h < n; h++) {
         const FrameRec &r = recs[h];
         sonde_m20_frame_t &o = out[h];
@@ -1585,7 +1615,7 @@ int sonde_engine_restart_channel(sonde_engine_t *e, int32_t channel) {
     HIPCHK(hipMemcpy(e->d_state + channel, &st, sizeof st, hipMemcpyHostToDevice));
     if (!e->last_frame.empty()) { memset(e->last_frame.data() + (size_t)channel * 518, 0, 518); memcpy(e->last_frame.data() + (size_t)channel * 518, kRs41HeaderBytes, 8); }
     if (!e->m10_bits.empty()) { const size_t per = e->m10_bits.size() / (size_t)C; memset(e->m10_bits.data() + (size_t)channel * per, 0, per); }
-    if (e->d_m10_bits) { const size_t per = (101 + 20) * 8 + 8; HIPCHK(hipStreamSynchronize(e->stream_b)); HIPCHK(hipMemset(e->d_m10_bits + (size_t)channel * per, 0, per)); }
+    if (e->d_m10_bits) { const size_t per = mxx_chars(e); HIPCHK(hipStreamSynchronize(e->stream_b)); HIPCHK(hipMemset(e->d_m10_bits + (size_t)channel * per, 0, per)); }
     return 0;
 }
 

@@ -154,6 +154,38 @@ def rs41_ecc_device(frames: np.ndarray, flen, level: int = 2):
     return fr, ecc, codes, synd
 
 
+M20_FRAME_BYTES = 101 + 64                    # FRAME_LEN + AUX_LEN (m20mod.c:83-87)
+M20_CHAN_CHARS = M20_FRAME_BYTES * 8 + 8      # bit characters a channel keeps from frame to frame, and the terminator
+
+
+_M20_ENTRIES = {"sonde_engine_fetch_m20_lagged": [C.c_void_p, C.POINTER(SondeM20Frame), C.c_int32, C.c_int32],
+                "sonde_m20_decode_device": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(SondeM20Frame), C.c_void_p]}
+
+
+def m20_entry(name: str):
+    """sonde_engine_fetch_m20_lagged / sonde_m20_decode_device with their argtypes (looked up on use: a library of an earlier revision given with SONDE_HIP_LIB
+    for an A/B run lacks them)"""
+    f = getattr(lib(), name)
+    f.argtypes = _M20_ENTRIES[name]
+    return f
+
+
+def decode_m20_hits_device(bits: np.ndarray, nbits, channel, n_channels: int, mv=None, with_chars: bool = False):
+    """The engines' per-hit M20 decoder (k_m20_hits) on hits in host memory (sonde_m20_decode_device, include/sonde_hip.h), in the given order: bits = [n, 165] u8,
+    the hard bits 8 a byte, LSB first; nbits[i] of them are valid; channel[i] says whose bit characters the hit goes through (they start at zero and persist).
+    -> ctypes array of n sonde_m20_frame_t (mv_pos = 0); with_chars: (that, the channels' characters afterwards [n_channels, 1328] u8)"""
+    b = np.ascontiguousarray(bits, dtype=np.uint8).reshape(-1, M20_FRAME_BYTES)
+    n = b.shape[0]
+    nb = np.ascontiguousarray(np.broadcast_to(np.asarray(nbits, dtype=np.int32), (n,)))
+    ch = np.ascontiguousarray(np.broadcast_to(np.asarray(channel, dtype=np.int32), (n,)))
+    m = None if mv is None else np.ascontiguousarray(np.broadcast_to(np.asarray(mv, dtype=np.float32), (n,)))
+    out = (SondeM20Frame * max(n, 1))()
+    chars = np.zeros((n_channels, M20_CHAN_CHARS), np.uint8) if with_chars else None
+    _chk(m20_entry("sonde_m20_decode_device")(b.ctypes.data, nb.ctypes.data, ch.ctypes.data, None if m is None else m.ctypes.data, n, int(n_channels), out,
+                                        None if chars is None else chars.ctypes.data))
+    return (out, chars) if with_chars else out
+
+
 class SondeError(RuntimeError):
     pass
 
@@ -353,6 +385,16 @@ class Engine:
             return self._m10buf, _chk(lib().sonde_engine_fetch_m10_lagged(self._h, self._m10buf, n, lag))
         return self._m10buf, _chk(lib().sonde_engine_fetch_m10(self._h, self._m10buf, n, int(finish)))
 
+    def fetch_m20_raw(self, finish: bool = False, lag: int = 0):
+        """M20 engines, and the M20 channels of a mixed one: the frames as a ctypes array of sonde_m20_frame_t and their count — no per-frame Python work.
+        lag = 1: only frames of calls before the latest one (sonde_engine_fetch_m20_lagged)."""
+        n = 4 * self._max_frames
+        if getattr(self, "_m20buf", None) is None:
+            self._m20buf = (SondeM20Frame * n)()
+        if lag and not finish:
+            return self._m20buf, _chk(m20_entry("sonde_engine_fetch_m20_lagged")(self._h, self._m20buf, n, lag))
+        return self._m20buf, _chk(lib().sonde_engine_fetch_m20(self._h, self._m20buf, n, int(finish)))
+
     def fetch_hits(self, finish: bool = False):
         """Function-level seam: header hits (score, position, polarity) with their soft bits, any sonde type (needs keep_soft)."""
         n = self._max_frames
@@ -450,7 +492,8 @@ SONDE_MIXED = 100
 class MixedEngine(Engine):
     """Mixed-type engine (sonde_engine_create_mixed): channel c carries a sonde of type kinds[c] ("rs41" / "dfm" / "m10" / "m20"); ONE decimator launch per call
     serves all channels, the IF-rate stages run per type.  ecc = {kind: level} (rs41mod --ecc2 = 2, dfm09mod --ecc = 1).  Frames come back per type:
-    fetch_frames* (RS41), fetch_dfm* (DFM), fetch_m10* / fetch_mxx (M10 / M20), channel numbers are the caller's."""
+    fetch_frames* (RS41), fetch_dfm* (DFM), fetch_m10_raw / fetch_m20_raw / fetch_mxx (M10 / M20; the _raw forms take lag like the others), channel numbers are
+    the caller's."""
 
     def __init__(self, fq, kinds, sample_rate: int, *, device: int = 0, lp_iq: bool = True, ecc: dict | None = None, thres: dict | None = None,
                  max_chunk: int | None = None, max_frames: int = 0, opt_min: bool = False, bits: int = 16, pipeline: bool = True):
