@@ -48,11 +48,11 @@ extern "C" {
 #define SONDE_RS92   92         /* rs92mod.c: Vaisala RS92-SGP / -NGP; the type of a soft-bit consumer (sonde_softin_dev_create_rs92, include/sonde_fsk.h) and the kind of a generic engine's device decoder (sonde_engine_set_family) */
 #define SONDE_IMET54 54         /* imet54mod.c: InterMet iMet-54 / iMet-50; the type of a soft-bit consumer (sonde_softin_dev_create_imet54, include/sonde_fsk.h) and the kind of a generic engine's device decoder (sonde_engine_set_family) */
 #define SONDE_MEISEI 11         /* meisei100mod.c: Meisei iMS-100 / RS-11G; the type of a soft-bit consumer (sonde_softin_dev_create_meisei, include/sonde_fsk.h) and the kind of a generic engine's device decoder (sonde_engine_set_family) */
-#define SONDE_MRZ    31         /* mp3h1mod.c: Meteo-Radiy MRZ / MP3-H1; only as the type of a soft-bit consumer (sonde_softin_dev_create_mrz, include/sonde_fsk.h) */
+#define SONDE_MRZ    31         /* mp3h1mod.c: Meteo-Radiy MRZ / MP3-H1; the type of a soft-bit consumer (sonde_softin_dev_create_mrz, include/sonde_fsk.h) and the kind of a generic engine's device decoder (sonde_engine_set_family, sonde_engine_set_family_mrz) */
 #define SONDE_MTS01  71         /* mts01mod.c: Meteosis MTS01; the type of a soft-bit consumer (sonde_softin_dev_create_mts01, include/sonde_fsk.h) and the kind of a generic engine's device decoder (sonde_engine_set_family) */
 #define SONDE_MIXED  100       /* cfg.sonde_type of sonde_engine_create_mixed: the type is a property of the channel (its group), not of the engine */
 #define SONDE_GENERIC 99        /* any other 2-FSK sonde of the reference's demod/mod family, described by a sonde_generic_t given to sonde_engine_create_generic;
-                                 * header hits + soft bits (sonde_engine_fetch_hits), framing stays with the caller — or, for four kinds, decoded records (sonde_engine_set_family) */
+                                 * header hits + soft bits (sonde_engine_fetch_hits), framing stays with the caller — or, for five kinds, decoded records (sonde_engine_set_family) */
 
 /* input forms (dsp.opt_iq of demod_mod.h:62; rs41mod.c:2674-2687,2786-2803) */
 #define SONDE_IN_IQ    0        /* baseband IQ, mixed by -fq and decimated to the IF rate (opt_iq = 5)        */
@@ -300,7 +300,7 @@ int  sonde_engine_fetch_soft1(sonde_engine_t *e, float *soft, int32_t max_frames
 /* find_header()'s threshold argument (demod_mod.c:1533) for the following process calls */
 int  sonde_engine_set_threshold(sonde_engine_t *e, float thres);
 
-/* Generic engines that carry Meisei, iMet-54, MTS01 or RS92 (the descriptions of family.FAMILY): the block codes of every header hit on the device, behind the
+/* Generic engines that carry Meisei, iMet-54, MTS01, RS92 or MRZ (the descriptions of family.FAMILY; MRZ: sonde_engine_set_family_mrz below): the block codes of every header hit on the device, behind the
  * frame sync that queued it on the same stream (k_family_hits, csrc/sonde_family_hits.hip; one wavefront per hit record), so that a decoded record comes to the host
  * instead of the hit's 1048 .. 2340 float soft bits.  Per kind the bit stage of sonde_<kind>_dec_frame (bit rule s >= 0, so -0.0 is a 1) and the end-of-frame
  * routine of the kind's soft-bit consumer: BCH(63,51) with the padding and word-parity rules | 8N1, de-interleave, Hamming(8,4), both check sums | the un-flip of a
@@ -311,13 +311,21 @@ typedef struct {
                                                  soft bits via sonde_engine_fetch_soft, text via sonde_<kind>_dec_frame */
     uint32_t mv_pos;  float mv;               /* exactly sonde_hit_t's values */
     int32_t  v[6];                            /* Meisei: err_frm, err_blks | iMet-54: ecc_frm, ecc_tlm, ecc_std, crc_std, crc_cont
-                                                 | MTS01: crcval, crcdat, crc_ok | RS92: ec */
+                                                 | MTS01: crcval, crcdat, crc_ok | RS92: ec
+                                                 | MRZ: crc_ok at 408 bits, crc_ok at 384 bits, crclen, crcval408 | crcval384 << 16, crcdat408 | crcdat384 << 16, bits_ofs */
     uint8_t  aux[12];                         /* Meisei: block_err[12] */
-    uint8_t  data[240];                       /* Meisei 75 (600 bits MSB first) | iMet-54 108 | MTS01 131 | RS92 240 */
+    uint8_t  data[240];                       /* Meisei 75 (600 bits MSB first) | iMet-54 108 | MTS01 131 | RS92 240 | MRZ 51 (408 bits from the header's first, MSB first) */
 } sonde_family_hit_t;
-/* Before the first process call, on a SONDE_GENERIC engine with keep_soft (not a mixed one): kind = SONDE_MEISEI / SONDE_IMET54 / SONDE_MTS01 / SONDE_RS92, whose
- * nbits and symlen the engine's description must have (SONDE_E_ARG otherwise); ecc = the decoder's --ecc (RS92 always corrects: ecc != 0). */
+/* Before the first process call, on a SONDE_GENERIC engine with keep_soft (not a mixed one): kind = SONDE_MEISEI / SONDE_IMET54 / SONDE_MTS01 / SONDE_RS92 /
+ * SONDE_MRZ, whose nbits and symlen the engine's description must have (SONDE_E_ARG otherwise); ecc = the decoder's --ecc (RS92 always corrects: ecc != 0; MRZ has
+ * no code to correct: ignored, and --ofs is the decoder's default 8). */
 int  sonde_engine_set_family(sonde_engine_t *e, int32_t kind, int32_t ecc);
+/* MRZ (k_mrz_hits, csrc/sonde_mrz_hits.hip): sonde_engine_set_family(e, SONDE_MRZ, ..) with the decoder's --ofs, 0 .. 64 (SONDE_E_ARG otherwise).  The host decoder
+ * reads 386 or 362 soft bits of a hit, by the CRC verdicts of the channel's earlier frames (408 bits ECEF, 384 bits lat / lon with the 22 header bits); the bytes
+ * behind the length in effect are zero, so the verdict depends on (bits, length, --ofs) alone.  The device gives it under both lengths, and the channel's decoder,
+ * which sees the records in order, picks: sonde_mrz_dec_decoded(data, nb, nb == 408 ? v[0] : v[1]) with nb = sonde_mrz_dec_frame_bits + 22.  A hit of fewer than
+ * 386 bits (end of input) comes with decoded = 0. */
+int  sonde_engine_set_family_mrz(sonde_engine_t *e, int32_t bits_ofs);
 /* The hits completed so far as decoded records (finish != 0: end of input, a hit in progress comes with decoded = 0); needs sonde_engine_set_family.
  * sonde_engine_fetch_soft answers for the hits just returned.  sonde_engine_fetch_hits keeps working on such an engine: a record is delivered once, by whichever
  * fetch takes it.  sonde_engine_set_device_ecc(e, 0) (everything queued fetched first) leaves the hits that follow undecoded, decoded = 0. */
@@ -325,6 +333,8 @@ int  sonde_engine_fetch_family(sonde_engine_t *e, sonde_family_hit_t *out, int32
 /* The same kernel on n hits in host memory (tests, tools): hit i = nbits[i] (<= stride) soft bits at soft + i * stride, in the polarity the engine stores.
  * out[i].channel = i, mv = 0, mv_pos = 0. */
 int  sonde_family_decode_device(int32_t kind, int32_t ecc, const float *soft, int64_t stride, const int32_t *nbits, int32_t n, sonde_family_hit_t *out);
+/* The same for MRZ hits (k_mrz_hits): stride >= 386, bits_ofs 0 .. 64. */
+int  sonde_mrz_decode_device(int32_t bits_ofs, const float *soft, int64_t stride, const int32_t *nbits, int32_t n, sonde_family_hit_t *out);
 
 /* DFM engines: frames completed so far (syncs).  The hits are sliced into frames and Hamming-decoded (dfm09mod.c:240-345) on the device behind the frame sync
  * (k_dfm_hits; the host decode remains as the A/B path, sonde_engine_set_device_ecc(e, 0)); only decoded frames come to the host, the soft bits on request.  cfg.ecc_level 0/1/2

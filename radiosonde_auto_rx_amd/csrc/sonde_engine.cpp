@@ -46,9 +46,9 @@ struct sonde_engine {
     // slot, {done, ticket}, the bit characters per channel of M10 or M20 (d_m10_bits: mxx_chars() of them a channel)
     sonde_dfm_frame_t *d_dfm_out = nullptr; sonde_m10_frame_t *d_m10_out = nullptr; sonde_m20_frame_t *d_m20_out = nullptr; unsigned *d_blk_done = nullptr; char *d_m10_bits = nullptr;
     std::vector<sonde_dfm_frame_t> h_dfm; std::vector<sonde_m10_frame_t> h_m10; std::vector<sonde_m20_frame_t> h_m20; bool soft_lazy = false; unsigned soft_lazy_start = 0;
-    // generic engines whose hits are decoded on the device (sonde_engine_set_family; k_family_hits, sonde_family_hits.hip): the kind, its --ecc, a record per ring
-    // slot, what the kind's kernel reads besides the hits; d_blk_done is its {done, ticket}
-    int fam_kind = 0, fam_ecc = 0; sonde_family_hit_t *d_fam_out = nullptr; const uint32_t *d_fam_tab = nullptr; const uint8_t *d_fam_gf = nullptr;
+    // generic engines whose hits are decoded on the device (sonde_engine_set_family; k_family_hits, sonde_family_hits.hip; k_mrz_hits, sonde_mrz_hits.hip): the
+    // kind, its --ecc (MRZ: its --ofs), a record per ring slot, what the kind's kernel reads besides the hits; d_blk_done is its {done, ticket}
+    int fam_kind = 0, fam_ecc = 0, fam_ofs = 8; sonde_family_hit_t *d_fam_out = nullptr; const uint32_t *d_fam_tab = nullptr; const uint8_t *d_fam_gf = nullptr;
     std::vector<sonde_family_hit_t> h_fam;
     uint32_t *d_ecc_list = nullptr; unsigned *d_ecc_cnt = nullptr;     // two work lists of max_frames record slots, alternating per call; {count[2], done[2]}
     hipEvent_t ev_a[4] = {}, ev_b[4] = {}, ev_if[4] = {};      // per call: decimator done (A), records complete (B / E), y ring read (B: IF chain done)
@@ -209,6 +209,8 @@ extern "C" void sonde_launch_m20_hits(const FrameRec *frames, int n_channels, in
 extern "C" void sonde_launch_family_hits(int kind, int ecc, const FrameRec *frames, const int *nbits_direct, const float *soft, long long stride, int max_frames,
                                          const unsigned *fcount, unsigned *done, const uint32_t *tab, const uint8_t *gf, sonde_family_hit_t *out, int grid, hipStream_t s);
 int sonde_family_tables(DevMem &mem, int kind, const uint32_t **tab, const uint8_t **gf);
+extern "C" void sonde_launch_mrz_hits(int bits_ofs, const FrameRec *frames, const int *nbits_direct, const float *soft, long long stride, int max_frames,
+                                      const unsigned *fcount, unsigned *done, sonde_family_hit_t *out, int grid, hipStream_t s);
 static bool blockcodes_on_device(const sonde_engine *e);
 // bit characters a channel of an M10 / M20 engine keeps from frame to frame: 8 per frame byte and the terminator (m10mod.c:90-94, m20mod.c:83-87)
 static inline size_t mxx_chars(const sonde_engine *e) { return (size_t)(e->cfg.sonde_type == SONDE_M20 ? 101 + 64 : 101 + 20) * 8 + 8; }
@@ -218,8 +220,11 @@ static bool family_on_device(const sonde_engine *e) { return e->dev_ecc && e->fa
 static void launch_blockcodes(sonde_engine *e) {
     const int grid = std::max(1, std::min(e->cfg.n_channels, 1024));
     if (family_on_device(e)) {
-        sonde_launch_family_hits(e->fam_kind, e->fam_ecc, e->d_frames, nullptr, e->d_soft, (long long)e->nbits, e->max_frames, e->d_fcount, e->d_blk_done, e->d_fam_tab,
-                                 e->d_fam_gf, e->d_fam_out, grid, e->stream_b);
+        if (e->fam_kind == SONDE_MRZ)
+            sonde_launch_mrz_hits(e->fam_ofs, e->d_frames, nullptr, e->d_soft, (long long)e->nbits, e->max_frames, e->d_fcount, e->d_blk_done, e->d_fam_out, grid, e->stream_b);
+        else
+            sonde_launch_family_hits(e->fam_kind, e->fam_ecc, e->d_frames, nullptr, e->d_soft, (long long)e->nbits, e->max_frames, e->d_fcount, e->d_blk_done, e->d_fam_tab,
+                                     e->d_fam_gf, e->d_fam_out, grid, e->stream_b);
         return;
     }
     if (!blockcodes_on_device(e)) return;
@@ -1491,17 +1496,23 @@ int sonde_engine_fetch_hits(sonde_engine_t *e, sonde_hit_t *out, int32_t max, in
     return n;                                  // frames dropped by a full queue: sonde_engine_overflowed()
 }
 
-int sonde_engine_set_family(sonde_engine_t *e, int32_t kind, int32_t ecc) {
+// ecc: the decoder's --ecc (MRZ has no code to correct: ignored); bits_ofs: MRZ's --ofs
+static int set_family_impl(sonde_engine_t *e, int32_t kind, int32_t ecc, int32_t bits_ofs) {
     // the descriptions of family.FAMILY: soft bits of a hit, symbol length
-    const int nb = kind == SONDE_MEISEI ? 1152 : kind == SONDE_IMET54 ? 2200 : kind == SONDE_MTS01 ? 1048 : kind == SONDE_RS92 ? 2340 : 0, sl = kind == SONDE_RS92 ? 2 : 1;
+    const int nb = kind == SONDE_MEISEI ? 1152 : kind == SONDE_IMET54 ? 2200 : kind == SONDE_MTS01 ? 1048 : kind == SONDE_RS92 ? 2340 : kind == SONDE_MRZ ? 386 : 0;
+    const int sl = kind == SONDE_RS92 || kind == SONDE_MRZ ? 2 : 1;
     if (!e || !e->groups.empty() || e->is_group || e->front_only || e->cfg.sonde_type != SONDE_GENERIC || !e->cfg.keep_soft || !e->d_soft || e->call > 0 || e->fam_kind) return SONDE_E_ARG;
-    if (!nb || e->nbits != nb || e->symlen != sl || (kind == SONDE_RS92 && !ecc)) return SONDE_E_ARG;      // (RS92's consumer always corrects)
+    if (!nb || e->nbits != nb || e->symlen != sl || (kind == SONDE_RS92 && !ecc) || bits_ofs < 0 || bits_ofs > 64) return SONDE_E_ARG;      // (RS92's consumer always corrects)
     if (!e->d_fam_out) TRY(e->mem.dalloc(&e->d_fam_out, (size_t)e->max_frames));
     if (!e->d_blk_done) TRY(e->mem.dalloc(&e->d_blk_done, 2));
-    TRY(sonde_family_tables(e->mem, kind, &e->d_fam_tab, &e->d_fam_gf));
-    e->fam_kind = kind; e->fam_ecc = ecc ? 1 : 0;
+    if (kind != SONDE_MRZ) TRY(sonde_family_tables(e->mem, kind, &e->d_fam_tab, &e->d_fam_gf));
+    e->fam_kind = kind; e->fam_ecc = ecc ? 1 : 0; e->fam_ofs = bits_ofs;
     return 0;
 }
+
+int sonde_engine_set_family(sonde_engine_t *e, int32_t kind, int32_t ecc) { return set_family_impl(e, kind, ecc, 8); }      // (8: mp3h1mod's --ofs default)
+
+int sonde_engine_set_family_mrz(sonde_engine_t *e, int32_t bits_ofs) { return set_family_impl(e, SONDE_MRZ, 0, bits_ofs); }
 
 int sonde_engine_fetch_family(sonde_engine_t *e, sonde_family_hit_t *out, int32_t max, int32_t finish) {
     if (!e || !e->groups.empty() || !out || max < 0 || !e->fam_kind) return SONDE_E_ARG;
@@ -1510,7 +1521,7 @@ int sonde_engine_fetch_family(sonde_engine_t *e, sonde_family_hit_t *out, int32_
     const bool on_dev = family_on_device(e);
     const int n = collect_records(e, 0, recs, nullptr, max);
     if (n < 0) return n;
-    // the hits were decoded on the device behind the frame sync (k_family_hits): only the records come over — the soft bits stay where they are until
+    // the hits were decoded on the device behind the frame sync (k_family_hits, k_mrz_hits): only the records come over — the soft bits stay where they are until
     // sonde_engine_fetch_soft asks for them (a hit that was not decoded gets its host decode that way)
     const unsigned start = e->read_idx - (unsigned)n;
     e->last_n = n; e->soft_lazy = true; e->soft_lazy_start = start;

@@ -405,15 +405,21 @@ class Engine:
             _chk(lib().sonde_engine_fetch_soft(self._h, soft.ctypes.data_as(C.c_void_p), k))
         return [dict(channel=buf[i].channel, nbits=buf[i].nbits, mv=buf[i].mv, mv_pos=buf[i].mv_pos, soft=soft[i, :buf[i].nbits].copy()) for i in range(k)]
 
-    def set_family(self, kind: str, ecc: int = 1):
-        """Generic engines carrying Meisei, iMet-54, MTS01 or RS92 (kind = a key of family.DEVICE_KINDS, the engine created with that FAMILY description): decode
-        every hit on the device behind the frame sync; results through fetch_family().  Before the first process call."""
-        from .family import DEVICE_KINDS
-        if kind not in DEVICE_KINDS:
+    def set_family(self, kind: str, ecc: int = 1, bits_ofs: int = 8):
+        """Generic engines carrying Meisei, iMet-54, MTS01, RS92 or MRZ (kind = a key of family.DEVICE_KINDS_ALL, the engine created with that FAMILY description):
+        decode every hit on the device behind the frame sync; results through fetch_family().  Before the first process call.  ecc: the decoder's --ecc (MRZ has
+        none); bits_ofs: MRZ's --ofs, which the FamilyDecoder printing the records must have too."""
+        from .family import DEVICE_KINDS_ALL
+        if kind not in DEVICE_KINDS_ALL:
             raise SondeError(f"set_family: hits of type {kind} are not decoded on the device")
+        if kind == "MRZ":
+            f = lib().sonde_engine_set_family_mrz
+            f.argtypes = [C.c_void_p, C.c_int32]
+            _chk(f(self._h, int(bits_ofs)))
+            return
         f = lib().sonde_engine_set_family
         f.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
-        _chk(f(self._h, DEVICE_KINDS[kind], int(ecc)))
+        _chk(f(self._h, DEVICE_KINDS_ALL[kind], int(ecc)))
 
     def fetch_family(self, finish: bool = False, max_hits: int | None = None):
         """After set_family(): the hits completed so far as decoded records (dicts of sonde_family_hit_t: channel, kind, nbits, decoded, mv_pos, mv, v, aux, data),

@@ -85,9 +85,11 @@ FAMILY["LMSX"] = dict(FAMILY["LMS6"], generic=dict(FAMILY["LMS6"]["generic"], sl
 LMS_BASE = {"LMSX": "LMS6"}                      # receiver bookkeeping: the scanner's name of a sonde's type
 
 
-# The kinds whose hits a generic engine decodes on the device (sonde_engine_set_family, include/sonde_hip.h): FAMILY key -> SONDE_* kind.  LMS6 / LMS-X and MRZ
-# keep the host path.
+# The kinds whose hits a generic engine decodes on the device (sonde_engine_set_family, include/sonde_hip.h): FAMILY key -> SONDE_* kind.  DEVICE_KINDS are the four
+# of k_family_hits, one verdict per hit; MRZ (k_mrz_hits) comes with a verdict for either frame length and its --ofs, so it has entries of its own
+# (decode_mrz_hits_device, Engine.set_family's bits_ofs).  Membership is asked of DEVICE_KINDS_ALL.  LMS6 / LMS-X keep the host path.
 DEVICE_KINDS = {"MEISEI": 11, "IMET5": 54, "MTS01": 71, "RS92": 92}
+DEVICE_KINDS_ALL = dict(DEVICE_KINDS, MRZ=31)
 
 
 class FamilyHit(C.Structure):
@@ -119,6 +121,25 @@ def decode_hits_device(kind: str, hits, ecc: int = 1):
     return [family_hit_dict(out[i]) for i in range(len(hits))]
 
 
+def decode_mrz_hits_device(hits, bits_ofs: int = 8):
+    """The engines' per-hit MRZ decoder (k_mrz_hits) on hits in host memory (sonde_mrz_decode_device): hits = float32 soft-bit arrays as the engine stores them, each
+    up to 386 long (a shorter one comes back with decoded = 0); bits_ofs = the decoder's --ofs.  -> dicts; channel = the hit's index."""
+    nb = FAMILY["MRZ"]["generic"]["nbits"]
+    soft = np.zeros((max(len(hits), 1), nb), np.float32)
+    n = np.zeros(max(len(hits), 1), np.int32)
+    for i, h in enumerate(hits):
+        h = np.asarray(h, np.float32)
+        soft[i, :len(h)] = h
+        n[i] = len(h)
+    out = (FamilyHit * max(len(hits), 1))()
+    fn = lib().sonde_mrz_decode_device
+    fn.argtypes = [_I, C.c_void_p, C.c_int64, C.c_void_p, _I, C.POINTER(FamilyHit)]
+    rc = fn(int(bits_ofs), soft.ctypes.data, nb, n.ctypes.data, len(hits), out)
+    if rc < 0:
+        raise SondeError(f"sonde_mrz_decode_device: {lib().sonde_strerror(rc).decode()} ({rc})")
+    return [family_hit_dict(out[i]) for i in range(len(hits))]
+
+
 class FamilyDecoder:
     """one decoder object of type `typ` (a key of FAMILY): state lives across hits like the reference's gpx_t"""
 
@@ -145,6 +166,7 @@ class FamilyDecoder:
             self._fn.argtypes = [C.c_void_p, C.c_void_p, _I, C.c_char_p, C.c_size_t]
         if typ == "MRZ":
             L.sonde_mrz_dec_frame_bits.argtypes = [C.c_void_p]
+            self.bits_ofs = int(o.bits_ofs) if o.bits_ofs_given else 8     # --ofs as sonde_mrz_dec_create takes it: a device record must have been made under it
         if typ == "RS92":                                              # without orbit data: frames and JSON-less text only, as `rs92mod` without -e / -a
             for kind in ("almanac", "ephemeris"):
                 path = kw.get(kind) or RS92_ORBITS[kind]
@@ -200,6 +222,13 @@ class FamilyDecoder:
         elif self.typ == "RS92":
             L.sonde_rs92_dec_corrected.argtypes = [C.c_void_p, C.c_char_p, _I, C.c_char_p, C.c_size_t]
             k = L.sonde_rs92_dec_corrected(self._h, d[:240], v[0], self._buf, len(self._buf))
+        elif self.typ == "MRZ":
+            # the device gave the CRC verdict under both frame lengths (k_mrz_hits): this decoder's state says which one it would have read the hit with
+            if v[5] != self.bits_ofs:
+                raise SondeError(f"MRZ: the record was decoded with --ofs {v[5]}, this decoder has --ofs {self.bits_ofs}")
+            nb = L.sonde_mrz_dec_frame_bits(self._h) + 22
+            L.sonde_mrz_dec_decoded.argtypes = [C.c_void_p, C.c_char_p, _I, _I, C.c_char_p, C.c_size_t]
+            k = L.sonde_mrz_dec_decoded(self._h, d[:52], nb, v[0] if nb == 408 else v[1], self._buf, len(self._buf))
         else:
             raise SondeError(f"{self.typ}: hits of this type are not decoded on the device")
         if k < 0:

@@ -1286,12 +1286,13 @@ def mrz_frame(k: int = 0, *, latlon: bool = False, lat=55.751244, lon=37.618423,
     return bytes(f)
 
 
-def mrz_symbols(n_seconds: int, repeats: int = 2, **kw) -> np.ndarray:
+def mrz_symbols(n_seconds: int, repeats: int = 2, k0: int = 0, **kw) -> np.ndarray:
     """half symbols at 2399 Bd: per second `repeats` copies of the frame back to back, each as AA + frame bytes MSB first in Manchester (1 -> 10,
-    0 -> 01, mp3h1mod.c:133-135), then AA AA and random idle symbols"""
+    0 -> 01, mp3h1mod.c:133-135), then AA AA and random idle symbols.  k0: the first second's frame counter (12: the serial numbers and the date, which
+    the decoder's JSON waits for, come in the first four seconds)"""
     out = []
     for k in range(n_seconds):
-        fr = mrz_frame(k, **kw)
+        fr = mrz_frame(k0 + k, **kw)
         bits = []
         for _ in range(repeats):
             bits += list(np.unpackbits(np.frombuffer(bytes([0xAA]) + fr, np.uint8)))
