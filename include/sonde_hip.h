@@ -44,7 +44,7 @@ extern "C" {
 
 #define SONDE_RD94RD41 94       /* rd94rd41drop.c: Vaisala RD94 / RD41 dropsondes; only as the type of a soft-bit consumer (sonde_softin_dev_create)
                                    and by name in the scanner; the engine of its own is include/sonde_drop.h */
-#define SONDE_LMS6   6          /* lms6Xmod.c: LMS6-403 / LMS-X; only as the type of a soft-bit consumer (sonde_softin_dev_create_lms6, include/sonde_fsk.h) */
+#define SONDE_LMS6   6          /* lms6Xmod.c: LMS6-403 / LMS-X; the type of a soft-bit consumer (sonde_softin_dev_create_lms6, include/sonde_fsk.h) and the kind of a generic engine's device decoder, with a record type and entries of its own (sonde_engine_set_family_lms6, sonde_engine_fetch_family_lms6) */
 #define SONDE_RS92   92         /* rs92mod.c: Vaisala RS92-SGP / -NGP; the type of a soft-bit consumer (sonde_softin_dev_create_rs92, include/sonde_fsk.h) and the kind of a generic engine's device decoder (sonde_engine_set_family) */
 #define SONDE_IMET54 54         /* imet54mod.c: InterMet iMet-54 / iMet-50; the type of a soft-bit consumer (sonde_softin_dev_create_imet54, include/sonde_fsk.h) and the kind of a generic engine's device decoder (sonde_engine_set_family) */
 #define SONDE_MEISEI 11         /* meisei100mod.c: Meisei iMS-100 / RS-11G; the type of a soft-bit consumer (sonde_softin_dev_create_meisei, include/sonde_fsk.h) and the kind of a generic engine's device decoder (sonde_engine_set_family) */
@@ -52,7 +52,7 @@ extern "C" {
 #define SONDE_MTS01  71         /* mts01mod.c: Meteosis MTS01; the type of a soft-bit consumer (sonde_softin_dev_create_mts01, include/sonde_fsk.h) and the kind of a generic engine's device decoder (sonde_engine_set_family) */
 #define SONDE_MIXED  100       /* cfg.sonde_type of sonde_engine_create_mixed: the type is a property of the channel (its group), not of the engine */
 #define SONDE_GENERIC 99        /* any other 2-FSK sonde of the reference's demod/mod family, described by a sonde_generic_t given to sonde_engine_create_generic;
-                                 * header hits + soft bits (sonde_engine_fetch_hits), framing stays with the caller — or, for five kinds, decoded records (sonde_engine_set_family) */
+                                 * header hits + soft bits (sonde_engine_fetch_hits), framing stays with the caller — or, for six kinds, decoded records (sonde_engine_set_family, _set_family_lms6) */
 
 /* input forms (dsp.opt_iq of demod_mod.h:62; rs41mod.c:2674-2687,2786-2803) */
 #define SONDE_IN_IQ    0        /* baseband IQ, mixed by -fq and decimated to the IF rate (opt_iq = 5)        */
@@ -335,6 +335,31 @@ int  sonde_engine_fetch_family(sonde_engine_t *e, sonde_family_hit_t *out, int32
 int  sonde_family_decode_device(int32_t kind, int32_t ecc, const float *soft, int64_t stride, const int32_t *nbits, int32_t n, sonde_family_hit_t *out);
 /* The same for MRZ hits (k_mrz_hits): stride >= 386, bits_ofs 0 .. 64. */
 int  sonde_mrz_decode_device(int32_t bits_ofs, const float *soft, int64_t stride, const int32_t *nbits, int32_t n, sonde_family_hit_t *out);
+
+/* Generic engines that carry LMS6-403 or LMS-X (family.FAMILY["LMS6"]: 4096 soft bits a hit, ["LMSX"]: 4720): the convolutional code of every header hit on the
+ * device, behind the frame sync that queued it (k_lms6_hits, csrc/sonde_lms6_hits.hip; one wavefront per hit record), so that at most 308 block bytes come to the
+ * host instead of 4096 / 4720 float soft bits.  Per hit what sonde_lms6_dec_block does up to block_bytes: the un-flip of a header of negative score, the sign
+ * alternation of every second raw bit from the phase the score gives, the K = 7 Viterbi decoder, deconv, bits2bytes.  The text comes from the record through
+ * sonde_lms6_dec_block_bytes(bytes, blen, len, mv, ..) on the channel's decoder (include/sonde_lms6.h), whose --vit / --vit2 must be the record's vit and whose
+ * block must be at least nbits long (sonde_lms6_dec_block_bits; a decoder that wants fewer bits gets the hit's soft bits through sonde_lms6_dec_block). */
+typedef struct {
+    int32_t  channel, kind, nbits, decoded;   /* kind = SONDE_LMS6; decoded 0: hit shorter than the engine's block (end of input), or device decoding switched off —
+                                                 everything behind mv zero, soft bits via sonde_engine_fetch_soft, text via sonde_lms6_dec_block */
+    uint32_t mv_pos;  float mv;               /* exactly sonde_hit_t's values */
+    int32_t  len, blen, err, vit;             /* raw positions decoded (80 + nbits), bytes cut, deconv's error index (0: none), 1 = --vit, 2 = --vit2 */
+    uint8_t  bytes[308];                      /* block_bytes, zero behind blen */
+} sonde_lms6_hit_t;
+/* Under sonde_engine_set_family's preconditions (a SONDE_GENERIC engine with keep_soft, not a mixed one, before the first process call, once), on a description of
+ * symlen 1 and 4096 or 4720 soft bits a hit; vit = 1 (--vit) or 2 (--vit2).  SONDE_E_ARG otherwise: the algebraic deconvolution alone (vit = 0) and --ecc3's
+ * second soft value are not decoded on the device.  sonde_engine_set_family(e, SONDE_LMS6, ..) stays SONDE_E_ARG. */
+int  sonde_engine_set_family_lms6(sonde_engine_t *e, int32_t vit);
+/* sonde_engine_fetch_family for such an engine, and only for such an engine (sonde_engine_fetch_family on it: SONDE_E_ARG): the same rules for finish,
+ * sonde_engine_fetch_soft, sonde_engine_fetch_hits and sonde_engine_set_device_ecc(e, 0). */
+int  sonde_engine_fetch_family_lms6(sonde_engine_t *e, sonde_lms6_hit_t *out, int32_t max, int32_t finish);
+/* The same kernel on n hits in host memory (tests, tools): hit i = nbits[i] (<= stride) soft bits at soft + i * stride, in the polarity the engine stores, with the
+ * header score mv[i] (required: its sign is the phase of the alternation); stride = 4096 or 4720 = the length a complete hit has.  out[i].channel = i, mv_pos = 0.
+ * Arguments are checked before the device is touched. */
+int  sonde_lms6_decode_device(int32_t vit, const float *soft, int64_t stride, const int32_t *nbits, const float *mv, int32_t n, sonde_lms6_hit_t *out);
 
 /* DFM engines: frames completed so far (syncs).  The hits are sliced into frames and Hamming-decoded (dfm09mod.c:240-345) on the device behind the frame sync
  * (k_dfm_hits; the host decode remains as the A/B path, sonde_engine_set_device_ecc(e, 0)); only decoded frames come to the host, the soft bits on request.  cfg.ecc_level 0/1/2

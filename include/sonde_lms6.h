@@ -48,6 +48,9 @@ int  sonde_lms6_dec_block_bits(const sonde_lms6_dec_t *d);
 /* 6 or 10 (| 0x0200 for the LMS6-403-2 frame sync): the type in effect; *symbol_rate_changed = 1 when the last block made the auto
  * detection switch between LMS6 (4800 Bd) and LMS-X (4797.8 Bd) — the caller's demodulator has to follow (lms6Xmod.c:1436-1462). */
 int  sonde_lms6_dec_type(const sonde_lms6_dec_t *d, int32_t *symbol_rate_changed);
+/* The decoder of the convolutional code in effect, after --json's implications: 0 = algebraic, 1 = --vit, 2 = --vit2; *ecc = 0, 1 or 3 likewise.  What a caller
+ * that brings block bytes decoded elsewhere (sonde_lms6_dec_block_bytes) has to have decoded them with. */
+int  sonde_lms6_dec_vit(const sonde_lms6_dec_t *d, int32_t *ecc);
 
 /* One header hit from a demodulator: nbits (<= block_bits) soft values of the bits behind the 64-bit header in RAW polarity, as
  * read_softbit2p() returns them (soft1: the second soft value per bit, may be NULL), mv = header score (its sign is the phase of the

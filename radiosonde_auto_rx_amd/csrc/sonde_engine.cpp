@@ -50,6 +50,8 @@ struct sonde_engine {
     // kind, its --ecc (MRZ: its --ofs), a record per ring slot, what the kind's kernel reads besides the hits; d_blk_done is its {done, ticket}
     int fam_kind = 0, fam_ecc = 0, fam_ofs = 8; sonde_family_hit_t *d_fam_out = nullptr; const uint32_t *d_fam_tab = nullptr; const uint8_t *d_fam_gf = nullptr;
     std::vector<sonde_family_hit_t> h_fam;
+    // the same for LMS6 / LMS-X (sonde_engine_set_family_lms6; k_lms6_hits, sonde_lms6_hits.hip): fam_kind = SONDE_LMS6, its --vit / --vit2, a record of its own type per ring slot
+    int fam_vit = 0; sonde_lms6_hit_t *d_lms_out = nullptr; std::vector<sonde_lms6_hit_t> h_lms;
     uint32_t *d_ecc_list = nullptr; unsigned *d_ecc_cnt = nullptr;     // two work lists of max_frames record slots, alternating per call; {count[2], done[2]}
     hipEvent_t ev_a[4] = {}, ev_b[4] = {}, ev_if[4] = {};      // per call: decimator done (A), records complete (B / E), y ring read (B: IF chain done)
     Pinned<unsigned> h_count;          // mapped: frame counter snapshot after each call's framesync
@@ -211,16 +213,21 @@ extern "C" void sonde_launch_family_hits(int kind, int ecc, const FrameRec *fram
 int sonde_family_tables(DevMem &mem, int kind, const uint32_t **tab, const uint8_t **gf);
 extern "C" void sonde_launch_mrz_hits(int bits_ofs, const FrameRec *frames, const int *nbits_direct, const float *soft, long long stride, int max_frames,
                                       const unsigned *fcount, unsigned *done, sonde_family_hit_t *out, int grid, hipStream_t s);
+extern "C" void sonde_launch_lms6_hits(int vit, int nb, const FrameRec *frames, const int *nbits_direct, const float *mv_direct, const float *soft, long long stride,
+                                       int max_frames, const unsigned *fcount, unsigned *done, sonde_lms6_hit_t *out, int grid, hipStream_t s);
 static bool blockcodes_on_device(const sonde_engine *e);
 // bit characters a channel of an M10 / M20 engine keeps from frame to frame: 8 per frame byte and the terminator (m10mod.c:90-94, m20mod.c:83-87)
 static inline size_t mxx_chars(const sonde_engine *e) { return (size_t)(e->cfg.sonde_type == SONDE_M20 ? 101 + 64 : 101 + 20) * 8 + 8; }
 // a generic engine whose hits are decoded behind the frame sync (sonde_engine_set_family), with the switch of sonde_engine_set_device_ecc as it stands
-static bool family_on_device(const sonde_engine *e) { return e->dev_ecc && e->fam_kind && e->d_soft && e->d_blk_done && e->d_fam_out; }
+static bool family_on_device(const sonde_engine *e) { return e->dev_ecc && e->fam_kind && e->d_soft && e->d_blk_done && (e->fam_kind == SONDE_LMS6 ? e->d_lms_out != nullptr : e->d_fam_out != nullptr); }
 // behind every frame-sync launch: the block codes of the hits it has queued (DFM Hamming(8,4), M10 / M20 checksums, the generic family's per-hit decoders), on the same stream
 static void launch_blockcodes(sonde_engine *e) {
     const int grid = std::max(1, std::min(e->cfg.n_channels, 1024));
     if (family_on_device(e)) {
-        if (e->fam_kind == SONDE_MRZ)
+        if (e->fam_kind == SONDE_LMS6)
+            sonde_launch_lms6_hits(e->fam_vit, e->nbits, e->d_frames, nullptr, nullptr, e->d_soft, (long long)e->nbits, e->max_frames, e->d_fcount, e->d_blk_done, e->d_lms_out, grid,
+                                   e->stream_b);
+        else if (e->fam_kind == SONDE_MRZ)
             sonde_launch_mrz_hits(e->fam_ofs, e->d_frames, nullptr, e->d_soft, (long long)e->nbits, e->max_frames, e->d_fcount, e->d_blk_done, e->d_fam_out, grid, e->stream_b);
         else
             sonde_launch_family_hits(e->fam_kind, e->fam_ecc, e->d_frames, nullptr, e->d_soft, (long long)e->nbits, e->max_frames, e->d_fcount, e->d_blk_done, e->d_fam_tab,
@@ -1514,8 +1521,39 @@ int sonde_engine_set_family(sonde_engine_t *e, int32_t kind, int32_t ecc) { retu
 
 int sonde_engine_set_family_mrz(sonde_engine_t *e, int32_t bits_ofs) { return set_family_impl(e, SONDE_MRZ, 0, bits_ofs); }
 
+// LMS6 / LMS-X: set_family_impl's preconditions, a record type of its own (a block has up to 308 bytes)
+int sonde_engine_set_family_lms6(sonde_engine_t *e, int32_t vit) {
+    if (!e || !e->groups.empty() || e->is_group || e->front_only || e->cfg.sonde_type != SONDE_GENERIC || !e->cfg.keep_soft || !e->d_soft || e->call > 0 || e->fam_kind) return SONDE_E_ARG;
+    if ((vit != 1 && vit != 2) || e->symlen != 1 || (e->nbits != 4096 && e->nbits != 4720)) return SONDE_E_ARG;      // (the descriptions of family.FAMILY["LMS6"] / ["LMSX"])
+    if (!e->d_lms_out) TRY(e->mem.dalloc(&e->d_lms_out, (size_t)e->max_frames));
+    if (!e->d_blk_done) TRY(e->mem.dalloc(&e->d_blk_done, 2));
+    e->fam_kind = SONDE_LMS6; e->fam_vit = vit;
+    return 0;
+}
+
+int sonde_engine_fetch_family_lms6(sonde_engine_t *e, sonde_lms6_hit_t *out, int32_t max, int32_t finish) {
+    if (!e || !e->groups.empty() || !out || max < 0 || e->fam_kind != SONDE_LMS6) return SONDE_E_ARG;
+    if (finish) launch_framesync(e, 1);
+    std::vector<FrameRec> recs;
+    const bool on_dev = family_on_device(e);
+    const int n = collect_records(e, 0, recs, nullptr, max);
+    if (n < 0) return n;
+    // as in sonde_engine_fetch_family: only the records come over, the soft bits stay where they are until sonde_engine_fetch_soft asks for them
+    const unsigned start = e->read_idx - (unsigned)n;
+    e->last_n = n; e->soft_lazy = true; e->soft_lazy_start = start;
+    if (on_dev && copy_decoded(e, e->d_lms_out, e->h_lms, start, n, 1)) return SONDE_E_NOGPU;
+    for (int h = 0; h < n; h++) {
+        const FrameRec &r = recs[h];
+        sonde_lms6_hit_t &o = out[h];
+        if (on_dev) o = e->h_lms[h];
+        else { memset(&o, 0, sizeof o); o.channel = r.channel; o.kind = SONDE_LMS6; o.nbits = r.nbytes; o.mv = r.mv; }      // device decoding is switched off: the host's
+        o.mv_pos = rel_pos(e, r);
+    }
+    return n;                                  // hits dropped by a full queue: sonde_engine_overflowed()
+}
+
 int sonde_engine_fetch_family(sonde_engine_t *e, sonde_family_hit_t *out, int32_t max, int32_t finish) {
-    if (!e || !e->groups.empty() || !out || max < 0 || !e->fam_kind) return SONDE_E_ARG;
+    if (!e || !e->groups.empty() || !out || max < 0 || !e->fam_kind || e->fam_kind == SONDE_LMS6) return SONDE_E_ARG;
     if (finish) launch_framesync(e, 1);
     std::vector<FrameRec> recs;
     const bool on_dev = family_on_device(e);

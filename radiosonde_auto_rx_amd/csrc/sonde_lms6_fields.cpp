@@ -404,6 +404,12 @@ int sonde_lms6_dec_type(const sonde_lms6_dec_t *d, int32_t *changed) {
     return d->typ;
 }
 
+int sonde_lms6_dec_vit(const sonde_lms6_dec_t *d, int32_t *ecc) {
+    if (!d) return SONDE_E_ARG;
+    if (ecc) *ecc = d->o.ecc;
+    return d->o.vit;
+}
+
 const char *sonde_lms6_raw_header(void) { return kRawHeader; }
 
 int sonde_lms6_dec_counts(const sonde_lms6_dec_t *d, int64_t *frames, int64_t *crc_ok) {

@@ -405,11 +405,18 @@ class Engine:
             _chk(lib().sonde_engine_fetch_soft(self._h, soft.ctypes.data_as(C.c_void_p), k))
         return [dict(channel=buf[i].channel, nbits=buf[i].nbits, mv=buf[i].mv, mv_pos=buf[i].mv_pos, soft=soft[i, :buf[i].nbits].copy()) for i in range(k)]
 
-    def set_family(self, kind: str, ecc: int = 1, bits_ofs: int = 8):
-        """Generic engines carrying Meisei, iMet-54, MTS01, RS92 or MRZ (kind = a key of family.DEVICE_KINDS_ALL, the engine created with that FAMILY description):
-        decode every hit on the device behind the frame sync; results through fetch_family().  Before the first process call.  ecc: the decoder's --ecc (MRZ has
-        none); bits_ofs: MRZ's --ofs, which the FamilyDecoder printing the records must have too."""
-        from .family import DEVICE_KINDS_ALL
+    def set_family(self, kind: str, ecc: int = 1, bits_ofs: int = 8, vit: int = 2):
+        """Generic engines carrying Meisei, iMet-54, MTS01, RS92, MRZ (kind = a key of family.DEVICE_KINDS_ALL) or LMS6 / LMS-X (a key of family.DEVICE_KINDS_LMS),
+        the engine created with that FAMILY description: decode every hit on the device behind the frame sync; results through fetch_family().  Before the first
+        process call.  ecc: the decoder's --ecc (MRZ has none; LMS6's Reed-Solomon code stays on the host); bits_ofs: MRZ's --ofs, vit: LMS6's --vit (1) or --vit2
+        (2), which the FamilyDecoder printing the records must have too."""
+        from .family import DEVICE_KINDS_ALL, DEVICE_KINDS_LMS
+        if kind in DEVICE_KINDS_LMS:
+            f = lib().sonde_engine_set_family_lms6
+            f.argtypes = [C.c_void_p, C.c_int32]
+            _chk(f(self._h, int(vit)))
+            self._family_lms = True
+            return
         if kind not in DEVICE_KINDS_ALL:
             raise SondeError(f"set_family: hits of type {kind} are not decoded on the device")
         if kind == "MRZ":
@@ -421,23 +428,34 @@ class Engine:
         f.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
         _chk(f(self._h, DEVICE_KINDS_ALL[kind], int(ecc)))
 
-    def fetch_family(self, finish: bool = False, max_hits: int | None = None):
-        """After set_family(): the hits completed so far as decoded records (dicts of sonde_family_hit_t: channel, kind, nbits, decoded, mv_pos, mv, v, aux, data),
-        for FamilyDecoder.decoded().  A record with decoded = 0 carries its soft bits ("soft") for the host decode; max_hits: the rest stays queued."""
-        from .family import FamilyHit, family_hit_dict
+    def fetch_family(self, finish: bool = False, max_hits: int | None = None, need_soft=None):
+        """After set_family(): the hits completed so far as decoded records (dicts of sonde_family_hit_t: channel, kind, nbits, decoded, mv_pos, mv, v, aux, data; on
+        an LMS6 / LMS-X engine of sonde_lms6_hit_t: .. mv, len, blen, err, vit, bytes), for FamilyDecoder.decoded().  A record with decoded = 0 carries its soft bits
+        ("soft") for the host decode, and so does a decoded one for which need_soft(record) is true; max_hits: the rest stays queued."""
+        from .family import FamilyHit, Lms6Hit, family_hit_dict, lms6_hit_dict
+        lms = getattr(self, "_family_lms", False)
+        T, as_dict = (Lms6Hit, lms6_hit_dict) if lms else (FamilyHit, family_hit_dict)
         n = self._max_frames if max_hits is None else int(max_hits)
-        buf = (FamilyHit * max(n, 1))()
-        f = lib().sonde_engine_fetch_family
-        f.argtypes = [C.c_void_p, C.POINTER(FamilyHit), C.c_int32, C.c_int32]
+        buf = (T * max(n, 1))()
+        f = lib().sonde_engine_fetch_family_lms6 if lms else lib().sonde_engine_fetch_family
+        f.argtypes = [C.c_void_p, C.POINTER(T), C.c_int32, C.c_int32]
         k = _chk(f(self._h, buf, n, int(finish)))
-        recs = [family_hit_dict(buf[i]) for i in range(k)]
-        if any(not r["decoded"] for r in recs):
-            soft = np.zeros((k, self.nbits), np.float32)
-            _chk(lib().sonde_engine_fetch_soft(self._h, soft.ctypes.data_as(C.c_void_p), k))
+        recs = [as_dict(buf[i]) for i in range(k)]
+        want = [not r["decoded"] or (need_soft is not None and bool(need_soft(r))) for r in recs]
+        if any(want):
+            soft = self.last_soft(k)
             for i, r in enumerate(recs):
-                if not r["decoded"]:
+                if want[i]:
                     r["soft"] = soft[i, :r["nbits"]].copy()
         return recs
+
+    def last_soft(self, k: int):
+        """the soft bits of the first k hits the last fetch_hits() / fetch_family() returned, [k, nbits] float32 (sonde_engine_fetch_soft): after fetch_family() they
+        are still on the device and come over only when asked for"""
+        soft = np.zeros((max(k, 1), self.nbits), np.float32)
+        if k:
+            _chk(lib().sonde_engine_fetch_soft(self._h, soft.ctypes.data_as(C.c_void_p), k))
+        return soft
 
     def fetch_mxx(self, finish: bool = False, verbose: int = 1):
         """M10 / M20 engines: frames as dicts (bytes, checksum verdicts, the `m10mod -r [-v]` / `m20mod -r [-v]` text line)."""

@@ -87,9 +87,11 @@ LMS_BASE = {"LMSX": "LMS6"}                      # receiver bookkeeping: the sca
 
 # The kinds whose hits a generic engine decodes on the device (sonde_engine_set_family, include/sonde_hip.h): FAMILY key -> SONDE_* kind.  DEVICE_KINDS are the four
 # of k_family_hits, one verdict per hit; MRZ (k_mrz_hits) comes with a verdict for either frame length and its --ofs, so it has entries of its own
-# (decode_mrz_hits_device, Engine.set_family's bits_ofs).  Membership is asked of DEVICE_KINDS_ALL.  LMS6 / LMS-X keep the host path.
+# (decode_mrz_hits_device, Engine.set_family's bits_ofs).  Membership is asked of DEVICE_KINDS_ALL.  LMS6 / LMS-X (k_lms6_hits) have a record type of their own
+# — a block has up to 308 bytes — so they are DEVICE_KINDS_LMS, with Lms6Hit, decode_lms6_hits_device and Engine.set_family's vit.
 DEVICE_KINDS = {"MEISEI": 11, "IMET5": 54, "MTS01": 71, "RS92": 92}
 DEVICE_KINDS_ALL = dict(DEVICE_KINDS, MRZ=31)
+DEVICE_KINDS_LMS = {"LMS6": 6, "LMSX": 6}
 
 
 class FamilyHit(C.Structure):
@@ -140,10 +142,48 @@ def decode_mrz_hits_device(hits, bits_ofs: int = 8):
     return [family_hit_dict(out[i]) for i in range(len(hits))]
 
 
+class Lms6Hit(C.Structure):
+    """sonde_lms6_hit_t (include/sonde_hip.h)"""
+    _fields_ = [("channel", _I), ("kind", _I), ("nbits", _I), ("decoded", _I), ("mv_pos", C.c_uint32), ("mv", C.c_float), ("len", _I), ("blen", _I), ("err", _I),
+                ("vit", _I), ("bytes", C.c_uint8 * 308)]
+
+
+def lms6_hit_dict(r: Lms6Hit) -> dict:
+    return dict(channel=r.channel, kind=r.kind, nbits=r.nbits, decoded=r.decoded, mv_pos=r.mv_pos, mv=r.mv, len=r.len, blen=r.blen, err=r.err, vit=r.vit,
+                bytes=bytes(r.bytes))
+
+
+def decode_lms6_hits_device(hits, mvs, vit: int = 2, lmsx: bool = False):
+    """The engines' per-hit LMS6 / LMS-X decoder (k_lms6_hits) on hits in host memory (sonde_lms6_decode_device): hits = float32 soft-bit arrays as the engine
+    stores them, each up to 4096 (lmsx: 4720) long (a shorter one comes back with decoded = 0); mvs = their header scores, whose sign is the phase of the raw bits'
+    sign alternation; vit = 1 (--vit) or 2 (--vit2).  -> dicts; channel = the hit's index."""
+    nb = FAMILY["LMSX" if lmsx else "LMS6"]["generic"]["nbits"]
+    if len(mvs) != len(hits):
+        raise SondeError("decode_lms6_hits_device: a header score per hit")
+    soft = np.zeros((max(len(hits), 1), nb), np.float32)
+    n = np.zeros(max(len(hits), 1), np.int32)
+    mv = np.zeros(max(len(hits), 1), np.float32)
+    for i, h in enumerate(hits):
+        h = np.asarray(h, np.float32)
+        if len(h) > nb:
+            raise SondeError(f"decode_lms6_hits_device: hit {i} has {len(h)} soft bits, a block has {nb}")
+        soft[i, :len(h)] = h
+        n[i] = len(h)
+        mv[i] = mvs[i]
+    out = (Lms6Hit * max(len(hits), 1))()
+    fn = lib().sonde_lms6_decode_device
+    fn.argtypes = [_I, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, _I, C.POINTER(Lms6Hit)]
+    rc = fn(int(vit), soft.ctypes.data, nb, n.ctypes.data, mv.ctypes.data, len(hits), out)
+    if rc < 0:
+        raise SondeError(f"sonde_lms6_decode_device: {lib().sonde_strerror(rc).decode()} ({rc})")
+    return [lms6_hit_dict(out[i]) for i in range(len(hits))]
+
+
 class FamilyDecoder:
     """one decoder object of type `typ` (a key of FAMILY): state lives across hits like the reference's gpx_t"""
 
-    def __init__(self, typ: str, *, freq_khz: int = 0, version: str = "sonde_hip", **kw):
+    def __init__(self, typ: str, /, *, freq_khz: int = 0, version: str = "sonde_hip", **kw):
+        # (typ is positional only: the LMS6 decoder has an option of that name, 0 = auto detection, 6 = --lms6, 10 = --lmsX)
         self.typ, self.f = typ, FAMILY[typ]
         L = lib()
         p = self.f["prefix"]
@@ -160,6 +200,7 @@ class FamilyDecoder:
             self._fn = L.sonde_lms6_dec_block
             self._fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, _I, C.c_float, C.c_float, C.c_double, C.c_char_p, C.c_size_t]
             L.sonde_lms6_dec_block_bits.argtypes = [C.c_void_p]
+            L.sonde_lms6_dec_vit.argtypes = [C.c_void_p, C.POINTER(_I)]
             self._last_pos = 0
         else:
             self._fn = getattr(L, f"sonde_{p}_dec_frame")
@@ -182,6 +223,19 @@ class FamilyDecoder:
 
     __del__ = close
 
+    def _lms_rate(self, mv_pos: int, if_sr: int) -> float:
+        """LMS6: frm_rate of the block behind the header at mv_pos, from the header before it (lms6Xmod.c:1372)"""
+        d = (int(mv_pos) - self._last_pos) & 0xFFFFFFFF
+        rate = 4800.0 * if_sr / d if d else float("inf")
+        if getattr(self, "moved", False):                                  # first block on another engine (receivers, LMS6 <-> LMS-X): no header position to take the
+            rate, self.moved = 4800.0, False                              # frame rate from; a rate outside 4000..5000 would send the decoder back (lms6Xmod.c:959)
+        self._last_pos = int(mv_pos)
+        return rate
+
+    def lms_block_bits(self) -> int:
+        """LMS6 only: raw bits the decoder reads behind a header for the type in effect, 4096 or 4720"""
+        return lib().sonde_lms6_dec_block_bits(self._h)
+
     def hit(self, h: dict, if_sr: int = 48000) -> str:
         soft = np.ascontiguousarray(h["soft"], np.float32)
         if self.f["pol"] == "raw" and h["mv"] < 0:
@@ -189,11 +243,7 @@ class FamilyDecoder:
         n = len(soft)
         if self.typ == "LMS6":
             n = min(n, lib().sonde_lms6_dec_block_bits(self._h))           # a decoder that went over to LMS-X wants more bits than a fixed description slices
-            d = (int(h["mv_pos"]) - self._last_pos) & 0xFFFFFFFF
-            rate = 4800.0 * if_sr / d if d else float("inf")
-            if getattr(self, "moved", False):                              # first block on another engine (receivers, LMS6 <-> LMS-X): no header position to take the
-                rate, self.moved = 4800.0, False                          # frame rate from; a rate outside 4000..5000 would send the decoder back (lms6Xmod.c:959)
-            self._last_pos = int(h["mv_pos"])
+            rate = self._lms_rate(h["mv_pos"], if_sr)
             k = self._fn(self._h, soft.ctypes.data, None, n, h["mv"], rate, (h["mv_pos"] + n * if_sr / 4800.0) / if_sr, self._buf, len(self._buf))
         else:
             if self.typ == "MRZ":
@@ -206,9 +256,28 @@ class FamilyDecoder:
     def decoded(self, rec: dict, if_sr: int = 48000) -> str:
         """one dict of Engine.fetch_family(): the characters the reference decoder prints for that hit, from the device's bytes and verdicts (no block code runs
         here).  A record the device did not decode (decoded = 0: a hit cut short by the end of input, or device decoding switched off) goes through hit() on its
-        soft bits."""
+        soft bits.  LMS6: so does a record longer than the block this decoder reads (an LMS6 decoder on an LMS-X engine, in the block of the change) — it has to
+        carry its soft bits (Engine.fetch_family's need_soft); a record no longer than that is what hit() would have decoded (an LMS-X decoder still on an LMS6
+        engine reads the 4096 bits that exist)."""
         if not rec["decoded"]:
             return self.hit(rec, if_sr)
+        if self.typ == "LMS6":
+            ecc = _I(0)
+            vit = lib().sonde_lms6_dec_vit(self._h, C.byref(ecc))
+            if vit != rec["vit"] or ecc.value == 3:
+                raise SondeError(f"LMS6: the record was decoded with vit = {rec['vit']}, this decoder has vit = {vit}, ecc = {ecc.value}")
+            n = rec["nbits"]
+            if n > self.lms_block_bits():
+                if "soft" not in rec:
+                    raise SondeError(f"LMS6: a record of {n} bits for a decoder that reads {self.lms_block_bits()}: its soft bits are needed (fetch_family's need_soft)")
+                return self.hit(rec, if_sr)
+            rate = self._lms_rate(rec["mv_pos"], if_sr)
+            fn = lib().sonde_lms6_dec_block_bytes
+            fn.argtypes = [C.c_void_p, C.c_char_p, _I, _I, C.c_float, C.c_float, C.c_double, C.c_char_p, C.c_size_t]
+            k = fn(self._h, rec["bytes"][:rec["blen"]], rec["blen"], rec["len"], rec["mv"], rate, (rec["mv_pos"] + n * if_sr / 4800.0) / if_sr, self._buf, len(self._buf))
+            if k < 0:
+                raise SondeError(f"LMS6: sonde_lms6_dec_block_bytes failed ({k})")
+            return self._buf.raw[:k].decode(errors="replace")
         L, p, d, v = lib(), self.f["prefix"], rec["data"], rec["v"]
         if self.typ == "MEISEI":
             L.sonde_meisei_dec_decoded.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_size_t]

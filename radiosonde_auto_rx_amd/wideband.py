@@ -22,7 +22,7 @@ import numpy as np
 
 from .engine import Engine, snap_fq
 from .scan import Scanner
-from .family import DEVICE_KINDS_ALL, FAMILY, LMS_BASE, FamilyDecoder
+from .family import DEVICE_KINDS_ALL, DEVICE_KINDS_LMS, FAMILY, LMS_BASE, FamilyDecoder
 from .imet4 import Imet4Engine, Imet4Printer
 from .mk2a import Mk2aEngine, Mk2aPrinter
 from .wxr import WxrEngine, WxrPrinter
@@ -48,8 +48,8 @@ class WidebandReceiver:
         of survey_s seconds of stream (Hann, survey_nfft points, 25 % of the band edge cropped), auto_rx's peak pick on it (snr_threshold dB over
         the median, min_distance, quantization, at most max_peaks — its defaults), then a Scanner(fq=peaks, dc=True) over the next dwell_s
         seconds (what `dft_detect` per peak is to auto_rx), then the next survey.  Peaks that already have a decoder are not scanned again.
-        device_family: the block codes of Meisei, iMet-54, MTS01, RS92 and MRZ hits run on the device behind the frame sync (Engine.set_family) and decoded records
-        come to the host instead of soft bits; LMS6 keeps the host path either way."""
+        device_family: the block codes of Meisei, iMet-54, MTS01, RS92, MRZ and LMS6 / LMS-X hits run on the device behind the frame sync (Engine.set_family) and
+        decoded records come to the host instead of soft bits (LMS6: the convolutional code; Reed-Solomon and everything behind it stay with the host decoder)."""
         self.device_family = device_family
         self.sr, self.cfreq, self.merge_hz, self.version, self.idle_s = sample_rate, cfreq_hz, merge_hz, version, idle_s
         self.t = 0.0                           # stream time in seconds
@@ -147,9 +147,9 @@ class WidebandReceiver:
         f = FAMILY[typ]
         eng = Engine([fq], self.sr, sonde="generic", generic=f["generic"], thres=f["thres"], auto=f["auto"], keep_soft=True, lp_iq=True,
                      max_chunk=self.chunk, max_frames=8)
-        eng.device_family = self.device_family and typ in DEVICE_KINDS_ALL
+        eng.device_family = self.device_family and (typ in DEVICE_KINDS_ALL or typ in DEVICE_KINDS_LMS)
         if eng.device_family:
-            eng.set_family(typ, ecc=FAMILY[typ]["kw"].get("ecc", 1))
+            eng.set_family(typ, ecc=FAMILY[typ]["kw"].get("ecc", 1), vit=FAMILY[typ]["kw"].get("vit", 2))
         return eng
 
     def _follow_lms(self, s):
@@ -272,7 +272,13 @@ class WidebandReceiver:
         if s["type"] in FAMILY:
             out = []
             on_dev = getattr(e, "device_family", False)      # the hit's block codes ran on the device: a decoded record, not soft bits
-            for h in (e.fetch_family(finish=finish) if on_dev else e.fetch_hits(finish=finish)):
+            tel = s["telemetry"]
+            # LMS6 / LMS-X: a block longer than the decoder reads (an LMS6 decoder on the LMS-X engine, the block of the change) is decoded from its soft bits
+            long_lms = (lambda r: r["nbits"] > tel.lms_block_bits()) if s["type"] in DEVICE_KINDS_LMS else None
+            hits = e.fetch_family(finish=finish, need_soft=long_lms) if on_dev else e.fetch_hits(finish=finish)
+            for i, h in enumerate(hits):
+                if on_dev and long_lms and "soft" not in h and long_lms(h):      # (the decoder changed its type on an earlier record of this very fetch)
+                    h["soft"] = e.last_soft(i + 1)[i, :h["nbits"]].copy()
                 s["frames"] += 1
                 js = FamilyDecoder.json_objects(s["telemetry"].decoded(h, e.info["if_sr"]) if on_dev else s["telemetry"].hit(h, e.info["if_sr"]))
                 s["good"] = s.get("good", 0) + (1 if js else 0)
@@ -496,7 +502,7 @@ def main(argv=None):
     ap.add_argument("--raster", type=int, default=10_000, help="scanner raster in Hz")
     ap.add_argument("--survey", type=float, default=None, metavar="SECONDS", help="auto_rx's cycle instead of the raster: a spectrum survey of that many seconds, peak pick, a scanner channel per peak")
     ap.add_argument("--channelize", action="store_true", help="polyphase channelizer front end (256 channels at sr / 200): for streams of several Msps")
-    ap.add_argument("--device-family", action="store_true", help="decode Meisei, iMet-54, MTS01, RS92 and MRZ hits on the device (not with --channelize)")
+    ap.add_argument("--device-family", action="store_true", help="decode Meisei, iMet-54, MTS01, RS92, MRZ and LMS6 / LMS-X hits on the device (not with --channelize)")
     ap.add_argument("--rs92-ephem", help="RINEX navigation file for RS92 positions (rs92mod -e)")
     ap.add_argument("--rs92-alm", help="SEM almanac for RS92 positions (rs92mod -a)")
     ap.add_argument("dash"); ap.add_argument("sr", type=int); ap.add_argument("bits", type=int)
