@@ -32,6 +32,8 @@ typedef struct sonde_ecc sonde_ecc_t;
 sonde_ecc_t *sonde_ecc_create(int code);                       /* NULL for an unknown code */
 void sonde_ecc_destroy(sonde_ecc_t *c);
 int  sonde_ecc_params(const sonde_ecc_t *c, int *N, int *t, int *R, int *K);
+/* The field's tables as GF_genTab (:136) makes them: *exp = 512 entries (alpha^i, periods repeated), *log = 256 entries (log 0 = 0).  They live as long as c. */
+int  sonde_ecc_tables(const sonde_ecc_t *c, const uint8_t **exp, const uint8_t **log);
 int  sonde_ecc_encode(const sonde_ecc_t *c, uint8_t *cw);
 int  sonde_ecc_decode(const sonde_ecc_t *c, uint8_t *cw, uint8_t *err_pos, uint8_t *err_val);
 int  sonde_ecc_decode_errera(const sonde_ecc_t *c, uint8_t *cw, int nera, const uint8_t *era_pos, uint8_t *err_pos, uint8_t *err_val);

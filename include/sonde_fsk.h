@@ -181,6 +181,12 @@ typedef struct {
 } sonde_lms6_softin_t;
 /* blocks completed by the push calls since the last fetch (per channel in stream order); returns the count (<= max) */
 int  sonde_softin_dev_fetch_lms6(sonde_softin_dev_t *s, sonde_lms6_softin_t *out, int32_t max);
+/* RS(255,223) of the blocks on the device as well (k_lms6_rs, csrc/sonde_lms6_rs.hip; sonde_lms6_rs_t, sonde_hip.h): with the switch on the kernel runs over a
+ * round's block records before they are copied, and the channels' decoders take its results (sonde_lms6_dec_block_rs) instead of decoding.  Off by default;
+ * nothing else of the interface changes, the stop-at-block rule of auto detection included.  A call in flight is completed first.  _stats: RS results taken from
+ * records / decoded on the host instead, over all channels (sonde_lms6_dec_rs_stats). */
+int  sonde_softin_dev_set_lms6_rs(sonde_softin_dev_t *s, int32_t on);
+int  sonde_softin_dev_lms6_rs_stats(sonde_softin_dev_t *s, int64_t *used, int64_t *missed);
 
 /* ---- SONDE_RS92 consumers: `rs92mod --softin [-i] --ecc ...` for every channel (auto_rx's pipe `fsk_demod --cs16 -b -20000 -u 20000 -s --stats=N 2 48000 4800 - - |
  * rs92mod -vx -v --crc --ecc --vel --json --softin -i -e <rinex> --ptu`, auto_rx/autorx/decode.py:976-987).  On the device, one wavefront per channel

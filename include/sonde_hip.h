@@ -361,6 +361,30 @@ int  sonde_engine_fetch_family_lms6(sonde_engine_t *e, sonde_lms6_hit_t *out, in
  * Arguments are checked before the device is touched. */
 int  sonde_lms6_decode_device(int32_t vit, const float *soft, int64_t stride, const int32_t *nbits, const float *mv, int32_t n, sonde_lms6_hit_t *out);
 
+/* RS(255,223) of LMS6 / LMS-X blocks on the device (k_lms6_rs, csrc/sonde_lms6_rs.hip; one wavefront per block record, csrc/sonde_rs223_dev.h): rs_decode
+ * (bch_ecc_mod.c:877-965, nera = 0; the code of bch_ecc_mod.h:99) under each hypothesis proc_frame (lms6Xmod.c:881-989) can ask for on the block bytes alone, since
+ * the device knows neither the channel's type nor its frame state.  Off by default; the channel's host decoder takes its results from the record instead of
+ * decoding (sonde_lms6_dec_block_rs, include/sonde_lms6.h) and does frame sync, CRC, auto detection and the text as before.
+ *   h6   the codeword at block_bytes[5 .. 259] (the type-6 branch with --ecc, :885-889): at = 5, always decoded
+ *   hX   the codeword at frmsync_X's position (:815-827; 5, 40 or 45) when the LMS-X sync is complete and blen > 100 (:966-975): at = that position; else at = 0,
+ *        err = 0 and nothing was decoded
+ *   h6X  hX on the bytes as h6 repaired them (a type-6 block that falls through into the type-10 branch under auto detection): only when h6.err > 0, otherwise
+ *        at = -1: the same as hX
+ * err = rs_decode's value: 0 clean, > 0 symbols repaired, -1 / -2 / -3 its failure codes.  pos[i], val[i], i < err: the reference's err_pos / err_val in its own
+ * order (ascending x of the Chien search); pos is the codeword index, the block byte it patches is bytes[at + 254 - pos[i]].  Entries behind err are zero.  A
+ * record with decoded == 0 or blen == 0 gets an all-zero result.  The block bytes themselves are never modified. */
+typedef struct { int32_t at, err; uint8_t pos[16], val[16]; } sonde_lms6_rs_hyp_t;   /* 40 B */
+typedef struct { sonde_lms6_rs_hyp_t h6, hX, h6X; } sonde_lms6_rs_t;                 /* 120 B */
+/* The kernel on n block records in host memory (tests, tools): record i = 308 bytes at bytes + i * stride (stride >= 308), zero behind blen[i] (0 .. 300).
+ * Arguments are checked before the device is touched. */
+int  sonde_lms6_rs_device(const uint8_t *bytes, int64_t stride, const int32_t *blen, int32_t n, sonde_lms6_rs_t *out);
+/* An engine under sonde_engine_set_family_lms6: k_lms6_rs behind k_lms6_hits on the same stream, over the same device records.  Legal after
+ * sonde_engine_set_family_lms6 and before the first process call; SONDE_E_ARG otherwise (an engine of another kind included). */
+int  sonde_engine_set_family_lms6_rs(sonde_engine_t *e, int32_t on);
+/* sonde_engine_fetch_family_lms6 with the RS record of every hit beside it: hits[] is byte for byte what sonde_engine_fetch_family_lms6 returns; rs[] is zeroed
+ * with the switch off (and for a hit that was not decoded).  The two fetches may be mixed: a record is delivered once. */
+int  sonde_engine_fetch_family_lms6_rs(sonde_engine_t *e, sonde_lms6_hit_t *hits, sonde_lms6_rs_t *rs, int32_t max, int32_t finish);
+
 /* DFM engines: frames completed so far (syncs).  The hits are sliced into frames and Hamming-decoded (dfm09mod.c:240-345) on the device behind the frame sync
  * (k_dfm_hits; the host decode remains as the A/B path, sonde_engine_set_device_ecc(e, 0)); only decoded frames come to the host, the soft bits on request.  cfg.ecc_level 0/1/2
  * = none / --ecc / --ecc2 (soft 2-bit pass).  finish != 0: end of input, also emits the complete frames of a hit

@@ -16,6 +16,7 @@
 
 #include <stddef.h>
 #include <stdint.h>
+#include "sonde_hip.h"      /* sonde_lms6_rs_t */
 
 #ifdef __cplusplus
 extern "C" {
@@ -64,6 +65,16 @@ int  sonde_lms6_dec_block(sonde_lms6_dec_t *d, const float *soft0, const float *
  * arguments and the output as above.  RS(255,223), frame sync, CRC, auto detection and the text run on exactly the state sonde_lms6_dec_block keeps.  Host only. */
 int  sonde_lms6_dec_block_bytes(sonde_lms6_dec_t *d, const uint8_t *bytes, int32_t blen, int32_t len, float mv, float frm_rate, double t_elapsed,
                                 char *out, size_t outlen);
+
+/* sonde_lms6_dec_block_bytes for a caller whose device has run RS(255,223) as well (k_lms6_rs; sonde_lms6_rs_t, include/sonde_hip.h): the two places where
+ * proc_frame calls rs_decode (lms6Xmod.c:885-889 at offset 5 of a type-6 block, :966-975 at frmsync_X's position of a type-10 block) take their result from *rs
+ * instead of decoding — h6 at offset 5; in the type-10 branch h6X when this call applied an h6 with err > 0 and h6X.at >= 0, otherwise hX.  The decoder still
+ * runs its own frmsync_X; a hypothesis whose `at` is not the offset about to be decoded (or rs == NULL) is replaced by sonde_ecc_decode here and counted as a
+ * miss.  State, text, JSON, counts and auto detection are exactly those of sonde_lms6_dec_block_bytes; a decoder without --ecc ignores the record.  Host only. */
+int  sonde_lms6_dec_block_rs(sonde_lms6_dec_t *d, const uint8_t *bytes, int32_t blen, int32_t len, float mv, float frm_rate, double t_elapsed,
+                             const sonde_lms6_rs_t *rs, char *out, size_t outlen);
+/* RS results taken from records / decoded here instead, over all sonde_lms6_dec_block_rs calls since creation. */
+int  sonde_lms6_dec_rs_stats(const sonde_lms6_dec_t *d, int64_t *used, int64_t *missed);
 
 /* Soft-bit input (`lms6Xmod --softin`, the consumer of `fsk_demod -s`): n float32 soft bits in, header search and block assembly
  * inside; finish != 0 at end of input (a block in progress is decoded with the bits that exist).  Output as above. */

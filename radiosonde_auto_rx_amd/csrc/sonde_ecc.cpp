@@ -130,6 +130,13 @@ int sonde_ecc_params(const sonde_ecc_t *c, int *N, int *t, int *R, int *K) {
     return 0;
 }
 
+int sonde_ecc_tables(const sonde_ecc_t *c, const uint8_t **exp, const uint8_t **log) {
+    if (!c) return -1;
+    if (exp) *exp = c->exp_a;
+    if (log) *log = c->log_a;
+    return 0;
+}
+
 int sonde_ecc_encode(const sonde_ecc_t *c, uint8_t *cw) {     // parity = message(X) mod g(X) (rs_encode :860)
     if (!c || !cw) return -1;
     Poly m, d, r;

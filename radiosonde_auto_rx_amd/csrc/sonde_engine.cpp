@@ -52,6 +52,9 @@ struct sonde_engine {
     std::vector<sonde_family_hit_t> h_fam;
     // the same for LMS6 / LMS-X (sonde_engine_set_family_lms6; k_lms6_hits, sonde_lms6_hits.hip): fam_kind = SONDE_LMS6, its --vit / --vit2, a record of its own type per ring slot
     int fam_vit = 0; sonde_lms6_hit_t *d_lms_out = nullptr; std::vector<sonde_lms6_hit_t> h_lms;
+    // RS(255,223) of those blocks on the device as well (sonde_engine_set_family_lms6_rs; k_lms6_rs, sonde_lms6_rs.hip): a record per ring slot, the field's tables,
+    // a {done, ticket} pair of its own that moves in step with d_blk_done
+    bool lms_rs = false; sonde_lms6_rs_t *d_lms_rs = nullptr; const uint8_t *d_lms_rs_tab = nullptr; unsigned *d_lms_rs_done = nullptr; std::vector<sonde_lms6_rs_t> h_lms_rs;
     uint32_t *d_ecc_list = nullptr; unsigned *d_ecc_cnt = nullptr;     // two work lists of max_frames record slots, alternating per call; {count[2], done[2]}
     hipEvent_t ev_a[4] = {}, ev_b[4] = {}, ev_if[4] = {};      // per call: decimator done (A), records complete (B / E), y ring read (B: IF chain done)
     Pinned<unsigned> h_count;          // mapped: frame counter snapshot after each call's framesync
@@ -215,6 +218,9 @@ extern "C" void sonde_launch_mrz_hits(int bits_ofs, const FrameRec *frames, cons
                                       const unsigned *fcount, unsigned *done, sonde_family_hit_t *out, int grid, hipStream_t s);
 extern "C" void sonde_launch_lms6_hits(int vit, int nb, const FrameRec *frames, const int *nbits_direct, const float *mv_direct, const float *soft, long long stride,
                                        int max_frames, const unsigned *fcount, unsigned *done, sonde_lms6_hit_t *out, int grid, hipStream_t s);
+extern "C" void sonde_launch_lms6_rs(const void *recs, long long stride, int off_bytes, int off_blen, int off_decoded, int max_frames, const unsigned *count,
+                                     unsigned *done, unsigned n, const uint8_t *tab, sonde_lms6_rs_t *out, int grid, hipStream_t s);
+int sonde_lms6_rs_tables(DevMem &mem, const uint8_t **tab);
 static bool blockcodes_on_device(const sonde_engine *e);
 // bit characters a channel of an M10 / M20 engine keeps from frame to frame: 8 per frame byte and the terminator (m10mod.c:90-94, m20mod.c:83-87)
 static inline size_t mxx_chars(const sonde_engine *e) { return (size_t)(e->cfg.sonde_type == SONDE_M20 ? 101 + 64 : 101 + 20) * 8 + 8; }
@@ -225,8 +231,13 @@ static void launch_blockcodes(sonde_engine *e) {
     const int grid = std::max(1, std::min(e->cfg.n_channels, 1024));
     if (family_on_device(e)) {
         if (e->fam_kind == SONDE_LMS6)
+        {
             sonde_launch_lms6_hits(e->fam_vit, e->nbits, e->d_frames, nullptr, nullptr, e->d_soft, (long long)e->nbits, e->max_frames, e->d_fcount, e->d_blk_done, e->d_lms_out, grid,
                                    e->stream_b);
+            if (e->lms_rs)                         // the same records [done, fcount), read from its own pair: both pairs start at 0 and end every launch at fcount
+                sonde_launch_lms6_rs(e->d_lms_out, (long long)sizeof(sonde_lms6_hit_t), (int)offsetof(sonde_lms6_hit_t, bytes), (int)offsetof(sonde_lms6_hit_t, blen),
+                                     (int)offsetof(sonde_lms6_hit_t, decoded), e->max_frames, e->d_fcount, e->d_lms_rs_done, 0u, e->d_lms_rs_tab, e->d_lms_rs, grid, e->stream_b);
+        }
         else if (e->fam_kind == SONDE_MRZ)
             sonde_launch_mrz_hits(e->fam_ofs, e->d_frames, nullptr, e->d_soft, (long long)e->nbits, e->max_frames, e->d_fcount, e->d_blk_done, e->d_fam_out, grid, e->stream_b);
         else
@@ -1280,6 +1291,7 @@ int sonde_engine_set_device_ecc(sonde_engine_t *e, int32_t on) {
         if (count != e->read_idx) return SONDE_E_ARG;
         const unsigned dn[2] = { count, 0u };
         if (on && hipMemcpy(e->d_blk_done, dn, sizeof dn, hipMemcpyHostToDevice) != hipSuccess) return SONDE_E_NOGPU;
+        if (on && e->d_lms_rs_done && hipMemcpy(e->d_lms_rs_done, dn, sizeof dn, hipMemcpyHostToDevice) != hipSuccess) return SONDE_E_NOGPU;      // (k_lms6_rs follows k_lms6_hits)
     }
     e->dev_ecc = on != 0;
     return 0;
@@ -1531,7 +1543,27 @@ int sonde_engine_set_family_lms6(sonde_engine_t *e, int32_t vit) {
     return 0;
 }
 
-int sonde_engine_fetch_family_lms6(sonde_engine_t *e, sonde_lms6_hit_t *out, int32_t max, int32_t finish) {
+int sonde_engine_set_family_lms6_rs(sonde_engine_t *e, int32_t on) {
+    if (!e || !e->groups.empty() || e->fam_kind != SONDE_LMS6 || !e->d_lms_out || e->call > 0) return SONDE_E_ARG;
+    if (on) {
+        if (!e->d_lms_rs) TRY(e->mem.dalloc(&e->d_lms_rs, (size_t)e->max_frames));
+        if (!e->d_lms_rs_done) TRY(e->mem.dalloc(&e->d_lms_rs_done, 2));
+        if (!e->d_lms_rs_tab) TRY(sonde_lms6_rs_tables(e->mem, &e->d_lms_rs_tab));
+    }
+    e->lms_rs = on != 0;
+    return 0;
+}
+
+static int fetch_family_lms6_impl(sonde_engine_t *e, sonde_lms6_hit_t *out, sonde_lms6_rs_t *rs, int32_t max, int32_t finish);
+
+int sonde_engine_fetch_family_lms6(sonde_engine_t *e, sonde_lms6_hit_t *out, int32_t max, int32_t finish) { return fetch_family_lms6_impl(e, out, nullptr, max, finish); }
+
+int sonde_engine_fetch_family_lms6_rs(sonde_engine_t *e, sonde_lms6_hit_t *hits, sonde_lms6_rs_t *rs, int32_t max, int32_t finish) {
+    if (!rs) return SONDE_E_ARG;
+    return fetch_family_lms6_impl(e, hits, rs, max, finish);
+}
+
+static int fetch_family_lms6_impl(sonde_engine_t *e, sonde_lms6_hit_t *out, sonde_lms6_rs_t *rs, int32_t max, int32_t finish) {
     if (!e || !e->groups.empty() || !out || max < 0 || e->fam_kind != SONDE_LMS6) return SONDE_E_ARG;
     if (finish) launch_framesync(e, 1);
     std::vector<FrameRec> recs;
@@ -1542,12 +1574,15 @@ int sonde_engine_fetch_family_lms6(sonde_engine_t *e, sonde_lms6_hit_t *out, int
     const unsigned start = e->read_idx - (unsigned)n;
     e->last_n = n; e->soft_lazy = true; e->soft_lazy_start = start;
     if (on_dev && copy_decoded(e, e->d_lms_out, e->h_lms, start, n, 1)) return SONDE_E_NOGPU;
+    const bool rs_dev = rs && on_dev && e->lms_rs;
+    if (rs_dev && copy_decoded(e, e->d_lms_rs, e->h_lms_rs, start, n, 1)) return SONDE_E_NOGPU;
     for (int h = 0; h < n; h++) {
         const FrameRec &r = recs[h];
         sonde_lms6_hit_t &o = out[h];
         if (on_dev) o = e->h_lms[h];
         else { memset(&o, 0, sizeof o); o.channel = r.channel; o.kind = SONDE_LMS6; o.nbits = r.nbytes; o.mv = r.mv; }      // device decoding is switched off: the host's
         o.mv_pos = rel_pos(e, r);
+        if (rs) { if (rs_dev) rs[h] = e->h_lms_rs[h]; else memset(&rs[h], 0, sizeof rs[h]); }
     }
     return n;                                  // hits dropped by a full queue: sonde_engine_overflowed()
 }

@@ -270,11 +270,39 @@ struct sonde_lms6_dec {
         }
         return p;
     }
-    void rs_block(uint8_t *bb, int at) {                        // codeword reversed in the block (:885-889)
+    int rs_block(uint8_t *bb, int at) {                         // codeword reversed in the block (:885-889)
         uint8_t cw[255], ep[32], ev[32];
         for (int j = 0; j < 255; j++) cw[254 - j] = bb[at + j];
-        sonde_ecc_decode(rs, cw, ep, ev);
+        const int e = sonde_ecc_decode(rs, cw, ep, ev);
         for (int j = 0; j < 255; j++) bb[at + j] = cw[254 - j];
+        return e;
+    }
+    // the same from a device record (sonde_lms6_dec_block_rs): the hypothesis decoded at `at` is applied, anything else is decoded here and counted as a miss
+    const sonde_lms6_rs_t *rsrec = nullptr; bool rs_call = false;         // inside sonde_lms6_dec_block_rs; its record (NULL: every result is decoded here, a miss)
+    long long rs_used = 0, rs_missed = 0;
+    int rs_from = 0;                                            // this block's type-6 result: 0 none, 1 from the record, 2 decoded here
+    int rs_block_hyp(uint8_t *bb, int at, const sonde_lms6_rs_hyp_t *h) {
+        if (!h || h->at != at || h->err > 16) { rs_missed++; return rs_block(bb, at); }
+        for (int i = 0; i < h->err; i++) if (h->pos[i] > 254) { rs_missed++; return rs_block(bb, at); }
+        for (int i = 0; i < h->err; i++) bb[at + 254 - h->pos[i]] ^= h->val[i];
+        rs_used++;
+        return h->err;
+    }
+    void rs_block6(uint8_t *bb) {
+        if (!rs_call) { rs_block(bb, SYNC_LEN); return; }
+        if (!rsrec) { rs_block_hyp(bb, SYNC_LEN, nullptr); return; }
+        const long long m = rs_missed;
+        rs_block_hyp(bb, SYNC_LEN, &rsrec->h6);
+        rs_from = rs_missed == m ? 1 : 2;
+    }
+    void rs_blockX(uint8_t *bb, int at) {
+        if (!rs_call) { rs_block(bb, at); return; }
+        if (!rsrec) { rs_block_hyp(bb, at, nullptr); return; }
+        // a type-6 block that fell through: the bytes are what the type-6 decoder left.  It repaired something: h6X; it left them alone: hX
+        const sonde_lms6_rs_hyp_t *h = &rsrec->hX;
+        if (rs_from == 2) h = nullptr;                          // (decoded here: what the bytes are now is not what either hypothesis saw, unless nothing changed)
+        else if (rs_from == 1 && rsrec->h6.err > 0 && rsrec->h6X.at >= 0) h = &rsrec->h6X;
+        rs_block_hyp(bb, at, h);
     }
 
     // ---- proc_frame (:829-989) --------------------------------------------------------------------------------------------------------
@@ -300,8 +328,9 @@ struct sonde_lms6_dec {
     // ---- proc_frame from block_bytes on (:881-989): bb[FRAME_LEN + 8], zero behind blen ---------------------------------------------------
     void proc_bytes(Out &w, uint8_t *bb, const int blen) {
         int p = SYNC_LEN;
+        rs_from = 0;
         if ((typ & 0xFF) == 6) {
-            if (o.ecc) rs_block(bb, SYNC_LEN);
+            if (o.ecc) rs_block6(bb);
             while (p - SYNC_LEN < FRM_LEN) {
                 if (sf6 == 0) {
                     while (p - SYNC_LEN < FRM_LEN) {                       // frmsync_6
@@ -334,7 +363,7 @@ struct sonde_lms6_dec {
                 }
                 if (frm_rate > 5000.0 || frm_rate < 4000.0) { if (auto_detect) { reset_dsp = 1; typ = 6; } }
             } else {
-                if (blen > 100 && o.ecc) rs_block(bb, p);
+                if (blen > 100 && o.ecc) rs_blockX(bb, p);
                 for (int j = 0; j < FRM_LEN; j++) frame[j] = bb[p + j];
                 emit(w, check_crc(frame));
             }
@@ -451,6 +480,22 @@ int sonde_lms6_dec_block_bytes(sonde_lms6_dec_t *d, const uint8_t *bytes, int32_
     d->proc_bytes(w, bb, blen);
     d->after_block();
     return finish_out(w, out, outlen);
+}
+
+int sonde_lms6_dec_block_rs(sonde_lms6_dec_t *d, const uint8_t *bytes, int32_t blen, int32_t len, float mv, float frm_rate, double t_elapsed,
+                            const sonde_lms6_rs_t *rs, char *out, size_t outlen) {
+    if (!d) return SONDE_E_ARG;
+    d->rsrec = rs; d->rs_call = true;
+    const int rc = sonde_lms6_dec_block_bytes(d, bytes, blen, len, mv, frm_rate, t_elapsed, out, outlen);
+    d->rsrec = nullptr; d->rs_call = false;
+    return rc;
+}
+
+int sonde_lms6_dec_rs_stats(const sonde_lms6_dec_t *d, int64_t *used, int64_t *missed) {
+    if (!d) return SONDE_E_ARG;
+    if (used) *used = d->rs_used;
+    if (missed) *missed = d->rs_missed;
+    return 0;
 }
 
 int sonde_lms6_dec_push_soft(sonde_lms6_dec_t *d, const float *soft, int32_t n, int32_t invert, int32_t finish, char *out, size_t outlen) {

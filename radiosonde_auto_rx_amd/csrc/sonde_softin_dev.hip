@@ -812,6 +812,9 @@ extern "C" void sonde_launch_rs41_ecc_batch_n(uint8_t *frames, const int32_t *fl
                                               const uint8_t *gf_exp, const uint8_t *gf_log, hipStream_t s);
 extern "C" int sonde_fsk_wait(sonde_fsk_t *f);
 extern "C" int sonde_fsk_host_frames(sonde_fsk_t *f, int32_t *out);
+extern "C" void sonde_launch_lms6_rs(const void *recs, long long stride, int off_bytes, int off_blen, int off_decoded, int max_frames, const unsigned *count,
+                                     unsigned *done, unsigned n, const uint8_t *tab, sonde_lms6_rs_t *out, int grid, hipStream_t s);
+int sonde_lms6_rs_tables(DevMem &mem, const uint8_t **tab);
 extern "C" int sonde_fsk_dev_view(sonde_fsk_t *f, const float **d_sd, long long *sd_cap, const FskChan **d_chan, int *bits_per_frame, int *n_ch, hipStream_t *stream);
 extern "C" int sonde_fsk_dev_reader_done(sonde_fsk_t *f, hipStream_t consumer_stream);
 extern "C" int sonde_fsk_dev_view_prev(sonde_fsk_t *f, const float **d_sd, long long *sd_cap, int *bits_per_frame, int *n_ch, int32_t *frames_out);
@@ -848,6 +851,8 @@ struct sonde_softin_dev {
     SoftinMeta *d_meta = nullptr; Pinned<SoftinMeta> h_meta;
     // SONDE_LMS6: the channels of a relaunch, the block length each channel has on the device, the decoders' tallies so far
     int l6_auto = 0; int *d_l6_list = nullptr; Pinned<int> h_l6_list, h_l6_len; std::vector<int> l6_len; std::vector<int64_t> l6_ok;
+    // RS(255,223) of a round's blocks on the device (sonde_softin_dev_set_lms6_rs; k_lms6_rs, sonde_lms6_rs.hip): a record per block record, and their landing buffer
+    bool l6_rs = false; sonde_lms6_rs_t *d_l6_rs = nullptr; Pinned<sonde_lms6_rs_t> h_l6_rs; const uint8_t *d_l6_rs_tab = nullptr;
     // LMS6 / RS92 / iMet-54 / Meisei / MRZ / MTS01: a host decoder per channel (what a sonde collects — calibration rows, configuration words, counters — is per channel)
     std::vector<void *> dec; void (*dec_free)(void *) = nullptr;
     sonde_gps_dev_t *gps = nullptr; bool gps_on = false;   // RS92: the device subset search of fetch_rs92 (sonde_softin_dev_set_rs92_gps), made on first use
@@ -921,6 +926,9 @@ static void launch_drop(sonde_softin_dev *s, const SoftinArgs &a, int nblocks, h
 static void launch_lms6(sonde_softin_dev *s, const SoftinArgs &a, int nblocks, hipStream_t st) {
     const SoftinLms6Args d{a, s->chan<Lms6Chan>(), s->recs<Lms6Block>(), s->opt, s->l6_auto};
     hipLaunchKernelGGL(k_softin_lms6, dim3(nblocks), dim3(64), 0, st, d);
+    if (s->l6_rs)                                  // over the round's block records [0, min(*count, cap)) where they lie, before they are copied
+        sonde_launch_lms6_rs(s->d_rec, (long long)sizeof(Lms6Block), (int)offsetof(Lms6Block, bytes), (int)offsetof(Lms6Block, blen), -1, s->cap, a.count, nullptr, 0u,
+                             s->d_l6_rs_tab, s->d_l6_rs, std::max(1, std::min(nblocks, 1024)), st);
 }
 
 // ---- a call's records on the host, a rule per record.  Frames of one channel stay in order: the slots of a call are handed out in completion order per channel, channels interleave.
@@ -1229,6 +1237,7 @@ static int softin_pass(sonde_softin_dev *s, hipStream_t st, const int nblocks, c
 static int softin_copy(sonde_softin_dev *s, hipStream_t st, const int from, const int to) {
     if (to <= from) return 0;
     const size_t n = (size_t)(to - from), rec = s->kind->rec;
+    if (s->l6_rs) HIPCHK(hipMemcpyAsync(s->h_l6_rs.data() + from, s->d_l6_rs + from, n * sizeof(sonde_lms6_rs_t), hipMemcpyDeviceToHost, st));
     if (rec) HIPCHK(hipMemcpyAsync(s->h_rec.data() + from * rec, s->d_rec + from * rec, n * rec, hipMemcpyDeviceToHost, st));
     else {
         HIPCHK(hipMemcpyAsync(s->h_meta.data() + from, s->d_meta + from, n * sizeof(SoftinMeta), hipMemcpyDeviceToHost, st));
@@ -1249,7 +1258,8 @@ static int softin_finish_lms6(sonde_softin_dev *s, hipStream_t st, long long n) 
             sonde_lms6_dec_t *d = s->decoder<sonde_lms6_dec_t>(b.channel);
             sonde_lms6_softin_t r; memset(&r, 0, sizeof r);
             const float nanv = __builtin_nanf("");             // dsp_t stays zeroed with soft input: frm_rate and the elapsed time are 0 / 0
-            const int len = sonde_lms6_dec_block_bytes(d, b.bytes, b.blen, b.pos, b.mv, nanv, (double)nanv, r.text, sizeof r.text);
+            const int len = s->l6_rs ? sonde_lms6_dec_block_rs(d, b.bytes, b.blen, b.pos, b.mv, nanv, (double)nanv, &s->h_l6_rs[i], r.text, sizeof r.text)
+                                     : sonde_lms6_dec_block_bytes(d, b.bytes, b.blen, b.pos, b.mv, nanv, (double)nanv, r.text, sizeof r.text);
             if (len < 0) return len;
             r.channel = b.channel; r.type = sonde_lms6_dec_type(d, nullptr); r.mv = b.mv; r.text_len = len; r.hdr_bit = b.hdr_bit; r.blen = b.blen; r.err = b.err;
             s->queue(r);
@@ -1403,6 +1413,26 @@ int sonde_softin_dev_fetch_m10(sonde_softin_dev_t *s, sonde_m10_frame_t *out, in
 int sonde_softin_dev_fetch_m20(sonde_softin_dev_t *s, sonde_m20_frame_t *out, int32_t max) { return softin_fetch_plain(s, SONDE_M20, out, max); }
 int sonde_softin_dev_fetch_drop(sonde_softin_dev_t *s, sonde_drop_frame_t *out, int32_t max) { return softin_fetch_plain(s, SONDE_RD94RD41, out, max); }
 int sonde_softin_dev_fetch_lms6(sonde_softin_dev_t *s, sonde_lms6_softin_t *out, int32_t max) { return softin_fetch_plain(s, SONDE_LMS6, out, max); }
+
+int sonde_softin_dev_set_lms6_rs(sonde_softin_dev_t *s, int32_t on) {
+    if (!s || s->type != SONDE_LMS6) return SONDE_E_ARG;
+    { const int rc = softin_finish(s); if (rc) return rc; }       // (a call in flight was launched under the switch as it stood)
+    if (on && !s->d_l6_rs) {
+        if (!s->dalloc(&s->d_l6_rs, (size_t)s->cap) || !s->h_l6_rs.alloc((size_t)s->cap)) return SONDE_E_NOGPU;
+        TRY(sonde_lms6_rs_tables(s->mem, &s->d_l6_rs_tab));
+    }
+    s->l6_rs = on != 0;
+    return 0;
+}
+
+int sonde_softin_dev_lms6_rs_stats(sonde_softin_dev_t *s, int64_t *used, int64_t *missed) {
+    if (!s || s->type != SONDE_LMS6) return SONDE_E_ARG;
+    int64_t u = 0, m = 0;
+    for (int c = 0; c < s->C; c++) { int64_t a = 0, b = 0; (void)sonde_lms6_dec_rs_stats(s->decoder<sonde_lms6_dec_t>(c), &a, &b); u += a; m += b; }
+    if (used) *used = u;
+    if (missed) *missed = m;
+    return 0;
+}
 
 int sonde_softin_dev_set_m20_skip(sonde_softin_dev_t *s, int32_t skip) {
     if (!s || s->type != SONDE_M20) return SONDE_E_ARG;

@@ -405,18 +405,26 @@ class Engine:
             _chk(lib().sonde_engine_fetch_soft(self._h, soft.ctypes.data_as(C.c_void_p), k))
         return [dict(channel=buf[i].channel, nbits=buf[i].nbits, mv=buf[i].mv, mv_pos=buf[i].mv_pos, soft=soft[i, :buf[i].nbits].copy()) for i in range(k)]
 
-    def set_family(self, kind: str, ecc: int = 1, bits_ofs: int = 8, vit: int = 2):
+    def set_family(self, kind: str, ecc: int = 1, bits_ofs: int = 8, vit: int = 2, rs: bool = False):
         """Generic engines carrying Meisei, iMet-54, MTS01, RS92, MRZ (kind = a key of family.DEVICE_KINDS_ALL) or LMS6 / LMS-X (a key of family.DEVICE_KINDS_LMS),
         the engine created with that FAMILY description: decode every hit on the device behind the frame sync; results through fetch_family().  Before the first
         process call.  ecc: the decoder's --ecc (MRZ has none; LMS6's Reed-Solomon code stays on the host); bits_ofs: MRZ's --ofs, vit: LMS6's --vit (1) or --vit2
-        (2), which the FamilyDecoder printing the records must have too."""
+        (2), which the FamilyDecoder printing the records must have too.  rs (LMS6 / LMS-X only): RS(255,223) of every block on the device as well
+        (sonde_engine_set_family_lms6_rs); fetch_family() then puts an Lms6Rs beside each hit ("rs"), which FamilyDecoder.decoded() passes on to the host decoder."""
         from .family import DEVICE_KINDS_ALL, DEVICE_KINDS_LMS
         if kind in DEVICE_KINDS_LMS:
             f = lib().sonde_engine_set_family_lms6
             f.argtypes = [C.c_void_p, C.c_int32]
             _chk(f(self._h, int(vit)))
             self._family_lms = True
+            if rs:
+                f = lib().sonde_engine_set_family_lms6_rs
+                f.argtypes = [C.c_void_p, C.c_int32]
+                _chk(f(self._h, 1))
+                self._family_lms_rs = True
             return
+        if rs:
+            raise SondeError(f"set_family: rs is LMS6's / LMS-X's, not {kind}'s")
         if kind not in DEVICE_KINDS_ALL:
             raise SondeError(f"set_family: hits of type {kind} are not decoded on the device")
         if kind == "MRZ":
@@ -432,15 +440,22 @@ class Engine:
         """After set_family(): the hits completed so far as decoded records (dicts of sonde_family_hit_t: channel, kind, nbits, decoded, mv_pos, mv, v, aux, data; on
         an LMS6 / LMS-X engine of sonde_lms6_hit_t: .. mv, len, blen, err, vit, bytes), for FamilyDecoder.decoded().  A record with decoded = 0 carries its soft bits
         ("soft") for the host decode, and so does a decoded one for which need_soft(record) is true; max_hits: the rest stays queued."""
-        from .family import FamilyHit, Lms6Hit, family_hit_dict, lms6_hit_dict
+        from .family import FamilyHit, Lms6Hit, Lms6Rs, family_hit_dict, lms6_hit_dict
         lms = getattr(self, "_family_lms", False)
         T, as_dict = (Lms6Hit, lms6_hit_dict) if lms else (FamilyHit, family_hit_dict)
         n = self._max_frames if max_hits is None else int(max_hits)
         buf = (T * max(n, 1))()
-        f = lib().sonde_engine_fetch_family_lms6 if lms else lib().sonde_engine_fetch_family
-        f.argtypes = [C.c_void_p, C.POINTER(T), C.c_int32, C.c_int32]
-        k = _chk(f(self._h, buf, n, int(finish)))
-        recs = [as_dict(buf[i]) for i in range(k)]
+        if lms and getattr(self, "_family_lms_rs", False):
+            rsb = (Lms6Rs * max(n, 1))()
+            f = lib().sonde_engine_fetch_family_lms6_rs
+            f.argtypes = [C.c_void_p, C.POINTER(T), C.POINTER(Lms6Rs), C.c_int32, C.c_int32]
+            k = _chk(f(self._h, buf, rsb, n, int(finish)))
+            recs = [dict(as_dict(buf[i]), rs=Lms6Rs.from_buffer_copy(rsb[i])) for i in range(k)]
+        else:
+            f = lib().sonde_engine_fetch_family_lms6 if lms else lib().sonde_engine_fetch_family
+            f.argtypes = [C.c_void_p, C.POINTER(T), C.c_int32, C.c_int32]
+            k = _chk(f(self._h, buf, n, int(finish)))
+            recs = [as_dict(buf[i]) for i in range(k)]
         want = [not r["decoded"] or (need_soft is not None and bool(need_soft(r))) for r in recs]
         if any(want):
             soft = self.last_soft(k)

@@ -179,6 +179,38 @@ def decode_lms6_hits_device(hits, mvs, vit: int = 2, lmsx: bool = False):
     return [lms6_hit_dict(out[i]) for i in range(len(hits))]
 
 
+class Lms6RsHyp(C.Structure):
+    """sonde_lms6_rs_hyp_t (include/sonde_hip.h)"""
+    _fields_ = [("at", _I), ("err", _I), ("pos", C.c_uint8 * 16), ("val", C.c_uint8 * 16)]
+
+
+class Lms6Rs(C.Structure):
+    """sonde_lms6_rs_t (include/sonde_hip.h): RS(255,223) of one LMS6 / LMS-X block under the three hypotheses the host decoder can ask for"""
+    _fields_ = [("h6", Lms6RsHyp), ("hX", Lms6RsHyp), ("h6X", Lms6RsHyp)]
+
+
+def decode_lms6_rs_device(blocks, blen):
+    """RS(255,223) of LMS6 / LMS-X blocks on the device (k_lms6_rs) on block records in host memory (sonde_lms6_rs_device): blocks = their block bytes (up to 308
+    each, zero behind blen[i]); -> a list of Lms6Rs, for FamilyDecoder.decoded(rec, rs=..)."""
+    n = len(blocks)
+    if len(blen) != n:
+        raise SondeError("decode_lms6_rs_device: a block length per block")
+    by = np.zeros((max(n, 1), 308), np.uint8)
+    for i, b in enumerate(blocks):
+        b = np.frombuffer(bytes(b), np.uint8)
+        if len(b) > 308:
+            raise SondeError(f"decode_lms6_rs_device: block {i} has {len(b)} bytes, a block has at most 308")
+        by[i, :len(b)] = b
+    bl = np.ascontiguousarray(list(blen) + [0] * (1 - min(n, 1)), np.int32)
+    out = (Lms6Rs * max(n, 1))()
+    fn = lib().sonde_lms6_rs_device
+    fn.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, _I, C.POINTER(Lms6Rs)]
+    rc = fn(by.ctypes.data, 308, bl.ctypes.data, n, out)
+    if rc < 0:
+        raise SondeError(f"sonde_lms6_rs_device: {lib().sonde_strerror(rc).decode()} ({rc})")
+    return [Lms6Rs.from_buffer_copy(out[i]) for i in range(n)]
+
+
 class FamilyDecoder:
     """one decoder object of type `typ` (a key of FAMILY): state lives across hits like the reference's gpx_t"""
 
@@ -253,7 +285,15 @@ class FamilyDecoder:
             raise SondeError(f"{self.typ}: decoder call failed ({k})")
         return self._buf.raw[:k].decode(errors="replace")
 
-    def decoded(self, rec: dict, if_sr: int = 48000) -> str:
+    def lms_rs_stats(self):
+        """LMS6 only: (RS results taken from device records, decoded here instead) over the decoded(rec, rs=..) calls so far (sonde_lms6_dec_rs_stats)"""
+        u, m = C.c_int64(0), C.c_int64(0)
+        fn = lib().sonde_lms6_dec_rs_stats
+        fn.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        fn(self._h, C.byref(u), C.byref(m))
+        return u.value, m.value
+
+    def decoded(self, rec: dict, if_sr: int = 48000, rs=None) -> str:
         """one dict of Engine.fetch_family(): the characters the reference decoder prints for that hit, from the device's bytes and verdicts (no block code runs
         here).  A record the device did not decode (decoded = 0: a hit cut short by the end of input, or device decoding switched off) goes through hit() on its
         soft bits.  LMS6: so does a record longer than the block this decoder reads (an LMS6 decoder on an LMS-X engine, in the block of the change) — it has to
@@ -272,9 +312,16 @@ class FamilyDecoder:
                     raise SondeError(f"LMS6: a record of {n} bits for a decoder that reads {self.lms_block_bits()}: its soft bits are needed (fetch_family's need_soft)")
                 return self.hit(rec, if_sr)
             rate = self._lms_rate(rec["mv_pos"], if_sr)
-            fn = lib().sonde_lms6_dec_block_bytes
-            fn.argtypes = [C.c_void_p, C.c_char_p, _I, _I, C.c_float, C.c_float, C.c_double, C.c_char_p, C.c_size_t]
-            k = fn(self._h, rec["bytes"][:rec["blen"]], rec["blen"], rec["len"], rec["mv"], rate, (rec["mv_pos"] + n * if_sr / 4800.0) / if_sr, self._buf, len(self._buf))
+            rs = rs if rs is not None else rec.get("rs")
+            t_end = (rec["mv_pos"] + n * if_sr / 4800.0) / if_sr
+            if rs is not None:                                             # the device's RS(255,223) record beside the hit (Engine.fetch_family under rs=True)
+                fn = lib().sonde_lms6_dec_block_rs
+                fn.argtypes = [C.c_void_p, C.c_char_p, _I, _I, C.c_float, C.c_float, C.c_double, C.POINTER(Lms6Rs), C.c_char_p, C.c_size_t]
+                k = fn(self._h, rec["bytes"][:rec["blen"]], rec["blen"], rec["len"], rec["mv"], rate, t_end, C.byref(rs), self._buf, len(self._buf))
+            else:
+                fn = lib().sonde_lms6_dec_block_bytes
+                fn.argtypes = [C.c_void_p, C.c_char_p, _I, _I, C.c_float, C.c_float, C.c_double, C.c_char_p, C.c_size_t]
+                k = fn(self._h, rec["bytes"][:rec["blen"]], rec["blen"], rec["len"], rec["mv"], rate, t_end, self._buf, len(self._buf))
             if k < 0:
                 raise SondeError(f"LMS6: sonde_lms6_dec_block_bytes failed ({k})")
             return self._buf.raw[:k].decode(errors="replace")

@@ -275,7 +275,7 @@ class SoftinDev:
     def __init__(self, n_channels: int, *, ecc: int = 2, softinv: bool = False, inv: bool = True, auto: bool = False, kind: str = "rs41",
                  vit: int = 2, typ: int = 0, json: bool = False, raw: bool = False, gpsweek: int = 0, freq_khz: int = 0, version: str = "", skip: bool = True,
                  rs92_opts: dict | None = None, ephemeris: str | None = None, almanac: str | None = None, imet54_opts: dict | None = None,
-                 meisei_opts: dict | None = None, mrz_opts: dict | None = None, mts01_opts: dict | None = None, gps_device: bool = False):
+                 meisei_opts: dict | None = None, mrz_opts: dict | None = None, mts01_opts: dict | None = None, gps_device: bool = False, lms6_rs: bool = False):
         """kind: "rs41" (rs41mod --softin), "dfm" (dfm09mod --softin: ecc 0 / 1 = --ecc / 2 = --ecc2), "m10" (m10mod --softin), "m20" (m20mod --softin: skip = the rest of
         the second behind a frame is dropped, as m20mod does below -vvv; auto_rx runs `m20mod --json --ptu -vvv --softin -i`: skip=False; ecc, inv and auto mean nothing to it), "drop" (rd94rd41drop --softin /
         --softinv [-i]: auto_rx runs it as softinv=True, inv=False; ecc and auto are ignored) or "lms6" (lms6Xmod --softin: vit 1 = --vit / 2 = --vit2, typ 0 = auto
@@ -316,6 +316,8 @@ class SoftinDev:
             o = Lms6Opts(raw=int(raw), ecc=1 if ecc else 0, vit=vit, json=int(json), typ=typ, gpsweek=gpsweek, jsn_freq_khz=freq_khz, version=version.encode())
             _chk(_lib().sonde_softin_dev_create_lms6(n_channels, C.byref(o), int(softinv), C.byref(h)))
             self._h, self.n_channels = h, n_channels
+            if lms6_rs:
+                self.set_lms6_rs(True)
             return
         _chk(_lib().sonde_softin_dev_create(n_channels, {"rs41": SONDE_RS41, "dfm": SONDE_DFM09, "m10": SONDE_M10, "m20": SONDE_M20, "drop": SONDE_RD94RD41}[kind], ecc, int(softinv), int(inv), int(auto), C.byref(h)))
         self._h, self.n_channels = h, n_channels
@@ -413,6 +415,21 @@ class SoftinDev:
         buf = (DropFrame * max_frames)()
         n = _chk(_lib().sonde_softin_dev_fetch_drop(self._h, buf, max_frames))
         return [_frame_dict(buf[i]) for i in range(n)]
+
+    def set_lms6_rs(self, on: bool):
+        """LMS6 consumers (lms6_rs=True at creation): RS(255,223) of the blocks on the device as well (k_lms6_rs); the channels' decoders take its results instead
+        of decoding.  Off by default; the text is the same either way."""
+        f = _lib().sonde_softin_dev_set_lms6_rs
+        f.argtypes = [C.c_void_p, C.c_int32]
+        _chk(f(self._h, int(bool(on))))
+
+    def lms6_rs_stats(self):
+        """LMS6 consumers: (RS results the decoders took from device records, decoded on the host instead), over all channels"""
+        u, m = C.c_int64(0), C.c_int64(0)
+        f = _lib().sonde_softin_dev_lms6_rs_stats
+        f.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        _chk(f(self._h, C.byref(u), C.byref(m)))
+        return u.value, m.value
 
     def fetch_lms6(self, max_blocks: int = 1024):
         """LMS6 consumers: a dict per completed block — channel, hdr_bit (the header's bit index in the channel's stream), mv, type (6 / 0x0206 / 10 in effect
