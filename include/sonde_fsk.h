@@ -20,6 +20,7 @@
 #include "sonde_meisei.h"
 #include "sonde_mrz.h"
 #include "sonde_mts01.h"
+#include "sonde_wxr.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -360,7 +361,42 @@ typedef struct {
 /* frames completed by the push calls since the last fetch (per channel in stream order); returns the count (<= max) */
 int  sonde_softin_dev_fetch_mts01(sonde_softin_dev_t *s, sonde_mts01_softin_t *out, int32_t max);
 
-/* tallies since creation: frames completed (SONDE_LMS6: blocks; accepted = the frames with a good CRC-16 that ended in them, the decoders' own count), frames accepted (RS41: rs41_ecc() >= 0; DFM: no block uncorrectable; M10 / M20: checksum good; RD94RD41: every block of the type print_frame chooses good; RS92: rs_decode >= 0; iMet-54: ecc_frm >= 0 and a check sum good, or ecc_std == 0 — the JSON rule without the status bits; Meisei: no block 0xE / 0xF; MRZ / MTS01: CRC-16 good, and their repaired and symbol tallies stay 0), frames repaired (RS92: rs_decode > 0; iMet-54: ecc_frm > 0; Meisei: any block 1 or 2), symbols / codewords repaired (RS92: the sum of the positive rs_decode values; iMet-54: of the positive ecc_frm; Meisei: the sum of the corrected bits), frames lost to a full buffer */
+/* ---- SONDE_WXR301 consumers: `weathex301d --softin [-i] [--pn9] ...` for every channel (auto_rx's pipe `fsk_demod --cs16 -s -b -40000 -u 40000 --mask 50000
+ * --stats=N 2 <96000|100000> <4800|5000> - - | weathex301d --softin -i --json [--pn9]`, auto_rx/autorx/decode.py:1414-1423, :1458-1467).  On the device, one wavefront
+ * per channel (weathex301d.c:607-648, :250-256, :272-294, :359-375): bit = (s >= 0), with -i (s <= 0) — +-0.0 is a 1 and a NaN a 0 either way; every bit enters a 40-bit
+ * ring that starts holding no bit at all; outside a frame a ring equal to AA AA AA 2D D4 (--pn9: AA AA AA C1 94) opens a frame of the header's 40 bits and the next
+ * 512; inside a frame the header is not searched for, and behind the 552nd bit the search resumes on a ring that holds the frame's last 40 bits.  Then the 69 bytes
+ * MSB first, with --pn9 bytes 6 .. 68 XORed with the PN9 sequence, chkval = xor8 << 8 | sum8 over the 53 bytes from ofs (6, --pn9: 8) against
+ * x[ofs + 53] << 8 | x[ofs + 54], and the frame id, serial and counter.  Per completed frame 176 bytes come to the host; sonde_wxr_print_decoded (include/sonde_wxr.h)
+ * prints from the record's bytes and verdict.  Only complete frames are delivered: a header open at the end of the input prints nothing.
+ * invert_stream XORs with opts->invert (the two inversions cancel each other, as for the dropsondes).  sonde_softin_dev_create with SONDE_WXR301 is SONDE_E_ARG (the
+ * kind needs its options); the other kinds' fetch calls refuse a WxR consumer and fetch_wxr refuses the other kinds.  One launch per push call.
+ * A push call holds at most 20 * n_channels + 16 frames over all channels (a call of n bits completes at most n / 552 + 1 per channel: ten for a second at 5000 Bd);
+ * frames beyond that are decoded, not delivered, and counted as dropped. */
+typedef struct {
+    int32_t pn9;             /* --pn9: header AA AA AA C1 94, PN9 de-whitening from byte 6, the check from byte 8                  */
+    int32_t invert;          /* -i                                                                                                */
+    int32_t reserved[6];
+} sonde_wxr_softin_opts_t;
+struct sonde_wxr_softin_rec {
+    int32_t  channel;
+    int32_t  reserved0;
+    uint64_t hdr_bit;        /* soft bits read before the one that completed the header (-t prints hdr_bit / 4800 or 5000)        */
+    uint8_t  raw[69];        /* the 552 frame bits, MSB first, before PN9 (what -R prints)                                        */
+    uint8_t  x[69];          /* behind PN9 (without --pn9 the same bytes): what -r prints and the fields are read from           */
+    uint8_t  reserved1[2];
+    uint32_t chkval;         /* xor8 << 8 | sum8 over x[ofs .. ofs + 52], as the device computed it                               */
+    uint32_t chkdat;         /* x[ofs + 53] << 8 | x[ofs + 54]                                                                    */
+    uint8_t  chk_ok;         /* the device's verdict                                                                              */
+    uint8_t  frid;           /* x[ofs + 6]                                                                                        */
+    uint8_t  reserved2[2];
+    uint32_t sn, cnt;        /* serial (x[ofs .. ofs + 3], little endian) and counter (x[ofs + 4], x[ofs + 5])                    */
+};                           /* 176 bytes: the sonde_wxr_softin_rec_t of include/sonde_wxr.h                                      */
+int  sonde_softin_dev_create_wxr(int32_t n_channels, const sonde_wxr_softin_opts_t *opts, int32_t invert_stream, sonde_softin_dev_t **out);
+/* frames completed by the push calls since the last fetch (per channel in stream order); returns the count (<= max) */
+int  sonde_softin_dev_fetch_wxr(sonde_softin_dev_t *s, sonde_wxr_softin_rec_t *out, int32_t max);
+
+/* tallies since creation: frames completed (SONDE_LMS6: blocks; accepted = the frames with a good CRC-16 that ended in them, the decoders' own count), frames accepted (RS41: rs41_ecc() >= 0; DFM: no block uncorrectable; M10 / M20: checksum good; RD94RD41: every block of the type print_frame chooses good; RS92: rs_decode >= 0; iMet-54: ecc_frm >= 0 and a check sum good, or ecc_std == 0 — the JSON rule without the status bits; Meisei: no block 0xE / 0xF; MRZ / MTS01: CRC-16 good, WXR301: chk_ok, and their repaired and symbol tallies stay 0), frames repaired (RS92: rs_decode > 0; iMet-54: ecc_frm > 0; Meisei: any block 1 or 2), symbols / codewords repaired (RS92: the sum of the positive rs_decode values; iMet-54: of the positive ecc_frm; Meisei: the sum of the corrected bits), frames lost to a full buffer */
 int  sonde_softin_dev_counts(sonde_softin_dev_t *s, int64_t *frames, int64_t *ecc_ok, int64_t *repaired, int64_t *symbols, int64_t *dropped);
 
 #ifdef __cplusplus

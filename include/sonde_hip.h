@@ -50,7 +50,8 @@ extern "C" {
 #define SONDE_MEISEI 11         /* meisei100mod.c: Meisei iMS-100 / RS-11G; the type of a soft-bit consumer (sonde_softin_dev_create_meisei, include/sonde_fsk.h) and the kind of a generic engine's device decoder (sonde_engine_set_family) */
 #define SONDE_MRZ    31         /* mp3h1mod.c: Meteo-Radiy MRZ / MP3-H1; the type of a soft-bit consumer (sonde_softin_dev_create_mrz, include/sonde_fsk.h) and the kind of a generic engine's device decoder (sonde_engine_set_family, sonde_engine_set_family_mrz) */
 #define SONDE_MTS01  71         /* mts01mod.c: Meteosis MTS01; the type of a soft-bit consumer (sonde_softin_dev_create_mts01, include/sonde_fsk.h) and the kind of a generic engine's device decoder (sonde_engine_set_family) */
-#define SONDE_MIXED  100       /* cfg.sonde_type of sonde_engine_create_mixed: the type is a property of the channel (its group), not of the engine */
+#define SONDE_WXR301 301        /* weathex301d.c: Weathex WxR-301D; only as the type of a soft-bit consumer (sonde_softin_dev_create_wxr, include/sonde_fsk.h); the engine of its own is include/sonde_wxr.h */
+#define SONDE_MIXED  100      /* cfg.sonde_type of sonde_engine_create_mixed: the type is a property of the channel (its group), not of the engine */
 #define SONDE_GENERIC 99        /* any other 2-FSK sonde of the reference's demod/mod family, described by a sonde_generic_t given to sonde_engine_create_generic;
                                  * header hits + soft bits (sonde_engine_fetch_hits), framing stays with the caller — or, for six kinds, decoded records (sonde_engine_set_family, _set_family_lms6) */
 

@@ -9,7 +9,9 @@
  *    (weathex301d.c:171-226, 649-707).  It hands out the 552 bit values of finished frames; many channels per call.
  *  - the printer (host only, no GPU): bits -> bytes -> PN9 -> check -> text, -r, -R, JSON (print_frame, :359-527), byte-identical to
  *    the reference's stdout, with the pairing of frame ids 1 and 2 that persists between frames.
- *  - the soft-bit framer (host only): the --softin loop of main (:607-648).
+ *  - the soft-bit framer: the --softin loop of main (:607-648).  For one stream it is host code (sonde_wxr_softin_push, what host/weathex301d --softin
+ *    runs); for a batch of channels behind the GPU modem it runs on the device (sonde_softin_dev_create_wxr, include/sonde_fsk.h), which also does bytes, PN9 and
+ *    the check, and sonde_wxr_print_decoded prints from its records.
  *
  * Not built (SONDE_E_ARG): float32 IQ input, rates with fewer than 2 or more than 4096 samples per bit.
  */
@@ -85,7 +87,8 @@ typedef struct {
     int32_t pn9;             /* --pn9                                                                                        */
     int32_t jsn_freq_khz;    /* "freq" of the JSON when > 0                                                                  */
     char    version[32];     /* "version" of the JSON; "" = omit                                                             */
-    int32_t reserved[4];
+    int32_t ts;              /* -t, sonde_wxr_print_decoded only: "<%8.3f> " of hdr_bit / 4800 (--pn9: 5000) in front of the frame's text  */
+    int32_t reserved[3];
 } sonde_wxr_opts_t;
 
 int  sonde_wxr_printer_create(const sonde_wxr_opts_t *opts, sonde_wxr_printer_t **out);
@@ -93,10 +96,15 @@ void sonde_wxr_printer_destroy(sonde_wxr_printer_t *p);
 /* print_frame (weathex301d.c:359-527) on the 552 bit values of a frame: writes what the reference prints into out (NUL-terminated; -R of
  * an unset bit puts a NUL inside, so take the length from the return value); returns the length or a negative SONDE_E_* code */
 int  sonde_wxr_print_frame(sonde_wxr_printer_t *p, const uint8_t *bits, char *out, size_t outlen);
+/* print_frame on a record of the device soft-bit consumer (sonde_softin_dev_fetch_wxr, include/sonde_fsk.h): the same text, -r, -R, -v, JSON and pairing of frame
+ * ids 1 and 2, with the -t prefix of the --softin loop in front (opts.ts), from the record's bytes (x; -R: raw), check values, verdict, frame id, serial and
+ * counter as the device left them — nothing is recomputed.  Returns the length or a negative SONDE_E_* code */
+typedef struct sonde_wxr_softin_rec sonde_wxr_softin_rec_t;      /* the struct is defined in include/sonde_fsk.h */
+int  sonde_wxr_print_decoded(sonde_wxr_printer_t *p, const sonde_wxr_softin_rec_t *rec, char *out, size_t outlen);
 /* (xor8 << 8) | sum8 (xor8sum, :318-330) */
 int  sonde_wxr_xor8sum(const uint8_t *bytes, int32_t len);
 
-/* ------------------------------------------------------------------ soft-bit framer (host code) */
+/* ------------------------------------------------------------------ soft-bit framer for one stream (host code; many channels: sonde_softin_dev_create_wxr) */
 typedef struct sonde_wxr_softin sonde_wxr_softin_t;
 
 int  sonde_wxr_softin_create(int32_t pn9, int32_t invert, sonde_wxr_softin_t **out);

@@ -25,12 +25,14 @@
 #include "sonde_softin_meisei_dev.h"
 #include "sonde_softin_mrz_dev.h"
 #include "sonde_softin_mts01_dev.h"
+#include "sonde_softin_wxr_dev.h"
 #include "../../include/sonde_drop.h"
 #include "../../include/sonde_rs92.h"
 #include "../../include/sonde_imet54.h"
 #include "../../include/sonde_meisei.h"
 #include "../../include/sonde_mrz.h"
 #include "../../include/sonde_mts01.h"
+#include "../../include/sonde_wxr.h"
 #include "sonde_devmem.h"
 #include <cstdio>
 #include <cstring>
@@ -599,6 +601,23 @@ void k_softin_mts01(const SoftinMts01Args A) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// Weathex WxR-301D: weathex301d --softin [-i] [--pn9] (weathex301d.c:607-648, :250-256, :272-294, :359-375) — no correlation: the sign of every soft bit goes into the
+// 40-bit ring (frame bits too), a frame is the header and the 512 bits behind a ring that equals AA AA AA 2D D4 / AA AA AA C1 94, and at its end the 69 bytes, the PN9
+// de-whitening and the xor8 / sum8 check run on the same wave: sonde_softin_wxr_dev.h, which the CPU wave emulator compiles as well.  The soft decisions are read
+// once, so nothing is staged: 216 B of LDS.  A record per completed frame; the text is the host's (sonde_wxr_print_decoded).
+// ------------------------------------------------------------------------------------------------
+struct SoftinWxrArgs { SoftinArgs base; SoftinWxrChan *chan; SoftinWxrRec *out; int inv, pn9; };
+
+__global__ __launch_bounds__(64)
+void k_softin_wxr(const SoftinWxrArgs A) {
+    const SoftinArgs &a = A.base;
+    __shared__ SoftinWxrLds s_l;
+    SoftinIn in;
+    if (!softin_input(a, in)) return;                  // (both inversions are in A.inv: the sign is not applied here)
+    wxr_wave_channel(A.chan + in.ch, in.x, in.nb, A.inv, A.pn9, &s_l, A.out, a.count, a.cap, in.ch, threadIdx.x);
+}
+
+// ------------------------------------------------------------------------------------------------
 // RD94 / RD41 dropsondes: rd94rd41drop --softin / --softinv [-i] (rd94rd41drop.c:1357-1386) — no correlation: the sign of every soft bit (s >= 0 after the two
 // inversions, which cancel each other) goes into the 40-bit ring, a frame is the 2360 raw bits behind a ring that equals FC 1D as Manchester-coded 8N1, and the
 // bits of a frame enter the ring too.  64 soft bits a pass: signs by ballot, every lane tests the ring as it stands behind its bit (values and "holds a bit"
@@ -837,8 +856,8 @@ struct sonde_softin_dev {
     int head = 0;                                  // records copied to the host without asking how many there are (what a call of a second normally completes)
     const SoftinKind *kind = nullptr;
     int ecc_level = 0;                             // RS41, DFM09
-    int opt = 0;                                   // the kind's own switch: M20 skip, dropsonde / RS92 inv, iMet-54 / Meisei ecc, LMS6 vit, MRZ classify (not -R)
-    int opt2 = 0;                                  // MRZ: --ofs
+    int opt = 0;                                   // the kind's own switch: M20 skip, dropsonde / RS92 / WxR inv, iMet-54 / Meisei ecc, LMS6 vit, MRZ classify (not -R)
+    int opt2 = 0;                                  // MRZ: --ofs; WxR: --pn9
     SoftinArgs args{};
     hipStream_t stream = nullptr;                  // the consumer's own, made by its first call (softin_enqueue): behind the modem's streams, in the order of use
     void *d_state = nullptr;                       // the channels between calls
@@ -919,6 +938,10 @@ static void launch_mrz(sonde_softin_dev *s, const SoftinArgs &a, int nblocks, hi
 static void launch_mts01(sonde_softin_dev *s, const SoftinArgs &a, int nblocks, hipStream_t st) {
     softin_launch_staged(k_softin_mts01, SoftinMts01Args{a, s->chan<SoftinMts01Chan>(), s->recs<SoftinMts01Rec>(), 0}, nblocks, st);
 }
+static void launch_wxr(sonde_softin_dev *s, const SoftinArgs &a, int nblocks, hipStream_t st) {
+    const SoftinWxrArgs d{a, s->chan<SoftinWxrChan>(), s->recs<SoftinWxrRec>(), s->opt, s->opt2};
+    hipLaunchKernelGGL(k_softin_wxr, dim3(nblocks), dim3(64), 0, st, d);
+}
 static void launch_drop(sonde_softin_dev *s, const SoftinArgs &a, int nblocks, hipStream_t st) {
     const SoftinDropArgs d{a, s->chan<SoftinDropChan>(), s->recs<DropFrame>(), s->opt};
     hipLaunchKernelGGL(k_softin_drop, dim3(nblocks), dim3(64), 0, st, d);
@@ -994,6 +1017,11 @@ static void tally_mts01(sonde_softin_dev *s, const SoftinMts01Rec &r) {
     s->queue(r); s->frames_total++;
     if (r.crc_ok) s->ecc_ok_total++;
 }
+static void tally_wxr(sonde_softin_dev *s, const SoftinWxrRec &r) {
+    if (r.channel < 0 || r.channel >= s->C) return;
+    s->queue(r); s->frames_total++;
+    if (r.chk_ok) s->ecc_ok_total++;
+}
 
 static const SoftinKind *softin_kind(const int type) {
     static const SoftinKind rs41{0, launch_rs41, tally_rs41}, dfm{sizeof(sonde_dfm_frame_t), launch_dfm, tally_all<sonde_dfm_frame_t, tally_dfm>},
@@ -1001,11 +1029,12 @@ static const SoftinKind *softin_kind(const int type) {
         drop{sizeof(DropFrame), launch_drop, tally_all<DropFrame, tally_drop>}, lms6{sizeof(Lms6Block), launch_lms6, nullptr},
         rs92{sizeof(SoftinRs92Rec), launch_rs92, tally_all<SoftinRs92Rec, tally_rs92>}, imet54{sizeof(SoftinImet54Rec), launch_imet54, tally_all<SoftinImet54Rec, tally_imet54>},
         meisei{sizeof(SoftinMeiseiRec), launch_meisei, tally_all<SoftinMeiseiRec, tally_meisei>},
-        mrz{sizeof(SoftinMrzRec), launch_mrz, tally_all<SoftinMrzRec, tally_mrz>}, mts01{sizeof(SoftinMts01Rec), launch_mts01, tally_all<SoftinMts01Rec, tally_mts01>};
+        mrz{sizeof(SoftinMrzRec), launch_mrz, tally_all<SoftinMrzRec, tally_mrz>}, mts01{sizeof(SoftinMts01Rec), launch_mts01, tally_all<SoftinMts01Rec, tally_mts01>},
+        wxr{sizeof(SoftinWxrRec), launch_wxr, tally_all<SoftinWxrRec, tally_wxr>};
     switch (type) {
         case SONDE_RS41: return &rs41;     case SONDE_DFM09: return &dfm;   case SONDE_M10: return &m10;       case SONDE_M20: return &m20;       case SONDE_RD94RD41: return &drop;
         case SONDE_LMS6: return &lms6;     case SONDE_RS92: return &rs92;   case SONDE_IMET54: return &imet54; case SONDE_MEISEI: return &meisei;
-        case SONDE_MRZ: return &mrz;       case SONDE_MTS01: return &mts01;
+        case SONDE_MRZ: return &mrz;       case SONDE_MTS01: return &mts01;   case SONDE_WXR301: return &wxr;
     }
     return nullptr;
 }
@@ -1210,6 +1239,24 @@ int sonde_softin_dev_create_mts01(int32_t n_channels, const sonde_mts01_opts_t *
     return softin_created(s, ok, out);
 }
 
+static_assert(sizeof(SoftinWxrRec) == sizeof(sonde_wxr_softin_rec_t) && sizeof(SoftinWxrRec) == 176, "the WxR record is the C ABI's");
+static_assert(offsetof(SoftinWxrRec, hdr_bit) == offsetof(sonde_wxr_softin_rec_t, hdr_bit) && offsetof(SoftinWxrRec, raw) == offsetof(sonde_wxr_softin_rec_t, raw)
+           && offsetof(SoftinWxrRec, x) == offsetof(sonde_wxr_softin_rec_t, x) && offsetof(SoftinWxrRec, chkval) == offsetof(sonde_wxr_softin_rec_t, chkval)
+           && offsetof(SoftinWxrRec, chk_ok) == offsetof(sonde_wxr_softin_rec_t, chk_ok) && offsetof(SoftinWxrRec, frid) == offsetof(sonde_wxr_softin_rec_t, frid)
+           && offsetof(SoftinWxrRec, sn) == offsetof(sonde_wxr_softin_rec_t, sn) && offsetof(SoftinWxrRec, cnt) == offsetof(sonde_wxr_softin_rec_t, cnt), "field for field");
+
+int sonde_softin_dev_create_wxr(int32_t n_channels, const sonde_wxr_softin_opts_t *opts, int32_t invert_stream, sonde_softin_dev_t **out) {
+    if (!out || n_channels < 1 || !opts) return SONDE_E_ARG;
+    sonde_softin_dev *s = nullptr;
+    SoftinWxrChan c; memset((void *)&c, 0, sizeof c);                                          // the ring holds no bit at all
+    // frames a call can hold over all channels (sonde_fsk.h): a call of n bits completes at most n / 552 + 1 per channel, ten for a second at 5000 Bd; twenty for
+    // two seconds.  A second normally completes nine.
+    if (const int rc = softin_new(n_channels, SONDE_WXR301, 20, 10, 0.f, invert_stream, &c, sizeof c, &s)) return rc;
+    s->opt = (invert_stream ? 1 : 0) ^ (opts->invert ? 1 : 0);                                 // the two inversions cancel each other, as for the dropsondes
+    s->opt2 = opts->pn9 ? 1 : 0;
+    return softin_created(s, true, out);
+}
+
 int sonde_softin_dev_rs92_load_ephemeris(sonde_softin_dev_t *s, const char *path) {
     if (!s || s->type != SONDE_RS92 || !path) return SONDE_E_ARG;
     for (int c = 0; c < s->C; c++) { const int rc = sonde_rs92_dec_load_ephemeris(s->decoder<sonde_rs92_dec_t>(c), path); if (rc) return rc; }
@@ -1380,9 +1427,9 @@ int sonde_softin_dev_push_device(sonde_softin_dev_t *s, const float *d_soft, int
 }  // extern "C"
 
 // Every fetch call: up to max of the queued records Q of a consumer of `type`, each through conv into out[i].  A consumer of another kind has no such records; the
-// calls of the kinds whose records carry a text made at fetch time (RS92, iMet-54, Meisei, MRZ, MTS01) and of M20 say so (SONDE_E_ARG), and so does every call on a
-// consumer of one of the five text kinds; the older calls on the older kinds return an empty queue.
-static bool softin_text_kind(const int t) { return t == SONDE_RS92 || t == SONDE_IMET54 || t == SONDE_MEISEI || t == SONDE_MRZ || t == SONDE_MTS01; }
+// calls of the kinds whose records carry a text made at fetch time (RS92, iMet-54, Meisei, MRZ, MTS01), of M20 and of WxR-301D say so (SONDE_E_ARG), and so does
+// every call on a consumer of one of those kinds but M20; the older calls on the older kinds return an empty queue.
+static bool softin_text_kind(const int t) { return t == SONDE_RS92 || t == SONDE_IMET54 || t == SONDE_MEISEI || t == SONDE_MRZ || t == SONDE_MTS01 || t == SONDE_WXR301; }
 // -> how many records of `rec` bytes this call takes from the front of the queue, or the error
 static int softin_fetch_count(sonde_softin_dev *s, const int type, const bool have_out, const int32_t max, const size_t rec) {
     if (!s) return SONDE_E_ARG;
@@ -1522,6 +1569,10 @@ int sonde_softin_dev_fetch_mts01(sonde_softin_dev_t *s, sonde_mts01_softin_t *ou
         o.text_len = sonde_mts01_dec_decoded(s->decoder<sonde_mts01_dec_t>(r.channel), r.bytes, r.crcval, r.crc_ok, o.text, sizeof o.text);
         if (o.text_len < 0) o.text[0] = 0;
     });
+}
+
+int sonde_softin_dev_fetch_wxr(sonde_softin_dev_t *s, sonde_wxr_softin_rec_t *out, int32_t max) {
+    return softin_fetch<SoftinWxrRec>(s, SONDE_WXR301, out, max, [](const SoftinWxrRec &r, sonde_wxr_softin_rec_t &o) { memcpy((void *)&o, (const void *)&r, sizeof o); });
 }
 
 int sonde_softin_dev_counts(sonde_softin_dev_t *s, int64_t *frames, int64_t *ecc_ok, int64_t *repaired, int64_t *symbols, int64_t *dropped) {

@@ -1,7 +1,9 @@
-// sonde_wxr_fields.cpp — host-only part of include/sonde_wxr.h: the printer (print_frame of the reference's weathex/weathex301d.c:359-527)
-// and the --softin bit loop of its main (:607-648).  No GPU.
+// sonde_wxr_fields.cpp — host-only part of include/sonde_wxr.h: the printer (print_frame of the reference's weathex/weathex301d.c:359-527), on a frame's bits
+// (sonde_wxr_print_frame) or on a record of the device soft-bit consumer (sonde_wxr_print_decoded), and the --softin bit loop of its main (:607-648) for one
+// stream.  No GPU.
 #include "../../include/sonde_hip.h"
 #include "../../include/sonde_wxr.h"
+#include "../../include/sonde_fsk.h"
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -64,34 +66,30 @@ extern "C" int sonde_wxr_printer_create(const sonde_wxr_opts_t *opts, sonde_wxr_
 
 extern "C" void sonde_wxr_printer_destroy(sonde_wxr_printer_t *p) { delete p; }
 
-extern "C" int sonde_wxr_print_frame(sonde_wxr_printer_t *p, const uint8_t *bits, char *out, size_t outlen) {
-    if (!p || !bits || !out) return SONDE_E_ARG;
+// what a frame's text is made from: the bytes behind PN9, the check as computed and as stored, the verdict, frame id, serial and counter — from the frame's bits
+// (sonde_wxr_print_frame) or as the device left them (sonde_wxr_print_decoded)
+struct WxrDecoded { const uint8_t *x; int chkval, chkdat, chk_ok; uint8_t frid; uint32_t sn, cnt; };
+
+// print_frame behind the verdict (:377-527); bit(j) = the character -R prints for frame bit j
+template <class BitF>
+static int wxr_print(sonde_wxr_printer_t *p, const WxrDecoded &d, const BitF &bit, const std::string &prefix, char *out, size_t outlen) {
     const sonde_wxr_opts_t &o = p->o;
     const int ofs = o.pn9 ? 8 : 6;
-    uint8_t x[FRAMELEN + 1];
-    for (int j = 0; j < FRAMELEN; j++) {                                    // bits2bytes, MSB first; whatever is not '1' counts as 0
-        int v = 0;
-        for (int i = 0; i < 8; i++) v = (v << 1) | (bits[8 * j + i] == 1);
-        if (o.pn9 && j >= 6) v ^= PN9b[(j - 6) % 64];
-        x[j] = (uint8_t)v;
-    }
-    const int chkval = (int)xor8sum(x + ofs, 53);
-    const int chkdat = (x[ofs + 53] << 8) | x[ofs + 54];
-    const int chk_ok = chkdat == chkval;
-    std::string s;
+    const uint8_t *x = d.x;
+    const int chkval = d.chkval, chkdat = d.chkdat, chk_ok = d.chk_ok;
+    std::string s = prefix;
     if (o.raw) {
         if (o.raw == 1) {
             for (int j = 0; j < FRAMELEN; j++) put(s, "%02X ", x[j]);
             put(s, " #  %s", chk_ok ? "[OK]" : "[NO]");
             if (o.vbs) put(s, " # [%04X:%04X]", chkdat, chkval);
         } else {
-            for (int j = 0; j < SONDE_WXR_BITS; j++) s.push_back(bits[j] == 0 ? '0' : bits[j] == 1 ? '1' : '\0');
+            for (int j = 0; j < SONDE_WXR_BITS; j++) s.push_back(bit(j));
         }
         s.push_back('\n');
     } else {
-        const uint32_t sn = x[ofs] | (x[ofs + 1] << 8) | (x[ofs + 2] << 16) | ((uint32_t)x[ofs + 3] << 24);
-        const uint32_t cnt = x[ofs + 4] | (x[ofs + 5] << 8);
-        const uint8_t frid = x[ofs + 6];
+        const uint32_t sn = d.sn, cnt = d.cnt;
+        const uint8_t frid = d.frid;
         if (frid == 1) {
             p->chk1ok = chk_ok; p->sn1 = sn; p->cnt1 = cnt;
             if (o.vbs) {
@@ -154,6 +152,38 @@ extern "C" int sonde_wxr_print_frame(sonde_wxr_printer_t *p, const uint8_t *bits
     memcpy(out, s.data(), s.size());
     out[s.size()] = 0;
     return (int)s.size();
+}
+
+extern "C" int sonde_wxr_print_frame(sonde_wxr_printer_t *p, const uint8_t *bits, char *out, size_t outlen) {
+    if (!p || !bits || !out) return SONDE_E_ARG;
+    const sonde_wxr_opts_t &o = p->o;
+    const int ofs = o.pn9 ? 8 : 6;
+    uint8_t x[FRAMELEN + 1];
+    for (int j = 0; j < FRAMELEN; j++) {                                    // bits2bytes, MSB first; whatever is not '1' counts as 0
+        int v = 0;
+        for (int i = 0; i < 8; i++) v = (v << 1) | (bits[8 * j + i] == 1);
+        if (o.pn9 && j >= 6) v ^= PN9b[(j - 6) % 64];
+        x[j] = (uint8_t)v;
+    }
+    WxrDecoded d;
+    d.x = x;
+    d.chkval = (int)xor8sum(x + ofs, 53);
+    d.chkdat = (x[ofs + 53] << 8) | x[ofs + 54];
+    d.chk_ok = d.chkdat == d.chkval;
+    d.sn = x[ofs] | (x[ofs + 1] << 8) | (x[ofs + 2] << 16) | ((uint32_t)x[ofs + 3] << 24);
+    d.cnt = x[ofs + 4] | (x[ofs + 5] << 8);
+    d.frid = x[ofs + 6];
+    return wxr_print(p, d, [bits](int j) { return bits[j] == 0 ? '0' : bits[j] == 1 ? '1' : '\0'; }, std::string(), out, outlen);
+}
+
+extern "C" int sonde_wxr_print_decoded(sonde_wxr_printer_t *p, const sonde_wxr_softin_rec_t *rec, char *out, size_t outlen) {
+    if (!p || !rec || !out) return SONDE_E_ARG;
+    const WxrDecoded d{rec->x, (int)rec->chkval, (int)rec->chkdat, rec->chk_ok ? 1 : 0, rec->frid, rec->sn, rec->cnt};
+    std::string prefix;
+    // the --softin loop's -t (main :628): bits read before the matching one over the bit rate, printed when the header is found
+    if (p->o.ts) put(prefix, "<%8.3f> ", (double)rec->hdr_bit / (double)(p->o.pn9 ? 5000 : 4800));
+    const uint8_t *raw = rec->raw;
+    return wxr_print(p, d, [raw](int j) { return (raw[j >> 3] >> (7 - (j & 7))) & 1 ? '1' : '0'; }, prefix, out, outlen);
 }
 
 // ------------------------------------------------------------------ --softin (main :607-648)

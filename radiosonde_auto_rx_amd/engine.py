@@ -25,6 +25,7 @@ SONDE_IMET54 = 54
 SONDE_MEISEI = 11
 SONDE_MRZ = 31
 SONDE_MTS01 = 71
+SONDE_WXR301 = 301
 LP_IQ, LP_FM = 1, 2
 TAP_DECIM, TAP_IFIQ, TAP_FM, TAP_BUFS, TAP_CORR = range(5)
 ABI_VERSION = 3

@@ -105,6 +105,24 @@ class Mts01SoftinRec(C.Structure):
 # `mts01mod --softin --json` (auto_rx starts this decoder on IQ; the pipe is the decoder's own)
 MTS01_DEFAULTS = dict(json=1)
 
+
+
+class WxrSoftinOpts(C.Structure):
+    """sonde_wxr_softin_opts_t (include/sonde_fsk.h)"""
+    _fields_ = [("pn9", C.c_int32), ("invert", C.c_int32), ("reserved", C.c_int32 * 6)]
+
+
+class WxrSoftinRec(C.Structure):
+    """sonde_wxr_softin_rec_t (include/sonde_fsk.h): 176 bytes"""
+    _fields_ = [("channel", C.c_int32), ("reserved0", C.c_int32), ("hdr_bit", C.c_uint64), ("raw", C.c_uint8 * 69), ("x", C.c_uint8 * 69), ("reserved1", C.c_uint8 * 2),
+                ("chkval", C.c_uint32), ("chkdat", C.c_uint32), ("chk_ok", C.c_uint8), ("frid", C.c_uint8), ("reserved2", C.c_uint8 * 2), ("sn", C.c_uint32),
+                ("cnt", C.c_uint32)]
+
+
+WXR_REC_FIELDS = ("channel", "hdr_bit", "raw", "x", "chkval", "chkdat", "chk_ok", "frid", "sn", "cnt")
+# auto_rx's `weathex301d --softin -i --json [--pn9]` (auto_rx/autorx/decode.py:1414-1423, :1458-1467)
+WXR_DEFAULTS = dict(pn9=0, inv=1)
+
 # the kinds whose consumer is made from the options struct of their host decoder: struct (family.py), auto_rx's defaults, create call
 _OPTS_KINDS = {"rs92": ("Rs92Opts", RS92_DEFAULTS, "sonde_softin_dev_create_rs92"), "imet54": ("Imet54Opts", IMET54_DEFAULTS, "sonde_softin_dev_create_imet54"),
                "meisei": ("MeiseiOpts", MEISEI_DEFAULTS, "sonde_softin_dev_create_meisei"), "mrz": ("MrzOpts", MRZ_DEFAULTS, "sonde_softin_dev_create_mrz"),
@@ -166,6 +184,8 @@ def _lib():
         L.sonde_softin_dev_fetch_mrz.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
         L.sonde_softin_dev_create_mts01.argtypes = [C.c_int32, C.POINTER(Mts01Opts), C.c_int32, C.POINTER(C.c_void_p)]
         L.sonde_softin_dev_fetch_mts01.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+        L.sonde_softin_dev_create_wxr.argtypes = [C.c_int32, C.POINTER(WxrSoftinOpts), C.c_int32, C.POINTER(C.c_void_p)]
+        L.sonde_softin_dev_fetch_wxr.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
         _proto = True
     return L
 
@@ -275,7 +295,8 @@ class SoftinDev:
     def __init__(self, n_channels: int, *, ecc: int = 2, softinv: bool = False, inv: bool = True, auto: bool = False, kind: str = "rs41",
                  vit: int = 2, typ: int = 0, json: bool = False, raw: bool = False, gpsweek: int = 0, freq_khz: int = 0, version: str = "", skip: bool = True,
                  rs92_opts: dict | None = None, ephemeris: str | None = None, almanac: str | None = None, imet54_opts: dict | None = None,
-                 meisei_opts: dict | None = None, mrz_opts: dict | None = None, mts01_opts: dict | None = None, gps_device: bool = False, lms6_rs: bool = False):
+                 meisei_opts: dict | None = None, mrz_opts: dict | None = None, mts01_opts: dict | None = None, gps_device: bool = False, lms6_rs: bool = False,
+                 wxr_opts: dict | None = None):
         """kind: "rs41" (rs41mod --softin), "dfm" (dfm09mod --softin: ecc 0 / 1 = --ecc / 2 = --ecc2), "m10" (m10mod --softin), "m20" (m20mod --softin: skip = the rest of
         the second behind a frame is dropped, as m20mod does below -vvv; auto_rx runs `m20mod --json --ptu -vvv --softin -i`: skip=False; ecc, inv and auto mean nothing to it), "drop" (rd94rd41drop --softin /
         --softinv [-i]: auto_rx runs it as softinv=True, inv=False; ecc and auto are ignored) or "lms6" (lms6Xmod --softin: vit 1 = --vit / 2 = --vit2, typ 0 = auto
@@ -289,7 +310,9 @@ class SoftinDev:
         this call mean nothing to it) or "mrz" (mp3h1mod --softin: mrz_opts = fields of family.MrzOpts over auto_rx's defaults aut 1, json 1, ptu 1 — inv there is
         -i, aut is --auto, bits_ofs with bits_ofs_given is --ofs; the frame length follows the device's CRC verdict) or "mts01" (mts01mod --softin: mts01_opts =
         fields of family.Mts01Opts over the default json 1; a header counts in either polarity and the bits are read raw, so an inverted stream needs softinv);
-        ecc, inv and auto of this call mean nothing to either"""
+        ecc, inv and auto of this call mean nothing to either; or "wxr" (weathex301d --softin: wxr_opts = pn9 (--pn9: 5000 Bd, header AA AA AA C1 94) and inv (-i) over
+        auto_rx's defaults pn9 0, inv 1; softinv XORs with inv, as for the dropsondes; bytes, PN9 and the check are the device's, WxrPrinter.decoded prints a record;
+        ecc, inv and auto of this call mean nothing to it)"""
         from .engine import SONDE_RS41, SONDE_DFM09, SONDE_M10, SONDE_M20, SONDE_RD94RD41
         h = C.c_void_p()
         self.kind, self.ecc = kind, ecc
@@ -311,6 +334,15 @@ class SoftinDev:
                 self.load_rs92_almanac(almanac)
             if gps_device:
                 self.set_rs92_gps(True)
+            return
+        if kind == "wxr":
+            kw = dict(WXR_DEFAULTS)
+            kw.update(wxr_opts or {})
+            o = WxrSoftinOpts(pn9=int(bool(kw.pop("pn9"))), invert=int(bool(kw.pop("inv"))))
+            if kw:
+                raise ValueError("wxr_opts has pn9 and inv, not %s" % sorted(kw))
+            _chk(_lib().sonde_softin_dev_create_wxr(n_channels, C.byref(o), int(softinv), C.byref(h)))
+            self._h, self.n_channels = h, n_channels
             return
         if kind == "lms6":
             o = Lms6Opts(raw=int(raw), ecc=1 if ecc else 0, vit=vit, json=int(json), typ=typ, gpsweek=gpsweek, jsn_freq_khz=freq_khz, version=version.encode())
@@ -504,6 +536,18 @@ class SoftinDev:
         frame's own characters are part of it, whatever a damaged frame holds: a character per byte, latin-1)"""
         return self._fetch_text("sonde_softin_dev_fetch_mts01", Mts01SoftinRec, max_frames, ("channel", "crcval", "crcdat", "crc_ok", "mv", "hdr_bit", "bytes"),
                                 encoding="latin-1")
+
+    def fetch_wxr(self, max_frames: int = 4096):
+        """WxR-301D consumers: a dict per completed frame — channel, hdr_bit (soft bits read before the one that completed the header), raw / x = the 69 frame bytes
+        before / behind PN9, chkval / chkdat / chk_ok (the device's xor8 << 8 | sum8, the stored one, the verdict), frid, sn, cnt: what wxr.WxrPrinter.decoded takes"""
+        buf = (WxrSoftinRec * max_frames)()
+        n = _chk(_lib().sonde_softin_dev_fetch_wxr(self._h, buf, max_frames))
+        out = []
+        for r in buf[:n]:
+            d = {k: getattr(r, k) for k in WXR_REC_FIELDS}
+            d.update({k: bytes(v) for k, v in d.items() if isinstance(v, C.Array)})
+            out.append(d)
+        return out
 
     def counts(self):
         v = [C.c_int64(0) for _ in range(5)]

@@ -1,5 +1,6 @@
 """ctypes mirror of include/sonde_wxr.h: the Weathex WxR-301D engine (GPU, many channels per call), its printer and its soft-bit framer
-(host code).
+for one stream (host code).  For many channels behind the GPU modem the soft-bit loop runs on the device: fsk.SoftinDev(n, kind="wxr") / fetch_wxr(), whose
+records WxrPrinter.decoded(rec) prints.
 
     eng = WxrEngine(fqs, 96000, if_bw_khz=64, opt_b=True)          # auto_rx: iq_dec --FM --IFbw 64 --lpFM --iq fq | weathex301d -b
     eng.process_host(x)           # x: (n_channels, n * 2) int16 IQ, n <= max_chunk, a multiple of dec_m
@@ -38,7 +39,7 @@ class WxrFrame(C.Structure):
 
 
 class WxrOpts(C.Structure):
-    _fields_ = [(n, C.c_int32) for n in ("raw", "vbs", "json", "pn9", "jsn_freq_khz")] + [("version", C.c_char * 32), ("reserved", C.c_int32 * 4)]
+    _fields_ = [(n, C.c_int32) for n in ("raw", "vbs", "json", "pn9", "jsn_freq_khz")] + [("version", C.c_char * 32), ("ts", C.c_int32), ("reserved", C.c_int32 * 3)]
 
 
 def _sigs(L):
@@ -58,6 +59,7 @@ def _sigs(L):
     L.sonde_wxr_printer_destroy.argtypes = [P]
     L.sonde_wxr_printer_destroy.restype = None
     L.sonde_wxr_print_frame.argtypes = [P, C.POINTER(C.c_uint8), C.c_char_p, C.c_size_t]
+    L.sonde_wxr_print_decoded.argtypes = [P, P, C.c_char_p, C.c_size_t]
     L.sonde_wxr_xor8sum.argtypes = [C.POINTER(C.c_uint8), C.c_int32]
     L.sonde_wxr_softin_create.argtypes = [C.c_int32, C.c_int32, C.POINTER(P)]
     L.sonde_wxr_softin_destroy.argtypes = [P]
@@ -93,11 +95,13 @@ def _frame_dict(f) -> dict:
 
 
 class WxrPrinter(PrinterHandle):
-    """frame bits -> the reference's text / -r / -R / JSON lines (host code, no GPU); remembers the id-1 frame the JSON of an id-2 frame needs."""
+    """frame bits, or a record of the device soft-bit consumer -> the reference's text / -r / -R / JSON lines (host code, no GPU); remembers the id-1 frame the
+    JSON of an id-2 frame needs."""
     _prefix = "sonde_wxr"
 
-    def __init__(self, *, raw: int = 0, vbs: bool = False, json: bool = False, pn9: bool = False, jsn_freq_khz: int = 0, version: str = ""):
-        o = WxrOpts(raw=int(raw), vbs=int(vbs), json=int(json), pn9=int(pn9), jsn_freq_khz=int(jsn_freq_khz), version=version.encode())
+    def __init__(self, *, raw: int = 0, vbs: bool = False, json: bool = False, pn9: bool = False, jsn_freq_khz: int = 0, version: str = "", ts: bool = False):
+        """ts = -t of the --softin loop: decoded() puts "<seconds> " of the record's hdr_bit in front (frame() has no time to print)"""
+        o = WxrOpts(raw=int(raw), vbs=int(vbs), json=int(json), pn9=int(pn9), jsn_freq_khz=int(jsn_freq_khz), version=version.encode(), ts=int(ts))
         self._open_printer(_sigs(lib()), o, 1 << 12)
 
     def frame(self, bits) -> str:
@@ -107,8 +111,22 @@ class WxrPrinter(PrinterHandle):
         return self._print("latin-1", b.ctypes.data_as(C.POINTER(C.c_uint8)))
 
 
+    def decoded(self, rec) -> str:
+        """the same text from a record of the device soft-bit consumer (a dict of fsk.SoftinDev.fetch_wxr, or a fsk.WxrSoftinRec): its bytes, check values, verdict,
+        frame id, serial and counter are printed as they are, nothing is recomputed"""
+        from .fsk import WXR_REC_FIELDS, WxrSoftinRec
+        if not isinstance(rec, WxrSoftinRec):
+            r = WxrSoftinRec()
+            for k in WXR_REC_FIELDS:
+                v = rec[k]
+                setattr(r, k, type(getattr(r, k))(*bytes(v)) if isinstance(v, (bytes, bytearray)) else int(v))
+            rec = r
+        n = self._call("print_decoded", self._h, C.byref(rec), self._out, len(self._out))
+        return self._out.raw[:n].decode("latin-1")
+
+
 class WxrSoftin(SoftinHandle):
-    """the --softin bit loop: float32 soft bits -> frames (host code, no GPU)"""
+    """the --softin bit loop for one stream: float32 soft bits -> frames (host code, no GPU; a batch of channels: fsk.SoftinDev(kind="wxr"))"""
     _prefix, _Frame, _frame_dict = "sonde_wxr", WxrFrame, staticmethod(_frame_dict)
 
     def __init__(self, *, pn9: bool = False, invert: bool = False):

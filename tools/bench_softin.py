@@ -38,10 +38,18 @@ A push is the kernel and the copies of its records (push_ms); the text is made w
 (sonde_mrz_dec_push_soft / sonde_mts01_dec_push_soft, one thread) on the same stream in the same run.  No speed threshold: the rows are the measured pair and the 9.6 / 4.8
 KB of soft decisions per channel and second that stay on the device.
 
+--kind wxr: the WxR-301D consumer (SoftinDev(kind="wxr"): k_softin_wxr with bytes, PN9 and the xor8 / sum8 check on the wave, auto_rx's form `weathex301d --softin -i
+--json --pn9`) — N channels x one second (5000 soft bits, the PN9 variant's rate) per push in device memory, a 13 s stream of frames 96 idle bits apart at sigma 0.3,
+negated as the modem delivers it, repeated.  13 warm-up pushes, then three rounds of --pushes timed ones: the median of the three round medians, with the smallest and
+the largest push of all.  A push is the kernel and the copies of its records (push_ms); the text (WxrPrinter.decoded per record) is timed apart (text_ms).  Beside it
+the host framer and printer (sonde_wxr_softin_push + sonde_wxr_print_frame, one thread) on the same stream in the same run: reported, not a threshold.  This consumer
+is there for the completeness of the device path — 176-byte records instead of 20 KB of soft bits per channel and second — not for speed; the one condition is that
+1024 channels take less than a second per second.
+
 --kind rs92 --gps-device: the text of the RS92 fetch alone, with the position solve's 4-satellite subset search on the host and on the device (SoftinDev(gps_device=True),
 DESIGN.md 4.11c), two consumers on the same pushes timed alternately in one run; rows of kind "rs92_gps" (the rs92 rows stay).
 
-    python tools/bench_softin.py [--kind lms6|m20|rs92|imet54|meisei|mrz|mts01|all] [--gps-device] [--channels 1,64,341,1024] [--pushes 39] [--vit 2] [--typ 0] [--out profiles/softin_bench.json]"""
+    python tools/bench_softin.py [--kind lms6|m20|rs92|imet54|meisei|mrz|mts01|wxr|all] [--gps-device] [--channels 1,64,341,1024] [--pushes 39] [--vit 2] [--typ 0] [--out profiles/softin_bench.json]"""
 import argparse
 import ctypes as C
 import json
@@ -552,6 +560,91 @@ def crc_rows(a, kind):
     return rows
 
 
+WXR_PER = 5000                                             # soft bits a second at the PN9 variant's rate
+
+
+def wxr_stream(sigma=0.3, seed=8):
+    """13 s at 5000 soft bits: PN9 frames 96 idle bits apart (tools/synth.py wxr_frames), noise on everything, negated (auto_rx runs the decoder with -i)"""
+    from tools import synth
+    rng = np.random.default_rng(seed)
+    n = 13 * WXR_PER
+    frames = synth.wxr_frames(n // 648, True)
+    bits = np.unpackbits(np.frombuffer(b"".join(b"\xAA" * 12 + f for f in frames), np.uint8))
+    bits = np.concatenate([bits, np.tile(np.array([1, 0], np.uint8), n)])[:n]
+    s = 2.0 * bits.astype(np.float64) - 1.0
+    return np.ascontiguousarray(-(s + rng.normal(0.0, sigma, n)), dtype=np.float32)
+
+
+def wxr_host_tier(s, pushes, nch):
+    """ms per push of one channel through the host framer and printer (one thread), [OK] lines of one channel"""
+    from radiosonde_auto_rx_amd.wxr import WxrPrinter, WxrSoftin
+    chans = [(WxrSoftin(pn9=True, invert=True), WxrPrinter(json=True, pn9=True)) for _ in range(nch)]
+    walls, ok = [], 0
+    for k in range(13 + pushes):
+        x = s[(k % 13) * WXR_PER:(k % 13 + 1) * WXR_PER]
+        t0 = time.perf_counter()
+        for fr, pr in chans:
+            text = "".join(pr.frame(f["bits"]) for f in fr.push(x))
+        dt = (time.perf_counter() - t0) * 1e3
+        if k >= 13:
+            walls.append(dt / nch)
+            ok += text.count("[OK]")
+    for fr, pr in chans:
+        fr.close(); pr.close()
+    return walls, ok
+
+
+def wxr_rows(a):
+    import torch
+    from radiosonde_auto_rx_amd.fsk import SoftinDev
+    from radiosonde_auto_rx_amd.wxr import WxrPrinter
+    s = wxr_stream()
+    hw, hok = wxr_host_tier(s, a.pushes, a.host_channels)
+    host_ms = statistics.median(hw)
+    rows = []
+    for nch in [int(c) for c in a.channels.split(",")]:
+        d = torch.from_numpy(s).to("cuda").repeat(nch, 1).contiguous()
+        torch.cuda.synchronize()
+        sf = SoftinDev(nch, kind="wxr", wxr_opts=dict(pn9=1, inv=1))
+        printers = [WxrPrinter(json=True, pn9=True) for _ in range(nch)]
+        rounds_w, rounds_t, walls, texts, ok, frames, good = [], [], [], [], 0, 0, 0
+        for k in range(13 + 3 * a.pushes):
+            p = d.data_ptr() + (k % 13) * WXR_PER * 4
+            t0 = time.perf_counter()
+            sf.push_device(p, d.shape[1], WXR_PER)
+            t1 = time.perf_counter()
+            recs = sf.fetch_wxr(20 * nch + 16)
+            text0 = ""
+            for r in recs:
+                t = printers[r["channel"]].decoded(r)
+                if r["channel"] == 0:
+                    text0 += t
+            t2 = time.perf_counter()
+            if k >= 13:
+                walls.append((t1 - t0) * 1e3); texts.append((t2 - t1) * 1e3)
+                frames += len(recs)
+                ok += text0.count("[OK]")
+                good += sum(r["chk_ok"] for r in recs)
+                if len(walls) % a.pushes == 0:
+                    rounds_w.append(statistics.median(walls[-a.pushes:])); rounds_t.append(statistics.median(texts[-a.pushes:]))
+        cnt = sf.counts()
+        sf.close()
+        for pr in printers:
+            pr.close()
+        wall, text = statistics.median(rounds_w), statistics.median(rounds_t)
+        row = {"kind": "wxr", "channels": nch, "pushes": a.pushes, "rounds": 3, "push_ms": round(wall, 3), "round_medians_ms": [round(v, 3) for v in rounds_w],
+               "min_ms": round(min(walls), 3), "max_ms": round(max(walls), 3),
+               "text_ms": round(text, 3), "text_min_ms": round(min(texts), 3), "text_max_ms": round(max(texts), 3), "push_plus_text_ms": round(wall + text, 3),
+               "channel_seconds_per_second": round(nch * 1e3 / (wall + text), 1), "a_second_in_less_than_a_second": bool(max(walls) + max(texts) < 1000.0),
+               "frames": frames, "chk_ok": good, "ok_channel0": ok, "dropped": cnt["dropped"],
+               "soft_bytes_per_channel_second_left_on_device": WXR_PER * 4, "record_bytes_per_channel_second": round(176 * frames / (3 * a.pushes) / nch, 1),
+               "host_tier_ms_per_channel_second": round(host_ms, 4), "host_tier_min_ms": round(min(hw), 4), "host_tier_max_ms": round(max(hw), 4),
+               "host_tier_ms_for_these_channels": round(host_ms * nch, 2), "host_tier_ok_one_channel": hok}
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    return rows
+
+
 def m20_rows(a):
     import torch
     from radiosonde_auto_rx_amd.fsk import SoftinDev
@@ -589,7 +682,7 @@ def m20_rows(a):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--kind", default="lms6", choices=["lms6", "m20", "rs92", "imet54", "meisei", "mrz", "mts01", "all"])
+    ap.add_argument("--kind", default="lms6", choices=["lms6", "m20", "rs92", "imet54", "meisei", "mrz", "mts01", "wxr", "all"])
     ap.add_argument("--channels", default="1,64,341,1024")
     ap.add_argument("--pushes", type=int, default=39)
     ap.add_argument("--vit", type=int, default=2)
@@ -610,7 +703,8 @@ def main():
 def main_rows(a):
     return (lms6_rows(a) if a.kind in ("lms6", "all") else []) + (m20_rows(a) if a.kind in ("m20", "all") else []) + (rs92_rows(a) if a.kind in ("rs92", "all") else []) \
         + (imet54_rows(a) if a.kind in ("imet54", "all") else []) + (meisei_rows(a) if a.kind in ("meisei", "all") else []) \
-        + (crc_rows(a, "mrz") if a.kind in ("mrz", "all") else []) + (crc_rows(a, "mts01") if a.kind in ("mts01", "all") else [])
+        + (crc_rows(a, "mrz") if a.kind in ("mrz", "all") else []) + (crc_rows(a, "mts01") if a.kind in ("mts01", "all") else []) \
+        + (wxr_rows(a) if a.kind in ("wxr", "all") else [])
 
 
 def write_rows(a, rows):
