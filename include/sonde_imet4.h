@@ -10,8 +10,13 @@
  *    (imet4iq.c:873-1315), byte-identical to the reference's stdout.
  *
  * Input above the IF rate the reference picks (48 / 32 / 96 / 64 kHz) goes through its decimating front end (decM > 1: IQ-dc removal and
- * the mixer table at the input rate, the decimator low-pass, k_imet4_decim) first.  Not built (SONDE_E_ARG): --decFM, --noLUT, float32 input,
- * rates whose filters do not fit the history rings (far above any sonde channel).
+ * the mixer table at the input rate, the decimator low-pass, k_imet4_decim) first.  Samples are 8-bit unsigned, 16-bit signed or float32, as the
+ * reference reads them.  Not built (SONDE_E_ARG): --decFM, --noLUT, rates whose filters do not fit the history rings (far above any sonde
+ * channel).
+ *
+ * An engine's channels can be handed out at run time (a receiver behind a channelizer): sonde_imet4_release_channel takes a channel out of
+ * the launches, sonde_imet4_restart_channel makes it a fresh channel at a new --iq fq, sonde_imet4_process_device_strided reads rows of a
+ * staging array whose stride is not the call's length.
  */
 #ifndef SONDE_IMET4_H
 #define SONDE_IMET4_H
@@ -27,7 +32,7 @@ extern "C" {
 
 typedef struct {
     int32_t sample_rate;     /* input rate (Hz)                                                                             */
-    int32_t bits;            /* 8 (unsigned) or 16 (signed) per sample component                                            */
+    int32_t bits;            /* per sample component: 8 (unsigned), 16 (signed) or 32 (float32, little-endian, taken as it is)   */
     int32_t iq;              /* 1: complex IQ (--iq fq), 0: FM audio (mono)                                                 */
     int32_t lp_iq;           /* --lpIQ / --lpbw: IF low-pass                                                                */
     int32_t lpbw_hz;         /* IF low-pass bandwidth; <= 0: the reference's default (16 kHz, 80 kHz with imet1)            */
@@ -57,10 +62,29 @@ void sonde_imet4_destroy(sonde_imet4_t *e);
  * for iq = 1) start at c * n * (iq ? 2 : 1).  SONDE_E_OVERFLOW: the frame queue of this call overflowed (frames lost; reported once). */
 int  sonde_imet4_process_host(sonde_imet4_t *e, const void *samples, int32_t n);
 int  sonde_imet4_process_device(sonde_imet4_t *e, const void *dev_samples, int32_t n);
+/* the same with channel c's samples starting at c * ch_stride samples (complex samples for iq = 1) instead of c * n: rows of a staging
+ * array of which the first n entries are valid.  ch_stride >= n, SONDE_E_ARG otherwise; n as for process_device.  float32 IQ input of
+ * either entry is 8-byte aligned.  A refused call leaves all state alone. */
+int  sonde_imet4_process_device_strided(sonde_imet4_t *e, const void *dev_samples, int64_t ch_stride, int32_t n);
 /* completed frames in channel / time order; returns their number (<= max) or a SONDE_E_* code.  Frames not fetched stay queued.
  * There is no finish / flush: a frame still in progress at the end of the input is never printed by the reference (imet4iq.c:1638), so
  * nothing is handed out for it. */
 int  sonde_imet4_fetch_frames(sonde_imet4_t *e, sonde_imet4_frame_t *out, int32_t max);
+
+/* ------------------------------------------------------------------ channels at run time
+ * After create every channel is active.  A released channel costs a launch nothing: its workgroups return before they read their input
+ * (which may be uninitialised memory) and write nothing — no state, no history, no frame.  Both calls are queued on the engine's stream
+ * between two process calls and do not wait for the device; SONDE_E_ARG for a channel out of range, and then nothing has changed.
+ *
+ * restart: from the next process call on the channel is what sonde_imet4_create builds for a channel at --iq fq (fq is ignored for FM
+ * audio): state, filter history and the frame in progress are as at create, frame.sample counts from the restart, and the channel is
+ * active.  No other channel is touched.
+ * release: the channel is inactive from the next process call on.  Frames already completed stay queued for sonde_imet4_fetch_frames.  The
+ * frame in progress is dropped: the reference never prints a frame that the end of its input cuts short (imet4iq.c:1638). */
+int  sonde_imet4_restart_channel(sonde_imet4_t *e, int32_t channel, double fq);
+int  sonde_imet4_release_channel(sonde_imet4_t *e, int32_t channel);
+/* 1: active, 0: released */
+int  sonde_imet4_channel_active(const sonde_imet4_t *e, int32_t channel);
 
 /* ------------------------------------------------------------------ testing taps (host code; not part of the decoding interface)
  * Read-only views of what the kernels left in device memory, for tests that compare every sample with a reference.  Each call waits for the

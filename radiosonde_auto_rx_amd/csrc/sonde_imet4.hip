@@ -13,6 +13,10 @@
 //     are computed again in the next tile under the schedule it implies.  Rings hold history by absolute sample index, so samples a
 //     truncated tile computed ahead are simply overwritten; the AFC's M-entry ring is written only for committed samples.
 // Complete 1000-bit frames go to a device queue.  With decM > 1, k_imet4_decim produces the IF samples first.
+// Input is 8-bit unsigned, 16-bit signed or float32 (taken as it is, imet4iq.c:235-237, 265-270, 329-332); a.bits is uniform over the launch.
+// Both kernels have two instantiations, picked per launch (a.rt): see k_imet4_afsk.
+// Channels are handed out at run time: a.active[c] == 0 ends a channel's workgroup before it reads anything, k_imet4_restart makes a channel
+// what create builds (sonde_imet4_restart_channel), and a channel's input row starts at c * a.ch_stride samples.
 //
 // Floating-point contraction is off in this file: the reference is plain C on x86-64 (every product and sum rounded on its own).
 #pragma clang fp contract(off)
@@ -74,8 +78,12 @@ __device__ __forceinline__ void emit(const Imet4Args &a, int c, Imet4Chan &st, u
 
 }  // namespace
 
-__global__ __launch_bounds__(64) void k_imet4_afsk(const Imet4Args a) {
+// RT: the engine's channels are handed out at run time or its samples are float32 — the active mask, the row stride and the float loads.
+// The launch picks RT = false where none of that is in use (8- / 16-bit samples, every channel active, rows n apart): that instantiation is
+// the kernel as it was before run-time channels, instruction for instruction.
+template <bool RT> __global__ __launch_bounds__(64) void k_imet4_afsk(const Imet4Args a) {
     const int c = blockIdx.x, lane = threadIdx.x;
+    if (RT && !a.active[c]) return;                                    // a released channel: nothing read, nothing written
     Imet4Chan st = a.chan[c];
     const uint32_t rmask = (uint32_t)a.ring - 1;
     float2 *zring = a.zring + (size_t)c * a.ring;
@@ -84,9 +92,10 @@ __global__ __launch_bounds__(64) void k_imet4_afsk(const Imet4Args a) {
     const float2 *ifin = a.ifbuf + (size_t)c * a.if_stride;
     float *bufs = a.bufs + (size_t)c * a.M;
     uint8_t *frame = a.frames + (size_t)c * IMET4_FRAME_STRIDE;
-    const size_t in_stride = (size_t)a.n * (a.iq ? 2 : 1);
+    const size_t in_stride = (RT ? (size_t)a.ch_stride : (size_t)a.n) * (a.iq ? 2 : 1);
     const uint8_t *in8 = (const uint8_t *)a.in + (a.bits == 8 ? in_stride * c : 0);
     const int16_t *in16 = (const int16_t *)a.in + (a.bits == 16 ? in_stride * c : 0);
+    const float *in32 = (const float *)a.in + (RT && a.bits == 32 ? in_stride * c : 0);
     const double bitlen = a.bitlen;
     const int nlag = (int)bitlen;
 
@@ -112,7 +121,8 @@ __global__ __launch_bounds__(64) void k_imet4_afsk(const Imet4Args a) {
                 if (act) { const float2 z = ifin[ix]; zr = z.x; zi = z.y; }
             } else {
                 if (act) {
-                    if (a.bits == 16) { xin = (float)(in16[2 * ix] / 32768.0); yin = (float)(in16[2 * ix + 1] / 32768.0); }
+                    if (RT && a.bits == 32) { const float2 z = ((const float2 *)in32)[ix]; xin = z.x; yin = z.y; }   // float32: as it is (imet4iq.c:265-270)
+                    else if (a.bits == 16) { xin = (float)(in16[2 * ix] / 32768.0); yin = (float)(in16[2 * ix + 1] / 32768.0); }
                     else { xin = (float)((in8[2 * ix] - 128) / 128.0); yin = (float)((in8[2 * ix + 1] - 128) / 128.0); }
                 }
                 const float br = xin - st.avgx, bi = yin - st.avgy;
@@ -146,7 +156,8 @@ __global__ __launch_bounds__(64) void k_imet4_afsk(const Imet4Args a) {
             const float wi = (float)((double)zi * (double)pr - (double)zr * (double)pi_);
             v = (float)(0.8 * atan2((double)wi, (double)wr) / kPi);
         } else if (act) {
-            if (a.bits == 16) v = (float)((float)(in16[ix] / 128.0) / 256.0);
+            if (RT && a.bits == 32) v = in32[ix];                                                              // imet4iq.c:235-237
+            else if (a.bits == 16) v = (float)((float)(in16[ix] / 128.0) / 256.0);
             else v = (float)((in8[ix] - 128) / 128.0);
         }
         if (a.lp_fm) {
@@ -283,16 +294,18 @@ __global__ __launch_bounds__(64) void k_imet4_afsk(const Imet4Args a) {
 // The decimating front end (decM > 1, f32read_cblock + the LUT mixer + lowpass(decXbuffer, ...) of f32_sample :468-489): per channel one
 // wavefront; base-rate samples in tiles of at most 64 (split at the IQ-dc block ends, whose double sums are in-order ladders), mixed and
 // written to a base ring by absolute index; then each lane one IF output, the decimator FIR over the ring in the reference's slot order.
-__global__ __launch_bounds__(64) void k_imet4_decim(const Imet4Args a) {
+template <bool RT> __global__ __launch_bounds__(64) void k_imet4_decim(const Imet4Args a) {
     const int c = blockIdx.x, lane = threadIdx.x;
+    if (RT && !a.active[c]) return;
     Imet4Chan st = a.chan[c];
     const unsigned long long bmask = (unsigned long long)a.bring_len - 1;
     float2 *ring = a.bring + (size_t)c * a.bring_len;
     float2 *out = a.ifbuf + (size_t)c * a.if_stride;
     const int D = a.decM;
-    const size_t in_stride = (size_t)a.n * D * 2;
+    const size_t in_stride = RT ? (size_t)a.ch_stride * 2 : (size_t)a.n * D * 2;
     const uint8_t *in8 = (const uint8_t *)a.in + (a.bits == 8 ? in_stride * c : 0);
     const int16_t *in16 = (const int16_t *)a.in + (a.bits == 16 ? in_stride * c : 0);
+    const float2 *in32 = (const float2 *)a.in + (RT && a.bits == 32 ? (size_t)a.ch_stride * c : 0);
     for (int t0 = 0; t0 < a.n; t0 += 64) {
         const int nI = min(64, a.n - t0);
         const long long nb = (long long)nI * D;
@@ -305,7 +318,8 @@ __global__ __launch_bounds__(64) void k_imet4_decim(const Imet4Args a) {
             const size_t ix = (size_t)t0 * D + (size_t)j0 + lane;
             float x = 0.f, y = 0.f;
             if (act) {
-                if (a.bits == 16) { x = (float)(in16[2 * ix] / 32768.0); y = (float)(in16[2 * ix + 1] / 32768.0); }
+                if (RT && a.bits == 32) { const float2 z = in32[ix]; x = z.x; y = z.y; }                       // imet4iq.c:329-332
+                else if (a.bits == 16) { x = (float)(in16[2 * ix] / 32768.0); y = (float)(in16[2 * ix + 1] / 32768.0); }
                 else { x = (float)((in8[2 * ix] - 128) / 128.0); y = (float)((in8[2 * ix + 1] - 128) / 128.0); }
                 const float br = x - st.avgx, bi = y - st.avgy;
                 double sn, cs;
@@ -342,8 +356,40 @@ __global__ __launch_bounds__(64) void k_imet4_decim(const Imet4Args a) {
     }
 }
 
+// Channel restart: the channel's record, rings, AFC buffer, IF row and frame bits become what create builds, and the channel is marked active.
+// Grid-stride over the longest of the rows; every index is checked against its own row length, so nothing outside channel c is written.
+__global__ __launch_bounds__(256) void k_imet4_restart(const Imet4Args a, const int c, const Imet4Chan fresh) {
+    const size_t step = (size_t)gridDim.x * blockDim.x;
+    const size_t ring = (size_t)a.ring, bring = (size_t)a.bring_len, nif = a.pre ? (size_t)a.if_stride : 1, M = (size_t)a.M;
+    float2 *zring = a.zring + (size_t)c * ring, *br = a.bring + (size_t)c * bring, *ifb = a.ifbuf + (size_t)c * nif;
+    float *fmring = a.fmring + (size_t)c * ring, *xring = a.xring + (size_t)c * ring, *bufs = a.bufs + (size_t)c * M;
+    uint8_t *frame = a.frames + (size_t)c * IMET4_FRAME_STRIDE;
+    size_t top = ring > bring ? ring : bring;
+    if (nif > top) top = nif;
+    if (M > top) top = M;
+    if ((size_t)IMET4_FRAME_STRIDE > top) top = IMET4_FRAME_STRIDE;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < top; i += step) {
+        if (i < ring) { zring[i] = make_float2(0.f, 0.f); fmring[i] = 0.f; xring[i] = 0.f; }
+        if (i < bring) br[i] = make_float2(0.f, 0.f);
+        if (i < nif) ifb[i] = make_float2(0.f, 0.f);
+        if (i < M) bufs[i] = 0.f;
+        if (i < (size_t)IMET4_FRAME_STRIDE) frame[i] = (i == 1 || i == 9) ? 1 : 0;      // bitframe's initial SOH character, imet4iq.c:847
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) { a.chan[c] = fresh; a.active[c] = 1; }
+}
+
+extern "C" int sonde_launch_imet4_restart(const Imet4Args *a, int c, const Imet4Chan *fresh, hipStream_t s) {
+    hipLaunchKernelGGL(k_imet4_restart, dim3(16), dim3(256), 0, s, *a, c, *fresh);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
 extern "C" int sonde_launch_imet4(const Imet4Args *a, hipStream_t s) {
-    if (a->pre) hipLaunchKernelGGL(k_imet4_decim, dim3(a->n_ch), dim3(64), 0, s, *a);
-    hipLaunchKernelGGL(k_imet4_afsk, dim3(a->n_ch), dim3(64), 0, s, *a);
+    if (a->rt) {
+        if (a->pre) hipLaunchKernelGGL(k_imet4_decim<true>, dim3(a->n_ch), dim3(64), 0, s, *a);
+        hipLaunchKernelGGL(k_imet4_afsk<true>, dim3(a->n_ch), dim3(64), 0, s, *a);
+    } else {
+        if (a->pre) hipLaunchKernelGGL(k_imet4_decim<false>, dim3(a->n_ch), dim3(64), 0, s, *a);
+        hipLaunchKernelGGL(k_imet4_afsk<false>, dim3(a->n_ch), dim3(64), 0, s, *a);
+    }
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }

@@ -34,11 +34,18 @@ struct Imet4Args {
     const void *in;
     Imet4Frame *q;
     int *q_count;
-    int q_cap, n_ch, n, iq, bits, dc, lp_iq, lp_fm, taps_iq, taps_fm, sr, M;   // n: IF samples per channel of the call
+    int q_cap, n_ch, n, iq, bits, dc, lp_iq, lp_fm, taps_iq, taps_fm, sr, M;   // n: IF samples per channel of the call; bits: 8, 16, 32 (float32)
     int ring, pre, decM, taps_dec, bring_len, if_stride;   // ring: history ring length (power of 2); pre: IF input from k_imet4_decim
     double bitlen, w1, w2;
     float head_sps;
+    // behind the fields above, whose offsets the 8- / 16-bit instantiation's code depends on
+    long long ch_stride;               // input samples (complex ones for IQ) between the starts of two channels' rows
+    int *active;                       // per channel: 0 = released (its workgroups return at once and touch nothing)
+    int rt;                            // per call, by the host: launch the instantiation with the mask, the row stride and the float loads
 };
 
 extern "C" int sonde_launch_imet4(const Imet4Args *a, hipStream_t s);
+// channel c becomes what sonde_imet4_create builds for a channel whose record is `fresh`: rings, AFC buffer, IF row and frame bits as at
+// create, active[c] = 1.  One small kernel on s, in order with the process calls around it.
+extern "C" int sonde_launch_imet4_restart(const Imet4Args *a, int c, const Imet4Chan *fresh, hipStream_t s);
 #endif

@@ -1,11 +1,15 @@
 """ctypes mirror of include/sonde_imet4.h: the iMet-4 / iMet-1-RS engine (GPU, many channels per call) and its printer (host code).
 
     eng = Imet4Engine(fqs, sr, bits=16, iq=True, lp_iq=True, dc=True)      # the auto_rx IMET form: --iq 0.0 --lpIQ --dc - 48000 16
-    eng.process_host(x)           # x: (n_channels, n * 2) int16 IQ (or (n_channels, n) for FM audio), n <= max_chunk, a multiple of dec_m
+    eng.process_host(x)           # x: (n_channels, n * 2) int16 IQ (or (n_channels, n) for FM audio), n <= max_chunk, a multiple of dec_m;
+                                  # bits=8: uint8, bits=32: float32 taken as it is
     for f in eng.fetch_frames():  # {"channel", "sample", "bits"}
         text = printer.frame(f["bits"])
 
-Imet4Printer(json=True).frame(bits) returns the characters the reference's imet4iq prints for that frame."""
+Imet4Printer(json=True).frame(bits) returns the characters the reference's imet4iq prints for that frame.
+
+Channels at run time (ChannelizedReceiver): release_channel(c) takes a channel out of the launches, restart_channel(c, fq) makes it a fresh
+channel at a new fq, process_device(ptr, n, ch_stride=...) reads rows of a staging array."""
 from __future__ import annotations
 
 import ctypes as C
@@ -54,6 +58,10 @@ def _sigs(L):
     L.sonde_imet4_destroy.restype = None
     L.sonde_imet4_process_host.argtypes = [P, P, C.c_int32]
     L.sonde_imet4_process_device.argtypes = [P, P, C.c_int32]
+    L.sonde_imet4_process_device_strided.argtypes = [P, P, C.c_int64, C.c_int32]
+    L.sonde_imet4_restart_channel.argtypes = [P, C.c_int32, C.c_double]
+    L.sonde_imet4_release_channel.argtypes = [P, C.c_int32]
+    L.sonde_imet4_channel_active.argtypes = [P, C.c_int32]
     L.sonde_imet4_fetch_frames.argtypes = [P, C.POINTER(Imet4Frame), C.c_int32]
     L.sonde_imet4_read_tap.argtypes = [P, C.c_int32, C.c_int32, C.c_int64, C.c_int32, P]
     L.sonde_imet4_read_state.argtypes = [P, C.c_int32, C.POINTER(Imet4State)]
@@ -110,10 +118,28 @@ class Imet4Engine(EngineHandle):
             raise SondeError(rc, "sonde_imet4_create")
 
     def process_host(self, x: np.ndarray):
-        dt = np.int16 if self.bits == 16 else np.uint8
+        dt = {8: np.uint8, 16: np.int16, 32: np.float32}[self.bits]
         x = np.ascontiguousarray(x, dtype=dt).reshape(self.n_ch, -1)
         n = x.shape[1] // (2 if self.iq else 1)
         self._call("process_host", self._h, x.ctypes.data, n)
+
+    def process_device(self, ptr: int, n: int, ch_stride: int | None = None):
+        """n samples per channel at device pointer ptr; channel c's row starts at c * ch_stride samples (complex ones for IQ), c * n when None"""
+        if ch_stride is None:
+            self._call("process_device", self._h, C.c_void_p(ptr), n)
+        else:
+            self._call("process_device_strided", self._h, C.c_void_p(ptr), int(ch_stride), n)
+
+    def restart_channel(self, c: int, fq: float = 0.0):
+        """from the next call on channel c is a fresh channel at --iq fq (FM audio: fq is ignored), and active"""
+        self._call("restart_channel", self._h, int(c), float(fq))
+
+    def release_channel(self, c: int):
+        """channel c takes no part in the calls that follow: nothing of it is read or written; its frame in progress is dropped"""
+        self._call("release_channel", self._h, int(c))
+
+    def channel_active(self, c: int) -> bool:
+        return bool(self._call("channel_active", self._h, int(c)))
 
     def read_tap(self, channel: int, tap: str, first: int, count: int) -> np.ndarray:
         """testing tap: `count` samples of TAPS[tap] from absolute IF sample `first`, which must still be inside the history ring (the last

@@ -10,6 +10,9 @@ telemetry tier.  Everything sample-rate runs on the GPU; this module is the orch
 
 prints one JSON object per decoded frame (the reference's `rs41mod --json` object, "freq" = channel frequency in kHz).
 
+With `--channelize` the stream goes through the polyphase channelizer first (ChannelizedReceiver, for streams of several Msps): RS41, DFM, M10,
+M20, the generic family and iMet-4 are decoded from its channels; MkIIa, WxR-301D and the dropsondes are decoded by the raster receiver only.
+
 With `--survey SECONDS` the receiver works the way auto_rx does instead of scanning a raster all the time: a spectrum survey of the stream
 (power.py, the rtl_power step), auto_rx's peak pick on it, and a scanner channel per peak for the samples that follow.
 """
@@ -323,10 +326,21 @@ class ChannelizedReceiver:
                   (sonde_engine_restart_channel), is fine-tuned to the offset the scanner measured inside its channelizer channel
                   (cfg.if_tune / sonde_engine_tune_channel) and is fed that channel's samples from then on -> telemetry JSON.
 
+    iMet-4 goes the same way through the iMet engine (imet4.py) on the channelizer's float32 samples, `imet4iq --iq <df> --lpIQ --dc - <if_sr> 32`
+    per slot: sonde_imet4_restart_channel at the scanner's offset for a detection, sonde_imet4_release_channel for a slot that has gone silent;
+    released slots cost a block nothing.  An iMet-1-RS (`--imet1`: 96 kHz IF) is started only where the channelizer's output rate is at least
+    96 kHz; elsewhere the log says once per sonde that it cannot be decoded at this channel rate.  The same holds for a channel rate at which
+    imet4iq would decimate (an iMet-4 in a 96 kHz or 100 kHz channel: decM 2): a block's length need not be a multiple of the decimation.
+
+    Not decoded here: MkIIa (+/- 50 kHz of deviation) and WxR-301D (64 kHz wide) do not fit a 50 kHz channelizer channel and are fed from the
+    wide stream (WidebandReceiver); the dropsondes' engine has no channel restart in its float32 base-rate form.  Their detections are dropped.
+
     Every block costs one channelizer launch, one scanner step and one launch sequence per sonde type, whatever the number of sondes."""
 
     TYPES = {"RS41": ("rs41", Rs41Telemetry), "DFM": ("dfm", DfmTelemetry), "M10": ("m10", M10Telemetry), "M20": ("m20", M20Telemetry)}
     # + the scanner's RS92 / LMS6 / MEISEI / IMET5 / MRZ / MTS01: generic sonde descriptions and the bit-rate tiers of family.py
+    # + IMET4 (IMET1RS at channel rates of 96 kHz and more): one Imet4Engine whose slots are restarted and released (IMET_AFSK)
+    IMET1_MIN_RATE = 96000                   # --imet1's designated IF rate
 
     def __init__(self, sample_rate: int, *, M: int = 256, D: int = 200, P: int = 16, cfreq_hz: int = 0, slots: int = 16, chunk: int | None = None,
                  version: str = "sonde_hip", device: int = 0, idle_s: float = 30.0):
@@ -334,6 +348,7 @@ class ChannelizedReceiver:
         (sonde_engine_finish_channel) and handed to the next detection of its type."""
         import torch
         self.idle_s, self.t = idle_s, 0.0
+        self.n_if = 0                           # IF samples per channel taken so far
         from .chan import Channelizer
         from .scan import IFIQ
         self.torch, self.sr, self.cfreq, self.version, self.slots, self.device = torch, sample_rate, cfreq_hz, version, slots, device
@@ -347,11 +362,26 @@ class ChannelizedReceiver:
         self.groups: dict[str, dict] = {}       # type -> {engine, stage, owner[slot] = sonde dict or None}
         self.sondes: list[dict] = []
         self.log: list[dict] = []
+        self._undecodable: list[float] = []     # sondes the log has named as not decodable at this channel rate (f_hz)
         self._rest = None
         torch.cuda.synchronize(dev)
 
     def _group(self, typ: str):
-        g = self.groups.get(typ)
+        if typ in self.groups:                                     # (None: a type this channel rate cannot decode)
+            return self.groups[typ]
+        g = None
+        if typ in IMET_AFSK:                        # imet4iq --iq <df> --lpIQ --dc [--imet1] - <if_sr> 32, a slot per sonde
+            with self.torch.cuda.device(self.device):              # the iMet engine lives on the device that is current at create
+                eng = Imet4Engine([0.0] * self.slots, self.if_sr, bits=32, iq=True, lp_iq=True, dc=True, imet1=(typ == "IMET1RS"), max_chunk=self.nmax)
+            if eng.dec_m != 1:                                     # imet4iq would decimate this channel rate: blocks of any length do not fit its calls
+                eng.close()
+                self.groups[typ] = None
+                return None
+            for slot in range(self.slots):                         # handed out by restart_channel
+                eng.release_channel(slot)
+            stage = self.torch.zeros(self.slots, self.nmax, 2, dtype=self.torch.float32, device=self.out.device)
+            self.torch.cuda.synchronize(self.out.device)
+            g = self.groups[typ] = dict(engine=eng, stage=stage, owner=[None] * self.slots, calls=0)
         if g is None:
             kw = dict(bits=32, iq_mode=3, if_tune=True, lp_iq=True, max_chunk=self.nmax, max_frames=8 * self.slots, device=self.device)
             if typ in FAMILY:
@@ -370,22 +400,55 @@ class ChannelizedReceiver:
     def _start(self, k: int, typ: str, df: float):
         f_hz = self.ch.channel_freq(k) + df * self.if_sr
         for s in self.sondes:                                    # the neighbouring channel sees a strong signal too
-            if LMS_BASE.get(s["type"], s["type"]) == typ and abs(s["f_hz"] - f_hz) < (FAMILY[typ]["sep_hz"] if typ in FAMILY else 20_000.0 if typ in ("M10", "M20") else 8_000.0):
+            if LMS_BASE.get(s["type"], s["type"]) == typ and abs(s["f_hz"] - f_hz) < (FAMILY[typ]["sep_hz"] if typ in FAMILY else 20_000.0 if typ in ("M10", "M20") + IMET_AFSK else 8_000.0):
                 return
+        # --imet1's 96 kHz IF does not fit the channel, or imet4iq decimates this channel rate (96 kHz and 100 kHz channels for an iMet-4: decM 2,
+        # and a block's length need not be a multiple of it): said once per sonde
+        if typ in IMET_AFSK and ((typ == "IMET1RS" and self.if_sr < self.IMET1_MIN_RATE) or self._group(typ) is None):
+            if not any(abs(f - f_hz) < 20_000.0 for f in self._undecodable):
+                self._undecodable.append(f_hz)
+                self.log.append(dict(event="not decodable at this channel rate", type=typ, f_hz=f_hz, channel=k, if_sr=self.if_sr))
+            return
         g = self._group(typ)
         if None not in g["owner"]:
             self.log.append(dict(event="no free channel", type=typ, f_hz=f_hz))
             return
         slot = g["owner"].index(None)
-        if g["calls"]:
-            g["engine"].restart_channel(slot)
-        g["engine"].tune_channel(slot, df)
         khz = int(round((self.cfreq + f_hz) / 1000.0)) if self.cfreq else 0
-        tel = FamilyDecoder(typ, freq_khz=khz, version=self.version) if typ in FAMILY else self.TYPES[typ][1](freq_khz=khz, version=self.version)
+        if typ in IMET_AFSK:
+            g["engine"].restart_channel(slot, df)                  # --iq df: the offset inside the channelizer channel, cycles per IF sample
+            tel = Imet4Printer(json=True, jsn_freq_khz=khz, version=self.version)
+        else:
+            if g["calls"]:
+                g["engine"].restart_channel(slot)
+            g["engine"].tune_channel(slot, df)
+            tel = FamilyDecoder(typ, freq_khz=khz, version=self.version) if typ in FAMILY else self.TYPES[typ][1](freq_khz=khz, version=self.version)
         s = dict(type=typ, f_hz=f_hz, chan=k, slot=slot, telemetry=tel, frames=0, khz=khz, t_last=self.t, seen=0)
         g["owner"][slot] = s
         self.sondes.append(s)
-        self.log.append(dict(event="detected", type=typ, f_hz=f_hz, channel=k, slot=slot, freq_khz=khz))
+        self.log.append(dict(event="detected", type=typ, f_hz=f_hz, channel=k, slot=slot, freq_khz=khz, if_sample=self.n_if))   # if_sample: the slot's first sample, counted in the channel's IF samples from the start of the stream
+
+    def add_channel(self, typ: str, f_hz: float):
+        """start a decoder of sonde type `typ` (a scanner type name the receiver decodes: "RS41", "DFM", "M10", "IMET4", "LMS6", ...) at f_hz
+        (Hz from the stream's centre) without waiting for the scanner, from the next block on — what a detection does: the nearest channelizer
+        channel and the offset that is left inside it."""
+        if typ not in self.TYPES and typ not in FAMILY and typ not in IMET_AFSK:
+            raise ValueError("the channelized receiver has no decoder for %r" % (typ,))
+        k = self.ch.nearest_channel(f_hz)
+        self._start(k, typ, (f_hz - self.ch.channel_freq(k)) / self.if_sr)
+
+    def _on_detection(self, d):
+        """one scanner detection -> a decoder slot of its type at the offset the scanner measured inside the channel"""
+        if d["type"] == "RS41" and d["score"] > 0:
+            self._start(d["channel"], "RS41", d["df"])
+        elif d["type"] == "DFM9":
+            self._start(d["channel"], "DFM", d["df"])
+        elif d["type"] in ("M10", "M20"):
+            self._start(d["channel"], d["type"], d["df"])
+        elif d["type"] in IMET_AFSK:                               # the scanner's AFSK check decided the variant
+            self._start(d["channel"], d["type"], d["df"])
+        elif d["type"] in FAMILY and (d["score"] > 0 or FAMILY[d["type"]]["auto"]):
+            self._start(d["channel"], d["type"], d["df"])
 
     def push(self, iq: np.ndarray, finish: bool = False):
         """iq: interleaved int16 I/Q of the wide stream; returns the JSON objects of this call."""
@@ -402,20 +465,18 @@ class ChannelizedReceiver:
             self.ch.sync()
             self.scanner.process_device(self.out.data_ptr(), self.nmax, m)
             for d in self.scanner.fetch():
-                if d["type"] == "RS41" and d["score"] > 0:
-                    self._start(d["channel"], "RS41", d["df"])
-                elif d["type"] == "DFM9":
-                    self._start(d["channel"], "DFM", d["df"])
-                elif d["type"] in ("M10", "M20"):
-                    self._start(d["channel"], d["type"], d["df"])
-                elif d["type"] in FAMILY and (d["score"] > 0 or FAMILY[d["type"]]["auto"]):
-                    self._start(d["channel"], d["type"], d["df"])
+                self._on_detection(d)
             for typ, g in list(self.groups.items()):
+                if g is None:                                                     # a type this channel rate cannot decode (_group)
+                    continue
                 for slot, s in enumerate(g["owner"]):
                     if s is not None:
                         g["stage"][slot, :m] = self.out[s["chan"], :m]
                 torch.cuda.synchronize(self.out.device)                           # the copies ran on torch's stream, the engine has its own
-                g["engine"].process_device(g["stage"].data_ptr(), self.nmax, m)
+                if typ in IMET_AFSK:
+                    g["engine"].process_device(g["stage"].data_ptr(), m, ch_stride=self.nmax)
+                else:
+                    g["engine"].process_device(g["stage"].data_ptr(), self.nmax, m)
                 g["calls"] += 1
                 out += self._drain(typ, g, False)
                 for slot, s in enumerate(g["owner"]):                             # channels that have gone silent go back to the pool
@@ -424,8 +485,11 @@ class ChannelizedReceiver:
                     if s.get("good", 0) != s["seen"]:                              # only frames that passed their check keep a channel
                         s["seen"], s["t_last"] = s.get("good", 0), self.t
                     elif self.t - s["t_last"] > self.idle_s:
-                        g["engine"].finish_channel(slot)
-                        out += self._drain(typ, g, False)                         # what the end of its stream still gave
+                        if typ in IMET_AFSK:                                       # the frame in progress prints nothing (imet4iq.c:1638)
+                            g["engine"].release_channel(slot)
+                        else:
+                            g["engine"].finish_channel(slot)
+                            out += self._drain(typ, g, False)                     # what the end of its stream still gave
                         g["owner"][slot] = None
                         s["telemetry"].close()
                         self.sondes.remove(s)
@@ -433,9 +497,11 @@ class ChannelizedReceiver:
             for s in [s for s in self.sondes if s["type"] in ("LMS6", "LMSX")]:     # after every engine has had this block: sondes whose decoder changed type
                 self._follow_lms(s)
             self.t += m / self.if_sr
+            self.n_if += m
         if finish:
             for typ, g in self.groups.items():
-                out += self._drain(typ, g, True)
+                if g is not None:
+                    out += self._drain(typ, g, True)
         return out
 
     def _follow_lms(self, s):
@@ -463,6 +529,17 @@ class ChannelizedReceiver:
 
     def _drain(self, typ, g, finish):
         e = g["engine"]
+        if typ in IMET_AFSK:                                       # as WidebandReceiver._drain: a frame is a sign of life when it printed a JSON object
+            out = []
+            for f in e.fetch_frames():
+                s = g["owner"][f["channel"]]
+                if s is None:
+                    continue
+                s["frames"] += 1
+                js = [json.loads(line) for line in s["telemetry"].frame(f["bits"]).split("\n") if line.startswith("{")]
+                s["good"] = s.get("good", 0) + (1 if js else 0)
+                out += js
+            return out
         if typ in FAMILY:                                          # header hits -> the type's bit-rate tier (family.py), one decoder object per sonde
             out = []
             for h in e.fetch_hits(finish=finish):
@@ -490,7 +567,8 @@ class ChannelizedReceiver:
     def close(self):
         self.scanner.close(); self.ch.close()
         for g in self.groups.values():
-            g["engine"].close()
+            if g is not None:
+                g["engine"].close()
         for s in self.sondes:
             s["telemetry"].close()
 
