@@ -11,7 +11,12 @@
  *    the reference's stdout, with the fields that persist from frame to frame.
  *  - the soft-bit framer (host only): the --softin / --softinv loop of main (:1357-1386), and the --rawhex line reader (:1450-1462).
  *
- * Not built (SONDE_E_ARG): float input, rates with fewer than 2 or more than 4096 samples per raw bit, the reference's unused option_res.
+ * Channels at run time: an engine created with bits = 32 (float32 IQ at a rate at which iq_dec does not decimate, what a channelizer produces) has a front
+ * end of its own on the device (k_fm_front: iq_dec.c f32read_cblock :337-382, the table mixer :674-711 / :571-573, the discriminator :593-596, re_lowpass
+ * :599-604, every channel on a sample clock that starts at its restart) and hands its channels out while it runs: restart, release and finish of one channel.
+ *
+ * Not built (SONDE_E_ARG): float32 FM samples, float32 IQ at rates at which iq_dec decimates (96 000 Hz, 100 000 Hz, ...), rates with fewer than 2 or more
+ * than 4096 samples per raw bit, the reference's unused option_res.
  */
 #ifndef SONDE_DROP_H
 #define SONDE_DROP_H
@@ -26,13 +31,14 @@ extern "C" {
 #define SONDE_DROP_FRAME_LEN 120         /* FRAME_LEN                                                                          */
 #define SONDE_DROP_RAWBITS 2400          /* RAWBITFRAME_LEN = 120 bytes * 10 bits (8N1) * 2 (Manchester)                        */
 
-#define SONDE_DROP_IN_IQ 0               /* baseband IQ, 8 (unsigned) or 16 (signed) bits per component                         */
+#define SONDE_DROP_IN_IQ 0               /* baseband IQ, 8 (unsigned) or 16 (signed) bits per component, or float32             */
 #define SONDE_DROP_IN_FM 1               /* FM samples: one real sample per frame, 8 (unsigned) or 16 (signed) bits             */
 
 typedef struct {
     int32_t sample_rate;     /* input rate (Hz)                                                                              */
     int32_t input;           /* SONDE_DROP_IN_IQ / SONDE_DROP_IN_FM                                                          */
-    int32_t bits;            /* per sample (component): 8 or 16                                                              */
+    int32_t bits;            /* per sample (component): 8 or 16; 32: float32 IQ taken as it is (iq_dec.c:361-364), IQ form at
+                                dec_m = 1 only                                                                               */
     int32_t invert;          /* -i                                                                                           */
     int32_t opt_b;           /* -b: integrate-and-dump behind the header                                                     */
     float   baud;            /* --br (kept when within 4700..4900, else 4800); <= 0: 4800                                    */
@@ -76,6 +82,26 @@ int  sonde_drop_process_device(sonde_drop_t *e, const void *dev_samples, int32_t
 int  sonde_drop_finish(sonde_drop_t *e);
 /* frames in channel / time order; returns their number (<= max) or a SONDE_E_* code.  Frames not fetched stay queued. */
 int  sonde_drop_fetch_frames(sonde_drop_t *e, sonde_drop_frame_t *out, int32_t max);
+
+/* ---- channels at run time: engines created with bits = 32 only (SONDE_E_ARG on every other engine, for a channel out of range, and for
+ * fq outside -0.5 .. 0.5).  restart / release only enqueue on the engine's stream, in order with the process calls. */
+/* process_device on rows ch_stride (>= n) samples apart: channel c's samples start at sample c * ch_stride.  The row of a released channel is not read. */
+int  sonde_drop_process_device_strided(sonde_drop_t *e, const void *dev_samples, int64_t ch_stride, int32_t n);
+/* from the next call on the channel is what create builds, at --iq fq, and active: the pipeline `iq_dec ... --iq fq - <rate> 32 | rd94rd41drop` started on
+ * the channel's next sample.  Its sample clock starts here: the IQ-dc schedule of iq_dec.c:752-758, the mixer table's index (:533), z0 (:552), the FM
+ * low-pass buffer (:747) and rd94rd41drop's sample_count, so sonde_drop_frame_t.sample counts from the restart. */
+int  sonde_drop_restart_channel(sonde_drop_t *e, int32_t channel, double fq);
+/* the channel takes no part in the calls that follow: nothing of it is read or written; a frame in progress is dropped */
+int  sonde_drop_release_channel(sonde_drop_t *e, int32_t channel);
+/* 1 / 0 */
+int  sonde_drop_channel_active(const sonde_drop_t *e, int32_t channel);
+/* the end of the input for one channel (main :1430-1445): with -b a frame whose header is open is completed with '0' bits and queued with complete = 0;
+ * then the channel is released.  Nothing happens to a released channel. */
+int  sonde_drop_finish_channel(sonde_drop_t *e, int32_t channel);
+/* testing tap: count samples of the channel's FM stream from its sample `first` (counted from its restart; still inside the ring of at least max_chunk
+ * samples, SONDE_E_RANGE otherwise) through iq_dec's 16-bit conversion (fwrite_fm_blk with --bo 16): what `iq_dec --FM --lpFM --wav --bo 16` writes.
+ * Returns count.  A released channel has no stream: SONDE_E_ARG. */
+int  sonde_drop_read_fm(sonde_drop_t *e, int32_t channel, int64_t first, int32_t count, int16_t *out);
 
 /* ------------------------------------------------------------------ printer (host code) */
 typedef struct sonde_drop_printer sonde_drop_printer_t;

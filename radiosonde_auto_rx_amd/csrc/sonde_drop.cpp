@@ -3,6 +3,8 @@
 // decimator, discriminator and FM low-pass) makes the FM stream of every channel in its device ring, and k_drop_slice reads it there
 // through iq_dec's 16-bit conversion.  FM form: the caller's integer samples go to k_drop_slice as they are.  One slicer launch per call,
 // which also completes finished frames (bytes, check masks); then the frame records into the host queue.
+// bits = 32 (float32 IQ at a rate iq_dec does not decimate): k_fm_front instead of the SONDE_FRONTEND engine, every channel on a sample clock of its
+// own, and channels handed out at run time (restart, release, finish of one channel; k_drop_slice_rt and k_drop_restart).
 #include "../../include/sonde_drop.h"
 #include "sonde_frame_engine.h"
 #include "sonde_drop_dev.h"
@@ -20,19 +22,33 @@ static sonde_drop_frame_t host_frame(const DropFrame &g) {
 
 struct sonde_drop : FmSliceEngine<DropArgs, sonde_drop_frame_t, sonde_drop_info_t> {
     // the front end (IQ form) and one slicer launch over n input samples per channel at dev_in
-    int run(const void *dev_in, int32_t n) {
+    int run(const void *dev_in, int32_t n) { return run(dev_in, n, -1); }
+    // in_stride: samples between two channels of dev_in (own front end), -1: n
+    int run(const void *dev_in, int32_t n, int64_t in_stride) {
         DropArgs c = a;
-        TRY(slicer_input(c, dev_in, n));
+        TRY(slicer_input(c, dev_in, n, in_stride));
+        return launch_drain(c, sonde_launch_drop, host_frame);
+    }
+    // the -b frame of the open header of channels ch0 .. ch0 + count - 1, completed with '0' bits (main :1430-1445)
+    int finish_from(int ch0, int count) {
+        DropArgs c = a;
+        c.in = own_front ? (const void *)fa.fm : d_in; c.n = 0; c.first = 0; c.finish = 1; c.ch0 = ch0; c.n_ch = count;
+        if (!own_front) c.ch_stride = 0;
         return launch_drain(c, sonde_launch_drop, host_frame);
     }
 };
 
 static float baud_of(const sonde_drop_cfg_t *cfg) { return cfg->baud > 0 && !(cfg->baud < 4700 || cfg->baud > 4900) ? cfg->baud : 4800.0f; }   // :1323
 constexpr int IF_TARGET = 48000;                                                                       // iq_dec.c without --IFbw
+constexpr float LPFM_HZ = 6e3f;                                                                        // iq_dec.c: dsp.lpFM_bw
 
 static int cfg_ok(const sonde_drop_cfg_t *cfg) {
     if (cfg->sample_rate < 1) return 0;
     if (cfg->input != SONDE_DROP_IN_IQ && cfg->input != SONDE_DROP_IN_FM) return 0;
+    if (cfg->bits == 32) {                                          // float32: IQ at a rate iq_dec does not decimate (the engine's own front end)
+        if (cfg->input != SONDE_DROP_IN_IQ) return 0;
+        return design_decimator_if(cfg->sample_rate, IF_TARGET, false).decM == 1;
+    }
     return cfg->bits == 8 || cfg->bits == 16;
 }
 
@@ -69,7 +85,10 @@ extern "C" int sonde_drop_create(const sonde_drop_cfg_t *cfg, int32_t n_ch, cons
     a.n_ch = n_ch; a.inv = cfg->invert ? 1 : 0; a.opt_b = cfg->opt_b ? 1 : 0; a.spb = inf.sps;
     // frames per channel and call: a run of n samples gives at most n / sps + 0.5 bits, a frame takes 2360 of them behind its header
     a.q_cap = n_ch * ((int)(2.0 * (max_chunk / inf.dec_m) / (2360.0 * inf.sps)) + 2);
-    if (cfg->input == SONDE_DROP_IN_IQ) {
+    if (cfg->input == SONDE_DROP_IN_IQ && cfg->bits == 32) {
+        TRY(e->create_own_front(cfg->sample_rate, fq, LPFM_HZ, DROP_IN_RING));
+        e->in_bytes = 8;
+    } else if (cfg->input == SONDE_DROP_IN_IQ) {
         TRY(e->create_front(cfg->sample_rate, cfg->bits, fq, IF_TARGET, DROP_IN_RING));
         e->in_bytes = (cfg->bits / 8) * 2;
     } else {
@@ -111,9 +130,73 @@ extern "C" int sonde_drop_finish(sonde_drop_t *e) {
     if (e->finished) return 0;
     e->finished = 1;
     if (!e->a.opt_b) return 0;
-    DropArgs a = e->a;
-    a.in = e->d_in; a.n = 0; a.first = 0; a.ch_stride = 0; a.finish = 1;
-    return e->launch_drain(a, sonde_launch_drop, host_frame);
+    return e->finish_from(0, e->n_ch);
+}
+
+// ---- channels at run time (engines created with bits = 32).  The calls only enqueue on the engine's stream (every process call ends synchronised, so the
+// stream is idle between calls and nothing waits here); the host mirror changes at once
+static int rt_check(const sonde_drop_t *e, int32_t channel) { return (!e || !e->own_front || channel < 0 || channel >= e->n_ch) ? SONDE_E_ARG : 0; }
+
+extern "C" int sonde_drop_process_device_strided(sonde_drop_t *e, const void *dev_samples, int64_t ch_stride, int32_t n) {
+    if (e && !e->own_front) return SONDE_E_ARG;
+    TRY(engine_call_check(e, dev_samples, n));
+    if (ch_stride < n) return SONDE_E_ARG;
+    return n == 0 ? 0 : e->run(dev_samples, n, ch_stride);
+}
+
+extern "C" int sonde_drop_restart_channel(sonde_drop_t *e, int32_t channel, double fq) {
+    TRY(rt_check(e, channel));
+    if (!(fq >= -0.5 && fq <= 0.5) || e->finished) return SONDE_E_ARG;
+    const FmFrontChan s = e->fresh_front(fq);
+    if (sonde_launch_drop_restart(&e->a, &e->fa, channel, &s, e->stream)) return SONDE_E_NOGPU;
+    e->active[(size_t)channel] = 1;
+    e->m_start[(size_t)channel] = e->m_done;
+    return 0;
+}
+
+extern "C" int sonde_drop_release_channel(sonde_drop_t *e, int32_t channel) {
+    TRY(rt_check(e, channel));
+    HIPCHK(hipMemsetAsync(e->fa.active + channel, 0, sizeof(int), e->stream));
+    e->active[(size_t)channel] = 0;
+    return 0;
+}
+
+extern "C" int sonde_drop_channel_active(const sonde_drop_t *e, int32_t channel) {
+    TRY(rt_check(e, channel));
+    return e->active[(size_t)channel] ? 1 : 0;
+}
+
+extern "C" int sonde_drop_finish_channel(sonde_drop_t *e, int32_t channel) {
+    TRY(rt_check(e, channel));
+    if (e->finished) return SONDE_E_ARG;
+    if (!e->active[(size_t)channel]) return 0;
+    const int rc = e->a.opt_b ? e->finish_from(channel, 1) : 0;
+    TRY(sonde_drop_release_channel(e, channel));
+    return rc;
+}
+
+// testing tap: host code only, the kernels and their arguments are as without it
+extern "C" int sonde_drop_read_fm(sonde_drop_t *e, int32_t channel, int64_t first, int32_t count, int16_t *out) {
+    TRY(rt_check(e, channel));
+    if ((!out && count) || count < 0 || first < 0 || !e->active[(size_t)channel]) return SONDE_E_ARG;   // a released channel has no stream to count in
+    const int64_t have = (int64_t)(e->m_done - e->m_start[(size_t)channel]), ring = e->fa.ring;
+    if (first + count > have || first < have - ring) return SONDE_E_RANGE;
+    HIPCHK(hipStreamSynchronize(e->stream));
+    std::vector<float> v((size_t)count);
+    const float *row = e->fa.fm + (size_t)channel * (size_t)ring;
+    int32_t done = 0;
+    while (done < count) {
+        const int64_t idx = (int64_t)((e->m_start[(size_t)channel] + (uint64_t)(first + done)) & (uint64_t)(ring - 1));
+        const int32_t run = (int32_t)std::min<int64_t>(count - done, ring - idx);
+        HIPCHK(hipMemcpy(v.data() + done, row + idx, (size_t)run * sizeof(float), hipMemcpyDeviceToHost));
+        done += run;
+    }
+    for (int32_t i = 0; i < count; i++) {                            // fwrite_fm_blk's 16-bit conversion, as DropSlice::load_sample
+        float x = v[(size_t)i] * 128.0f;
+        x *= 256.0f;
+        out[i] = (int16_t)(int)x;
+    }
+    return count;
 }
 
 extern "C" int sonde_drop_fetch_frames(sonde_drop_t *e, sonde_drop_frame_t *out, int32_t max) { return engine_fetch_frames(e, out, max); }

@@ -3,6 +3,7 @@
 #ifndef SONDE_DROP_DEV_H
 #define SONDE_DROP_DEV_H
 #include "sonde_slice_dev.h"
+#include "sonde_fm_front_dev.h"
 
 #define DROP_RAWBITS 2400           // RAWBITFRAME_LEN
 #define DROP_FRAME_LEN 120
@@ -23,7 +24,10 @@ struct DropFrame {
 
 typedef SliceArgs<int32_t, DropFrame> DropArgs;
 
+// (a->active set: the run-time-channel form k_drop_slice_rt, workgroup b on channel a->ch0 + b)
 extern "C" int sonde_launch_drop(const DropArgs *a, hipStream_t s);
+// k_drop_restart: channel c of an engine with a front end of its own (sonde_fm_front_dev.h) becomes what create builds, and active
+extern "C" int sonde_launch_drop_restart(const DropArgs *a, const FmFrontArgs *f, int c, const FmFrontChan *fresh, hipStream_t s);
 
 #ifdef __HIPCC__
 // start and length of the checked bytes; the check word follows them, high byte first.  0..4: chksum16 (RD94), 5..11: CRC-16 (RD41)

@@ -7,6 +7,7 @@
 #include "sonde_devmem.h"
 #include "sonde_host.h"
 #include <hip/hip_runtime.h>
+#include "sonde_fm_front_dev.h"
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
@@ -108,12 +109,20 @@ template <class Info> int fm_front_design(Info &inf, int sample_rate, int if_tar
     return d.if_sr;
 }
 
+// k_fm_front (sonde_fm_front.hip) over a->n samples of every active channel
+extern "C" int sonde_launch_fm_front(const FmFrontArgs *a, hipStream_t s);
+
 // Args: SliceArgs of the slicer kernel (sonde_slice_dev.h); Info: the info record of the engine's public header
 template <class Args, class Frame, class Info> struct FmSliceEngine : FrameEngine<Frame> {
     Args a{};
     Info info{};
     sonde_engine_t *front = nullptr;                 // IQ form
     uint64_t m_done = 0;                             // IF samples the front end has made per channel
+    bool own_front = false;                          // IQ form on float32 at decM = 1: k_fm_front instead of a SONDE_FRONTEND engine
+    FmFrontArgs fa{};
+    int sample_rate = 0;                             // the mixer table of a channel is designed at it
+    std::vector<uint8_t> active;                     // host mirror of fa.active (the device copy changes on the stream, in order with the calls)
+    std::vector<uint64_t> m_start;                   // m_done at the channel's restart: where its own sample count begins in the FM ring
 
     ~FmSliceEngine() {
         this->close_stream();
@@ -134,8 +143,52 @@ template <class Args, class Frame, class Info> struct FmSliceEngine : FrameEngin
         a.kind = ring_kind; a.ch_stride = fi.ring_len; a.mask = (uint32_t)fi.ring_len - 1;
         return 0;
     }
-    // this call's input of the slicer: the front end's FM ring behind n more input samples (IQ form), or dev_in as it is
-    int slicer_input(Args &c, const void *dev_in, int32_t n) {
+    // ---- the engine's own front end (k_fm_front): float32 IQ at a rate iq_dec does not decimate, channels handed out at run time
+    // the record create and a restart build for a channel at fq (--iq fq)
+    FmFrontChan fresh_front(double fq) const {
+        FmFrontChan s;
+        memset(&s, 0, sizeof s);
+        s.maxlim = (uint32_t)info.if_rate;                                      // iq_dec.c:752-758 at decM = 1
+        s.maxcnt = s.maxlim / 32;
+        if (s.maxcnt < 1) s.maxcnt = 1;
+        const Mixer m = design_mixer(-std::max(-0.5, std::min(0.5, fq)), sample_rate);
+        s.f0 = m.f0; s.lut_len = (uint32_t)m.lut_len;
+        return s;
+    }
+    // lpfm_hz: iq_dec's dsp.lpFM_bw; a's view of the FM ring (ring_kind: the slicer's input kind for it) and of the active mask.  The caller has checked
+    // that info.dec_m is 1
+    int create_own_front(int sample_rate_, const double *fq, float lpfm_hz, int ring_kind) {
+        sample_rate = sample_rate_;
+        const std::vector<float> w = design_lowpass(lpfm_hz / (float)info.if_rate, info.taps_fm);
+        auto pow2 = [](long long v) { long long p = 1; while (p < v) p <<= 1; return p; };
+        const long long ring = pow2(std::max(this->max_chunk, 64)), rring = pow2((long long)w.size() + 128);
+        if ((int)w.size() > FMF_TAPS_MAX || rring > FMF_RING_MAX || ring > (1LL << 30)) return SONDE_E_ARG;
+        fa.n_ch = this->n_ch; fa.taps = (int)w.size(); fa.ring = (int)ring; fa.rring = (int)rring;
+        std::vector<FmFrontChan> ch((size_t)this->n_ch);
+        for (int c = 0; c < this->n_ch; c++) ch[(size_t)c] = fresh_front(fq[c]);
+        TRY(this->upload(&fa.chan, ch));
+        TRY(this->dalloc(&fa.fm, (size_t)this->n_ch * (size_t)ring));
+        TRY(this->dalloc(&fa.raw, (size_t)this->n_ch * (size_t)rring));
+        TRY(this->upload(&fa.ws2, dup_taps(w)));
+        TRY(this->upload(&fa.active, std::vector<int>((size_t)this->n_ch, 1)));
+        active.assign((size_t)this->n_ch, 1);                                   // every channel runs from create on
+        m_start.assign((size_t)this->n_ch, 0);
+        own_front = true;
+        a.kind = ring_kind; a.ch_stride = ring; a.mask = (uint32_t)ring - 1; a.active = fa.active; a.ch0 = 0;
+        return 0;
+    }
+    // this call's input of the slicer: the front end's FM ring behind n more input samples (IQ form), or dev_in as it is.  in_stride: samples between two
+    // channels of dev_in
+    int slicer_input(Args &c, const void *dev_in, int32_t n, int64_t in_stride = -1) {
+        if (own_front) {
+            if ((uintptr_t)dev_in & 7u) return SONDE_E_ARG;                     // 8-byte loads of (I, Q)
+            FmFrontArgs f = fa;
+            f.in = (const FmfIQ *)dev_in; f.n = n; f.ch_stride = in_stride < 0 ? n : in_stride; f.first = (uint32_t)(m_done & c.mask);
+            if (sonde_launch_fm_front(&f, this->stream)) return SONDE_E_NOGPU;
+            c.in = fa.fm; c.n = n; c.first = f.first;
+            m_done += (uint64_t)n;
+            return 0;
+        }
         if (!front) { c.in = dev_in; c.n = n; c.first = 0; c.ch_stride = n; return 0; }
         const int rc = sonde_engine_process_device(front, dev_in, n, n);
         if (rc < 0) return rc;

@@ -57,6 +57,9 @@ template <class S, class Frame> struct SliceArgs {
     uint32_t first, mask;              // sample i of the call is in[(first + i) & mask]
     int q_cap, n_ch, n, kind, inv, opt_b, finish;
     float spb;
+    // channels handed out at run time (the RT form of slice(); unused, and behind every field the other form reads, otherwise)
+    int *active;                       // 0: the channel's workgroup returns before it reads anything
+    int ch0;                           // workgroup b works on channel ch0 + b (a launch for one channel: its finish)
 };
 
 #ifdef __HIPCC__
@@ -80,11 +83,14 @@ __device__ __forceinline__ void push_bits(u64 &hist, u64 &valid, int k, int b) {
 }
 
 // (a by value, as the kernel gets it; the register counts of both forms are in profiles/wxr_rocprofv3.txt and profiles/drop_rocprofv3.txt)
-template <class T> __device__ __forceinline__ void slice(const typename T::Args a) {
+// RT: the engine's channels are handed out at run time — the active mask, and a launch that starts at channel a.ch0 (one channel finished on its own).  RT = false
+// is the slicer as it was before run-time channels, instruction for instruction.
+template <class T, bool RT = false> __device__ __forceinline__ void slice(const typename T::Args a) {
     typedef typename T::sample_t S;
     constexpr int BIT0 = T::HDR_PRESET ? SLICE_HEADLEN : 0;              // bit_count while no header is open
     __shared__ uint8_t fb[T::STRIDE];
-    const int c = blockIdx.x, lane = threadIdx.x;
+    const int c = RT ? (int)blockIdx.x + a.ch0 : (int)blockIdx.x, lane = threadIdx.x;
+    if (RT && !a.active[c]) return;                                      // a released channel: nothing read, nothing written
     uint8_t *fbg = a.frames + (size_t)c * T::STRIDE;
     for (int j = lane; j < T::STRIDE; j += 64) fb[j] = fbg[j];
     const SliceChan<S> st0 = a.chan[c];

@@ -9,7 +9,12 @@ framer (host code).
 
     DropEngine.fm(n_channels, 48000, bits=16)               # the slicer alone, on integer FM samples of the caller
 
-DropPrinter(json=True).frame(bytes) returns the characters the reference's rd94rd41drop prints for that frame."""
+DropPrinter(json=True).frame(bytes) returns the characters the reference's rd94rd41drop prints for that frame.
+
+Channels at run time (ChannelizedReceiver): DropEngine(fqs, sr, bits=32) takes float32 IQ at a rate at which iq_dec does not decimate;
+release_channel(c) takes a channel out of the launches, restart_channel(c, fq) makes it a fresh channel at a new fq, finish_channel(c) ends its
+stream (with -b the frame of an open header is handed out) and releases it, process_device(ptr, n, ch_stride=...) reads rows of a staging
+array."""
 from __future__ import annotations
 
 import ctypes as C
@@ -52,6 +57,12 @@ def _sigs(L):
     L.sonde_drop_process_host.argtypes = [P, P, C.c_int32]
     L.sonde_drop_process_device.argtypes = [P, P, C.c_int32]
     L.sonde_drop_finish.argtypes = [P]
+    L.sonde_drop_process_device_strided.argtypes = [P, P, C.c_int64, C.c_int32]
+    L.sonde_drop_restart_channel.argtypes = [P, C.c_int32, C.c_double]
+    L.sonde_drop_release_channel.argtypes = [P, C.c_int32]
+    L.sonde_drop_channel_active.argtypes = [P, C.c_int32]
+    L.sonde_drop_finish_channel.argtypes = [P, C.c_int32]
+    L.sonde_drop_read_fm.argtypes = [P, C.c_int32, C.c_int64, C.c_int32, P]
     L.sonde_drop_fetch_frames.argtypes = [P, C.POINTER(DropFrame), C.c_int32]
     L.sonde_drop_printer_create.argtypes = [C.POINTER(DropOpts), C.POINTER(P)]
     L.sonde_drop_printer_destroy.argtypes = [P]
@@ -118,7 +129,8 @@ def _cfg(sr, input, bits, invert, opt_b, baud):
 
 
 def design(sr: int, *, input: int = IN_IQ, bits: int = 16, baud: float = 0.0) -> dict:
-    """IF rate, decimation, tap counts and samples per raw bit of that configuration (host code, no GPU)"""
+    """IF rate, decimation, tap counts and samples per raw bit of that configuration (host code, no GPU); bits=32 where the engine takes
+    float32 (IQ at dec_m = 1), a SondeError elsewhere"""
     L = _sigs(lib())
     cfg, inf = _cfg(sr, input, bits, False, False, baud), DropInfo()
     rc = L.sonde_drop_design(C.byref(cfg), C.byref(inf))
@@ -190,7 +202,37 @@ class DropEngine(EngineHandle):
 
     def process_host(self, x: np.ndarray):
         per = 2 if self.input == IN_IQ else 1
-        x = np.ascontiguousarray(x, dtype=np.int16 if self.bits == 16 else np.uint8).reshape(self.n_ch, -1)
+        x = np.ascontiguousarray(x, dtype={8: np.uint8, 16: np.int16, 32: np.float32}[self.bits]).reshape(self.n_ch, -1)
         self._call("process_host", self._h, x.ctypes.data, x.shape[1] // per)
 
     finish = EngineHandle._finish
+
+    # ---- channels at run time: engines created with bits=32
+    def process_device(self, ptr: int, n: int, ch_stride: int | None = None):
+        """n samples per channel at device pointer ptr; channel c's row starts at c * ch_stride complex samples, c * n when None"""
+        if ch_stride is None:
+            self._call("process_device", self._h, C.c_void_p(ptr), n)
+        else:
+            self._call("process_device_strided", self._h, C.c_void_p(ptr), int(ch_stride), n)
+
+    def restart_channel(self, c: int, fq: float = 0.0):
+        """from the next call on channel c is a fresh channel at --iq fq, and active; its frames' "sample" counts from here"""
+        self._call("restart_channel", self._h, int(c), float(fq))
+
+    def release_channel(self, c: int):
+        """channel c takes no part in the calls that follow: nothing of it is read or written; its frame in progress is dropped"""
+        self._call("release_channel", self._h, int(c))
+
+    def finish_channel(self, c: int):
+        """the end of channel c's stream: with -b the frame of an open header is queued with complete = False; then the channel is released"""
+        self._call("finish_channel", self._h, int(c))
+
+    def channel_active(self, c: int) -> bool:
+        return bool(self._call("channel_active", self._h, int(c)))
+
+    def read_fm(self, channel: int, first: int, count: int) -> np.ndarray:
+        """testing tap: `count` samples of the channel's FM stream from its sample `first` (counted from its restart, still inside the ring) as
+        `iq_dec --FM --lpFM --wav --bo 16` writes them (int16)"""
+        out = np.empty(count, np.int16)
+        self._call("read_fm", self._h, int(channel), int(first), int(count), out.ctypes.data)
+        return out

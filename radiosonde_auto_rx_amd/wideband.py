@@ -37,6 +37,7 @@ IMET_AFSK = ("IMET4", "IMET1RS")          # dft_detect's IMETafsk outcomes (sond
 MK2LMS = "MK2LMS"                         # LMS6-1680 / MkIIa (scan type 18): decoded by mk2a.py
 WXR = ("WXR301", "WXRPN9")                # Weathex WxR-301D, 4800 Bd / PN9 at 5000 Bd (scan types 16, 17): decoded by wxr.py
 DROP = ("RD94RD41", "RD94", "RD41")       # Vaisala dropsondes (scan type 10): decoded by drop.py; the frames say which of the two it is
+DROP_POOLS = ("RD94RD41", "RD94RD41 -i")  # ChannelizedReceiver: the dropsonde engine's -i is engine-wide, so a pool of slots per polarity
 OWN_DEC = (MK2LMS,) + WXR + DROP          # engines with a decimation of their own: pieces are cut for them in push()
 
 
@@ -332,14 +333,21 @@ class ChannelizedReceiver:
     96 kHz; elsewhere the log says once per sonde that it cannot be decoded at this channel rate.  The same holds for a channel rate at which
     imet4iq would decimate (an iMet-4 in a 96 kHz or 100 kHz channel: decM 2): a block's length need not be a multiple of the decimation.
 
+    The dropsondes (RD94RD41) go through the dropsonde engine (drop.py) in its float32 form, `iq_dec --FM --lpFM --wav --bo 16 --iq <df> - <if_sr> 32 |
+    rd94rd41drop -b --json [-i]` per slot: sonde_drop_restart_channel at the scanner's offset, and sonde_drop_finish_channel for a slot that has gone silent
+    (with -b the frame of an open header is still printed).  The decoder's -i is engine-wide, so there are two pools of slots, one per polarity, each created
+    by the first detection that needs it: a negative score takes a slot of the -i pool.  A channel rate at which iq_dec would decimate (96 kHz, 100 kHz)
+    is logged once per sonde as not decodable at this channel rate.
+
     Not decoded here: MkIIa (+/- 50 kHz of deviation) and WxR-301D (64 kHz wide) do not fit a 50 kHz channelizer channel and are fed from the
-    wide stream (WidebandReceiver); the dropsondes' engine has no channel restart in its float32 base-rate form.  Their detections are dropped.
+    wide stream (WidebandReceiver).  Their detections are dropped.
 
     Every block costs one channelizer launch, one scanner step and one launch sequence per sonde type, whatever the number of sondes."""
 
     TYPES = {"RS41": ("rs41", Rs41Telemetry), "DFM": ("dfm", DfmTelemetry), "M10": ("m10", M10Telemetry), "M20": ("m20", M20Telemetry)}
     # + the scanner's RS92 / LMS6 / MEISEI / IMET5 / MRZ / MTS01: generic sonde descriptions and the bit-rate tiers of family.py
     # + IMET4 (IMET1RS at channel rates of 96 kHz and more): one Imet4Engine whose slots are restarted and released (IMET_AFSK)
+    # + RD94RD41: one DropEngine per polarity whose slots are restarted, finished and released (DROP_POOLS)
     IMET1_MIN_RATE = 96000                   # --imet1's designated IF rate
 
     def __init__(self, sample_rate: int, *, M: int = 256, D: int = 200, P: int = 16, cfreq_hz: int = 0, slots: int = 16, chunk: int | None = None,
@@ -382,6 +390,17 @@ class ChannelizedReceiver:
             stage = self.torch.zeros(self.slots, self.nmax, 2, dtype=self.torch.float32, device=self.out.device)
             self.torch.cuda.synchronize(self.out.device)
             g = self.groups[typ] = dict(engine=eng, stage=stage, owner=[None] * self.slots, calls=0)
+        if typ in DROP_POOLS:                       # iq_dec --FM --lpFM --wav --bo 16 --iq <df> - <if_sr> 32 | rd94rd41drop -b --json [-i], a slot per sonde
+            if DropEngine.dec_m_of(self.if_sr) != 1:               # iq_dec would decimate this channel rate: the engine's float32 form does not
+                self.groups[typ] = None
+                return None
+            with self.torch.cuda.device(self.device):              # the engine lives on the device that is current at create
+                eng = DropEngine([0.0] * self.slots, self.if_sr, bits=32, invert=(typ == DROP_POOLS[1]), opt_b=True, max_chunk=self.nmax)
+            for slot in range(self.slots):                         # handed out by restart_channel
+                eng.release_channel(slot)
+            stage = self.torch.zeros(self.slots, self.nmax, 2, dtype=self.torch.float32, device=self.out.device)
+            self.torch.cuda.synchronize(self.out.device)
+            g = self.groups[typ] = dict(engine=eng, stage=stage, owner=[None] * self.slots, calls=0)
         if g is None:
             kw = dict(bits=32, iq_mode=3, if_tune=True, lp_iq=True, max_chunk=self.nmax, max_frames=8 * self.slots, device=self.device)
             if typ in FAMILY:
@@ -397,25 +416,30 @@ class ChannelizedReceiver:
             g = self.groups[typ] = dict(engine=eng, stage=stage, owner=[None] * self.slots, calls=0)
         return g
 
-    def _start(self, k: int, typ: str, df: float):
+    def _start(self, k: int, typ: str, df: float, invert: bool = False):
         f_hz = self.ch.channel_freq(k) + df * self.if_sr
+        pool = DROP_POOLS[int(bool(invert))] if typ == DROP[0] else typ      # the engine that decodes it (self.groups)
         for s in self.sondes:                                    # the neighbouring channel sees a strong signal too
             if LMS_BASE.get(s["type"], s["type"]) == typ and abs(s["f_hz"] - f_hz) < (FAMILY[typ]["sep_hz"] if typ in FAMILY else 20_000.0 if typ in ("M10", "M20") + IMET_AFSK else 8_000.0):
                 return
         # --imet1's 96 kHz IF does not fit the channel, or imet4iq decimates this channel rate (96 kHz and 100 kHz channels for an iMet-4: decM 2,
         # and a block's length need not be a multiple of it): said once per sonde
-        if typ in IMET_AFSK and ((typ == "IMET1RS" and self.if_sr < self.IMET1_MIN_RATE) or self._group(typ) is None):
+        if (typ in IMET_AFSK and ((typ == "IMET1RS" and self.if_sr < self.IMET1_MIN_RATE) or self._group(typ) is None)) or \
+                (typ == DROP[0] and self._group(pool) is None):    # (a dropsonde where iq_dec decimates the channel rate)
             if not any(abs(f - f_hz) < 20_000.0 for f in self._undecodable):
                 self._undecodable.append(f_hz)
                 self.log.append(dict(event="not decodable at this channel rate", type=typ, f_hz=f_hz, channel=k, if_sr=self.if_sr))
             return
-        g = self._group(typ)
+        g = self._group(pool)
         if None not in g["owner"]:
             self.log.append(dict(event="no free channel", type=typ, f_hz=f_hz))
             return
         slot = g["owner"].index(None)
         khz = int(round((self.cfreq + f_hz) / 1000.0)) if self.cfreq else 0
-        if typ in IMET_AFSK:
+        if typ == DROP[0]:
+            g["engine"].restart_channel(slot, df)                  # --iq df; the slot's sample clock starts here
+            tel = DropPrinter(json=True, type=0, jsn_freq_khz=khz, version=self.version)
+        elif typ in IMET_AFSK:
             g["engine"].restart_channel(slot, df)                  # --iq df: the offset inside the channelizer channel, cycles per IF sample
             tel = Imet4Printer(json=True, jsn_freq_khz=khz, version=self.version)
         else:
@@ -426,16 +450,18 @@ class ChannelizedReceiver:
         s = dict(type=typ, f_hz=f_hz, chan=k, slot=slot, telemetry=tel, frames=0, khz=khz, t_last=self.t, seen=0)
         g["owner"][slot] = s
         self.sondes.append(s)
-        self.log.append(dict(event="detected", type=typ, f_hz=f_hz, channel=k, slot=slot, freq_khz=khz, if_sample=self.n_if))   # if_sample: the slot's first sample, counted in the channel's IF samples from the start of the stream
+        if typ == DROP[0]:
+            s["invert"] = bool(invert)
+        self.log.append(dict(event="detected", type=typ, f_hz=f_hz, channel=k, slot=slot, freq_khz=khz, if_sample=self.n_if, **({"invert": bool(invert)} if typ == DROP[0] else {})))   # if_sample: the slot's first sample, counted in the channel's IF samples from the start of the stream
 
-    def add_channel(self, typ: str, f_hz: float):
-        """start a decoder of sonde type `typ` (a scanner type name the receiver decodes: "RS41", "DFM", "M10", "IMET4", "LMS6", ...) at f_hz
-        (Hz from the stream's centre) without waiting for the scanner, from the next block on — what a detection does: the nearest channelizer
-        channel and the offset that is left inside it."""
-        if typ not in self.TYPES and typ not in FAMILY and typ not in IMET_AFSK:
+    def add_channel(self, typ: str, f_hz: float, invert: bool = False):
+        """start a decoder of sonde type `typ` (a scanner type name the receiver decodes: "RS41", "DFM", "M10", "IMET4", "LMS6", "RD94RD41", ...) at
+        f_hz (Hz from the stream's centre) without waiting for the scanner, from the next block on — what a detection does: the nearest channelizer
+        channel and the offset that is left inside it.  invert: the decoder's -i (dropsondes only; a detection sets it from the sign of its score)."""
+        if typ not in self.TYPES and typ not in FAMILY and typ not in IMET_AFSK and typ != DROP[0]:
             raise ValueError("the channelized receiver has no decoder for %r" % (typ,))
         k = self.ch.nearest_channel(f_hz)
-        self._start(k, typ, (f_hz - self.ch.channel_freq(k)) / self.if_sr)
+        self._start(k, typ, (f_hz - self.ch.channel_freq(k)) / self.if_sr, invert and typ == DROP[0])
 
     def _on_detection(self, d):
         """one scanner detection -> a decoder slot of its type at the offset the scanner measured inside the channel"""
@@ -447,6 +473,8 @@ class ChannelizedReceiver:
             self._start(d["channel"], d["type"], d["df"])
         elif d["type"] in IMET_AFSK:                               # the scanner's AFSK check decided the variant
             self._start(d["channel"], d["type"], d["df"])
+        elif d["type"] == DROP[0]:                                 # either polarity: a negative score takes a slot of the -i pool
+            self._start(d["channel"], DROP[0], d["df"], invert=d["score"] < 0)
         elif d["type"] in FAMILY and (d["score"] > 0 or FAMILY[d["type"]]["auto"]):
             self._start(d["channel"], d["type"], d["df"])
 
@@ -473,7 +501,7 @@ class ChannelizedReceiver:
                     if s is not None:
                         g["stage"][slot, :m] = self.out[s["chan"], :m]
                 torch.cuda.synchronize(self.out.device)                           # the copies ran on torch's stream, the engine has its own
-                if typ in IMET_AFSK:
+                if typ in IMET_AFSK or typ in DROP_POOLS:
                     g["engine"].process_device(g["stage"].data_ptr(), m, ch_stride=self.nmax)
                 else:
                     g["engine"].process_device(g["stage"].data_ptr(), self.nmax, m)
@@ -493,15 +521,20 @@ class ChannelizedReceiver:
                         g["owner"][slot] = None
                         s["telemetry"].close()
                         self.sondes.remove(s)
-                        self.log.append(dict(event="released", type=typ, f_hz=s["f_hz"], slot=slot, frames=s["frames"]))
+                        self.log.append(dict(event="released", type=DROP[0] if typ in DROP_POOLS else typ, f_hz=s["f_hz"], slot=slot, frames=s["frames"]))
             for s in [s for s in self.sondes if s["type"] in ("LMS6", "LMSX")]:     # after every engine has had this block: sondes whose decoder changed type
                 self._follow_lms(s)
             self.t += m / self.if_sr
             self.n_if += m
         if finish:
             for typ, g in self.groups.items():
-                if g is not None:
-                    out += self._drain(typ, g, True)
+                if g is None:
+                    continue
+                if typ in DROP_POOLS:                                             # the frame in progress at the end is printed as it is (rd94rd41drop.c:1430-1445)
+                    for slot, s in enumerate(g["owner"]):
+                        if s is not None:
+                            g["engine"].finish_channel(slot)
+                out += self._drain(typ, g, True)
         return out
 
     def _follow_lms(self, s):
@@ -537,6 +570,17 @@ class ChannelizedReceiver:
                     continue
                 s["frames"] += 1
                 js = [json.loads(line) for line in s["telemetry"].frame(f["bits"]).split("\n") if line.startswith("{")]
+                s["good"] = s.get("good", 0) + (1 if js else 0)
+                out += js
+            return out
+        if typ in DROP_POOLS:                                      # JSON only for a frame with every block good; its "type" says which of the two it is
+            out = []
+            for f in e.fetch_frames():
+                s = g["owner"][f["channel"]]
+                if s is None:
+                    continue
+                s["frames"] += 1
+                js = [json.loads(line) for line in s["telemetry"].frame(f["bytes"]).split("\n") if line.startswith("{")]
                 s["good"] = s.get("good", 0) + (1 if js else 0)
                 out += js
             return out

@@ -11,7 +11,10 @@ The single-core time of the reference's `iq_dec | rd94rd41drop` on such a captur
 (tools/make_golden_drop.py prints it: one run, not a benchmark); it is passed in with --ref-seconds-per-signal-s only to be quoted next to
 the result.
 
-    python tools/bench_drop.py [--seconds 2] [--channels 1,64,1024] [--forms iq,soft] [--out profiles/drop_bench.json]"""
+--bits 32 times the IQ form on float32 (the int16 capture / 32768: k_fm_front + k_drop_slice_rt, the engine of the channelized receiver);
+--idle-slots K releases the last K channels of that engine before the first call, as a pool with free slots runs.
+
+    python tools/bench_drop.py [--seconds 2] [--channels 1,64,1024] [--forms iq,soft] [--bits 16|32] [--idle-slots K] [--out profiles/drop_bench.json]"""
 import argparse
 import json
 import os
@@ -31,8 +34,12 @@ def main():
     ap.add_argument("--forms", default="iq,soft")
     ap.add_argument("--repeat", type=int, default=3)
     ap.add_argument("--out", default="")
+    ap.add_argument("--bits", type=int, default=16, choices=(16, 32), help="IQ form: int16, or float32 (the engine with run-time channels)")
+    ap.add_argument("--idle-slots", type=int, default=0, help="with --bits 32: that many channels are released before the first call")
     ap.add_argument("--ref-seconds-per-signal-s", type=float, default=0.0)
     a = ap.parse_args()
+    if a.idle_slots and a.bits != 32:
+        ap.error("--idle-slots needs --bits 32 (the engine whose channels are handed out at run time)")
     import torch
     from radiosonde_auto_rx_amd.drop import DropEngine
     from radiosonde_auto_rx_amd.fsk import FskModem, SoftinDev
@@ -44,13 +51,18 @@ def main():
     rows = []
     for form in a.forms.split(","):
         for nch in [int(c) for c in a.channels.split(",")]:
-            x = torch.from_numpy(np.ascontiguousarray(one[:2 * chunk * (calls + 1)])).to("cuda")
+            if form == "iq" and a.bits == 32:
+                x = torch.from_numpy(np.ascontiguousarray(one[:2 * chunk * (calls + 1)]).astype(np.float32) / np.float32(32768.0)).to("cuda")
+            else:
+                x = torch.from_numpy(np.ascontiguousarray(one[:2 * chunk * (calls + 1)])).to("cuda")
             blocks = [x[2 * chunk * k:2 * chunk * (k + 1)].repeat(nch).contiguous() for k in range(calls + 1)]
             torch.cuda.synchronize()
             walls, nf = [], 0
             for _ in range(a.repeat):
                 if form == "iq":
-                    eng = DropEngine([0.0] * nch, sr, opt_b=True, max_chunk=chunk)
+                    eng = DropEngine([0.0] * nch, sr, bits=a.bits, opt_b=True, max_chunk=chunk)
+                    for c in range(max(0, nch - a.idle_slots), nch if a.idle_slots else 0):
+                        eng.release_channel(c)
                     step = lambda k: eng.process_device(blocks[k].data_ptr(), chunk)
                 else:
                     md = FskModem(sr, 4800, n_channels=nch, P=10, nsym=50, lower=-20000, upper=20000, max_chunk=chunk)
@@ -72,7 +84,8 @@ def main():
                     md.close(); sf.close()
             sig = calls * chunk / sr
             wall = statistics.median(walls)
-            row = {"form": form, "sr": sr, "channels": nch, "signal_s": sig, "call_ms_per_signal_s": round(wall / sig, 3),
+            f32 = {"bits": a.bits, "idle_slots": min(a.idle_slots, nch)} if form == "iq" and a.bits == 32 else {}     # (the default run's rows keep their keys)
+            row = {"form": form, "sr": sr, "channels": nch, **f32, "signal_s": sig, "call_ms_per_signal_s": round(wall / sig, 3),
                    "min_ms_per_signal_s": round(min(walls) / sig, 3), "max_ms_per_signal_s": round(max(walls) / sig, 3), "repeat": a.repeat,
                    "x_realtime_all_channels": round(sig * 1e3 / wall, 2), "channel_seconds_per_second": round(nch * sig * 1e3 / wall, 1),
                    "frames": nf}
